@@ -737,6 +737,40 @@ def emit(out):
     print(compact_line(out), file=LINE_OUT or sys.stdout, flush=True)
 
 
+DUMP_LIMIT = 64 * 10 ** 6      # --dump-outputs: bytes of all files together
+
+
+def dump_outputs(d, last, learner, limit=DUMP_LIMIT, seed=0):
+    """--dump-outputs DIR: what the timed path handed its caller in its LAST step, as DIR/<name>.npy, so that two builds can be
+    compared output for output on the same seeded inputs:
+      episode_<key>   the rollout's 11-key episode dict (EpisodeBatch; float32, `u` holds action indices) for a fixed, seeded
+                      sample of its episodes, as many as the budget holds; episode_index (float64): which episodes
+      episode_reward, episode_won   the rollout's per-episode statistics, every episode (float32)
+      loss            the value learner.train() returned (float32);  params: the learner's flat parameters after that update
+    At most `limit` bytes in all.  `last` = Pipeline.last.  Returns the names written."""
+    from marl_amd.rollout import EpisodeBatch, RolloutStats
+    episodes, st, loss = last
+    rec = episodes.record
+    rewards, wins = (st.rewards(), st.wins()) if isinstance(st, RolloutStats) else st
+    out = {"loss": np.array([float(loss)], np.float32),
+           "params": learner._flat.flat.detach().float().cpu().numpy(),
+           "episode_reward": np.asarray(rewards, np.float32), "episode_won": np.asarray(wins, np.float32)}
+    per_episode = sum(v.numel() for _, v in EpisodeBatch(rec.slice(0, 1)).items()) * 4 + 8
+    headers = 128 * (len(out) + len(EpisodeBatch.KEYS) + 1)          # one .npy header per file
+    n = int(min(rec.E, (limit - headers - sum(v.nbytes for v in out.values())) // per_episode))
+    idx = np.sort(np.random.default_rng(seed).choice(rec.E, n, replace=False))      # own generator: np.random is untouched
+    out["episode_index"] = idx.astype(np.float64)
+    sample = EpisodeBatch(rec.index_select(torch.as_tensor(idx, device=rec.obs.device)))
+    for k, v in sample.items():
+        out["episode_" + k] = v.float().cpu().numpy()
+    os.makedirs(d, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    total = sum(os.path.getsize(os.path.join(d, k + ".npy")) for k in out)
+    assert total <= limit, (total, limit)
+    return sorted(out)
+
+
 class Pipeline:
     """The contract's step for one arithmetic mode: batched rollout of the rank's envs (T lock-steps, played straight into the
     replay ring) -> store -> sample -> one learner.train()."""
@@ -765,13 +799,16 @@ class Pipeline:
         self.buf = ReplayBuffer(args)
         self.worker.record_sink = self.buf          # training rollouts are played straight into the replay ring
         np.random.seed(1 + rank)
+        self.rank = rank
         self.train_steps = 0
         self.lazy_stats = []
+        self.last = None
 
     def one_step(self):
         o, E = self.o, self.E
         if o.blocking_loss:
-            episodes, _, _, steps = self.worker.generate_episodes(E)
+            episodes, rewards, wins, steps = self.worker.generate_episodes(E)
+            st = (rewards, wins)
         else:
             # same rollout, same device-side statistics; their copy to the host is enqueued instead of awaited (the env
             # steps are summed from the handles after the timed region's final barrier)
@@ -782,6 +819,7 @@ class Pipeline:
         batch = self.buf.sample(min(self.buf.current_size, self.args.batch_size))
         loss = self.learner.train(batch, self.train_steps)
         self.train_steps += 1
+        self.last = (episodes, st, loss)         # what the caller of the step received (--dump-outputs)
         return steps, loss
 
     def barrier(self):
@@ -789,9 +827,10 @@ class Pipeline:
             torch.distributed.barrier()
         torch.cuda.synchronize()
 
-    def timed_region(self, timers, dev):
+    def timed_region(self, timers, dev, dump_dir=None):
         """W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize on both sides; the MAX over ranks of the
-        time and the SUM of the env steps.  Returns (seconds, env steps, last loss)."""
+        time and the SUM of the env steps.  Returns (seconds, env steps, last loss).  `dump_dir`: rank 0 writes the outputs of
+        the last timed step there (dump_outputs), after the final barrier and before anything else runs on the device."""
         o = self.o
         for _ in range(o.warmup):
             self.one_step()
@@ -823,6 +862,11 @@ class Pipeline:
             timers.on = False
         finally:
             gc.enable()
+        # read the last step's loss here: a deferred handle's pinned slot is reused a few updates later (LossReadback.RING),
+        # and the legs below go on training
+        loss = float(loss)
+        if dump_dir and self.rank == 0:
+            dump_outputs(dump_dir, self.last, self.learner)
         env_steps += sum(st.steps() for st in self.lazy_stats[first:first + o.steps])
         if self.graphed:
             self.learner.graphs, keep = None, self.learner.graphs
@@ -929,6 +973,9 @@ def main():
                          "wide-state QMIX forward (config 5: HBM bound on reading the states when --mixer-dtype bf16)")
     ap.add_argument("--dry", action="store_true", help="multi-GPU pre-flight only: init RCCL, one all-reduce of the real "
                     "gradient-buffer size, print the result and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (episodes of its rollout - a fixed, seeded sample -, their "
+                         "statistics, the loss, the updated parameters) as DIR/<name>.npy, at most 64 MB in all (rank 0)")
     o = ap.parse_args()
     if o.cpu_probe:
         print(cpu_probe(o.alg, o.shape, o.T or SHAPES[o.shape][4], o.cpu_envs, o.cpu_probe))
@@ -1004,7 +1051,7 @@ def main():
 
     # HIP-event timing of every heavy C-ABI call inside the timed region (on the stream it is launched on)
     timers = KernelTimers(ops, args, E)
-    dt, env_steps, loss = pipe.timed_region(timers, dev)
+    dt, env_steps, loss = pipe.timed_region(timers, dev, o.dump_outputs)
 
     # separately timed legs (after the contract's timed region): learner-only and rollout-only, three passes each, the MEDIAN
     # counts and all three are in the full result

@@ -125,6 +125,19 @@ def test_reference_style_main_flow_on_dropin(tmp_path):
     assert p.returncode == 0 and "MAIN_FLOW_OK" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
 
 
+def test_reference_style_matrix_game_flow_on_dropin(tmp_path):
+    """matrix_game_test.py's steps written against the reference's module paths (tests/dropin_matrix_game_flow.py) through the
+    launcher: QTRAN-base on the matrix game trains on the MI355X classes and reads its Q tables."""
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, "-m", "marl_amd.dropin", os.path.join(root, "tests", "dropin_matrix_game_flow.py")],
+                       cwd=str(tmp_path), capture_output=True, text=True, timeout=600,
+                       env=dict(os.environ, PYTHONPATH=root, MPLBACKEND="Agg"))
+    assert p.returncode == 0 and "MATRIX_FLOW_OK" in p.stdout, (p.stdout[-1500:], p.stderr[-3000:])
+
+
 def test_main_flow_vectorises_a_real_smac_install(tmp_path):
     """A `smac` package that IS importable (here: a stand-in whose StarCraft2Env is a serial host environment with the
     reference's env API) + MARL_N_ENVS > 1: the launcher wraps it in HostVectorEnv, and main.py's flow trains on the lock-step

@@ -110,27 +110,30 @@ def test_reference_import_lines_resolve_to_dropin(golden_dir):
 
 
 def test_reference_matrix_game_script_runs_on_dropin():
-    """With the reference checkout present (build container only): its own matrix_game_test.py, unchanged, through the
-    launcher.  Without a GPU the run must get as far as the learner's constructor (every import, get_common_args,
-    the env, SharedMAC and RolloutWorker resolved to marl_amd) and stop at "no CPU fallback"; with a GPU the full
-    20 000-iteration script is the job of tests/test_gpu_runner.py's shorter harness."""
+    """The steps of the reference's matrix_game_test.py, written against its module paths (tests/dropin_matrix_game_flow.py),
+    through the launcher.  Without a GPU the run must get as far as the learner's constructor (every import, get_common_args,
+    the env, SharedMAC and RolloutWorker resolved to marl_amd) and stop at "no CPU fallback"; with a GPU the same script
+    trains (tests/test_gpu_runner.py::test_reference_style_matrix_game_flow_on_dropin)."""
+    import re
     import subprocess
-    script = "/root/reference/matrix_game_test.py"
-    if not os.path.exists(script):
-        import pytest
-        pytest.skip("reference checkout not present")
     if torch.cuda.is_available():
         import pytest
         pytest.skip("covered by the GPU harness")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    script = os.path.join(root, "tests", "dropin_matrix_game_flow.py")
     import tempfile
-    with tempfile.TemporaryDirectory() as tmp:      # the script writes ./result/...
+    with tempfile.TemporaryDirectory() as tmp:      # nothing lands in the tree
         p = subprocess.run([sys.executable, "-m", "marl_amd.dropin", script], cwd=tmp, capture_output=True, text=True,
                            env=dict(os.environ, PYTHONPATH=root, MPLBACKEND="Agg"), timeout=300)
     assert p.returncode != 0
     assert "Init RolloutWorker" in p.stdout                              # marl_amd.rollout.RolloutWorker.__init__
     assert "QTRANLearner runs only on the MI355X HIP kernels (no CPU fallback)" in p.stderr, p.stderr[-2000:]
-    assert "marl_amd/algorithm/qtran_learner.py" in p.stderr and "/root/reference/rollout.py" not in p.stderr
+    # every frame of the traceback below the launcher lies in the script or in marl_amd
+    frames = re.findall(r'File "([^"]+)"', p.stderr)
+    i = frames.index(script)
+    pkg = os.path.join(root, "marl_amd") + os.sep
+    assert frames[i + 1:] and all(f.startswith(pkg) for f in frames[i + 1:]), frames
+    assert any(f.endswith(os.path.join("marl_amd", "algorithm", "qtran_learner.py")) for f in frames)
 
 
 def test_matrix_game_get_episodes_matches_reference(golden_dir):
