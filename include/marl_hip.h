@@ -309,8 +309,8 @@ int marl_agent_unroll_x6_supported(int B, int T, int N, int O, int A, int last_a
 /* 1 when a NON-SAVING launch of marl_agent_unroll_fwd_x6 on this batch (saved = gi_in = hs = NULL: the target network's unroll and the
  * double-Q continuation of reference q_learner.py:104-110) runs on the round-6 decomposition (csrc/agent_x6p.hip: the recurrent team
  * multiplies x W_ih and h W_hh in one chain, five row tiles per workgroup, two barriers per step): whole-chip launches (cu_budget 0 /
- * 256) of more than 512 row tiles of 2s3z-sized agents (<= 96 input columns, <= 16 actions).  The learner then keeps no input-side
- * gate sums (gi_out / gi_in) for that batch. */
+ * 256) of more than 512 row tiles of 2s3z-sized agents (<= 96 input columns, <= 16 actions), given h0 and h_last on 16-byte boundaries
+ * (other alignments run on csrc/agent_x6.hip).  The learner then keeps no input-side gate sums (gi_out / gi_in) for that batch. */
 int marl_agent_unroll_x6_plain_r6(int B, int T, int N, int O, int A, int last_action, int reuse_network, int cu_budget);
 int marl_agent_unroll_fwd_x6(const marl_agent_weights_t* w, const float* obs, long obs_bs, int obs_t0,
                              const int* ufed, long u_bs, int u_t0, const int* ep_len, const int* ep_map,
@@ -509,7 +509,11 @@ int marl_synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rs
  * "bf16x6"): same arguments, same environment, same epsilon-greedy choice, same record - the integer fields agree with
  * marl_synth_rollout wherever no two available actions' Q values lie within fp32 rounding of each other (the choice is an argmax).
  * fc1 is evaluated as (bias + W1[:, obs | id] in) + W1[:, O + last action]: the observation part on the matrix cores a step ahead,
- * the chosen action's column added in fp32.  Supported: H = 64, 1 <= A <= 16, O a multiple of 4, O + A + N <= 160, N <= 64. */
+ * the chosen action's column added in fp32.  marl_synth_rollout_x6_supported_flags(), exactly: H = 64, O a multiple of 4, input width
+ * I = O (+ A if last_action) (+ N if reuse_network) <= 224, A <= 16 while I <= 160 and A <= 32 beyond (two action tiles exist only at
+ * seven fc1 chunks), N <= 64 and within the row tiles of one workgroup.  The flags are those the launch will be given.
+ * marl_synth_rollout_x6_supported() is the same predicate with both flags on. */
+int marl_synth_rollout_x6_supported_flags(int N, int O, int A, int last_action, int reuse_network);
 int marl_synth_rollout_x6_supported(int N, int O, int A);
 /* How marl_synth_rollout_x6 runs a batch of E environments (two decompositions of the same arithmetic, picked by batch size:
  * csrc/rollout_x6_v1.hip holds at most three row tiles of 16 (episode, agent) rows per workgroup, csrc/rollout_x6.hip up to five):

@@ -590,7 +590,9 @@ extern "C" int marl_agent_unroll_fwd_x6(const marl_agent_weights_t* w, const flo
   if (w->H != H || cu_budget < 0 || cu_budget > 256 || !marl_agent_unroll_x6_supported(B, T, N, O, A, last_action, reuse_network))
     return (int)hipErrorInvalidValue;
   if (saved && gi_in) return (int)hipErrorInvalidValue;      // a launch stores the input-side sums or reads them
-  if (!saved && !gi_in && !hs) {                             // a plain unroll of a large batch: the round-6 decomposition (agent_x6p.hip)
+  // a plain unroll of a large batch: the round-6 decomposition (agent_x6p.hip), which reads h0 and writes h_last as 16-byte vectors;
+  // this file's kernel takes the other alignments
+  if (!saved && !gi_in && !hs && !(reinterpret_cast<uintptr_t>(h0) & 15) && !(reinterpret_cast<uintptr_t>(h_last) & 15)) {
     const int tpw = marl_agent_x6p_tiles(B, T, N, O, A, last_action, reuse_network, cu_budget);
     if (tpw) return marl_agent_x6p_launch(w, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, ep_len, ep_map, h0, q, h_last, B, T, N, O, A, last_action,
                                           reuse_network, tpw, stream);

@@ -685,24 +685,27 @@ static bool rx6_use_v1(int E, int N, int O, int A, int last_action, int reuse_ne
 
 ST_DEFINE_SETTER(marl_debug_stamps_rollout_x6)
 
-// shapes the split rollout covers: H = 64, observation width a multiple of 4, input width <= 224 (three / five / seven fc1 chunks:
-// 2s3z-, 3s5z- and MMM2-sized agents), <= 16 actions up to 160 input columns and <= 32 beyond (two action tiles of fc2 and of the
-// choice), whole environments in at most five (wide inputs: four / three) row tiles; an environment's agents in one wave
-extern "C" int marl_synth_rollout_x6_supported(int N, int O, int A) {
+// shapes the split rollout covers: H = 64, observation width a multiple of 4, input width I = O [+ A] [+ N] <= 224 (three / five / seven
+// fc1 chunks: 2s3z-, 3s5z- and MMM2-sized agents), <= 16 actions up to 160 input columns and <= 32 beyond (two action tiles of fc2 and
+// of the choice exist only at seven chunks), whole environments in at most five (wide inputs: four / three) row tiles; an environment's
+// agents in one wave.  The flags decide I, so they decide the chunk count and with it whether A > 16 is covered
+extern "C" int marl_synth_rollout_x6_supported_flags(int N, int O, int A, int last_action, int reuse_network) {
   if (A < 1 || N < 1 || O < 4 || (O & 3)) return 0;
-  const int I = O + A + N;
+  const int I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
   if (I > 224 || A > (I > 160 ? 32 : 16)) return 0;
   const int KI = (I + 31) / 32 * 32;
   const int mt = rx6_max_tiles(KI);
   if (N > 16 * mt || N > 64) return 0;                   // a whole environment in one workgroup; its agents on one wave (env step)
   return rx6_lds((N + 15) / 16, KI, A, 1) <= 160 * 1024 ? 1 : 0;
 }
+// the same with both flags on (the input row [obs | last action | agent id])
+extern "C" int marl_synth_rollout_x6_supported(int N, int O, int A) { return marl_synth_rollout_x6_supported_flags(N, O, A, 1, 1); }
 
 // how marl_synth_rollout_x6 would run a batch (what bench.py's roofline model counts products by): plan[0] = decomposition (1: round 5,
 // rollout_x6_v1.hip; 2: round 6, this file), plan[1] = workgroups, plan[2] = row tiles of 16 (episode, agent) rows per workgroup,
 // plan[3] = environments per workgroup, plan[4] = fc1 chunks of 32 input columns.  Returns 0, or hipErrorInvalidValue for unsupported shapes
 extern "C" int marl_synth_rollout_x6_plan(int E, int N, int O, int A, int last_action, int reuse_network, int* plan) {
-  if (!plan || E <= 0 || !marl_synth_rollout_x6_supported(N, O, A)) return (int)hipErrorInvalidValue;
+  if (!plan || E <= 0 || !marl_synth_rollout_x6_supported_flags(N, O, A, last_action, reuse_network)) return (int)hipErrorInvalidValue;
   const int I = O + (last_action ? A : 0) + (reuse_network ? N : 0), KI = (I + 31) / 32 * 32;
   int epw;
   if (rx6_use_v1(E, N, O, A, last_action, reuse_network)) {
@@ -733,7 +736,7 @@ extern "C" int marl_synth_rollout_x6(const marl_agent_weights_t* w, unsigned see
     return marl_rollout_x6_v1(w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded, length, won,
                               h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network, stream);
   if (E <= 0 || T <= 0) return 0;
-  if (w->H != H || state_ld < S || !marl_synth_rollout_x6_supported(N, O, A)) return (int)hipErrorInvalidValue;
+  if (w->H != H || state_ld < S || !marl_synth_rollout_x6_supported_flags(N, O, A, last_action, reuse_network)) return (int)hipErrorInvalidValue;
   if (reinterpret_cast<uintptr_t>(obs) & 15) return (int)hipErrorInvalidValue;
   RX6Args a;
   a.W1 = w->fc1_w; a.b1 = w->fc1_b; a.Wih = w->w_ih; a.Whh = w->w_hh; a.bih = w->b_ih; a.bhh = w->b_hh;
@@ -750,6 +753,7 @@ extern "C" int marl_synth_rollout_x6(const marl_agent_weights_t* w, unsigned see
   if ((double)E * (T + 1) * N * (O > A ? O : A) >= 2147483648.0 || (double)E * (T + 1) * state_ld >= 2147483648.0)
     return (int)hipErrorInvalidValue;
   const int nk1 = a.KI > 160 ? 7 : a.KI > 96 ? 5 : 3;
+  if (A > 16 && nk1 != 7) return (int)hipErrorInvalidValue;      // only the seven-chunk instantiations carry two action tiles
   const int epw = rx6_epw(E, N, a.KI, A);
   if (epw < 1) return (int)hipErrorInvalidValue;
   a.EPW = epw;

@@ -436,8 +436,8 @@ def synth_rollout_supported(N, O, A):
     return bool(_lib.load().marl_synth_rollout_supported(N, O, A))
 
 
-def synth_rollout_x6_supported(N, O, A):
-    return bool(_lib.load().marl_synth_rollout_x6_supported(N, O, A))
+def synth_rollout_x6_supported(N, O, A, last_action=True, reuse_network=True):
+    return bool(_lib.load().marl_synth_rollout_x6_supported_flags(N, O, A, 1 if last_action else 0, 1 if reuse_network else 0))
 
 
 def synth_rollout_x6_plan(E, N, O, A, last_action=True, reuse_network=True):

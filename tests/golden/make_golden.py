@@ -53,6 +53,10 @@ CASES = [
     ("qplex_MMM2", "MMM2", "qplex", 3, 4, [4, 2, 3], {}),
     ("qmix_MMM2_hyper2", "MMM2", "qmix", 3, 5, [5, 2, 4], {"two_hyper_layers": True}),
     ("qplex_3s5z", "3s5z", "qplex", 3, 4, [3, -1, 4], {}),
+    # the agent's input row without the last action (share_params.py:47-50): 186 / 136 / 85 input columns
+    ("qmix_MMM2_nolast", "MMM2", "qmix", 3, 5, [5, 3, 4], {"last_action": False}),
+    ("qtran_3s5z_nolast", "3s5z", "qtran_base", 3, 5, [5, 2, -1], {"last_action": False}),
+    ("qmix_2s3z_nolast", "2s3z", "qmix", 3, 5, [5, -1, 3], {"last_action": False}),
 ]
 TRAIN_STEPS = [0, 1, 200, 201]   # 200 crosses the target-sync boundary (quirk Q6)
 
@@ -203,6 +207,29 @@ def gen_rollout():
     print("rollout fixtures written")
 
 
+def gen_rollout_nolast():
+    """The serial SMAC-shaped greedy rollout with last_action=False (share_params.py:47-50: the input row is [obs | agent id]):
+    2s3z-sized agents (85 input columns) and MMM2-sized ones (186 columns, 18 actions)."""
+    out = {}
+    for tag, shape, E in (("2s3z", "2s3z", 6), ("MMM2", "MMM2", 4)):
+        args = seeded.make_args(shape, "qmix", episode_limit=8, last_action=False)
+        mac = SharedMAC(args)
+        load(mac.agent, seeded.seeded_state(seeded.agent_param_shapes(args), seed=11, scale=3.0))
+        sy = orl.SynthSMAC(args.n_agents, args.obs_shape, args.state_shape, args.n_actions, 8, seed=5)
+        args.epsilon = 0.0
+        w = RolloutWorker(orl.SerialSynthEnv(sy), mac, args)
+        np.random.seed(9)
+        ep, rew, wins, steps = w.generate_episodes(E, evaluate=True)
+        for k in ("u", "r", "padded", "terminated", "avail_u", "avail_u_next"):
+            out["%s/%s" % (tag, k)] = np.asarray(ep[k], dtype=np.float64)
+        out["%s/o_checksum" % tag] = np.array(seeded.checksum([ep["o"], ep["o_next"], ep["s"], ep["s_next"]]))
+        out["%s/rewards" % tag] = np.array(rew, dtype=np.float64)
+        out["%s/wins" % tag] = np.array(wins)
+        out["%s/steps" % tag] = np.array(steps)
+    np.savez_compressed(os.path.join(HERE, "rollout_nolast.npz"), **out)
+    print("rollout_nolast fixtures written")
+
+
 def gen_replay():
     out = {}
     args = seeded.make_args("2s3z", "qmix", episode_limit=3, buffer_size=7)
@@ -242,6 +269,8 @@ if __name__ == "__main__":
     for c in CASES:
         if not only or c[0] in only.split(","):
             gen_learner_case(c)
+    if not only or "rollout_nolast" in only.split(","):
+        gen_rollout_nolast()
     if not only:
         gen_rollout()
         gen_replay()

@@ -20,6 +20,10 @@ CASES = [
     ("qplex_MMM2", "MMM2", "qplex", 3, 4, [4, 2, 3], {}),
     ("qmix_MMM2_hyper2", "MMM2", "qmix", 3, 5, [5, 2, 4], {"two_hyper_layers": True}),
     ("qplex_3s5z", "3s5z", "qplex", 3, 4, [3, -1, 4], {}),
+    # the agent's input row without the last action (share_params.py:47-50): 186 / 136 / 85 input columns
+    ("qmix_MMM2_nolast", "MMM2", "qmix", 3, 5, [5, 3, 4], {"last_action": False}),
+    ("qtran_3s5z_nolast", "3s5z", "qtran_base", 3, 5, [5, 2, -1], {"last_action": False}),
+    ("qmix_2s3z_nolast", "2s3z", "qmix", 3, 5, [5, -1, 3], {"last_action": False}),
 ]
 TRAIN_STEPS = [0, 1, 200, 201]
 

@@ -88,6 +88,16 @@ def test_split_kernel_capability_predicates():
     assert rx6(5, 80, 11) == 1 and rx6(8, 128, 14) == 1 and rx6(2, 4, 3) == 1 and rx6(49, 40, 5) == 1 and rx6(33, 100, 5) == 1
     assert rx6(10, 176, 18) == 1 and rx6(4, 180, 32) == 1 and rx6(4, 180, 33) == 0 and rx6(10, 200, 18) == 0
     assert rx6(5, 80, 17) == 0 and rx6(5, 82, 11) == 0 and rx6(65, 40, 5) == 0 and rx6(64, 40, 5) == 1 and rx6(49, 176, 18) == 0
+    # the flag-aware predicate: the same with both flags on; the flags decide the input width and with it the chunk count - two action
+    # tiles only beyond 160 columns of the REAL row
+    rx6f = lib.marl_synth_rollout_x6_supported_flags
+    for shp in ((5, 80, 11), (8, 128, 14), (2, 4, 3), (49, 40, 5), (33, 100, 5), (10, 176, 18), (4, 180, 32), (4, 180, 33), (10, 200, 18),
+                (5, 80, 17), (5, 82, 11), (65, 40, 5), (64, 40, 5), (49, 176, 18), (4, 140, 20)):
+        assert rx6f(*shp, 1, 1) == rx6(*shp), shp
+    assert rx6f(4, 140, 20, 0, 1) == 0              # 144 columns without the last action: five chunks, one action tile
+    assert rx6f(4, 140, 20, 1, 1) == 1              # 164 columns: seven chunks, two action tiles
+    assert rx6f(10, 176, 18, 0, 1) == 1             # MMM2 without the last action: 186 columns, still seven chunks
+    assert rx6f(10, 176, 18, 1, 0) == 1 and rx6f(10, 176, 18, 0, 0) == 1 and rx6f(10, 140, 18, 0, 0) == 0
     # ... and how a batch runs: the round-5 decomposition while it holds one row tile per workgroup, the round-6 one (up to five tiles)
     # beyond - (decomposition, workgroups, row tiles, environments per workgroup, fc1 chunks)
     import ctypes
@@ -101,6 +111,9 @@ def test_split_kernel_capability_predicates():
     assert plan(2048, 8, 128, 14) == (2, 256, 4, 8, 5) and plan(100, 49, 40, 5) == (2, 100, 4, 1, 3)
     assert plan(1024, 10, 176, 18) == (2, 256, 3, 4, 7) and plan(2048, 10, 176, 18) == (2, 512, 3, 4, 7)      # MMM2: three tiles at most
     assert lib.marl_synth_rollout_x6_plan(512, 10, 200, 18, 1, 1, (ctypes.c_int * 5)()) != 0
+    assert lib.marl_synth_rollout_x6_plan(2048, 4, 140, 20, 0, 1, (ctypes.c_int * 5)()) != 0      # (the flag-aware predicate)
+    out = (ctypes.c_int * 5)()
+    assert lib.marl_synth_rollout_x6_plan(2048, 10, 176, 18, 0, 1, out) == 0 and tuple(out) == (2, 512, 3, 4, 7)
     # the fused-head split pair: the padded input width must leave a free column in its last 64-column block
     m3 = lambda k, n3=1: lib.marl_mlp3_x6_supported(__import__("ctypes").byref(_src_cpu(k)), k, 64, 64, n3, 10)
     assert m3(112) == 1 and m3(120) == 1 and m3(175) == 1 and m3(188) == 1

@@ -395,3 +395,64 @@ def test_qplex_mmm2_heads_run_fused_and_match_oracle():
             assert mx._fused_family(mods, xsa if fname == "ac" else xs, nout) is not None, fname
     _linearity(learner, rec, Tm, Eq, 2, "full:qplex_MMM2_96x40")
     _sub_batch_vs_oracle(case, args, learner, rec, [0, 1, 47, 95], Tm, "full:qplex_MMM2_96x40")
+
+
+@pytest.mark.parametrize("gemm_mode", MODES)
+def test_qmix_2s3z_2048_without_last_action_shard(gemm_mode, monkeypatch):
+    """QMIX on 2s3z with last_action=False (the agent's input row is [obs | agent id]: 85 columns) at 2048 envs x T = 40, 10 240
+    agent rows.  (a) the plain schedule over the whole chip (experiments no_pair): in bf16x6 mode the target unroll is a plain split
+    unroll of 640 row tiles and runs on csrc/agent_x6p.hip - asserted from the launches - and what the full batch produced for
+    sampled episodes equals the CPU oracle's; (b) the same under the chain schedule (forced when its model does not pick it);
+    (c) shard linearity and the sampled sub-batch with every gradient against the oracle."""
+    import inspect
+    from marl_amd.hostutil import DeviceBatch
+    from marl_amd import ops
+    E2, T2 = 2048, 40
+    name = "full:qmix_2s3z_nolast_2048x40[%s]" % gemm_mode
+    case, args, learner, rec = _shard_world("2s3z", "qmix", E2, T2, seed=43, over={"last_action": False}, gemm_mode=gemm_mode)
+    assert not args.last_action and args.reuse_network
+    N, O, A = args.n_agents, args.obs_shape, args.n_actions
+    assert learner.eval_net.agent.fc1.weight.shape[1] == O + N
+    assert int(rec.padded.sum().item()) > 0, "ragged episodes wanted"
+    Tm = DeviceBatch.first_terminated_len(rec.term, args.episode_limit)
+    idx = [0, 1, E2 // 2 - 1, E2 // 2, E2 - 200, E2 - 1]
+    plain_r6 = []
+    orig = ops.agent_unroll_fwd_x6
+    sig = inspect.signature(orig)
+
+    def spy(*a, **kw):
+        c = sig.bind(*a, **kw)
+        c.apply_defaults()
+        c = c.arguments
+        if (c["saved"] is None and c["gi_in"] is None and c["hs"] is None and
+                ops.agent_unroll_x6_plain_r6(c["B"], c["T"], c["N"], c["O"], c["A"], c["last_action"], c["reuse_network"], c["cu_budget"])):
+            plain_r6.append((c["B"], c["T"], bool(c["last_action"])))
+        return orig(*a, **kw)
+
+    monkeypatch.setattr(ops, "agent_unroll_fwd_x6", spy)
+    # (a) eval and target unrolls back to back over the whole chip
+    learner.pair.enabled = False
+    try:
+        _, dbg = _grads(learner, rec, Tm)
+    finally:
+        learner.pair.enabled = True
+    if gemm_mode == "bf16x6":
+        assert ops.agent_unroll_x6_plain_r6(E2, Tm, N, O, A, False, True)
+        assert (E2, Tm, False) in plain_r6, plain_r6          # (the target unroll: no activations, no gate sums read)
+    else:
+        assert plain_r6 == []
+    _full_batch_samples_vs_oracle(case, args, dbg, rec, idx, Tm, name)
+    # (b) the chain schedule
+    forced = learner.pair.forced_split
+    if learner.pair.chain_split(E2 * N, Tm, O) is None:
+        learner.pair.forced_split = 160
+    try:
+        split = learner.pair.chain_split(E2 * N, Tm, O)
+        assert split is not None and split[0] + split[1] == 256, split
+        _, dbg_chain = _grads(learner, rec, Tm)
+    finally:
+        learner.pair.forced_split = forced
+    _full_batch_samples_vs_oracle(case, args, dbg_chain, rec, idx, Tm, name)
+    # (c)
+    _linearity(learner, rec, Tm, E2, 2, name)
+    _sub_batch_vs_oracle(case, args, learner, rec, idx, Tm, name)

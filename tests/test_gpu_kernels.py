@@ -505,8 +505,15 @@ def test_wgrad_split_state_and_encoder_columns(dev, M, S, E_):
 
 
 # ------------------------------------------------------------------------------------- agent
-def _agent_case(shape, B, T, dev, seed=0, with_h0=False):
-    args = seeded.make_args(shape, "qmix", episode_limit=T)
+# (last_action, reuse_network) besides the default (1, 1): the agent's input row is [obs | one-hot(last action) | one-hot(agent id)]
+# with either one-hot block left out (controller/share_params.py:47-50) - the input width, the fc1 chunk count, the id column's place
+# and whether the last action's fc1 table is used all follow from these flags
+FLAGS_OFF = [(0, 1), (1, 0), (0, 0)]
+FLAGS_OFF_IDS = ["nolast", "noid", "nolast-noid"]
+
+
+def _agent_case(shape, B, T, dev, seed=0, with_h0=False, la=1, rn=1):
+    args = seeded.make_args(shape, "qmix", episode_limit=T, last_action=bool(la), reuse_network=bool(rn))
     p_np = seeded.seeded_state(seeded.agent_param_shapes(args), seed=11 + seed, scale=2.0)
     rng = np.random.default_rng(seed)
     N, O, A = args.n_agents, args.obs_shape, args.n_actions
@@ -524,15 +531,30 @@ def _oracle_unroll(args, p_np, obs, ufed, h0, requires_grad=False):
     bb, tt, nn = np.nonzero(ufed >= 0)
     oh[bb, tt, nn, ufed[bb, tt, nn]] = 1
     h = torch.zeros(B * N, 64) if h0 is None else torch.tensor(h0)
-    q, hs, hl = nets.agent_unroll(p, torch.tensor(obs), torch.tensor(oh), h)
+    q, hs, hl = nets.agent_unroll(p, torch.tensor(obs), torch.tensor(oh), h, args.last_action, args.reuse_network)
     return p, q, hs, hl
+
+
+def _flags(args):
+    return dict(last_action=args.last_action, reuse_network=args.reuse_network)
+
+
+def _fc1_input(args, obs_d, u_d, M):
+    """the fc1 weight gradient's input rows as the learner builds them (algorithm/common.py): the fed action's one-hot only with
+    last_action, the agent id only with reuse_network"""
+    from marl_amd import ops
+    N, O, A = args.n_agents, args.obs_shape, args.n_actions
+    kw = dict(idx=u_d.view(M, 1), nhot=1, hot_w=A) if args.last_action else {}
+    I = O + (A if args.last_action else 0) + (N if args.reuse_network else 0)
+    assert I == seeded.agent_param_shapes(args)[0][1][1]
+    return ops.src(obs_d.view(M, O), nid=N if args.reuse_network else 0, **kw), I
 
 
 @pytest.mark.parametrize("shape,B,T,with_h0", [("2s3z", 7, 5, False), ("2s3z", 70, 3, True), ("matrix", 9, 1, False),
                                                ("3s5z", 5, 4, True), ("MMM2", 4, 3, False)])
-def test_agent_unroll_fwd(dev, shape, B, T, with_h0):
+def test_agent_unroll_fwd(dev, shape, B, T, with_h0, la=1, rn=1):
     from marl_amd import ops
-    args, p_np, obs, ufed, h0 = _agent_case(shape, B, T, dev, with_h0=with_h0)
+    args, p_np, obs, ufed, h0 = _agent_case(shape, B, T, dev, with_h0=with_h0, la=la, rn=rn)
     N, O, A = args.n_agents, args.obs_shape, args.n_actions
     with torch.no_grad():
         _, q_ref, hs_ref, hl_ref = _oracle_unroll(args, p_np, obs, ufed, h0)
@@ -543,7 +565,7 @@ def test_agent_unroll_fwd(dev, shape, B, T, with_h0):
     hl = torch.empty(B * N, 64, device=dev)
     saved = torch.empty(ops.saved_shape(T, B, N), device=dev)  # opaque tile layout, 6 planes per row-step
     ops.agent_unroll_fwd(w, cu(obs, dev), T * N, 0, cu(ufed, dev, torch.int32), T * N, 0,
-                         cu(h0, dev) if h0 is not None else None, q, hs, hl, saved, B, T, N, O, A)
+                         cu(h0, dev) if h0 is not None else None, q, hs, hl, saved, B, T, N, O, A, **_flags(args))
     close(q, q_ref, 1e-4, msg="q")
     close(hs, hs_ref, 1e-4, msg="hs")
     close(hl, hl_ref, 1e-4, msg="h_last")
@@ -552,6 +574,39 @@ def test_agent_unroll_fwd(dev, shape, B, T, with_h0):
     # (and one more slab: the hidden state after the last step, where the backward pass looks for h(T-1))
     hprev = torch.cat([hprev, hs_ref[:, -1:]], 1)
     close(ops.saved_plane(saved, 0, B * N).reshape(T + 1, B, N, 64).permute(1, 0, 2, 3), hprev, 1e-4, msg="hprev")
+
+
+@pytest.mark.parametrize("la,rn", FLAGS_OFF, ids=FLAGS_OFF_IDS)
+@pytest.mark.parametrize("shape,B,T,with_h0", [("2s3z", 7, 5, False), ("2s3z", 900, 4, True), ("matrix", 9, 1, False),
+                                               ("3s5z", 5, 4, True), ("MMM2", 4, 3, False), ("MMM2", 450, 3, True)])
+def test_agent_unroll_fwd_flags(dev, shape, B, T, with_h0, la, rn):
+    """test_agent_unroll_fwd with the last action and / or the agent id left out of the input row: one and two row tiles per
+    workgroup (> 256 tiles), the vector and the element-wise (matrix game: one observation column) input paths"""
+    test_agent_unroll_fwd(dev, shape, B, T, with_h0, la, rn)
+
+
+@pytest.mark.parametrize("shape", ["matrix", "2s3z", "3s5z", "MMM2"])
+@pytest.mark.parametrize("rows", [1, 5, 37, 4100])
+def test_rnn_q_net_forward_matches_oracle_step(dev, shape, rows):
+    """RNNQNet.forward (network/q_network.py, the reference class surface: rows of an already concatenated input) == one oracle
+    agent step at 1e-4 on q and h - input widths 6, 96, 150 (not a multiple of 4: the element-wise input path) and 204"""
+    from marl_amd.network.q_network import RNNQNet
+    args = seeded.make_args(shape, "qmix")
+    shapes = seeded.agent_param_shapes(args)
+    I = shapes[0][1][1]
+    assert I == {"matrix": 6, "2s3z": 96, "3s5z": 150, "MMM2": 204}[shape]
+    p_np = seeded.seeded_state(shapes, seed=17, scale=2.0)
+    net = RNNQNet(I, args)
+    net.load_state_dict({k: torch.tensor(v) for k, v in p_np.items()})
+    rng = np.random.default_rng(rows)
+    x = rng.standard_normal((rows, I)).astype(np.float32)
+    h0 = (rng.standard_normal((rows, 64)) * 0.5).astype(np.float32)
+    q, h = net(torch.tensor(x), torch.tensor(h0))
+    with torch.no_grad():
+        q_ref, h_ref = nets.agent_step({k: torch.tensor(v) for k, v in p_np.items()}, torch.tensor(x), torch.tensor(h0))
+    assert q.shape == (rows, args.n_actions) and h.shape == (rows, 64)
+    close(q, q_ref, 1e-4, msg="q")
+    close(h, h_ref, 1e-4, msg="h")
 
 
 def test_agent_unroll_shifted_storage(dev):
@@ -581,17 +636,18 @@ def test_agent_unroll_shifted_storage(dev):
 
 @pytest.mark.parametrize("B,T,with_h0,ragged,ut0", [(1700, 6, True, True, 0), (2100, 5, False, True, -1), (4096, 4, True, False, 0),
                                                      (4100, 4, True, True, 0), (9000, 4, False, True, 0), (2621, 7, True, True, -1)])
-def test_agent_unroll_x6_plain_round6_decomposition(dev, B, T, with_h0, ragged, ut0):
+def test_agent_unroll_x6_plain_round6_decomposition(dev, B, T, with_h0, ragged, ut0, la=1, rn=1):
     """csrc/agent_x6p.hip (non-saving split unrolls of more than 512 row tiles: the recurrent team runs x W_ih + h W_hh down one
     accumulator chain, three to five row tiles per workgroup, two barriers per step) against the CPU oracle at the unroll bound (1e-4)
     and beside csrc/agent_x6.hip on the same inputs (unroll_r6 = 0; the two differ only in where the last action's fc1 column is added):
     (T+1)-slot storage read through an episode map, the shifted / unshifted fed action, ragged episode lengths, a carried hidden state,
     three / four / five tiles per workgroup, several rounds of workgroups, a partial last workgroup."""
     from marl_amd import ops, experiments
-    args, p_np, _, _, _ = _agent_case("2s3z", B, T, dev, with_h0=with_h0)
+    args, p_np, _, _, _ = _agent_case("2s3z", B, T, dev, with_h0=with_h0, la=la, rn=rn)
     N, O, A = args.n_agents, args.obs_shape, args.n_actions
-    assert ops.agent_unroll_x6_plain_r6(B, T, N, O, A) and not ops.agent_unroll_x6_plain_r6(B, T, N, O, A, cu_budget=128)
-    assert not ops.agent_unroll_x6_plain_r6(1600, T, N, O, A)            # 500 row tiles: one round of two-tile workgroups of agent_x6.hip
+    fl = _flags(args)
+    assert ops.agent_unroll_x6_plain_r6(B, T, N, O, A, **fl) and not ops.agent_unroll_x6_plain_r6(B, T, N, O, A, cu_budget=128, **fl)
+    assert not ops.agent_unroll_x6_plain_r6(1600, T, N, O, A, **fl)      # 500 row tiles: one round of two-tile workgroups of agent_x6.hip
     rng = np.random.default_rng(B + T)
     E = B + 2
     store = rng.standard_normal((E, T + 1, N, O)).astype(np.float32)
@@ -606,10 +662,10 @@ def test_agent_unroll_x6_plain_round6_decomposition(dev, B, T, with_h0, ragged, 
     outs = {}
     for r6 in (1, 0):
         with experiments.override(unroll_r6=r6):
-            assert ops.agent_unroll_x6_plain_r6(B, T, N, O, A) == bool(r6)
+            assert ops.agent_unroll_x6_plain_r6(B, T, N, O, A, **fl) == bool(r6)
             q, hl = torch.full((B, T, N, A), 9.0, device=dev), torch.full((B * N, 64), 9.0, device=dev)
             ops.agent_unroll_fwd_x6(w, sd, (T + 1) * N, t0, ud, T * N, ut0, cu(h0, dev) if h0 is not None else None, q, None, hl, None,
-                                    B, T, N, O, A, ep_len=ld, ep_map=ed)
+                                    B, T, N, O, A, ep_len=ld, ep_map=ed, **fl)
             outs[r6] = (q.cpu(), hl.cpu())
     obs = store[emap][:, t0:t0 + T].copy()
     for b in range(B):
@@ -628,10 +684,52 @@ def test_agent_unroll_x6_plain_round6_decomposition(dev, B, T, with_h0, ragged, 
     print("plain unroll B=%d T=%d: max |q - oracle|: agent_x6p %.2e, agent_x6 %.2e" % (B, T, e6, e5))
 
 
+@pytest.mark.parametrize("la,rn", FLAGS_OFF, ids=FLAGS_OFF_IDS)
+@pytest.mark.parametrize("B,T,with_h0,ragged,ut0", [(1700, 6, True, True, 0), (2621, 7, True, True, -1), (4100, 4, False, True, 0)])
+def test_agent_unroll_x6_plain_round6_decomposition_flags(dev, B, T, with_h0, ragged, ut0, la, rn):
+    """the same without the last action (85 input columns) and / or the agent id (91, 80): three, four and five row tiles per
+    workgroup"""
+    test_agent_unroll_x6_plain_round6_decomposition(dev, B, T, with_h0, ragged, ut0, la, rn)
+
+
+@pytest.mark.parametrize("which", ["h0", "h_last", "both"])
+def test_agent_unroll_x6_plain_unaligned_hidden_state(dev, which):
+    """A plain split unroll of a batch the round-6 decomposition takes, with h0 and / or h_last 4 bytes off a 16-byte boundary
+    (csrc/agent_x6p.hip moves them as 16-byte vectors): it runs on csrc/agent_x6.hip instead - the oracle's q and final hidden
+    state at 1e-4, and bit for bit what that kernel gives on aligned buffers"""
+    from marl_amd import ops, experiments
+    B, T = 2621, 5
+    args, p_np, obs, ufed, h0 = _agent_case("2s3z", B, T, dev, seed=4, with_h0=True)
+    N, O, A = args.n_agents, args.obs_shape, args.n_actions
+    assert ops.agent_unroll_x6_plain_r6(B, T, N, O, A)
+    with torch.no_grad():
+        _, q_ref, _, hl_ref = _oracle_unroll(args, p_np, obs, ufed, h0)
+    w = ops.agent_weights({k: cu(v, dev) for k, v in p_np.items()})
+    od, ud = cu(obs, dev), cu(ufed, dev, torch.int32)
+
+    def run(off_h0, off_hl, r6=1):
+        hb = torch.zeros(B * N * 64 + 4, device=dev)
+        h0d = hb[off_h0:off_h0 + B * N * 64].view(B * N, 64)
+        h0d.copy_(cu(h0, dev))
+        lb = torch.full((B * N * 64 + 4,), 9.0, device=dev)
+        hl = lb[off_hl:off_hl + B * N * 64].view(B * N, 64)
+        assert h0d.data_ptr() % 16 == 4 * off_h0 and hl.data_ptr() % 16 == 4 * off_hl
+        q = torch.full((B, T, N, A), 9.0, device=dev)
+        with experiments.override(unroll_r6=r6):
+            ops.agent_unroll_fwd_x6(w, od, T * N, 0, ud, T * N, 0, h0d, q, None, hl, None, B, T, N, O, A)
+        return q.cpu(), hl.cpu()
+
+    q, hl = run(*{"h0": (1, 0), "h_last": (0, 1), "both": (1, 3)}[which])
+    close(q, q_ref, 1e-4, msg="q")
+    close(hl, hl_ref, 1e-4, msg="h_last")
+    q5, hl5 = run(0, 0, r6=0)
+    assert torch.equal(q, q5) and torch.equal(hl, hl5)
+
+
 @pytest.mark.parametrize("shape,B,T,cus", [("2s3z", 37, 5, 4), ("2s3z", 700, 6, 48), ("3s5z", 40, 4, 8), ("2s3z", 9, 2, 2),
                                             ("2s3z", 37, 5, 16), ("2s3z", 300, 7, 256), ("3s5z", 21, 4, 64),
                                             ("MMM2", 60, 4, 16), ("MMM2", 1000, 3, 256), ("MMM2", 30, 5, 128)])
-def test_double_q_unroll_reuses_input_side_work_bitwise(dev, shape, B, T, cus):
+def test_double_q_unroll_reuses_input_side_work_bitwise(dev, shape, B, T, cus, la=1, rn=1):
     """gi_out / gi_in (include/marl_hip.h): an unroll over steps 1..T of (T+1)-slot storage that READS the input-side gate sums
     an unroll over steps 0..T-1 stored == the same unroll computing everything, bit for bit - with ragged episode lengths
     (steps ep_len - 1 and T - 1 are computed in full), an episode map, a carried hidden state and a partial last row tile.
@@ -640,8 +738,9 @@ def test_double_q_unroll_reuses_input_side_work_bitwise(dev, shape, B, T, cus):
     tiles per workgroup are more rows than the prefetch registers of the reading launch cover (it fetches the rest when it
     refills the tile), and the launch it is compared with is the half-tile prefetch kernel."""
     from marl_amd import ops
-    args, p_np, _, _, _ = _agent_case(shape, B, T, dev)
+    args, p_np, _, _, _ = _agent_case(shape, B, T, dev, la=la, rn=rn)
     N, O, A = args.n_agents, args.obs_shape, args.n_actions
+    fl = _flags(args)
     assert ops.agent_unroll_reuse_supported(B, T, N, O, A, cus)
     rng = np.random.default_rng(B + T)
     E = B + 3                                                  # storage holds more episodes than the batch
@@ -658,15 +757,34 @@ def test_double_q_unroll_reuses_input_side_work_bitwise(dev, shape, B, T, cus):
     q0, h_last = torch.empty(B, T, N, A, device=dev), torch.empty(B * N, H, device=dev)
     # eval pass: slots 0..T-1, last action = the previous step's (u_t0 = -1), stores activations and gate sums
     ops.agent_unroll_fwd(w, store, (T + 1) * N, 0, u, T * N, -1, None, q0, None, h_last, saved, B, T, N, O, A,
-                         ep_len=ep_len, ep_map=emap, cu_budget=cus, gi_out=gi)
+                         ep_len=ep_len, ep_map=emap, cu_budget=cus, gi_out=gi, **fl)
     outs = []
     for reuse in (True, False):
         q, hl = torch.empty(B, T, N, A, device=dev), torch.empty(B * N, H, device=dev)
         ops.agent_unroll_fwd(w, store, (T + 1) * N, 1, u, T * N, 0, h_last, q, None, hl, None, B, T, N, O, A,
-                             ep_len=ep_len, ep_map=emap, cu_budget=cus, gi_in=gi if reuse else None)
+                             ep_len=ep_len, ep_map=emap, cu_budget=cus, gi_in=gi if reuse else None, **fl)
         outs.append((q.cpu(), hl.cpu()))
     assert torch.isfinite(outs[0][0]).all()
     assert torch.equal(outs[0][0], outs[1][0]) and torch.equal(outs[0][1], outs[1][1])
+    # ... and the continuation against the oracle (what the stored sums hold depends on the input row: the flags)
+    ep_obs, u_np = store.cpu().numpy()[emap.cpu().numpy()], u.cpu().numpy()
+    past = np.arange(T)[None, :] >= lens[:, None]                         # steps t >= ep_len feed zero observations
+    o_ev, o_ct = ep_obs[:, :T].copy(), ep_obs[:, 1:T + 1].copy()
+    o_ev[past], o_ct[past] = 0, 0
+    with torch.no_grad():
+        _, _, _, hl_ref = _oracle_unroll(args, p_np, o_ev, np.concatenate([np.full((B, 1, N), -1), u_np[:, :-1]], 1), None)
+        _, q_ref, _, _ = _oracle_unroll(args, p_np, o_ct, u_np, hl_ref.numpy())
+    close(h_last, hl_ref, 1e-4, msg="h_last of the storing launch")
+    close(outs[0][0], q_ref, 1e-4, msg="q of the reading launch")
+
+
+@pytest.mark.parametrize("la,rn", FLAGS_OFF, ids=FLAGS_OFF_IDS)
+@pytest.mark.parametrize("shape,B,T,cus", [("2s3z", 37, 5, 4), ("2s3z", 300, 7, 256), ("3s5z", 40, 4, 8), ("MMM2", 60, 4, 16),
+                                            ("MMM2", 1000, 3, 256)])
+def test_double_q_unroll_reuses_input_side_work_bitwise_flags(dev, shape, B, T, cus, la, rn):
+    """the same without the last action and / or the agent id: several row tiles per workgroup and one (the software-pipelined
+    kernel); the reading launch's q is also held to the oracle"""
+    test_double_q_unroll_reuses_input_side_work_bitwise(dev, shape, B, T, cus, la, rn)
 
 
 @pytest.mark.parametrize("shape,B,T,cus", [("2s3z", 37, 5, 4), ("2s3z", 300, 7, 16), ("3s5z", 40, 4, 8), ("MMM2", 60, 4, 16),
@@ -719,16 +837,17 @@ def test_saving_unroll_variants_equal_register_prefetch_bitwise(dev, shape, B, T
                                                        ("2s3z", 900, 9, False, True), ("2s3z", 2100, 12, True, True),
                                                        ("3s5z", 9, 5, True, True), ("3s5z", 600, 4, False, True),
                                                        ("MMM2", 5, 5, True, True), ("MMM2", 300, 4, False, True)])
-def test_agent_unroll_x6_split(dev, shape, B, T, with_h0, ragged):
+def test_agent_unroll_x6_split(dev, shape, B, T, with_h0, ragged, la=1, rn=1):
     """Unroll that saves nothing on the bf16x6 split kernels (csrc/agent_x6.hip, opt-in gemm_mode): q, hs and the final hidden state
     against the CPU oracle at the bound of test_agent_unroll_fwd (1e-4), and beside the fp32 MFMA kernel on the same inputs -
     (T+1)-slot storage read through an episode map with the shifted last action, ragged episode lengths (rows past their end
     feed zeros), a carried hidden state, partial last row tile, one and two row tiles per workgroup (> 256 tiles)."""
     from marl_amd import ops
     # (3s5z: 150 input columns = five fc1 chunks; MMM2: 204 = seven, and 18 actions = two action tiles; one row tile per workgroup)
-    args, p_np, _, _, _ = _agent_case(shape, B, T, dev, with_h0=with_h0)
+    args, p_np, _, _, _ = _agent_case(shape, B, T, dev, with_h0=with_h0, la=la, rn=rn)
     N, O, A = args.n_agents, args.obs_shape, args.n_actions
-    assert ops.agent_unroll_x6_supported(B, T, N, O, A)
+    fl = _flags(args)
+    assert ops.agent_unroll_x6_supported(B, T, N, O, A, **fl)
     rng = np.random.default_rng(B + T)
     E = B + 2
     store = rng.standard_normal((E, T + 1, N, O)).astype(np.float32)
@@ -745,9 +864,9 @@ def test_agent_unroll_x6_split(dev, shape, B, T, with_h0, ragged):
         q, hs, hl = torch.full((B, T, N, A), 9.0, device=dev), torch.full((B, T, N, 64), 9.0, device=dev), torch.full((B * N, 64), 9.0, device=dev)
         h0d = cu(h0, dev) if h0 is not None else None
         if mode == "x6":
-            ops.agent_unroll_fwd_x6(w, sd, (T + 1) * N, 1, ud, T * N, 0, h0d, q, hs, hl, None, B, T, N, O, A, ep_len=ld, ep_map=ed)
+            ops.agent_unroll_fwd_x6(w, sd, (T + 1) * N, 1, ud, T * N, 0, h0d, q, hs, hl, None, B, T, N, O, A, ep_len=ld, ep_map=ed, **fl)
         else:
-            ops.agent_unroll_fwd(w, sd, (T + 1) * N, 1, ud, T * N, 0, h0d, q, hs, hl, None, B, T, N, O, A, ep_len=ld, ep_map=ed)
+            ops.agent_unroll_fwd(w, sd, (T + 1) * N, 1, ud, T * N, 0, h0d, q, hs, hl, None, B, T, N, O, A, ep_len=ld, ep_map=ed, **fl)
         outs[mode] = (q.cpu(), hs.cpu(), hl.cpu())
     obs = store[emap][:, 1:T + 1].copy()
     for b in range(B):
@@ -761,6 +880,17 @@ def test_agent_unroll_x6_split(dev, shape, B, T, with_h0, ragged):
     e6 = float((outs["x6"][0].double() - q_ref.double()).abs().max())
     e32 = float((outs["f32"][0].double() - q_ref.double()).abs().max())
     print("agent unroll B=%d T=%d: max |q - oracle|: bf16x6 %.2e, fp32 MFMA %.2e" % (B, T, e6, e32))
+
+
+@pytest.mark.parametrize("la,rn", FLAGS_OFF, ids=FLAGS_OFF_IDS)
+@pytest.mark.parametrize("shape,B,T,with_h0,ragged", [("2s3z", 7, 5, False, False), ("2s3z", 2100, 12, True, True),
+                                                       ("3s5z", 9, 5, True, True), ("3s5z", 600, 4, False, True),
+                                                       ("MMM2", 5, 5, True, True), ("MMM2", 300, 4, False, True)])
+def test_agent_unroll_x6_split_flags(dev, shape, B, T, with_h0, ragged, la, rn):
+    """test_agent_unroll_x6_split without the last action and / or the agent id: 2s3z 85 / 91 / 80 input columns (three fc1 chunks),
+    3s5z 136 / 142 / 128 (five; four at 128), MMM2 186 / 194 / 176 (seven chunks, two action tiles); one and two row tiles per
+    workgroup"""
+    test_agent_unroll_x6_split(dev, shape, B, T, with_h0, ragged, la, rn)
 
 
 @pytest.mark.parametrize("shape,B,T,cus", [("2s3z", 37, 5, 0), ("2s3z", 700, 6, 48), ("2s3z", 9, 4, 2), ("2s3z", 300, 7, 256), ("2s3z", 1700, 5, 128),
@@ -851,16 +981,15 @@ def test_agent_unroll_bwd_from_x6_saved(dev, B, T):
                                                        ("2s3z", 333, 3, 2, True), ("2s3z", 13, 9, 1, True), ("2s3z", 900, 3, 1, False),
                                                        ("2s3z", 1003, 4, 2, True), ("MMM2", 30, 4, 1, False), ("MMM2", 450, 3, 2, True),
                                                        ("3s5z", 61, 5, 2, True)])
-def test_agent_unroll_bwd_x6_split(dev, shape, B, T, pairs, with_dhs):
+def test_agent_unroll_bwd_x6_split(dev, shape, B, T, pairs, with_dhs, la=1, rn=1):
     """BPTT on the bf16x6 split kernels (csrc/agent_bwd_x6.hip, opt-in gemm_mode): one or two sparse (action, value) pairs per row
     (the second pair with one value per (episode, step) shared by its agents, as QTRAN uses it), an optional external gradient on
     hs, one row tile per workgroup (up to 256 tiles) and two (beyond; row counts that leave the last workgroup with a partial or a
     missing second tile) - every gradient and dxp against
     torch autograd of the oracle unroll at the bounds of test_agent_unroll_bwd, beside the fp32 MFMA kernel on the same inputs."""
     from marl_amd import ops
-    args, p_np, obs, ufed, h0 = _agent_case(shape, B, T, dev, seed=3)
+    args, p_np, obs, ufed, h0 = _agent_case(shape, B, T, dev, seed=3, la=la, rn=rn)
     N, O, A = args.n_agents, args.obs_shape, args.n_actions      # (MMM2: 18 actions = two action tiles of the fc2 gradient)
-    I = O + A + N
     assert ops.agent_unroll_bwd_x6_supported(B, T, N, A)
     p, q_ref, hs_ref, _ = _oracle_unroll(args, p_np, obs, ufed, None, requires_grad=True)
     g = torch.Generator().manual_seed(5)
@@ -885,9 +1014,10 @@ def test_agent_unroll_bwd_x6_split(dev, shape, B, T, pairs, with_dhs):
     q, hs = torch.empty(B, T, N, A, device=dev), torch.empty(B, T, N, 64, device=dev)
     saved = torch.empty(ops.saved_shape(T, B, N), device=dev)
     obs_d, u_d = cu(obs, dev), cu(ufed, dev, torch.int32)
-    ops.agent_unroll_fwd(w, obs_d, T * N, 0, u_d, T * N, 0, None, q, hs, None, saved, B, T, N, O, A)
+    ops.agent_unroll_fwd(w, obs_d, T * N, 0, u_d, T * N, 0, None, q, hs, None, saved, B, T, N, O, A, **_flags(args))
     names = ("rnn.weight_ih", "rnn.weight_hh", "rnn.bias_ih", "rnn.bias_hh", "fc2.weight", "fc2.bias")
     M = B * T * N
+    fc1_in, I = _fc1_input(args, obs_d, u_d, M)
     out = {}
     for mode in ("x6", "f32"):
         grads = {k: torch.zeros_like(v) for k, v in pd.items()}
@@ -897,8 +1027,7 @@ def test_agent_unroll_bwd_x6_split(dev, shape, B, T, pairs, with_dhs):
                              B, T, N, A, dq_idx=cu(idx, dev, torch.int32), dq_val=cu(v1, dev),
                              dq_idx2=cu(idx2, dev, torch.int32) if idx2 is not None else None,
                              dq_val2=cu(v2, dev) if v2 is not None else None, dq_gdiv=gdiv, x6=(mode == "x6"))
-        ops.linear_wgrad(dxp.view(M, 64), ops.src(obs_d.view(M, O), idx=u_d.view(M, 1), nhot=1, hot_w=A, nid=N),
-                         grads["fc1.weight"], grads["fc1.bias"], M, 64, I)
+        ops.linear_wgrad(dxp.view(M, 64), fc1_in, grads["fc1.weight"], grads["fc1.bias"], M, 64, I)
         out[mode] = (grads, dxp, dh0)
         for k in p:
             ref = p[k].grad
@@ -910,15 +1039,23 @@ def test_agent_unroll_bwd_x6_split(dev, shape, B, T, pairs, with_dhs):
     print("BPTT B=%d T=%d: worst scaled gradient error vs autograd: bf16x6 %.2e, fp32 MFMA %.2e" % (B, T, worst["x6"], worst["f32"]))
 
 
+@pytest.mark.parametrize("la,rn", FLAGS_OFF, ids=FLAGS_OFF_IDS)
+@pytest.mark.parametrize("shape,B,T,pairs,with_dhs", [("2s3z", 7, 5, 1, False), ("2s3z", 1003, 4, 2, True), ("MMM2", 30, 4, 1, False),
+                                                       ("MMM2", 450, 3, 2, True), ("3s5z", 61, 5, 2, True)])
+def test_agent_unroll_bwd_x6_split_flags(dev, shape, B, T, pairs, with_dhs, la, rn):
+    """test_agent_unroll_bwd_x6_split without the last action and / or the agent id (the fc1 weight gradient's input rows built
+    as the learner builds them)"""
+    test_agent_unroll_bwd_x6_split(dev, shape, B, T, pairs, with_dhs, la, rn)
+
+
 @pytest.mark.parametrize("shape,B,T", [("2s3z", 7, 5), ("MMM2", 3, 3), ("matrix", 9, 1), ("2s3z", 40, 6), ("2s3z", 3300, 3)])
-def test_agent_unroll_bwd(dev, shape, B, T):
+def test_agent_unroll_bwd(dev, shape, B, T, la=1, rn=1):
     """BPTT delta kernel + wgrad reductions vs torch autograd of the oracle unroll.  Up to four row tiles per workgroup a
     sparse dq runs the one-barrier pipelined kernel and a dense one the two-phase kernel (compared with each other below);
     B = 3300 (16 500 rows = five row tiles per workgroup, the headline layout) runs the two-phase kernel for both."""
     from marl_amd import ops
-    args, p_np, obs, ufed, h0 = _agent_case(shape, B, T, dev, seed=1)
+    args, p_np, obs, ufed, h0 = _agent_case(shape, B, T, dev, seed=1, la=la, rn=rn)
     N, O, A = args.n_agents, args.obs_shape, args.n_actions
-    I = O + A + N
     p, q_ref, hs_ref, _ = _oracle_unroll(args, p_np, obs, ufed, None, requires_grad=True)
     g = torch.Generator().manual_seed(2)
     dq = torch.randn(B, T, N, A, generator=g)
@@ -931,7 +1068,8 @@ def test_agent_unroll_bwd(dev, shape, B, T):
     hs = torch.empty(B, T, N, 64, device=dev)
     saved = torch.empty(ops.saved_shape(T, B, N), device=dev)
     obs_d, u_d = cu(obs, dev), cu(ufed, dev, torch.int32)
-    ops.agent_unroll_fwd(w, obs_d, T * N, 0, u_d, T * N, 0, None, q, hs, None, saved, B, T, N, O, A)
+    ops.agent_unroll_fwd(w, obs_d, T * N, 0, u_d, T * N, 0, None, q, hs, None, saved, B, T, N, O, A, **_flags(args))
+    close(q, q_ref.detach(), 1e-4, msg="q")
     dxp = torch.empty(B, T, N, 64, device=dev)
     dq_d = cu(dq, dev)
     M = B * T * N
@@ -939,8 +1077,8 @@ def test_agent_unroll_bwd(dev, shape, B, T):
     ops.agent_unroll_bwd(w, dq_d, cu(dhs, dev), saved, hs, dxp, None,
                          {k: grads[k] for k in ("rnn.weight_ih", "rnn.weight_hh", "rnn.bias_ih", "rnn.bias_hh",
                                                 "fc2.weight", "fc2.bias")}, B, T, N, A)
-    ops.linear_wgrad(dxp.view(M, 64), ops.src(obs_d.view(M, O), idx=u_d.view(M, 1), nhot=1, hot_w=A, nid=N),
-                     grads["fc1.weight"], grads["fc1.bias"], M, 64, I)
+    fc1_in, I = _fc1_input(args, obs_d, u_d, M)
+    ops.linear_wgrad(dxp.view(M, 64), fc1_in, grads["fc1.weight"], grads["fc1.bias"], M, 64, I)
     for k in p:
         ref = p[k].grad
         scale = max(1.0, float(ref.abs().max()))
@@ -976,6 +1114,14 @@ def test_agent_unroll_bwd(dev, shape, B, T):
     close(dxd, dxc, 1e-6, 1e-5)
     for k in names:
         close(gd[k], gc[k], 1e-5, 1e-5, msg="two-pair sparse " + k)
+
+
+@pytest.mark.parametrize("la,rn", FLAGS_OFF, ids=FLAGS_OFF_IDS)
+@pytest.mark.parametrize("shape,B,T", [("2s3z", 7, 5), ("MMM2", 3, 3), ("matrix", 9, 1), ("2s3z", 3300, 3)])
+def test_agent_unroll_bwd_flags(dev, shape, B, T, la, rn):
+    """test_agent_unroll_bwd without the last action and / or the agent id: the saving unroll's planes and the fc1 weight gradient
+    over the input row the flags leave (one to five row tiles per workgroup)"""
+    test_agent_unroll_bwd(dev, shape, B, T, la, rn)
 
 
 # ------------------------------------------------------------------------------------- per-row

@@ -20,20 +20,22 @@ def _mac(args, scale=3.0):
 
 
 @pytest.mark.parametrize("eps,evaluate", [(0.0, True), (0.5, False), (1.0, False)])
-def test_batched_rollout_matches_oracle(eps, evaluate, gemm_mode):
+def test_batched_rollout_matches_oracle(eps, evaluate, gemm_mode, shape="2s3z", E=37, last_action=True):
     """(gemm_mode "bf16x6": the whole-rollout kernel is csrc/rollout_x6.hip - the agent step as split products; the per-step paths
     it is compared with run the fp32 kernels: the integer fields agree because no two available actions' Q values of these cases
     lie within rounding of each other)"""
     from marl_amd.rollout import RolloutWorker
     from marl_amd.env.synthetic_smac import SyntheticSMACEnv
     from marl_amd import ops
-    T, E = 8, 37
-    args = seeded.make_args("2s3z", "qmix", episode_limit=T, epsilon=eps, seed=77)
+    T = 8
+    args = seeded.make_args(shape, "qmix", episode_limit=T, epsilon=eps, seed=77, last_action=last_action)
     args.anneal_epsilon = 0.01
     args.gemm_mode = gemm_mode
-    assert ops.synth_rollout_x6_supported(5, 80, 11)
+    dims = (args.n_agents, args.obs_shape, args.state_shape, args.n_actions)
+    N, O, S, A = dims
+    assert ops.synth_rollout_x6_supported(N, O, A, last_action, True)
     mac, agent = _mac(args)
-    env = SyntheticSMACEnv(E, 5, 80, 120, 11, T, seed=5, env0=2)
+    env = SyntheticSMACEnv(E, *dims, T, seed=5, env0=2)
     w = RolloutWorker(env, mac, args)
     ep, rew, wins, steps = w.generate_episodes(E, evaluate=evaluate)
     # the whole-rollout kernel wrote the per-episode statistics itself (reward sums | won | length; compared with the
@@ -44,14 +46,14 @@ def test_batched_rollout_matches_oracle(eps, evaluate, gemm_mode):
     # three device paths, one record: whole-rollout persistent kernel (default), one fused env kernel per
     # lock-step, and the separate select / step / observe kernels
     for mode in ("fused_step", "unfused"):
-        w2 = RolloutWorker(SyntheticSMACEnv(E, 5, 80, 120, 11, T, seed=5, env0=2), mac, args)
+        w2 = RolloutWorker(SyntheticSMACEnv(E, *dims, T, seed=5, env0=2), mac, args)
         w2.rollout_mode = mode
         ep_u, _, _, steps_u = w2.generate_episodes(E, evaluate=evaluate)
         assert steps_u == steps, mode
         for f in ("obs", "state", "avail", "u", "r", "term", "padded", "length", "won"):
             assert torch.equal(getattr(ep.record, f), getattr(ep_u.record, f)), (mode, f)
         np.testing.assert_allclose(w2.epsilon, w.epsilon, rtol=1e-12)
-    sy = orl.SynthSMAC(5, 80, 120, 11, T, seed=5)
+    sy = orl.SynthSMAC(*dims, T, seed=5)
     oep, orew, owins, osteps, oeps = orl.batched_rollout(agent, args, sy, E, eps, evaluate=evaluate, rseed=77, env0=2)
     got = ep.numpy()
     for k in ("u", "padded", "terminated", "avail_u", "avail_u_next", "u_onehot"):
@@ -67,6 +69,18 @@ def test_batched_rollout_matches_oracle(eps, evaluate, gemm_mode):
                                                  rseed=77, env0=2, episode=1)
     assert steps2 == osteps2
     np.testing.assert_array_equal(ep2.numpy()["u"], oep2["u"])
+
+
+@pytest.mark.parametrize("shape,E,plan", [("2s3z", 37, 1), ("2s3z", 2048, 2), ("3s5z", 300, 1), ("MMM2", 37, 2)])
+@pytest.mark.parametrize("eps,evaluate", [(0.0, True), (0.5, False)])
+def test_batched_rollout_without_last_action_matches_oracle(eps, evaluate, shape, E, plan, gemm_mode):
+    """test_batched_rollout_matches_oracle with last_action=False (input row [obs | agent id]: 85 / 136 / 186 columns): the
+    whole-rollout kernel, fused_step and unfused give one record, equal to the oracle's; in bf16x6 mode 2s3z runs the round-5
+    decomposition at 37 envs and the round-6 one at 2048, MMM2 (seven fc1 chunks, two action tiles) the round-6 one"""
+    from marl_amd import ops
+    sh = seeded.SHAPES[shape]
+    assert ops.synth_rollout_x6_plan(E, sh["n_agents"], sh["obs_shape"], sh["n_actions"], last_action=False)[0] == plan
+    test_batched_rollout_matches_oracle(eps, evaluate, gemm_mode, shape, E, last_action=False)
 
 
 def test_serial_rollout_matches_reference_fixture(golden_dir):
@@ -320,7 +334,7 @@ def test_host_vector_env_matches_reference_greedy_fixture(golden_dir):
 
 @pytest.mark.parametrize("shape,E,T,eps", [("2s3z", 37, 8, 0.3), ("2s3z", 1024, 6, 0.5), ("2s3z", 2048, 5, 0.0), ("2s3z", 3000, 5, 1.0),
                                            ("2s3z", 4096, 7, 0.2), ("2s3z", 4500, 4, 0.2), ("3s5z", 300, 6, 0.4), ("3s5z", 2048, 5, 0.1)])
-def test_split_rollout_decompositions_agree_bitwise(shape, E, T, eps):
+def test_split_rollout_decompositions_agree_bitwise(shape, E, T, eps, last_action=True):
     """csrc/rollout_x6.hip (round 6: the recurrent team runs x W_ih and h W_hh down one accumulator chain, three barriers per lock-step,
     up to five row tiles per workgroup) against csrc/rollout_x6_v1.hip (round 5: gate sums handed over through LDS, four barriers,
     three tiles): the same additions in the same order, so every field of the record and the final hidden state agree BIT FOR BIT -
@@ -329,7 +343,7 @@ def test_split_rollout_decompositions_agree_bitwise(shape, E, T, eps):
     from marl_amd.env.synthetic_smac import SyntheticSMACEnv
     from marl_amd import experiments
     dims = {"2s3z": (5, 80, 120, 11), "3s5z": (8, 128, 216, 14)}[shape]
-    args = seeded.make_args(shape, "qmix", episode_limit=T, epsilon=eps, seed=31)
+    args = seeded.make_args(shape, "qmix", episode_limit=T, epsilon=eps, seed=31, last_action=last_action)
     args.anneal_epsilon = 0.02
     args.gemm_mode = "bf16x6"
     mac, _ = _mac(args)
@@ -349,9 +363,16 @@ def test_split_rollout_decompositions_agree_bitwise(shape, E, T, eps):
         assert int((ra.u >= 0).sum()) > 0
 
 
+@pytest.mark.parametrize("shape,E,T,eps", [("2s3z", 37, 8, 0.3), ("2s3z", 1024, 6, 0.5), ("2s3z", 4096, 7, 0.2), ("3s5z", 300, 6, 0.4),
+                                           ("3s5z", 2048, 5, 0.1)])
+def test_split_rollout_decompositions_agree_bitwise_without_last_action(shape, E, T, eps):
+    """the two split rollout decompositions with last_action=False (85 / 136 input columns): bit for bit"""
+    test_split_rollout_decompositions_agree_bitwise(shape, E, T, eps, last_action=False)
+
+
 @pytest.mark.parametrize("N,O,S,A,E,T", [(49, 40, 60, 5, 23, 6), (1, 8, 10, 3, 700, 5), (16, 64, 100, 16, 300, 5), (33, 100, 70, 5, 40, 4),
                                          (10, 176, 322, 18, 37, 6), (10, 176, 322, 18, 1024, 4), (4, 180, 50, 32, 300, 5), (7, 152, 64, 16, 200, 5)])
-def test_split_rollout_edge_shapes_match_the_per_step_path(N, O, S, A, E, T):
+def test_split_rollout_edge_shapes_match_the_per_step_path(N, O, S, A, E, T, last_action=True, x6=True):
     """shapes only the round-6 split rollout kernel covers in one launch (an environment of up to 64 agents across several row tiles;
     one-agent environments, 80 to a workgroup; 16 actions = a full DPP row; MMM2-sized agents: seven fc1 chunks and TWO action tiles -
     18 and 32 actions; 175 input columns and 16 actions): the whole-rollout record == the per-step kernels' record
@@ -360,8 +381,8 @@ def test_split_rollout_edge_shapes_match_the_per_step_path(N, O, S, A, E, T):
     from marl_amd.env.synthetic_smac import SyntheticSMACEnv
     from marl_amd import ops
     import types
-    assert ops.synth_rollout_x6_supported(N, O, A)
-    args = seeded.make_args("2s3z", "qmix", episode_limit=T, epsilon=0.4, seed=5)
+    assert ops.synth_rollout_x6_supported(N, O, A, last_action, True) == x6
+    args = seeded.make_args("2s3z", "qmix", episode_limit=T, epsilon=0.4, seed=5, last_action=last_action)
     args.n_agents, args.obs_shape, args.state_shape, args.n_actions = N, O, S, A
     args.anneal_epsilon = 0.03
     args.gemm_mode = "bf16x6"
@@ -378,3 +399,42 @@ def test_split_rollout_edge_shapes_match_the_per_step_path(N, O, S, A, E, T):
     oep, orew, owins, osteps, _ = orl.batched_rollout(agent, args, sy, E, 0.4, rseed=5, env0=1)
     np.testing.assert_array_equal(ep.numpy()["u"], oep["u"])
     assert steps == osteps
+
+
+@pytest.mark.parametrize("N,O,S,A,E,T,x6", [(49, 40, 60, 5, 23, 6, True), (16, 64, 100, 16, 300, 5, True), (10, 176, 322, 18, 37, 6, True),
+                                            (10, 176, 322, 18, 1024, 4, True), (4, 180, 50, 32, 300, 5, True), (7, 152, 64, 16, 200, 5, True),
+                                            (4, 140, 50, 20, 300, 5, False), (4, 140, 50, 20, 2048, 4, False)])
+def test_split_rollout_edge_shapes_without_last_action(N, O, S, A, E, T, x6):
+    """the edge shapes with last_action=False.  The input row is A columns narrower, which decides the fc1 chunk count and with it
+    whether more than 16 actions are covered: 4 agents, 140 observation columns and 20 actions make 144 columns - five chunks,
+    one action tile - so that batch is not the split kernel's (x6 False) and runs on the fp32 whole-rollout kernel, whose record
+    must still equal the per-step path's and the oracle's"""
+    test_split_rollout_edge_shapes_match_the_per_step_path(N, O, S, A, E, T, last_action=False, x6=x6)
+
+
+@pytest.mark.parametrize("tag,shape,E", [("2s3z", "2s3z", 6), ("MMM2", "MMM2", 4)])
+def test_rollouts_without_last_action_match_reference_fixture(tag, shape, E, golden_dir):
+    """the reference RolloutWorker's greedy record with last_action=False (tests/golden/rollout_nolast.npz) == the serial path
+    (SharedMAC.choose_action per agent on a serial env) and == the same environments stepped in lock-step through HostVectorEnv"""
+    from marl_amd.rollout import RolloutWorker
+    from marl_amd.env.host_vector import HostVectorEnv
+    fix = np.load(golden_dir + "/rollout_nolast.npz")
+    args = seeded.make_args(shape, "qmix", episode_limit=8, last_action=False)
+    args.epsilon = 0.0
+    mac, _ = _mac(args)
+    dims = (args.n_agents, args.obs_shape, args.state_shape, args.n_actions)
+    sy = orl.SynthSMAC(*dims, 8, seed=5)
+    w = RolloutWorker(orl.SerialSynthEnv(sy), mac, args)
+    np.random.seed(9)
+    ep, rew, wins, steps = w.generate_episodes(E, evaluate=True)
+    for k in ("u", "r", "padded", "terminated", "avail_u", "avail_u_next"):
+        np.testing.assert_allclose(np.asarray(ep[k], dtype=np.float64), fix["%s/%s" % (tag, k)], atol=1e-6, err_msg="serial " + k)
+    assert steps == int(fix["%s/steps" % tag]) and list(wins) == list(fix["%s/wins" % tag])
+    w = RolloutWorker(HostVectorEnv([orl.SerialSynthEnv(sy, env_id=i) for i in range(E)], seed=5), mac, args)
+    ep, rew, wins, steps = w.generate_episodes(E, evaluate=True)
+    got = ep.numpy()
+    for k in ("u", "r", "padded", "terminated", "avail_u", "avail_u_next"):
+        np.testing.assert_allclose(got[k], fix["%s/%s" % (tag, k)], atol=1e-6, err_msg="host vector " + k)
+    chk = seeded.checksum([got["o"], got["o_next"], got["s"], got["s_next"]])
+    np.testing.assert_allclose(chk, float(fix["%s/o_checksum" % tag]), rtol=1e-6)
+    assert steps == int(fix["%s/steps" % tag]) and list(wins) == list(fix["%s/wins" % tag])

@@ -45,9 +45,10 @@ def test_forward_pieces(case, golden_dir):
     N, H = args.n_agents, args.rnn_hidden_dim
     with torch.no_grad():
         h0 = torch.zeros(B * N, H)
-        q_cur, h_cur, h_last = nets.agent_unroll(st.agent, bt["o"], nets.shifted_onehot(bt["u_onehot"]), h0)
-        q_cont, _, _ = nets.agent_unroll(st.agent, bt["o_next"], bt["u_onehot"], h_last)
-        q_nxt, h_nxt, _ = nets.agent_unroll(st.agent, bt["o_next"], bt["u_onehot"], h0)
+        fl = (args.last_action, args.reuse_network)
+        q_cur, h_cur, h_last = nets.agent_unroll(st.agent, bt["o"], nets.shifted_onehot(bt["u_onehot"]), h0, *fl)
+        q_cont, _, _ = nets.agent_unroll(st.agent, bt["o_next"], bt["u_onehot"], h_last, *fl)
+        q_nxt, h_nxt, _ = nets.agent_unroll(st.agent, bt["o_next"], bt["u_onehot"], h0, *fl)
         tol = dict(atol=2e-5, rtol=1e-5)
         np.testing.assert_allclose(q_cur.numpy(), fix["fwd/q_cur"], **tol)
         np.testing.assert_allclose(h_cur.numpy(), fix["fwd/h_cur"], **tol)
@@ -139,6 +140,29 @@ def test_smac_shaped_rollout_matches_reference(golden_dir):
                            epb["s"].astype(np.float64), epb["s_next"].astype(np.float64)])
     np.testing.assert_allclose(chk, float(fix["smac_greedy/o_checksum"]), rtol=1e-9)
     assert stepsb == int(fix["smac_greedy/steps"])
+
+
+@pytest.mark.parametrize("tag,shape,E", [("2s3z", "2s3z", 6), ("MMM2", "MMM2", 4)])
+def test_smac_shaped_rollout_without_last_action_matches_reference(tag, shape, E, golden_dir):
+    """The greedy SMAC-shaped rollout with last_action=False (input row [obs | agent id]): serial and batched restatements vs the
+    reference RolloutWorker (tests/golden/make_golden.py:gen_rollout_nolast)."""
+    fix = np.load(os.path.join(golden_dir, "rollout_nolast.npz"))
+    args = seeded.make_args(shape, "qmix", episode_limit=8, last_action=False)
+    agent = seeded.seeded_state(seeded.agent_param_shapes(args), seed=11, scale=3.0)
+    assert agent["fc1.weight"].shape[1] == args.obs_shape + args.n_agents
+    sy = orl.SynthSMAC(args.n_agents, args.obs_shape, args.state_shape, args.n_actions, 8, seed=5)
+    np.random.seed(9)
+    args.epsilon = 0.0
+    ep, rew, wins, steps, _ = orl.serial_rollout(agent, args, orl.SerialSynthEnv(sy), E, 0.0, True)
+    epb, rewb, winsb, stepsb, _ = orl.batched_rollout(agent, args, sy, E, 0.0, evaluate=True)
+    for got in (ep, epb):
+        for k in ("u", "r", "padded", "terminated", "avail_u", "avail_u_next"):
+            np.testing.assert_allclose(np.asarray(got[k], dtype=np.float64), fix["%s/%s" % (tag, k)], atol=1e-6, err_msg=k)
+        chk = seeded.checksum([np.asarray(got[k], dtype=np.float64) for k in ("o", "o_next", "s", "s_next")])
+        np.testing.assert_allclose(chk, float(fix["%s/o_checksum" % tag]), rtol=1e-9)
+    assert steps == stepsb == int(fix["%s/steps" % tag])
+    assert list(wins) == list(fix["%s/wins" % tag])
+    np.testing.assert_allclose(rew, fix["%s/rewards" % tag], atol=1e-6)
 
 
 def test_max_episode_len_quirk_q2():
