@@ -260,7 +260,14 @@ __global__ void qplex_mix_fwd_kernel(const float* w_raw, const float* v, const f
           lam += kk * sigmoidf_(ag[(r * K + k) * N + i]) * sigmoidf_(ac[(r * K + k) * N + i]);
         }
         if (lam_out) lam_out[r * N + i] = lam;
-        at += (qt - mt) * (minus_one ? lam - 1.f : lam);
+        // the product is rounded before it is summed, as the tiled kernel does (it goes through LDS there): a fused
+        // multiply-add here would make a_tot differ from the tiled kernel's in the last bits
+        float ad;
+        {
+#pragma clang fp contract(off)
+          ad = (qt - mt) * (minus_one ? lam - 1.f : lam);
+        }
+        at += ad;
       }
     }
     if (v_tot) v_tot[r] = vt;
@@ -285,7 +292,11 @@ __global__ void qplex_mix_bwd_kernel(const float* w_raw, const float* q, const f
       dv[r * N + i] = weighted ? gr : 0.f;
       // a_tot path: only lambda gets gradient
       const float mi = max_q[r * N + i];
-      const float adv = weighted ? (w * qi - w * mi) : (qi - mi);
+      float adv;
+      {
+#pragma clang fp contract(off)   // both products rounded, as in the tiled kernel (no fused multiply-add)
+        adv = weighted ? (w * qi - w * mi) : (qi - mi);
+      }
       const float dlam = gr * adv;
       for (int k = 0; k < K; ++k) {
         const float kr = key[r * K + k];
@@ -304,7 +315,8 @@ __global__ void qplex_mix_bwd_kernel(const float* w_raw, const float* q, const f
 // whose key / agents / action head outputs are CONTIGUOUS blocks of QR*K and QR*K*N floats - they are copied
 // HBM <-> LDS with 16-byte coalesced accesses and all per-row arithmetic runs out of LDS.  (One thread per row read
 // them with a 200-byte lane stride: 0.9 ms forward / 1.75 ms backward at 491 520 rows, 14-28x the HBM time.)
-// Same operation order per row as the kernels above => bitwise identical results.
+// Same operation order per row as the kernels above, and the same rounding (no product is fused into the add that sums
+// it: the contract(off) blocks) => bitwise identical results (tests/test_gpu_kernels.py: test_qplex_mix_matrix).
 __device__ __forceinline__ void tile_in(float* dst, const float* src, long n_valid, long n_tile) {
   // n_tile floats of LDS; the first n_valid come from src (16-byte aligned, n_valid % 4 == 0 except in the last tile)
   const long n4 = n_valid >> 2;
@@ -392,7 +404,11 @@ __global__ __launch_bounds__(TPB) void qplex_mix_bwd_tiled_kernel(const float* w
       dw_raw[gi] = weighted ? gr * qi * (wr > 0.f ? 1.f : (wr < 0.f ? -1.f : 0.f)) : 0.f;
       dv[gi] = weighted ? gr : 0.f;
       const float mi = max_q[gi];
-      const float adv = weighted ? (w * qi - w * mi) : (qi - mi);
+      float adv;
+      {
+#pragma clang fp contract(off)   // as in the row-per-thread kernel
+        adv = weighted ? (w * qi - w * mi) : (qi - mi);
+      }
       dls[e] = gr * adv;
     }
     __syncthreads();

@@ -128,17 +128,29 @@ def _mlp3(p, prefix, x):
     return lin(p, prefix + ".4", x)
 
 
+def _lambda_net(p, prefix, x, layers):
+    """One DMAQ_SI_Weight extractor (network/mixer.py:116-139) of 1, 2 or 3 Linear layers with ReLU between."""
+    if layers == 1:
+        return lin(p, prefix, x)
+    if layers == 2:
+        return lin(p, prefix + ".2", torch.relu(lin(p, prefix + ".0", x)))
+    if layers == 3:
+        return _mlp3(p, prefix, x)
+    raise ValueError("adv_hypernet_layers must be 1, 2 or 3, got %r" % (layers,))
+
+
 def qplex_lambda(p, states, actions_onehot, args):
     """DMAQ_SI_Weight.forward (network/mixer.py:149-171): (rows,S),(rows,N*A) -> (rows,N)."""
     S, N, A = args.state_shape, args.n_agents, args.n_actions
     s = states.reshape(-1, S)
     a = actions_onehot.reshape(-1, N * A)
     sa = torch.cat([s, a], dim=1)
+    nl = args.adv_hypernet_layers
     lam = 0.0
     for k in range(args.num_kernel):
-        key = _mlp3(p, "si_weight.key_extractors.%d" % k, s)        # (rows,1)
-        ag = _mlp3(p, "si_weight.agents_extractors.%d" % k, s)      # (rows,N)
-        ac = _mlp3(p, "si_weight.action_extractors.%d" % k, sa)     # (rows,N)
+        key = _lambda_net(p, "si_weight.key_extractors.%d" % k, s, nl)      # (rows,1)
+        ag = _lambda_net(p, "si_weight.agents_extractors.%d" % k, s, nl)    # (rows,N)
+        ac = _lambda_net(p, "si_weight.action_extractors.%d" % k, sa, nl)   # (rows,N)
         lam = lam + (key.abs() + 1e-10) * torch.sigmoid(ag) * torch.sigmoid(ac)
     return lam
 

@@ -105,22 +105,31 @@ def qmix_param_shapes(args):
     return out
 
 
+def _lambda_net(prefix, in_f, embed, out_f, layers):
+    """One lambda-net extractor of DMAQ_SI_Weight (network/mixer.py:116-139): a bare Linear for 1 layer,
+    Sequential(Linear, ReLU, Linear) for 2, Sequential(Linear, ReLU, Linear, ReLU, Linear) for 3."""
+    if layers == 1:
+        return _lin(prefix, out_f, in_f)
+    if layers == 2:
+        return _lin(prefix + ".0", embed, in_f) + _lin(prefix + ".2", out_f, embed)
+    if layers == 3:
+        return _lin(prefix + ".0", embed, in_f) + _lin(prefix + ".2", embed, embed) + _lin(prefix + ".4", out_f, embed)
+    raise ValueError("adv_hypernet_layers must be 1, 2 or 3, got %r" % (layers,))
+
+
 def qplex_param_shapes(args):
-    """DMAQer + DMAQ_SI_Weight (network/mixer.py:85-147, 184-209), adv_hypernet_layers=3."""
+    """DMAQer + DMAQ_SI_Weight (network/mixer.py:85-147, 184-209), adv_hypernet_layers 1, 2 or 3."""
     S, N, A = args.state_shape, args.n_agents, args.n_actions
     HE, AE, K = args.hypernet_embed, args.adv_hypernet_embed, args.num_kernel
-    assert args.adv_hypernet_layers == 3
+    nl = args.adv_hypernet_layers
     out = _lin("hyper_w_final.0", HE, S) + _lin("hyper_w_final.2", N, HE)
     out += _lin("V.0", HE, S) + _lin("V.2", N, HE)
     for k in range(K):
-        p = "si_weight.key_extractors.%d" % k
-        out += _lin(p + ".0", AE, S) + _lin(p + ".2", AE, AE) + _lin(p + ".4", 1, AE)
+        out += _lambda_net("si_weight.key_extractors.%d" % k, S, AE, 1, nl)
     for k in range(K):
-        p = "si_weight.agents_extractors.%d" % k
-        out += _lin(p + ".0", AE, S) + _lin(p + ".2", AE, AE) + _lin(p + ".4", N, AE)
+        out += _lambda_net("si_weight.agents_extractors.%d" % k, S, AE, N, nl)
     for k in range(K):
-        p = "si_weight.action_extractors.%d" % k
-        out += _lin(p + ".0", AE, S + N * A) + _lin(p + ".2", AE, AE) + _lin(p + ".4", N, AE)
+        out += _lambda_net("si_weight.action_extractors.%d" % k, S + N * A, AE, N, nl)
     return out
 
 

@@ -6,7 +6,10 @@ Run in the build container only (the reference never travels):
 Writes small ``.npz`` fixtures next to this file.  Inputs and weights are NOT stored: they
 are regenerated from numpy PCG64 seeds by ``oracle/seeded.py`` (a checksum of them is
 stored to detect drift).  Large tensors (gradients, post-step parameters) are pinned by
-their per-tensor L2 norm, sum and a fixed strided sample (``seeded.sample_indices``).
+their per-tensor L2 norm and a fixed strided sample (``seeded.sample_indices``); gradients and parameters are pinned
+after the first two updates only, the ones the tests compare (test_oracle_golden.py, test_gpu_learners.py: steps 200 and
+201 are checked through the loss, the gradient norm and the target agent).  Fixtures written before that rule also carry
+a per-tensor sum and the later steps' pins, which nothing reads.
 """
 import os
 import sys
@@ -57,6 +60,12 @@ CASES = [
     ("qmix_MMM2_nolast", "MMM2", "qmix", 3, 5, [5, 3, 4], {"last_action": False}),
     ("qtran_3s5z_nolast", "3s5z", "qtran_base", 3, 5, [5, 2, -1], {"last_action": False}),
     ("qmix_2s3z_nolast", "2s3z", "qmix", 3, 5, [5, -1, 3], {"last_action": False}),
+    # QPLEX's own switches (mixer.py:116-139, 243-246, 275-282): 1- and 2-layer lambda-nets on the grouped marl_linear
+    # composition, the lambda form of the advantage mix, and no transformation net
+    ("qplex_2s3z_nl1", "2s3z", "qplex", 3, 4, [4, 2, -1], {"adv_hypernet_layers": 1}),
+    ("qplex_3s5z_nl2_lam", "3s5z", "qplex", 3, 4, [-1, 4, 2], {"adv_hypernet_layers": 2, "is_minus_one": False}),
+    ("qplex_2s3z_noweight", "2s3z", "qplex", 3, 4, [4, 3, -1], {"weighted_head": False}),
+    ("qplex_MMM2_nl1", "MMM2", "qplex", 3, 4, [4, 2, 3], {"adv_hypernet_layers": 1}),
 ]
 TRAIN_STEPS = [0, 1, 200, 201]   # 200 crosses the target-sync boundary (quirk Q6)
 
@@ -66,14 +75,13 @@ def load(module, state):
 
 
 def pin(prefix, named, out):
-    """norm / sum / strided sample per tensor."""
+    """norm / strided sample per tensor."""
     for name, t in named:
         if t is None:
             out["%s/%s/none" % (prefix, name)] = np.array(1)
             continue
         a = t.detach().cpu().numpy().astype(np.float64).ravel()
         out["%s/%s/norm" % (prefix, name)] = np.array(np.sqrt((a * a).sum()))
-        out["%s/%s/sum" % (prefix, name)] = np.array(a.sum())
         out["%s/%s/samp" % (prefix, name)] = a[seeded.sample_indices(a.size)].astype(np.float32)
 
 
@@ -152,9 +160,10 @@ def gen_learner_case(case):
             losses.append(learner.train(b, ts))
             names = [n for n, _ in named_params(learner)]
             assert len(names) == len(captured["grads"])
-            pin("step%d/grad" % i, list(zip(names, captured["grads"])), out)
+            if i <= 1:
+                pin("step%d/grad" % i, list(zip(names, captured["grads"])), out)
+                pin("step%d/param" % i, named_params(learner), out)
             out["step%d/grad_norm" % i] = np.array(float(captured["norm"]))
-            pin("step%d/param" % i, named_params(learner), out)
             pin("step%d/target_agent" % i, [("agent." + k, p) for k, p in learner.target_net.agent.named_parameters()], out)
         out["losses"] = np.array(losses, dtype=np.float64)
         out["meta/T_used"] = np.array(learner.max_episode_len)

@@ -24,6 +24,12 @@ CASES = [
     ("qmix_MMM2_nolast", "MMM2", "qmix", 3, 5, [5, 3, 4], {"last_action": False}),
     ("qtran_3s5z_nolast", "3s5z", "qtran_base", 3, 5, [5, 2, -1], {"last_action": False}),
     ("qmix_2s3z_nolast", "2s3z", "qmix", 3, 5, [5, -1, 3], {"last_action": False}),
+    # QPLEX's own switches (mixer.py:116-139, 243-246, 275-282): 1- and 2-layer lambda-nets on the grouped marl_linear
+    # composition, the lambda form of the advantage mix, and no transformation net
+    ("qplex_2s3z_nl1", "2s3z", "qplex", 3, 4, [4, 2, -1], {"adv_hypernet_layers": 1}),
+    ("qplex_3s5z_nl2_lam", "3s5z", "qplex", 3, 4, [-1, 4, 2], {"adv_hypernet_layers": 2, "is_minus_one": False}),
+    ("qplex_2s3z_noweight", "2s3z", "qplex", 3, 4, [4, 3, -1], {"weighted_head": False}),
+    ("qplex_MMM2_nl1", "MMM2", "qplex", 3, 4, [4, 2, 3], {"adv_hypernet_layers": 1}),
 ]
 TRAIN_STEPS = [0, 1, 200, 201]
 

@@ -456,3 +456,47 @@ def test_qmix_2s3z_2048_without_last_action_shard(gemm_mode, monkeypatch):
     # (c)
     _linearity(learner, rec, Tm, E2, 2, name)
     _sub_batch_vs_oracle(case, args, learner, rec, idx, Tm, name)
+
+
+def _qplex_composition_case(shape, over, envs, T_, seed, name, gemm_mode):
+    """A QPLEX shard whose lambda-nets are not three layers deep (adv_hypernet_layers 1 or 2, mixer.py:116-131): the thirty
+    extractors run on the grouped marl_linear / marl_linear_wgrad composition (DMAQer._lambda_fwd / hip_backward) - asserted
+    first - at a size that reaches its large-M GEMM and weight-gradient paths (the golden cases have about 20 rows).  Shard
+    linearity, then the sampled sub-batch's forward, loss and EVERY gradient against the CPU oracle."""
+    from marl_amd import ops
+    from marl_amd.hostutil import DeviceBatch
+    name = "%s[%s]" % (name, gemm_mode)
+    case, args, learner, rec = _shard_world(shape, "qplex", envs, T_, seed=seed, over=over, gemm_mode=gemm_mode)
+    for k, v in over.items():
+        assert getattr(args, k) == v, k
+    assert int(rec.padded.sum().item()) > 0, "ragged episodes wanted"
+    Tm = DeviceBatch.first_terminated_len(rec.term, args.episode_limit)
+    mx = learner.mixer
+    rows = envs * Tm
+    s = DeviceBatch.from_record(rec, args, T=Tm).s
+    xs = ops.src(s)
+    xsa = ops.src(s, idx=torch.zeros(rows, args.n_agents, dtype=torch.int32, device=rec.obs.device), nhot=args.n_agents,
+                  hot_w=args.n_actions)
+    from marl_amd.network.mixer import _linears
+    for fname, mods, nout in mx.si_weight.families():
+        assert len(mods) == args.num_kernel and len(_linears(mods[0])) == args.adv_hypernet_layers, fname
+        assert mx._fused_family(mods, xsa if fname == "ac" else xs, nout) is None, fname
+    idx = [0, 1, envs // 2 - 1, envs // 2, envs - 100, envs - 1]
+    _linearity(learner, rec, Tm, envs, 2, name)
+    _sub_batch_vs_oracle(case, args, learner, rec, idx, Tm, name)
+
+
+@pytest.mark.parametrize("gemm_mode", MODES)
+def test_qplex_2s3z_one_layer_lambda_nets_shard(gemm_mode):
+    """QPLEX on 2s3z with adv_hypernet_layers = 1 at 512 envs x T = 120: every extractor is one Linear - 1-column key heads,
+    5-column agents / action heads, and the [state | one-hot actions] source (175 columns) feeding the output layer directly."""
+    _qplex_composition_case("2s3z", {"adv_hypernet_layers": 1}, 512, 120, 47, "full:qplex_2s3z_nl1_512x120", gemm_mode)
+
+
+@pytest.mark.parametrize("gemm_mode", MODES)
+def test_qplex_3s5z_two_layer_lambda_nets_no_transform_shard(gemm_mode):
+    """QPLEX on 3s5z with adv_hypernet_layers = 2, weighted_head = False and is_minus_one = False at 512 envs x T = 120: the
+    Linear-ReLU-Linear extractors (the backward's ReLU gate on the one hidden layer), no transformation net (hyper_w_final
+    and V must get exactly zero gradient: the reference's None) and the lambda form of the advantage mix."""
+    _qplex_composition_case("3s5z", {"adv_hypernet_layers": 2, "weighted_head": False, "is_minus_one": False}, 512, 120, 53,
+                            "full:qplex_3s5z_nl2_noweight_lam_512x120", gemm_mode)

@@ -1296,6 +1296,163 @@ def test_qplex_mix(dev):
         close(o, ref.grad, 1e-4)
 
 
+def _qplex_qr(N, K):
+    """rows per workgroup of the tiled duplex mixing kernels for 16-byte aligned head operands (csrc/mixers.hip:
+    qplex_tile_rows); 0 = the row-per-thread kernels"""
+    for qr in (128, 64, 32):
+        if qr * (2 * K * N + K + 2 * N) * 4 <= 64 * 1024:
+            return qr
+    return 0
+
+
+def _qplex_mix_inputs(R, N, K, seed, edges=True):
+    """w_raw, v, q, max_q, key, ag, ac, g (float64).  With ``edges``: exact zeros in w_raw and key (sign(0) = 0 in the
+    gradients) and agents / action head outputs at +-40 and +-100 (saturated sigmoids)."""
+    g = torch.Generator().manual_seed(seed)
+    w_raw, v, q = (torch.randn(R, N, generator=g, dtype=torch.float64) for _ in range(3))
+    mx = q + torch.rand(R, N, generator=g, dtype=torch.float64)
+    key = torch.randn(R, K, generator=g, dtype=torch.float64)
+    ag, ac = (torch.randn(R, K, N, generator=g, dtype=torch.float64) for _ in range(2))
+    gq = torch.randn(R, generator=g, dtype=torch.float64)
+    if edges:
+        w_raw[torch.rand(R, N, generator=g) < 0.15] = 0.0
+        key[torch.rand(R, K, generator=g) < 0.15] = 0.0
+        sat = torch.tensor([40.0, -40.0, 100.0, -100.0], dtype=torch.float64)
+        for t in (ag, ac):
+            m = torch.rand(R, K, N, generator=g) < 0.2
+            t[m] = sat[torch.randint(0, 4, (int(m.sum()),), generator=g)]
+    # the fp32 values the kernels see, so that the reference starts from the same numbers
+    return [x.float().double() for x in (w_raw, v, q, mx, key, ag, ac, gq)]
+
+
+def _qplex_mix_reference(ins, weighted, minus_one, is_v=False):
+    """DMAQer.forward's mixing arithmetic (reference network/mixer.py:226-288) in float64 autograd, adv detached
+    (mixer.py:237).  Returns v_tot, a_tot, lambda and the six gradients of (v_tot + a_tot) . g; a parameter that does not
+    take part (w_raw / v with weighted_head off) gets an all-zero gradient (the reference's None)."""
+    w_raw, v, q, mx, key, ag, ac, gq = (x.clone().requires_grad_(True) for x in ins)
+    w = w_raw.abs() + 1e-10
+    qt = w * q + v if weighted else q
+    mt = w * mx + v if weighted else mx
+    lam = ((key.abs() + 1e-10).unsqueeze(2) * torch.sigmoid(ag) * torch.sigmoid(ac)).sum(1)
+    v_tot = qt.sum(1)
+    a_tot = ((qt - mt).detach() * ((lam - 1.0) if minus_one else lam)).sum(1)
+    srcs = (q, w_raw, v, key, ag, ac)
+    gs = torch.autograd.grad(((v_tot + a_tot) * gq.detach()).sum(), srcs, allow_unused=True)
+    grads = [torch.zeros_like(x) if gi is None else gi for x, gi in zip(srcs, gs)]
+    return v_tot.detach(), a_tot.detach(), lam.detach(), grads
+
+
+def _dev_buffers(dev, shapes, off, fill=None):
+    """one device tensor per shape, each starting ``off`` floats past a 256-byte boundary (off = 1: 4 bytes off the
+    16-byte grid)"""
+    out = []
+    for shp in shapes:
+        n = int(np.prod(shp))
+        base = torch.empty(n + 64, device=dev)
+        assert base.data_ptr() % 256 == 0
+        t = base[off:off + n].view(*shp)
+        if fill is not None:
+            t.fill_(fill)
+        out.append(t)
+    return out
+
+
+def _qplex_mix_run(dev, ins, R, N, K, weighted, minus_one, off):
+    """forward (v_tot, a_tot, lambda) and backward (dq, dw_raw, dv, dkey, dag, dac) of the duplex mixing kernels with every
+    operand ``off`` floats past an aligned address; outputs start as NaN so that an unwritten entry cannot pass"""
+    from marl_amd import ops
+    shapes = [(R, N), (R, N), (R, N), (R, N), (R, K), (R, K, N), (R, K, N), (R,)]
+    dins = _dev_buffers(dev, shapes, off)
+    for d, x in zip(dins, ins):
+        d.copy_(x.float().to(dev))
+    w_raw, v, q, mx, key, ag, ac, gq = dins
+    vt, at, lo = _dev_buffers(dev, [(R,), (R,), (R, N)], off, fill=float("nan"))
+    ops.qplex_mix_fwd(w_raw, v, q, mx, key, ag, ac, vt, at, lo, R, N, K, weighted, minus_one)
+    outs = _dev_buffers(dev, [(R, N), (R, N), (R, N), (R, K), (R, K, N), (R, K, N)], off, fill=float("nan"))
+    ops.qplex_mix_bwd(w_raw, q, mx, key, ag, ac, gq, *outs, R, N, K, weighted, minus_one)
+    torch.cuda.synchronize()
+    return [t.cpu() for t in (vt, at, lo)], [t.cpu() for t in outs]
+
+
+FLAGS = [(1, 1), (1, 0), (0, 1), (0, 0)]       # (weighted_head, is_minus_one)
+
+
+def _check_qplex_mix(dev, R, N, K, seed, atol=1e-4):
+    ins = _qplex_mix_inputs(R, N, K, seed)
+    w_raw, key = ins[0], ins[4]
+    bwd = {}
+    for weighted, minus_one in FLAGS:
+        tag = "R=%d N=%d K=%d weighted=%d minus_one=%d" % (R, N, K, weighted, minus_one)
+        v_tot, a_tot, lam, grads = _qplex_mix_reference(ins, weighted, minus_one)
+        fwd, gout = _qplex_mix_run(dev, ins, R, N, K, weighted, minus_one, off=0)
+        for o, ref, nm in zip(fwd, (v_tot, a_tot, lam), ("v_tot", "a_tot", "lambda")):
+            close(o, ref, atol, msg="%s %s" % (tag, nm))
+        for o, ref, nm in zip(gout, grads, ("dq", "dw_raw", "dv", "dkey", "dag", "dac")):
+            close(o, ref, atol, msg="%s %s" % (tag, nm))
+        dq, dw, dv, dkey = gout[:4]
+        # sign(0) = 0: a zero w_raw / key takes no gradient through |.|
+        assert torch.all(dw[w_raw == 0] == 0) and torch.all(dkey[key == 0] == 0), tag
+        if not weighted:
+            assert torch.all(dw == 0) and torch.all(dv == 0), tag
+        # every operand 4 bytes off the 16-byte grid: the row-per-thread kernels, bit for bit the tiled kernels' results
+        fwd_u, gout_u = _qplex_mix_run(dev, ins, R, N, K, weighted, minus_one, off=1)
+        for a, b, nm in zip(fwd + gout, fwd_u + gout_u, ("v_tot", "a_tot", "lambda", "dq", "dw_raw", "dv", "dkey", "dag", "dac")):
+            assert torch.equal(a, b), "%s %s: unaligned (row kernel) != aligned" % (tag, nm)
+        bwd[(weighted, minus_one)] = gout
+    for weighted in (0, 1):     # the backward does not depend on the advantage form: d a_tot / d lambda = adv either way
+        for a, b in zip(bwd[(weighted, 1)], bwd[(weighted, 0)]):
+            assert torch.equal(a, b), "backward depends on minus_one (weighted=%d)" % weighted
+
+
+@pytest.mark.parametrize("N,K", [(5, 10), (10, 10), (20, 10), (25, 10), (1, 1)],
+                         ids=["qr128", "qr64", "qr32", "rowkernel", "n1k1"])
+@pytest.mark.parametrize("which", ["1", "qr-1", "qr", "qr+1", "257"])
+def test_qplex_mix_matrix(dev, N, K, which):
+    """The duplex mixing kernels (csrc/mixers.hip: qplex_mix_fwd / bwd, tiled and row-per-thread) at every switch and
+    tiling: weighted_head x is_minus_one, tilings QR = 128 / 64 / 32 and the row kernel (N = 25 at K = 10), row counts
+    around one tile.  Inputs carry exact zeros in w_raw and key and saturated sigmoid arguments.  Against float64
+    autograd of the reference formula; the unaligned launch (row kernels) must equal the aligned one bit for bit, and
+    the backward must not depend on is_minus_one."""
+    qr = _qplex_qr(N, K)
+    assert qr == {(5, 10): 128, (10, 10): 64, (20, 10): 32, (25, 10): 0, (1, 1): 128}[(N, K)]
+    q = qr or 32
+    R = {"1": 1, "qr-1": q - 1, "qr": q, "qr+1": q + 1, "257": 257}[which]
+    _check_qplex_mix(dev, R, N, K, seed=1000 * N + 10 * K + R)
+
+
+def test_qplex_mix_grid_stride(dev):
+    """more rows than 4096 workgroups of QR rows cover: the tiled kernels' grid-stride loop runs a second pass (and the
+    row kernels theirs), N = 2, K = 3 (QR = 128)"""
+    N, K = 2, 3
+    assert _qplex_qr(N, K) == 128
+    R = 4096 * 128 + 333
+    _check_qplex_mix(dev, R, N, K, seed=77)
+
+
+@pytest.mark.parametrize("N,K", [(5, 10), (25, 10), (1, 1)])
+def test_qplex_mix_is_v_forward(dev, N, K):
+    """the is_v call (DMAQer.forward with is_v=True, mixer.py:283-285): max_q = NULL, no heads.  v_tot is right for both
+    weighted_head settings, and neither a_tot nor lambda is written even when their buffers are passed."""
+    from marl_amd import ops
+    for R in (1, 257, 4096 * 64 + 5):
+        ins = _qplex_mix_inputs(R, N, 1, seed=R + N)       # (the heads are not read: one per row keeps the host side small)
+        for weighted in (0, 1):
+            w_, v_, q_ = ins[:3]
+            v_tot = ((w_.abs() + 1e-10) * q_ + v_ if weighted else q_).sum(1)
+            for off in (0, 1):
+                w_raw, v, q = _dev_buffers(dev, [(R, N)] * 3, off)
+                for d, x in zip((w_raw, v, q), ins[:3]):
+                    d.copy_(x.float().to(dev))
+                vt = _dev_buffers(dev, [(R,)], off, fill=float("nan"))[0]
+                at, lo = _dev_buffers(dev, [(R,), (R, N)], off, fill=7.0)
+                ops.qplex_mix_fwd(w_raw, v, q, None, None, None, None, vt, None, None, R, N, K, weighted, 1)
+                close(vt, v_tot, 1e-4, msg="R=%d weighted=%d off=%d" % (R, weighted, off))
+                vt2 = _dev_buffers(dev, [(R,)], off, fill=float("nan"))[0]
+                ops.qplex_mix_fwd(w_raw, v, q, None, None, None, None, vt2, at, lo, R, N, K, weighted, 1)
+                assert torch.equal(vt.cpu(), vt2.cpu())
+                assert torch.all(at == 7.0) and torch.all(lo == 7.0), "is_v forward wrote a_tot / lambda"
+
+
 def test_losses_and_optimizer(dev):
     from marl_amd import ops
     g = torch.Generator().manual_seed(8)

@@ -175,6 +175,31 @@ def test_state_dicts_match_reference_checkpoints(golden_dir):
     assert checked >= 20
 
 
+def test_qplex_state_dict_names_for_every_lambda_net_depth():
+    """DMAQer's checkpoint names and shapes (in order) equal seeded.qplex_param_shapes - the table the golden generator
+    loads strictly into the reference's modules - for adv_hypernet_layers 1, 2 and 3 (mixer.py:116-139: a bare Linear,
+    Linear-ReLU-Linear, three Linears), on a map whose state width is a multiple of 4 and on one whose is not.  Any other
+    depth raises in both, as the reference does."""
+    import pytest
+    from marl_amd.network.mixer import DMAQer
+    for shape in ("2s3z", "MMM2"):
+        for nl in (1, 2, 3):
+            args = seeded.make_args(shape, "qplex", adv_hypernet_layers=nl)
+            got = [(k, tuple(v.shape)) for k, v in DMAQer(args).state_dict().items()]
+            want = seeded.qplex_param_shapes(args)
+            assert got == want, (shape, nl)
+            K, N = args.num_kernel, args.n_agents
+            assert len(want) == 8 + 3 * K * 2 * nl
+            last = "" if nl == 1 else ".%d" % (2 * (nl - 1))
+            assert dict(want)["si_weight.key_extractors.0%s.weight" % last] == (1, args.state_shape if nl == 1 else 64)
+            assert dict(want)["si_weight.action_extractors.%d%s.bias" % (K - 1, last)] == (N,)
+        args = seeded.make_args(shape, "qplex", adv_hypernet_layers=4)
+        with pytest.raises(Exception):
+            DMAQer(args)
+        with pytest.raises(ValueError):
+            seeded.qplex_param_shapes(args)
+
+
 def test_launcher_vectorises_an_importable_smac(tmp_path, monkeypatch):
     """`python -m marl_amd.dropin` with a real `smac` on the path: MARL_N_ENVS > 1 swaps smac.env.StarCraft2Env for a
     factory of HostVectorEnv over that many real environments (not called here - it needs the GPU); <= 1 leaves it alone."""

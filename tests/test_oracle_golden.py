@@ -19,7 +19,7 @@ def _pinned(fix, prefix):
 
 
 def check_pins(fix, prefix, named, atol, rtol):
-    """Compare tensors against norm/sum/sample pins written by make_golden.pin()."""
+    """Compare tensors against the norm / sample pins written by make_golden.pin()."""
     names = _pinned(fix, prefix)
     assert names, prefix
     got = dict(named)
