@@ -233,8 +233,8 @@ int marl_qmix_fused_loss_bwd_x6(const marl_qmix_weights_t* w, const marl_src_t* 
  * last chunk) and multiply them by packed weights that are exactly zero, so these pad columns must hold FINITE values (0 * NaN
  * would poison q_tot); EpisodeRecord zero-initialises them, a caller with its own buffers must do the same.
  * marl_qmix_wide_fwd_kernel(): the name prefix (rocprofv3 kernel trace) of the forward kernel a call with this shape launches -
- * "qmix_wide_kernel<false" (streaming), "qmix_wide_res_fwd_kernel" (bf16, weights resident in LDS: preceded by the pack kernel and
- * a memset of q_tot) or "qmix_wide_res32_fwd_kernel". */
+ * "qmix_wide_kernel<false" (streaming) or "qmix_wide_res_fwd_kernel" (bf16, weights resident in LDS: preceded by the pack kernel and
+ * a memset of q_tot). */
 int marl_qmix_wide_supported(int N, int S, int E);
 const char* marl_qmix_wide_fwd_kernel(long rows, int N, int S, int flags);
 size_t marl_qmix_wide_workspace(long rows, int N, int S, int backward);
@@ -530,9 +530,10 @@ const char* marl_hip_version(void);
 
 /* Experiment switches (A/B measurements, variant tests): one table per process; NO entry point reads the environment.
  * Names and defaults: "fwd_xs" 1 (the double-Q unroll reads the eval unroll's input-side gate sums - replaces the work
- * q_learner.py:110 repeats), "fwd_dma" 0 (LDS-DMA observation tile of the saving unroll), "fwd_w2l" 1 (six prefetch registers for
- * wide observations), "bwd_pipe_max_rt" 4 (row tiles per workgroup up to which the one-barrier BPTT runs), "wgrad_tall" 1 (LDS-staged
- * tall weight-gradient kernel), "wide_res" 1 / "wide_res32" 0 (resident-weights forward of the wide-state QMIX mixer, mixer.py:57-80).
+ * q_learner.py:110 repeats), "fwd_w2l" 1 (six prefetch registers for wide observations), "bwd_pipe_max_rt" 4 (row tiles per
+ * workgroup up to which the one-barrier BPTT runs), "wgrad_tall" 1 (LDS-staged tall weight-gradient kernel), "wide_res" 1
+ * (resident-weights forward of the wide-state QMIX mixer, mixer.py:57-80), "rollout_v1" 0 / "unroll_r6" 1 (split rollout and
+ * unroll kernel choice, common.h: MarlSwitches).
  * Results do not depend on them beyond fp32 summation order.  set: 0, or -1 for an unknown name; get: the value, or INT_MIN.
  * marl_amd/experiments.py forwards the MARL_* environment variables of the same names once, at import. */
 int marl_experiment_set(const char* name, int value);

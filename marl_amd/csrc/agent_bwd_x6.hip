@@ -53,8 +53,6 @@ struct BX6Args {
 
 __host__ __device__ inline long slab_floats(int A) { return 2L * 192 * 64 + (long)A * 64 + 2 * 192 + A; }
 
-#define WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-#define X6_TERMS(OP) OP(m, m) OP(h, l) OP(l, h) OP(h, m) OP(m, h) OP(h, h)
 // two split multiplies (A0 B0, A1 B1) on four accumulators: the small products on c0 / c1, the large ones on c2 / c3
 #define X6_TERMS4(A0, B0, A1, B1, c0, c1, c2, c3)                                                                   \
   c0 = mm(A0.m, B0.m, c0); c1 = mm(A1.m, B1.m, c1); c2 = mm(A0.h, B0.m, c2); c3 = mm(A1.h, B1.m, c3);               \
@@ -62,7 +60,6 @@ __host__ __device__ inline long slab_floats(int A) { return 2L * 192 * 64 + (lon
   c0 = mm(A0.l, B0.h, c0); c1 = mm(A1.l, B1.h, c1); c2 = mm(A0.h, B0.h, c2); c3 = mm(A1.h, B1.h, c3);
 
 __device__ __forceinline__ long sv_off(long tile_t, int plane, int c, int lane) { return ((tile_t * 6 + plane) * 4 + c) * 256 + lane * 4; }
-__device__ __forceinline__ f32x4 splat(float v) { return (f32x4){v, v, v, v}; }
 
 // B fragment of W^T for  out[row][unit] = sum_k G[row][k] W[k][unit]:  lane (g, j): W[32 c + 8g + (0..7)][u0 + j]  (W: [192][64])
 __device__ __forceinline__ F3 wTfrag(const float* W, int c, int u0, int lane) {

@@ -5,17 +5,20 @@
 
 #define MARL_WAVE 64
 
+// workgroup barrier that only drains LDS traffic: global stores (saved activations) and the
+// prefetch loads stay in flight across it (a __syncthreads() would wait vmcnt(0) every time)
+#define WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
+
 // Experiment switches (A/B measurements and variant tests): ONE table per process, set through marl_experiment_set() (optim.hip;
 // marl_amd/experiments.py reads the MARL_* environment once at import and forwards it).  No launch path reads the environment.
-//   fwd_xs (1): the double-Q unroll reads the eval unroll's input-side gate sums;  fwd_dma (0): LDS-DMA observation tile of the
-//   saving unroll;  fwd_w2l (1): six prefetch registers / fc2 fragments in LDS for wide observations;  bwd_pipe_max_rt (4): row
-//   tiles up to which the pipelined BPTT runs;  wgrad_tall (1): LDS-staged tall weight-gradient kernel;  wide_res (1) / wide_res32
-//   (0): resident-weights forward of the wide-state QMIX mixer (16- / 32-row tiles);  rollout_v1 (0 = by batch size): 1 forces the split
+//   fwd_xs (1): the double-Q unroll reads the eval unroll's input-side gate sums;  fwd_w2l (1): six prefetch registers / fc2
+//   fragments in LDS for wide observations;  bwd_pipe_max_rt (4): row tiles up to which the pipelined BPTT runs;  wgrad_tall (1):
+//   LDS-staged tall weight-gradient kernel;  wide_res (1): resident-weights forward of the wide-state QMIX mixer;  rollout_v1 (0 = by batch size): 1 forces the split
 //   whole-rollout kernel of round 5 (rollout_x6_v1.hip: four barriers per lock-step, at most three row tiles per workgroup), 2 the one
 //   of round 6 (rollout_x6.hip: three barriers, up to five tiles);  unroll_r6 (1): non-saving split unrolls of large batches on
 //   agent_x6p.hip (the round-6 decomposition: five row tiles per workgroup, two barriers per step)
 struct MarlSwitches {
-  int fwd_xs, fwd_dma, fwd_w2l, bwd_pipe_max_rt, wgrad_tall, wide_res, wide_res32, rollout_v1, unroll_r6;
+  int fwd_xs, fwd_w2l, bwd_pipe_max_rt, wgrad_tall, wide_res, rollout_v1, unroll_r6;
 };
 extern "C" const MarlSwitches* marl_switches(void);      // optim.hip
 
@@ -183,6 +186,19 @@ __device__ __forceinline__ float slab_sum(const float* p, long stride, int w0, i
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// max over each aligned group of 16 lanes with DPP moves (no LDS crossbar round trips)
+template <int CTRL>
+__device__ __forceinline__ float dpp_mov(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float group_max16(float v) {
+  v = fmaxf(v, dpp_mov<0xB1>(v));     // quad_perm [1,0,3,2]
+  v = fmaxf(v, dpp_mov<0x4E>(v));     // quad_perm [2,3,0,1]
+  v = fmaxf(v, dpp_mov<0x141>(v));    // row_half_mirror: the other quad of each 8 lanes
+  v = fmaxf(v, dpp_mov<0x140>(v));    // row_mirror: the other half of the row
   return v;
 }
 

@@ -21,7 +21,6 @@ constexpr int BNW = 4;            // backward: waves per workgroup (= 16-row til
 #define KEEP_ST(v, p) __builtin_nontemporal_store((v), (p))
 #define KEEP_LD(p) __builtin_nontemporal_load(p)
 #endif
-#define WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 
 struct Mlp3Args {
   ConcatSrc x;

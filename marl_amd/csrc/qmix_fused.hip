@@ -35,8 +35,6 @@ constexpr int SS = 128 + 4;       // LDS row stride of the state tile
 constexpr int NAG = 5;            // agent groups (N <= 5); groups 5, 6, 7 = b1, w2, h
 constexpr int PP = 136;           // X6: pitch (bf16 elements) of the state planes: 272-byte rows spread the 16-byte fragment reads of a 16-lane group over all banks
 
-#define WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
 struct QmixArgs {
   const float *W[4], *Bv[4];      // segment weights (rows x S) and biases: w1, b1, w2, h
   const float *wb2, *bb2;         // hyper_b2.2: (1,E), (1)

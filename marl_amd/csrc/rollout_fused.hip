@@ -19,21 +19,6 @@ constexpr int H = 64;
 constexpr int HS = H + MARL_PAD_H;
 constexpr int RNT = 512;
 
-#define WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
-
-// max over each aligned group of 16 lanes with DPP moves (no LDS crossbar round trips)
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float group_max16(float v) {
-  v = fmaxf(v, dpp_mov<0xB1>(v));     // quad_perm [1,0,3,2]
-  v = fmaxf(v, dpp_mov<0x4E>(v));     // quad_perm [2,3,0,1]
-  v = fmaxf(v, dpp_mov<0x141>(v));    // row_half_mirror: the other quad of each 8 lanes
-  v = fmaxf(v, dpp_mov<0x140>(v));    // row_mirror: the other half of the row
-  return v;
-}
-
 struct RollArgs {
   const float *W1, *b1, *Wih, *Whh, *bih, *bhh, *W2, *b2;
   const float* eps;       // [T] epsilon of each lock-step (device), or null: the schedule below

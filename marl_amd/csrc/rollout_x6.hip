@@ -38,7 +38,6 @@ constexpr int H = 64;
 constexpr int RNT = 512;
 constexpr int HP = 72;            // pitch (bf16) of the 64-wide planes
 
-#define WG_BARRIER() asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory")
 #ifdef MARL_STAMPS
 #define ST_RESET() ST_NOW(st_prev_)
 #else
@@ -47,71 +46,6 @@ constexpr int HP = 72;            // pitch (bf16) of the 64-wide planes
 #ifndef OI_CUT_16
 #define OI_CUT_16 9      // sixteenths of a slot's observation items team R generates before the choice barrier (A/B builds)
 #endif
-#define X6_TERMS(OP) OP(m, m) OP(h, l) OP(l, h) OP(h, m) OP(m, h) OP(h, h)
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float group_max16(float v) {
-  v = fmaxf(v, dpp_mov<0xB1>(v));     // quad_perm [1,0,3,2]
-  v = fmaxf(v, dpp_mov<0x4E>(v));     // quad_perm [2,3,0,1]
-  v = fmaxf(v, dpp_mov<0x141>(v));    // row_half_mirror
-  v = fmaxf(v, dpp_mov<0x140>(v));    // row_mirror
-  return v;
-}
-// B fragment of W (row-major, ldw floats per row): lane (g, j): W[row0 + j][32 c + 8g .. + 7]  (rows >= rows_valid and columns >= K: 0)
-__device__ __forceinline__ F3 wfrag(const float* W, int ldw, int row0, int rows_valid, int K, int c, int lane) {
-  const int i = lane & 15, g = lane >> 4, row = row0 + i;
-  float v[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int k = 32 * c + 8 * g + j;
-    v[j] = (row < rows_valid && k < K) ? W[(long)row * ldw + k] : 0.f;
-  }
-  return split8((f32x4){v[0], v[1], v[2], v[3]}, (f32x4){v[4], v[5], v[6], v[7]});
-}
-// A fragment from a plane tile (hi plane at pl, the others ps elements further): lane (g, m) reads row m, columns 32 c + 8g .. + 7
-__device__ __forceinline__ F3 bfrag(const short* pl, int pitch, int ps, int c, int lane) {
-  const int m = lane & 15, g = lane >> 4;
-  const short* p = pl + m * pitch + 32 * c + 8 * g;
-  F3 f;
-  f.h = *reinterpret_cast<const i32x4*>(p);
-  f.m = *reinterpret_cast<const i32x4*>(p + ps);
-  f.l = *reinterpret_cast<const i32x4*>(p + 2 * ps);
-  return f;
-}
-// accumulator tile (rows row0 + r, r = 0..3, of column col) -> planes
-__device__ __forceinline__ void put4(short* pl, int pitch, int ps, int row0, int col, const f32x4& v) {
-  const F3h f = split4(v);
-  short* p = pl + row0 * pitch + col;
-  const int d[3][2] = {{f.h[0], f.h[1]}, {f.m[0], f.m[1]}, {f.l[0], f.l[1]}};
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    p[k * ps] = (short)d[k][0];
-    p[k * ps + pitch] = (short)((unsigned)d[k][0] >> 16);
-    p[k * ps + 2 * pitch] = (short)d[k][1];
-    p[k * ps + 3 * pitch] = (short)((unsigned)d[k][1] >> 16);
-  }
-}
-// accumulator tile of a TRANSPOSED product (weights as the A operand: lane (q, m) holds columns col0 .. col0 + 3 of row `row`) -> planes:
-// one 8-byte write per plane (the row-major products' put4 above needs four 2-byte writes per plane)
-__device__ __forceinline__ void put4t(short* pl, int pitch, int ps, int row, int col0, const f32x4& v) {
-  const F3h f = split4(v);
-  short* p = pl + row * pitch + col0;
-  *reinterpret_cast<i32x2*>(p) = f.h;
-  *reinterpret_cast<i32x2*>(p + ps) = f.m;
-  *reinterpret_cast<i32x2*>(p + 2 * ps) = f.l;
-}
-__device__ __forceinline__ f32x4 splat(float v) { return (f32x4){v, v, v, v}; }
-// the gate math of agent_x6.hip (every fused / unfused operation spelled out)
-__device__ __forceinline__ float gru_h_x6(float ar, float az, float ain, float ahn, float hp) {
-  const float r = __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __builtin_amdgcn_exp2f(__fmul_rn(ar, -1.4426950408889634f))));
-  const float z = __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __builtin_amdgcn_exp2f(__fmul_rn(az, -1.4426950408889634f))));
-  const float e = __builtin_amdgcn_exp2f(__fmul_rn(__fmaf_rn(r, ahn, ain), 2.8853900817779268f));
-  const float n = __fmaf_rn(-2.0f, __builtin_amdgcn_rcpf(__fadd_rn(e, 1.0f)), 1.0f);
-  return __fmaf_rn(z, hp, __fmul_rn(__fsub_rn(1.0f, z), n));
-}
 
 struct RX6Args {
   const float *W1, *b1, *Wih, *Whh, *bih, *bhh, *W2, *b2;

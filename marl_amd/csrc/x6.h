@@ -1,4 +1,4 @@
-// bf16x6 split arithmetic shared by the split kernels (mlp3_x6.hip, agent_x6.hip): an fp32 operand element is split EXACTLY into
+// bf16x6 split arithmetic shared by the split kernels (the *_x6*.hip files, qmix_fused.hip): an fp32 operand element is split EXACTLY into
 // three bf16 terms, a = hi + mid + lo (round to nearest even each: 8 + 8 + 8 significand bits), and an fp32 product is the six bf16
 // products mid.mid, hi.lo, lo.hi, hi.mid, mid.hi, hi.hi accumulated in fp32 by v_mfma_f32_16x16x32_bf16, smallest first (the dropped
 // terms mid.lo, lo.mid, lo.lo are <= 2^-24 of a product).  Lane maps: tools/probe/x6_layout_probe.hip.
@@ -76,3 +76,70 @@ __device__ __forceinline__ void mm6h(const F3h& a, const F3h& b, f32x4& c) {
   c = mmh(a.h, b.m, c); c = mmh(a.m, b.h, c); c = mmh(a.h, b.h, c);
 }
 
+
+// the six products of a split multiply, smallest first (mm6), for schedules that interleave several accumulators
+#define X6_TERMS(OP) OP(m, m) OP(h, l) OP(l, h) OP(h, m) OP(m, h) OP(h, h)
+
+// Operand fragments and plane stores of the split kernels (agent_x6.hip, agent_x6p.hip, rollout_x6.hip, rollout_x6_v1.hip).  ONE
+// definition each: the bitwise tests between these kernels (rollout round 6 == round 5, x6p == x6, reading stored gate sums ==
+// computing them) hold only while every kernel does the same arithmetic.
+// fragment of W (row-major, ldw floats per row): lane (g, i) holds W[row0 + i][32 c + 8g .. + 7] - the A operand of the products
+// with the activations as B, the B operand of those with the activations as A  (rows >= rows_valid and columns >= K: 0)
+__device__ __forceinline__ F3 wfrag(const float* W, int ldw, int row0, int rows_valid, int K, int c, int lane) {
+  const int i = lane & 15, g = lane >> 4, row = row0 + i;
+  float v[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const int k = 32 * c + 8 * g + j;
+    v[j] = (row < rows_valid && k < K) ? W[(long)row * ldw + k] : 0.f;
+  }
+  return split8((f32x4){v[0], v[1], v[2], v[3]}, (f32x4){v[4], v[5], v[6], v[7]});
+}
+// fragment from a plane tile (hi plane at pl, the others ps elements further): lane (g, m) reads row m, columns 32 c + 8g .. + 7
+__device__ __forceinline__ F3 bfrag(const short* pl, int pitch, int ps, int c, int lane) {
+  const int m = lane & 15, g = lane >> 4;
+  const short* p = pl + m * pitch + 32 * c + 8 * g;
+  F3 f;
+  f.h = *reinterpret_cast<const i32x4*>(p);
+  f.m = *reinterpret_cast<const i32x4*>(p + ps);
+  f.l = *reinterpret_cast<const i32x4*>(p + 2 * ps);
+  return f;
+}
+// accumulator tile (rows row0 + r, r = 0..3, of column col) -> planes: one 2-byte write per row and plane
+__device__ __forceinline__ void put4(short* pl, int pitch, int ps, int row0, int col, const f32x4& v) {
+  const F3h f = split4(v);
+  short* p = pl + row0 * pitch + col;
+  const int d[3][2] = {{f.h[0], f.h[1]}, {f.m[0], f.m[1]}, {f.l[0], f.l[1]}};
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    p[k * ps] = (short)d[k][0];
+    p[k * ps + pitch] = (short)((unsigned)d[k][0] >> 16);
+    p[k * ps + 2 * pitch] = (short)d[k][1];
+    p[k * ps + 3 * pitch] = (short)((unsigned)d[k][1] >> 16);
+  }
+}
+// accumulator tile of a TRANSPOSED product (weights as the A operand: lane (q, m) holds columns col0 .. col0 + 3 of row `row`) -> planes:
+// one 8-byte write per plane (put4 above needs four 2-byte writes per plane)
+__device__ __forceinline__ void put4t(short* pl, int pitch, int ps, int row, int col0, const f32x4& v) {
+  const F3h f = split4(v);
+  short* p = pl + row * pitch + col0;
+  *reinterpret_cast<i32x2*>(p) = f.h;
+  *reinterpret_cast<i32x2*>(p + ps) = f.m;
+  *reinterpret_cast<i32x2*>(p + 2 * ps) = f.l;
+}
+__device__ __forceinline__ f32x4 splat(float v) { return (f32x4){v, v, v, v}; }
+// GRU gate math (common.h: gru_point_plain) with every fused / unfused operation spelled out: all instantiations round the same
+// way, so the launch that reads stored gate sums == the one that computes them, bit for bit, whatever the compiler would contract
+__device__ __forceinline__ void gru_point_x6(float ar, float az, float ain, float ahn, float hp, float& r, float& z, float& n, float& h) {
+  r = __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __builtin_amdgcn_exp2f(__fmul_rn(ar, -1.4426950408889634f))));
+  z = __builtin_amdgcn_rcpf(__fadd_rn(1.0f, __builtin_amdgcn_exp2f(__fmul_rn(az, -1.4426950408889634f))));
+  const float e = __builtin_amdgcn_exp2f(__fmul_rn(__fmaf_rn(r, ahn, ain), 2.8853900817779268f));
+  n = __fmaf_rn(-2.0f, __builtin_amdgcn_rcpf(__fadd_rn(e, 1.0f)), 1.0f);
+  h = __fmaf_rn(z, hp, __fmul_rn(__fsub_rn(1.0f, z), n));
+}
+// the same, the new hidden state alone (the rollouts and the plain unrolls)
+__device__ __forceinline__ float gru_h_x6(float ar, float az, float ain, float ahn, float hp) {
+  float r, z, n, h;
+  gru_point_x6(ar, az, ain, ahn, hp, r, z, n, h);
+  return h;
+}

@@ -6,15 +6,13 @@ plain attributes; tests flip either through ``set()`` / the ``override()`` conte
 
 library switches (environment variable -> name, default):
     MARL_FWD_XS -> fwd_xs 1           the double-Q unroll reads the eval unroll's input-side gate sums
-    MARL_FWD_DMA -> fwd_dma 0         LDS-DMA observation tile of the activation-saving unroll
     MARL_FWD_W2L -> fwd_w2l 1         six prefetch registers / fc2 fragments in LDS for wide observations
     MARL_BWD_PIPE_MAX_RT -> bwd_pipe_max_rt 4
     MARL_WGRAD_TALL -> wgrad_tall 1   LDS-staged tall weight-gradient kernel
-    MARL_WIDE_RES -> wide_res 1, MARL_WIDE_RES32 -> wide_res32 0    resident-weights forward of the wide-state QMIX mixer
+    MARL_WIDE_RES -> wide_res 1       resident-weights forward of the wide-state QMIX mixer
     MARL_UNROLL_R6 -> unroll_r6 1     non-saving split unrolls of more than 512 row tiles on csrc/agent_x6p.hip (0: csrc/agent_x6.hip everywhere)
     MARL_ROLLOUT_V1 -> rollout_v1 0   split whole-rollout kernel: 0 = by batch size, 1 = round 5 (csrc/rollout_x6_v1.hip), 2 = round 6 (csrc/rollout_x6.hip)
 host switches:
-    MARL_BIG_PAIR -> big_pair 0       batches beyond the pair's tile cap: eval chain and target unroll in flight together (two streams)
     MARL_NO_PAIR -> no_pair 0         the eval and target unrolls back to back instead of side by side on two streams
     MARL_NO_CHAIN -> no_chain 0       never the chain schedule (eval -> double-Q continuation beside the target unroll)
     MARL_CHAIN_SPLIT -> chain_split None    CUs of the chain side (0 = never chain, else a multiple of 8 in [8, 248])
@@ -28,8 +26,8 @@ import contextlib
 import os
 import warnings
 
-LIB_DEFAULTS = {"fwd_xs": 1, "fwd_dma": 0, "fwd_w2l": 1, "bwd_pipe_max_rt": 4, "wgrad_tall": 1, "wide_res": 1, "wide_res32": 0, "rollout_v1": 0, "unroll_r6": 1}
-HOST_DEFAULTS = {"big_pair": 0, "no_pair": 0, "no_chain": 0, "chain_split": None, "mlp3_keep": 1, "x6_bwd_min_wg": 1, "force_reducer": 0}
+LIB_DEFAULTS = {"fwd_xs": 1, "fwd_w2l": 1, "bwd_pipe_max_rt": 4, "wgrad_tall": 1, "wide_res": 1, "rollout_v1": 0, "unroll_r6": 1}
+HOST_DEFAULTS = {"no_pair": 0, "no_chain": 0, "chain_split": None, "mlp3_keep": 1, "x6_bwd_min_wg": 1, "force_reducer": 0}
 
 
 def _env_int(name, default):
@@ -92,7 +90,7 @@ def set(name, value):      # noqa: A001 - mirrors marl_experiment_set
 
 @contextlib.contextmanager
 def override(**kw):
-    """with experiments.override(fwd_dma=1): ...   - restores the previous values on exit"""
+    """with experiments.override(fwd_w2l=0): ...   - restores the previous values on exit"""
     old = {k: get(k) for k in kw}
     try:
         for k, v in kw.items():

@@ -5,25 +5,31 @@ import re
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 
-def test_library_switch_table_roundtrip():
+def test_library_switch_table_roundtrip_rejects_retired_names():
     from marl_amd import _lib, experiments
     lib = _lib.load()
     for name, default in experiments.LIB_DEFAULTS.items():
         assert lib.marl_experiment_get(name.encode()) == experiments.get(name)
     assert lib.marl_experiment_set(b"no_such_switch", 1) == -1 and lib.marl_experiment_get(b"no_such_switch") == -2 ** 31
-    with experiments.override(fwd_dma=1, bwd_pipe_max_rt=2, no_chain=1):
-        assert lib.marl_experiment_get(b"fwd_dma") == 1 and lib.marl_experiment_get(b"bwd_pipe_max_rt") == 2
+    with experiments.override(fwd_w2l=0, bwd_pipe_max_rt=2, no_chain=1):
+        assert lib.marl_experiment_get(b"fwd_w2l") == 0 and lib.marl_experiment_get(b"bwd_pipe_max_rt") == 2
         assert experiments.get("no_chain") == 1
         # the wide-state forward's kernel choice follows the table (a host function of the C-ABI)
         experiments.set("wide_res", 0)
         assert lib.marl_qmix_wide_fwd_kernel(122880, 10, 322, 1).decode().startswith("qmix_wide_kernel<false")
         experiments.set("wide_res", 1)
         assert lib.marl_qmix_wide_fwd_kernel(122880, 10, 322, 1).decode() == "qmix_wide_res_fwd_kernel"
-    assert lib.marl_experiment_get(b"fwd_dma") == 0 and lib.marl_experiment_get(b"bwd_pipe_max_rt") == 4 and experiments.get("no_chain") == 0
+    assert lib.marl_experiment_get(b"fwd_w2l") == 1 and lib.marl_experiment_get(b"bwd_pipe_max_rt") == 4 and experiments.get("no_chain") == 0
+    # retired variants are gone from both tables
+    assert lib.marl_experiment_set(b"fwd_dma", 1) == -1 and lib.marl_experiment_set(b"wide_res32", 1) == -1
+    with pytest.raises(KeyError):
+        experiments.set("big_pair", 1)
 
 
 def test_environment_is_read_once_at_import():
@@ -66,7 +72,7 @@ def test_graph_policy_from_args_and_split_step_model():
     assert x6.chain_split(4096 * 5, 120, 80) is None and f32.chain_split(4096 * 5, 120, 80) is None      # large batches: plain schedule
 
 
-def test_get_answers_library_switches_from_the_library_and_set_bumps_the_generation():
+def test_get_reads_library_switches_from_the_library_and_set_bumps_the_generation():
     """a C-ABI caller may flip a library switch through marl_experiment_set directly - the host's decisions read the
     library's table, not a Python mirror; every experiments.set() moves the generation a captured hipGraph schedule is keyed by."""
     from marl_amd import experiments, _lib
@@ -76,9 +82,9 @@ def test_get_answers_library_switches_from_the_library_and_set_bumps_the_generat
         assert lib.marl_experiment_set(b"fwd_xs", 0) == 0
         assert experiments.get("fwd_xs") == 0                     # not the value this module last wrote
         g0 = experiments.generation
-        with experiments.override(rollout_v1=2, big_pair=1):
-            assert lib.marl_experiment_get(b"rollout_v1") == 2 and experiments.get("big_pair") == 1 and experiments.generation > g0
-        assert lib.marl_experiment_get(b"rollout_v1") == 0 and experiments.get("big_pair") == 0
+        with experiments.override(rollout_v1=2, no_pair=1):
+            assert lib.marl_experiment_get(b"rollout_v1") == 2 and experiments.get("no_pair") == 1 and experiments.generation > g0
+        assert lib.marl_experiment_get(b"rollout_v1") == 0 and experiments.get("no_pair") == 0
         assert lib.marl_experiment_set(b"no_such_switch", 1) != 0
     finally:
         lib.marl_experiment_set(b"fwd_xs", 1)

@@ -789,13 +789,12 @@ def test_double_q_unroll_reuses_input_side_work_bitwise_flags(dev, shape, B, T, 
 
 @pytest.mark.parametrize("shape,B,T,cus", [("2s3z", 37, 5, 4), ("2s3z", 300, 7, 16), ("3s5z", 40, 4, 8), ("MMM2", 60, 4, 16),
                                             ("MMM2", 1024, 3, 256), ("MMM2", 30, 5, 128)])
-def test_saving_unroll_variants_equal_register_prefetch_bitwise(dev, shape, B, T, cus):
-    """Variants of the activation-saving unroll == the plain four-register prefetch kernel, bit for bit (q, the final hidden
-    state, all six saved planes and the input-side gate sums; ragged episode lengths - rows past their end feed zeros -, an
-    episode map, (T+1)-slot storage with the shifted last action, a partial last row tile):
-      * experiments fwd_dma = 1 (MARL_FWD_DMA=1): observation tile and fed-back actions filled by LDS-DMA (opt-in experiment);
-      * the default for wide observations with two action tiles (MMM2 at >= 3 row tiles per workgroup: six prefetch
-        registers, fc2 fragments in LDS) against fwd_w2l = 0."""
+def test_saving_unroll_w2l_equals_register_prefetch_bitwise(dev, shape, B, T, cus):
+    """The W2L variant of the activation-saving unroll == the plain four-register prefetch kernel, bit for bit (q, the final
+    hidden state, all six saved planes and the input-side gate sums; ragged episode lengths - rows past their end feed zeros -,
+    an episode map, (T+1)-slot storage with the shifted last action, a partial last row tile): the default for wide
+    observations with two action tiles (MMM2 at >= 3 row tiles per workgroup: six prefetch registers, fc2 fragments in LDS)
+    against fwd_w2l = 0."""
     import os
     from marl_amd import ops
     args, p_np, _, _, _ = _agent_case(shape, B, T, dev)
@@ -812,8 +811,8 @@ def test_saving_unroll_variants_equal_register_prefetch_bitwise(dev, shape, B, T
     w = ops.agent_weights({k: cu(v, dev) for k, v in p_np.items()})
     outs = {}
     from marl_amd import experiments
-    for mode in ("0", "1", "w2l"):
-        with experiments.override(fwd_dma=0 if mode == "w2l" else int(mode), fwd_w2l=1 if mode == "w2l" else 0):
+    for mode in ("0", "w2l"):
+        with experiments.override(fwd_w2l=1 if mode == "w2l" else 0):
             for t0, ut0 in ((0, -1), (1, 0)):
                 saved = torch.zeros(ops.saved_shape(T, B, N), device=dev)
                 gi = torch.zeros(ops.saved_shape(T, B, N, planes=3), device=dev)
@@ -824,7 +823,7 @@ def test_saving_unroll_variants_equal_register_prefetch_bitwise(dev, shape, B, T
                 planes = [ops.saved_plane(saved, k, rows).cpu() for k in range(6)] + [ops.saved_plane(gi, k, rows).cpu() for k in range(3)]
                 outs[(mode, t0)] = (q.cpu(), hl.cpu(), planes)
     for t0 in (0, 1):
-        for other in ("1", "w2l"):
+        for other in ("w2l",):
             a, b = outs[("0", t0)], outs[(other, t0)]
             assert torch.isfinite(a[0]).all()
             assert torch.equal(a[0], b[0]), "%s: q (t0=%d)" % (other, t0)
@@ -1836,7 +1835,7 @@ def _qmix_reference(P, s, q, gq, N, E, bf16, wgrad_fp32=False):
 
 
 @pytest.mark.parametrize("R,remap", [(40007, False), (32768, False), (36000, True)])
-def test_qmix_wide_resident_forward(dev, R, remap):
+def test_qmix_wide_res16_forward(dev, R, remap):
     """bf16 forward with the weights resident in LDS (qmix_wide_res_fwd_kernel: MMM2 shape, >= 32 768 rows; each row's q_tot is
     the sum of two embedding halves computed by two workgroups) vs torch-CPU with the hypernet operands rounded to bf16,
     and vs the streaming kernel (experiments wide_res = 0) - the two differ only in the order of the final sums."""
@@ -1878,16 +1877,15 @@ def test_qmix_wide_resident_forward(dev, R, remap):
     qd = cu(q, dev)
     res = {}
     from marl_amd import experiments
-    # res16: 16-row tiles (the default); res32: 32-row tiles, transposed product, mixing in registers (opt-in); stream: the streaming kernel
-    for mode, sw in (("res32", dict(wide_res=1, wide_res32=1)), ("res16", dict(wide_res=1, wide_res32=0)), ("stream", dict(wide_res=0, wide_res32=0))):
-        with experiments.override(**sw):
+    # res16: 16-row tiles, weights resident in LDS (the default); stream: the streaming kernel
+    for mode, wide_res in (("res16", 1), ("stream", 0)):
+        with experiments.override(wide_res=wide_res):
             out = torch.full((R,), 9.0, device=dev)
             ops.qmix_wide_fwd(ops.qmix_weights(Wd), xs, qd, out, R, N, S, E, bf16=True)
             res[mode] = out.cpu()
     scale = max(1.0, float(qt.abs().max()))
-    for mode in ("res32", "res16"):
-        close(res[mode], qt, 1e-4 * scale, 1e-4, msg="q_tot (%s)" % mode)
-        close(res[mode], res["stream"], 2e-6 * scale, 1e-5, msg="%s vs streaming kernel" % mode)
+    close(res["res16"], qt, 1e-4 * scale, 1e-4, msg="q_tot (res16)")
+    close(res["res16"], res["stream"], 2e-6 * scale, 1e-5, msg="res16 vs streaming kernel")
 
 
 @pytest.mark.parametrize("R,N,S,bf16", [(333, 10, 322, False), (64, 10, 322, False), (5000, 10, 322, False), (100, 3, 50, False),

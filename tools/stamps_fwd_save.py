@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Segment shares of the activation-saving unroll alone (diagnostic build), register prefetch vs LDS-DMA:
+"""Segment shares of the activation-saving unroll alone (diagnostic build):
     python tools/stamps_fwd_save.py [shape] [envs]"""
 import os, sys, ctypes
 HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -27,14 +27,11 @@ store = torch.randn(B, T + 1, N, O, device=dev)
 u = torch.randint(0, A, (B, T, N), device=dev, dtype=torch.int32)
 q = torch.empty(B, T, N, A, device=dev); hl = torch.empty(B * N, 64, device=dev)
 saved = torch.empty(ops.saved_shape(T, B, N), device=dev); gi = torch.empty(ops.saved_shape(T, B, N, planes=3), device=dev)
-for mode in ("0", "1"):
-    from marl_amd import experiments
-    experiments.set("fwd_dma", int(mode))
-    for _ in range(2):
-        buf.zero_()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ops.agent_unroll_fwd(w, store, (T + 1) * N, 0, u, T * N, -1, None, q, None, hl, saved, B, T, N, O, A, gi_out=gi)
-        e1.record(); torch.cuda.synchronize()
-    print("MARL_FWD_DMA=%s : %.3f ms (stamped build)" % (mode, e0.elapsed_time(e1)))
-    show(buf.cpu().view(16, 16).numpy(), SEGS["fwd"], "fwd save, DMA=" + mode, B, T)
+for _ in range(2):
+    buf.zero_()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    ops.agent_unroll_fwd(w, store, (T + 1) * N, 0, u, T * N, -1, None, q, None, hl, saved, B, T, N, O, A, gi_out=gi)
+    e1.record(); torch.cuda.synchronize()
+print("%.3f ms (stamped build)" % e0.elapsed_time(e1))
+show(buf.cpu().view(16, 16).numpy(), SEGS["fwd"], "fwd save", B, T)

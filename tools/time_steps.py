@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Per-step wall time of the bench pipeline (rollout -> store -> sample -> train), with leg split."""
+"""Per-step wall time of the bench pipeline (rollout -> store -> sample -> train), with leg split.
+A/B of the unroll's row-tile constants: build a variant (tools/build_variant.sh pipe2 "-DMARL_FWD_PIPE_MAX_RT=2" agent.hip)
+and select it with MARL_HIP_LIB=marl_amd/variants/libmarl_hip_pipe2.so."""
 import os, sys, time
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -10,9 +12,6 @@ from marl_amd.rollout import RolloutWorker
 from marl_amd.env.synthetic_smac import SyntheticSMACEnv
 from marl_amd.common.replaybuffer import ReplayBuffer
 E = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
-if os.environ.get("MARL_PIPE_MAX_RT"):
-    from marl_amd import _lib
-    _lib.load().marl_debug_set_pipe_max_rt(int(os.environ["MARL_PIPE_MAX_RT"]))
 args = bench.make_args("qmix", "2s3z", 0); args.buffer_size = 2 * E; args.batch_size = E
 mac = SharedMAC(args); learner = QLearner(mac, args)
 env = SyntheticSMACEnv(E, args.n_agents, args.obs_shape, args.state_shape, args.n_actions, args.episode_limit, seed=1, fixed_length=True)
