@@ -3,8 +3,7 @@
 // environment that stands in for StarCraft II (main.py:16-20 is not vendored).  Everything random
 // is a pure function of (seed, stream, env, step, index) through a 32-bit hash, so the numpy
 // restatement in oracle/rollout.py reproduces it bit for bit.
-#include "common.h"
-#include "synth_hash.h"
+#include "synth_env.h"
 #include "../../include/marl_hip.h"
 
 namespace {
@@ -30,8 +29,8 @@ __global__ void select_kernel(const float* q, const float* avail, long avail_es,
     const unsigned tgl = (unsigned)(tg ? tg[e] : tg0);
     const bool explore = u01(hkey(rseed, ST_EXPLORE, (unsigned)(env0 + e), tgl, (unsigned)n)) < eps;
     if (explore && navail > 0) {
-      int k = (int)floorf(u01(hkey(rseed, ST_PICK, (unsigned)(env0 + e), tgl, (unsigned)n)) * (float)navail);
-      if (k > navail - 1) k = navail - 1;
+      int k;
+      env_pick(u01(hkey(rseed, ST_PICK, (unsigned)(env0 + e), tgl, (unsigned)n)), navail, k);
       int c = 0;
       for (int a = 0; a < A; ++a) {
         if (av[a] == 0.f) continue;
@@ -48,7 +47,7 @@ __global__ void synth_lengths_kernel(unsigned seed, int env0, int episode, int* 
   if (e >= E) return;
   const int lmin = T / 2 > 1 ? T / 2 : 1;
   len[e] = lmin + (int)(hkey(seed, ST_LEN, (unsigned)(env0 + e), (unsigned)episode, 0u) % (unsigned)(T - lmin + 1));
-  if (won) won[e] = (int)(hkey(seed, ST_WON, (unsigned)(env0 + e), (unsigned)episode, 0u) & 1u);
+  if (won) won[e] = env_won(seed, (unsigned)(env0 + e), episode);
 }
 
 // one block row per env slot; slot t of the (T+1)-slot storage.  Slots past the episode end are zero
@@ -57,11 +56,11 @@ __global__ void synth_observe_kernel(unsigned seed, int env0, int episode, int t
                                      float* state, long SL, float* avail, int E, int T, int N, int O, int S, int A) {
   const int e = blockIdx.x;
   const bool live = t <= len[e];
-  const unsigned env = (unsigned)(env0 + e), tg = (unsigned)(episode * (T + 1) + t);
+  const unsigned env = (unsigned)(env0 + e), tg = env_tg(episode, T, t);
   float* o = obs + ((long)e * (T + 1) + t) * N * O;
-  for (int i = threadIdx.x; i < N * O; i += TPB) o[i] = live ? 2.0f * u01(hkey(seed, ST_OBS, env, tg, (unsigned)i)) - 1.0f : 0.f;
+  for (int i = threadIdx.x; i < N * O; i += TPB) o[i] = live ? env_value(hprefix(seed, ST_OBS, env, tg), (unsigned)i) : 0.f;
   float* s = state + ((long)e * (T + 1) + t) * SL;       // SL = row stride of the state storage (>= S)
-  for (int i = threadIdx.x; i < S; i += TPB) s[i] = live ? 2.0f * u01(hkey(seed, ST_STATE, env, tg, (unsigned)i)) - 1.0f : 0.f;
+  for (int i = threadIdx.x; i < S; i += TPB) s[i] = live ? env_value(hprefix(seed, ST_STATE, env, tg), (unsigned)i) : 0.f;
   float* a = avail + ((long)e * (T + 1) + t) * N * A;
   for (int i = threadIdx.x; i < N * A; i += TPB) {
     float v = 0.f;
@@ -76,12 +75,12 @@ __global__ void synth_step_kernel(unsigned seed, int env0, int episode, int t, c
   if (e >= E) return;
   const int L = len[e];
   const bool live = t < L;
-  const unsigned env = (unsigned)(env0 + e), tg = (unsigned)(episode * (T + 1) + t);
+  const unsigned env = (unsigned)(env0 + e), tg = env_tg(episode, T, t);
   float acc = 0.f;
   for (int n = 0; n < N; ++n) {
     const int a = live ? act[(long)e * N + n] : -1;
     u[((long)e * T + t) * N + n] = a;
-    if (live) acc = acc + (u01(hkey(seed, ST_REWARD, env, tg, (unsigned)(n * A + a))) - 0.5f);
+    if (live) acc = acc + env_reward_term(hprefix(seed, ST_REWARD, env, tg), (unsigned)(n * A + a));
   }
   r[(long)e * T + t] = live ? acc * (1.0f / (float)N) : 0.f;
   term[(long)e * T + t] = live ? (t + 1 >= L ? 1.f : 0.f) : 1.f;
@@ -98,7 +97,7 @@ __global__ void synth_fused_step_kernel(unsigned seed, unsigned rseed, int env0,
   const int e = blockIdx.x;
   const int L = len[e];
   const bool live = t < L;
-  const unsigned env = (unsigned)(env0 + e), tg = (unsigned)(episode * (T + 1) + t);
+  const unsigned env = (unsigned)(env0 + e), tg = env_tg(episode, T, t);
   if (threadIdx.x < N) {
     const int n = threadIdx.x;
     int arg = -1;
@@ -114,8 +113,8 @@ __global__ void synth_fused_step_kernel(unsigned seed, unsigned rseed, int env0,
       if (arg < 0) arg = 0;
       const bool explore = u01(hkey(rseed, ST_EXPLORE, env, tg, (unsigned)n)) < eps;
       if (explore && navail > 0) {
-        int k = (int)floorf(u01(hkey(rseed, ST_PICK, env, tg, (unsigned)n)) * (float)navail);
-        if (k > navail - 1) k = navail - 1;
+        int k;
+        env_pick(u01(hkey(rseed, ST_PICK, env, tg, (unsigned)n)), navail, k);
         int c = 0;
         for (int a = 0; a < A; ++a) {
           if (av[a] == 0.f) continue;
@@ -131,7 +130,7 @@ __global__ void synth_fused_step_kernel(unsigned seed, unsigned rseed, int env0,
   if (threadIdx.x == 0) {
     float acc = 0.f;
     if (live)
-      for (int n = 0; n < N; ++n) acc = acc + (u01(hkey(seed, ST_REWARD, env, tg, (unsigned)(n * A + act[n]))) - 0.5f);
+      for (int n = 0; n < N; ++n) acc = acc + env_reward_term(hprefix(seed, ST_REWARD, env, tg), (unsigned)(n * A + act[n]));
     r[(long)e * T + t] = live ? acc * (1.0f / (float)N) : 0.f;
     term[(long)e * T + t] = live ? (t + 1 >= L ? 1.f : 0.f) : 1.f;
     padded[(long)e * T + t] = live ? 0.f : 1.f;
@@ -141,9 +140,9 @@ __global__ void synth_fused_step_kernel(unsigned seed, unsigned rseed, int env0,
   const bool live1 = t1 <= L;
   const unsigned tg1 = tg + 1u;
   float* o = obs + ((long)e * (T + 1) + t1) * N * O;
-  for (int i = threadIdx.x; i < N * O; i += TPB) o[i] = live1 ? 2.0f * u01(hkey(seed, ST_OBS, env, tg1, (unsigned)i)) - 1.0f : 0.f;
+  for (int i = threadIdx.x; i < N * O; i += TPB) o[i] = live1 ? env_value(hprefix(seed, ST_OBS, env, tg1), (unsigned)i) : 0.f;
   float* sp = state + ((long)e * (T + 1) + t1) * SL;
-  for (int i = threadIdx.x; i < S; i += TPB) sp[i] = live1 ? 2.0f * u01(hkey(seed, ST_STATE, env, tg1, (unsigned)i)) - 1.0f : 0.f;
+  for (int i = threadIdx.x; i < S; i += TPB) sp[i] = live1 ? env_value(hprefix(seed, ST_STATE, env, tg1), (unsigned)i) : 0.f;
   float* ap = avail + ((long)e * (T + 1) + t1) * N * A;
   for (int i = threadIdx.x; i < N * A; i += TPB) {
     float v = 0.f;

@@ -7,17 +7,13 @@
 // agent of its environments the epsilon-greedy choice, the env step (reward / terminated / padding)
 // and the next observation are computed in place - no inter-workgroup communication at all.
 // The MFMA phases are those of agent_fwd_kernel (agent.hip); the environment is the counter-hash
-// env of synth_hash.h, so the episode record is bit-identical to the launch-per-step path and to the
+// env of synth_env.h, so the episode record is bit-identical to the launch-per-step path and to the
 // numpy oracle.
-#include "common.h"
-#include "synth_hash.h"
-#include "../../include/marl_hip.h"
+#include "synth_rollout.h"
 
 namespace {
 
-constexpr int H = 64;
 constexpr int HS = H + MARL_PAD_H;
-constexpr int RNT = 512;
 
 struct RollArgs {
   const float *W1, *b1, *Wih, *Whh, *bih, *bhh, *W2, *b2;
@@ -90,7 +86,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
     if (a.fixed_len) L = T;
     elen[e] = L;
     a.length[b] = L;
-    const int won_ = (int)(hkey(a.seed, ST_WON, env, (unsigned)a.episode, 0u) & 1u);
+    const int won_ = env_won(a.seed, env, a.episode);
     a.won[b] = won_;
     if (a.stats && b0 + e < a.E) { a.stats[a.E + b] = (float)won_; a.stats[2L * a.E + b] = (float)L; }
   }
@@ -108,7 +104,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
   // prefixes of slot t (3 of the 4 hash rounds depend only on (stream, env, t)): one thread per row
   auto gen_prefix = [&](int t) {
     if (tid < rows) {
-      const unsigned tg = (unsigned)(a.episode * (T + 1) + t);
+      const unsigned tg = env_tg(a.episode, T, t);
       const unsigned env = (unsigned)(a.env0 + b0 + rowe[tid]);
       pfx[tid] = hprefix(a.seed, ST_OBS, env, tg);
       pfx[rows + tid] = hprefix(a.seed, ST_AVAIL, env, tg);
@@ -141,7 +137,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
         const unsigned idx = (unsigned)(mt.w * O + k);
         u32x4 v;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = bits(2.0f * u01(hfin(po, idx + (unsigned)i)) - 1.0f) & lm;
+        for (int i = 0; i < 4; ++i) v[i] = bits(env_value(po, idx + (unsigned)i)) & lm;
         *reinterpret_cast<u32x4*>(a.obs + (long)mt.x + tNO + k) = v;
         if (to_lds) {                              // padded steps feed zeros (rollout.py:122-133)
           u32x4 w;
@@ -156,7 +152,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
         const int k = e - r * O;
         const int4 mt = rmeta[r];
         const unsigned lm = t <= mt.z ? 0xffffffffu : 0u, fm = t < mt.z ? 0xffffffffu : 0u;
-        const unsigned v = bits(2.0f * u01(hfin(pfx[r], (unsigned)(mt.w * O + k))) - 1.0f) & lm;
+        const unsigned v = bits(env_value(pfx[r], (unsigned)(mt.w * O + k))) & lm;
         reinterpret_cast<unsigned*>(a.obs)[(long)mt.x + tNO + k] = v;
         if (to_lds) reinterpret_cast<unsigned*>(In)[r * KS + k] = v & fm;
       }
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
       const int k = e - r * A;
       const int4 mt = rmeta[r];
       const float uu = u01(hfin(pfx[rows + r], (unsigned)(mt.w * A + k)));
-      const bool on = (t <= mt.z) & ((k == 0) | (uu < 0.7f));
+      const bool on = (t <= mt.z) & env_avail(uu, k);
       const float v = on ? 1.f : 0.f;
       a.avail[(long)mt.y + tNA + k] = v;
       if (Av) Av[r * A + k] = v;
@@ -180,7 +176,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
         const unsigned lm = t <= mt.y ? 0xffffffffu : 0u;
         u32x4 v;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = bits(2.0f * u01(hfin(ps, (unsigned)(k + i))) - 1.0f) & (k + i < S ? lm : 0u);
+        for (int i = 0; i < 4; ++i) v[i] = bits(env_value(ps, (unsigned)(k + i))) & (k + i < S ? lm : 0u);
         if (mt.z) *reinterpret_cast<u32x4*>(a.state + (long)mt.x + tS + k) = v;
       }
     } else {
@@ -189,7 +185,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
         const int k = e - el * S;
         const int4 mt = emeta[el];
         const unsigned lm = t <= mt.y ? 0xffffffffu : 0u;
-        const unsigned v = bits(2.0f * u01(hfin(pfx[2 * rows + el], (unsigned)k)) - 1.0f) & lm;
+        const unsigned v = bits(env_value(pfx[2 * rows + el], (unsigned)k)) & lm;
         if (mt.z) reinterpret_cast<unsigned*>(a.state)[(long)mt.x + tS + k] = v;
       }
     }
@@ -208,7 +204,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
   __syncthreads();
   gen_prefix(1);          // consumed by gen_slot(1) after the first barrier of step 0
   if (tid < rows) {       // uniforms of the first choice; tile counters
-    const unsigned env = (unsigned)(a.env0 + b0 + rowe[tid]), tg0 = (unsigned)(a.episode * (T + 1));
+    const unsigned env = (unsigned)(a.env0 + b0 + rowe[tid]), tg0 = env_tg(a.episode, T, 0);
     uex[tid] = u01(hkey(a.rseed, ST_EXPLORE, env, tg0, (unsigned)rown[tid]));
     uex[rows + tid] = u01(hkey(a.rseed, ST_PICK, env, tg0, (unsigned)rown[tid]));
     if (tid < 4) tilecnt[tid] = 0;
@@ -265,7 +261,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
   for (int t = 0; t < T; ++t) {
     const float eps = eps_next;                    // scalar load issued a step ahead
     if (a.eps) { if (t + 1 < T) eps_next = a.eps[t + 1]; }
-    else { eps_d = eps_d > a.eps_min ? eps_d - a.eps_anneal : eps_d; eps_next = (float)eps_d; }
+    else { eps_d = eps_anneal_step(eps_d, a.eps_anneal, a.eps_min); eps_next = (float)eps_d; }
     // ---------------- phase 1: x = relu(fc1(in))
     for (int rt = team; rt < a.RT; rt += 4) {
       const bool two = rt + 2 < a.RT;
@@ -360,7 +356,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
     // of slot t+2, whose observation is generated during the gates of step t+1
     if (tid >= RNT - 128 && tid - (RNT - 128) < rows) {
       const int r = tid - (RNT - 128);
-      const unsigned tg2 = (unsigned)(a.episode * (T + 1) + t) + 2u;
+      const unsigned tg2 = env_tg(a.episode, T, t) + 2u;
       const unsigned env = (unsigned)(a.env0 + b0 + rowe[r]);
       pfx[r] = hprefix(a.seed, ST_OBS, env, tg2);
       pfx[rows + r] = hprefix(a.seed, ST_AVAIL, env, tg2);
@@ -393,7 +389,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
     // ---------------- epsilon-greedy choice (share_params.py:66-70): 16*AC lanes per (env, agent) row, lane = action;
     // first-index argmax over the available actions by a lane-group max + ballot, the explored action is the
     // kk-th set bit of the availability mask (the serial per-thread form of this took 13-35 % of a lock-step)
-    const unsigned tg = (unsigned)(a.episode * (T + 1) + t);
+    const unsigned tg = env_tg(a.episode, T, t);
     {
       constexpr int LG = 16 * AC;
       constexpr unsigned GM = LG == 32 ? 0xffffffffu : ((1u << LG) - 1u);
@@ -413,8 +409,8 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
         const int navail = __popc(am);
         int arg = em ? __ffs(em) - 1 : (am ? __ffs(am) - 1 : 0);
         const bool explore = uex[rr] < eps;
-        int kk = (int)floorf(uex[rows + rr] * (float)navail);
-        if (kk > navail - 1) kk = navail - 1;
+        int kk;
+        env_pick(uex[rows + rr], navail, kk);
         const bool sel = explore && on && __popc(am & ((1u << gl) - 1u)) == kk;
         const unsigned sm = (unsigned)(__ballot(sel) >> sh) & GM;
         if (sm) arg = __ffs(sm) - 1;
@@ -447,7 +443,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
       float term = 0.f;
       if (live) {
         const unsigned pre = hprefix(a.seed, ST_REWARD, (unsigned)(a.env0 + b0 + es_el), tg);
-        term = u01(hfin(pre, (unsigned)(es_n * A + act[es_el * N + es_n]))) - 0.5f;
+        term = env_reward_term(pre, (unsigned)(es_n * A + act[es_el * N + es_n]));
       }
       float acc = 0.f;
       for (int n0 = 0; n0 < N; n0 += 4) {          // four shuffles in flight; the sum stays in agent order
@@ -487,14 +483,18 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
 
 ST_DEFINE_SETTER(marl_debug_stamps_rollout)
 
-// a workgroup holds whole environments (EPW*N rows padded to 16*RT, RT <= 8); the fc1 slice + the row state
-// must fit the 160 KB LDS (widest input assumed: last action and agent id appended)
-static int max_rt(int I, int A) {
+// LDS bytes of a workgroup of rt row tiles of width-I inputs: the fc1 slice + the row state
+static size_t roll_lds(int I, int A, int rt) {
   const int KC = (I + 15) / 16, KS = KC * 16 + MARL_PAD_K;
   const size_t fixed = (size_t)4 * KC * 64 * 16 + 16;
   const size_t per_row = (size_t)(KS + 3 * HS + (A + 1) + 2 * A) * 4 + 16 + 12 + 32 + 8;
+  return fixed + per_row * 16 * rt;
+}
+// a workgroup holds whole environments (EPW*N rows padded to 16*RT, RT <= 8) within the 160 KB LDS (widest input assumed: last
+// action and agent id appended)
+static int max_rt(int I, int A) {
   int rt = 0;
-  for (int c = 1; c <= 8; ++c) if (fixed + per_row * 16 * c <= 160 * 1024) rt = c;
+  for (int c = 1; c <= 8; ++c) if (roll_lds(I, A, c) <= 160 * 1024) rt = c;
   return rt;
 }
 
@@ -509,45 +509,20 @@ extern "C" int marl_synth_rollout(const marl_agent_weights_t* w, unsigned seed, 
                                   float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
                                   int O, int S, int A, int last_action, int reuse_network, void* stream) {
   if (E <= 0 || T <= 0) return 0;
-  if (w->H != H || A > 32 || A < 1 || N < 1 || N > 64 || state_ld < S) return (int)hipErrorInvalidValue;
+  if (A > 32 || A < 1 || N < 1 || N > 64) return (int)hipErrorInvalidValue;
   RollArgs a;
-  a.W1 = w->fc1_w; a.b1 = w->fc1_b; a.Wih = w->w_ih; a.Whh = w->w_hh; a.bih = w->b_ih; a.bhh = w->b_hh;
-  a.W2 = w->fc2_w; a.b2 = w->fc2_b;
-  a.eps = eps; a.eps0 = eps0; a.eps_anneal = eps_anneal; a.eps_min = eps_min; a.obs = obs; a.state = state; a.SL = state_ld; a.avail = avail; a.u = u; a.r = r; a.term = term; a.padded = padded;
-  a.length = length; a.won = won; a.h_out = h_out; a.stats = stats;
-  a.seed = seed; a.rseed = rseed; a.env0 = env0; a.episode = episode; a.fixed_len = fixed_len;
-  a.E = E; a.T = T; a.N = N; a.O = O; a.S = S; a.A = A;
-  a.has_act = last_action ? 1 : 0; a.has_id = reuse_network ? 1 : 0;
-  a.I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
+  if (const int e = rollout_args(a, w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded,
+                                 length, won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network))
+    return e;
   a.KC = (a.I + 15) / 16;
-  a.R = (long)E * N;
-  const int KS = a.KC * 16 + MARL_PAD_K;
-  const size_t fixed = (size_t)4 * a.KC * 64 * 16 + 16;
-  const size_t per_row = (size_t)(KS + 3 * HS + (A + 1) + 2 * A) * 4 + 16 + 12 + 32 + 8;
-  // environments per workgroup: one workgroup per CU when the batch allows it (a lock-step is latency
-  // bound, so small batches spread over all CUs with partly filled tiles), capped by the LDS budget
-  // record offsets are 32-bit element offsets inside the kernel
-  if ((double)E * (T + 1) * N * (O > A ? O : A) >= 2147483648.0 || (double)E * (T + 1) * state_ld >= 2147483648.0)
-    return (int)hipErrorInvalidValue;
   const int rt_max = max_rt(a.I, A);
   if (16 * rt_max < N) return (int)hipErrorInvalidValue;
+  // environments per workgroup: one workgroup per CU when the batch allows it (a lock-step is latency
+  // bound, so small batches spread over all CUs with partly filled tiles), capped by the LDS budget
   int epw = (E + 255) / 256;
   if (epw * N > 16 * rt_max) epw = (16 * rt_max) / N;
   a.EPW = epw;
   a.RT = (epw * N + 15) / 16;
-  const size_t lds = fixed + per_row * a.RT * 16;
-  dim3 grid((unsigned)((E + epw - 1) / epw)), block(RNT);
-  hipStream_t s = (hipStream_t)stream;
-  hipError_t e;
-  if (A <= 16) {
-    e = hipFuncSetAttribute((const void*)synth_rollout_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((synth_rollout_kernel<1>), grid, block, lds, s, a);
-  } else {
-    e = hipFuncSetAttribute((const void*)synth_rollout_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return (int)e;
-    hipLaunchKernelGGL((synth_rollout_kernel<2>), grid, block, lds, s, a);
-  }
-  MARL_CHECK_LAUNCH();
-  return 0;
+  return launch_rollout(A <= 16 ? (const void*)synth_rollout_kernel<1> : (const void*)synth_rollout_kernel<2>, (E + epw - 1) / epw,
+                        roll_lds(a.I, A, a.RT), a, stream);
 }

@@ -1,6 +1,6 @@
 // Whole-rollout persistent kernel with the agent step as bf16x6 split products (x6.h; args.gemm_mode = "bf16x6"): ONE launch plays all
 // T lock-steps of E synthetic SMAC-shaped environments (reference rollout.py:60-101 + controller/share_params.py:37-72, vectorised).
-// Same environment (synth_hash.h), same epsilon-greedy choice, same episode record as rollout_fused.hip (the fp32 MFMA kernel); the
+// Same environment (synth_env.h), same epsilon-greedy choice, same episode record as rollout_fused.hip (the fp32 MFMA kernel); the
 // agent's products (network/q_network.py:16-21) are six bf16 MFMA products each, fp32 accumulate.
 //
 // Round 6 decomposition (the round-5 one lives on in rollout_x6_v1.hip as this kernel's bitwise twin).  What bounded the first one:
@@ -22,21 +22,9 @@
 // fc1 = (bias + W1[:, obs | id] in) - on the matrix cores - + W1[:, O + u], one column of fp32 weights added per row once u is known
 // (a table in LDS).  Availability lives in LDS as one bit mask per row and slot (a ring of four slots: no hazards).
 #include "x6.h"
-#include "synth_hash.h"
-#include "../../include/marl_hip.h"
-
-// the round-5 kernel (rollout_x6_v1.hip)
-int marl_rollout_x6_v1_supported(int N, int O, int A);
-int marl_rollout_x6_v1(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, int fixed_len, const float* eps,
-                       float* obs, float* state, long state_ld, float* avail, int* u, float* r, float* term, float* padded, int* length,
-                       int* won, float* h_out, float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int O,
-                       int S, int A, int last_action, int reuse_network, void* stream);
+#include "synth_rollout.h"
 
 namespace {
-
-constexpr int H = 64;
-constexpr int RNT = 512;
-constexpr int HP = 72;            // pitch (bf16) of the 64-wide planes
 
 #ifdef MARL_STAMPS
 #define ST_RESET() ST_NOW(st_prev_)
@@ -46,25 +34,6 @@ constexpr int HP = 72;            // pitch (bf16) of the 64-wide planes
 #ifndef OI_CUT_16
 #define OI_CUT_16 9      // sixteenths of a slot's observation items team R generates before the choice barrier (A/B builds)
 #endif
-
-struct RX6Args {
-  const float *W1, *b1, *Wih, *Whh, *bih, *bhh, *W2, *b2;
-  const float* eps;       // [T] epsilon of each lock-step (device), or null: the schedule below
-  double eps0, eps_anneal, eps_min;
-  float* stats;           // [3][E] or null: per episode  sum_t r | won | length
-  float *obs, *state, *avail;   // (E,T+1,N,O) (E,T+1,SL >= S) (E,T+1,N,A)
-  long SL;
-  int* u;                 // (E,T,N)
-  float *r, *term, *padded;     // (E,T)
-  int *length, *won;      // (E)
-  float* h_out;           // (E*N,64) final hidden state or null
-  unsigned seed, rseed;
-  int env0, episode, fixed_len;
-  int E, T, N, O, S, A, I, KI;
-  int EPW;                // whole environments per workgroup
-  int has_act, has_id;
-  long R;
-};
 
 template <int RTC, int NK1, int AC = 1>      // row tiles per workgroup, fc1 chunks of 32 input columns, action tiles of 16 (fc2 / the choice)
 __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
@@ -117,7 +86,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
     int b = b0 + e; if (b > a.E - 1) b = a.E - 1;
     const int L = ep_len(b);
     a.length[b] = L;
-    const int won_ = (int)(hkey(a.seed, ST_WON, (unsigned)(a.env0 + b), (unsigned)a.episode, 0u) & 1u);
+    const int won_ = env_won(a.seed, (unsigned)(a.env0 + b), a.episode);
     a.won[b] = won_;
     if (a.stats && b0 + e < a.E) { a.stats[a.E + b] = (float)won_; a.stats[2L * a.E + b] = (float)L; }
     emeta[e] = make_int4((b0 + e) * (T + 1) * (int)a.SL, L, b0 + e < a.E ? 1 : 0, 0);
@@ -145,7 +114,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
   auto kstream = [](int kind) { return kind == K_OBS ? ST_OBS : kind == K_AVAIL ? ST_AVAIL : kind == K_STATE ? ST_STATE : kind == K_REWARD ? ST_REWARD : kind == K_EXPLORE ? ST_EXPLORE : ST_PICK; };
   // prefix of (kind, local env el) at time index tt -> entry par
   auto put_prefix = [&](int kind, int el, int tt, int par) {
-    const unsigned tg = (unsigned)(a.episode * (T + 1) + tt);
+    const unsigned tg = env_tg(a.episode, T, tt);
     Pp(kind, par)[el] = hprefix(kind >= K_EXPLORE ? a.rseed : a.seed, (unsigned)kstream(kind), (unsigned)(a.env0 + b0 + el), tg);
   };
   const float inv_nE = 1.0f / (float)nenv_wg, inv_rows = 1.0f / (float)rows;
@@ -162,7 +131,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
       const unsigned idx = (unsigned)((mt.w & 0xffff) * O + k);
       u32x4 v;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = bits(2.0f * u01(hfin(po, idx + (unsigned)i)) - 1.0f) & lm;
+      for (int i = 0; i < 4; ++i) v[i] = bits(env_value(po, idx + (unsigned)i)) & lm;
       *reinterpret_cast<u32x4*>(a.obs + (long)mt.x + tNO + k) = v;
       if (to_lds) {                              // padded steps feed zeros (rollout.py:122-133); split once, here
         f32x4 w;
@@ -189,7 +158,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
       const int k = e - r * A;
       const int4 mt = rmeta[r];
       const float uu = u01(hfin(pA[mt.w >> 16], (unsigned)((mt.w & 0xffff) * A + k)));
-      const bool on = (t <= mt.z) & ((k == 0) | (uu < 0.7f));
+      const bool on = (t <= mt.z) & env_avail(uu, k);
       a.avail[(long)mt.y + tNA + k] = on ? 1.f : 0.f;
       if (on) atomicOr(am + r, 1u << k);
     }
@@ -203,7 +172,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
         const unsigned lm = t <= mt.y ? 0xffffffffu : 0u;
         u32x4 v;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = bits(2.0f * u01(hfin(ps, (unsigned)(k + i))) - 1.0f) & (k + i < S ? lm : 0u);
+        for (int i = 0; i < 4; ++i) v[i] = bits(env_value(ps, (unsigned)(k + i))) & (k + i < S ? lm : 0u);
         if (mt.z) *reinterpret_cast<u32x4*>(a.state + (long)mt.x + tS + k) = v;
       }
     } else {
@@ -212,7 +181,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
         const int k = e - el * S;
         const int4 mt = emeta[el];
         const unsigned lm = t <= mt.y ? 0xffffffffu : 0u;
-        const unsigned v = bits(2.0f * u01(hfin(pS[el], (unsigned)k)) - 1.0f) & lm;
+        const unsigned v = bits(env_value(pS[el], (unsigned)k)) & lm;
         if (mt.z) reinterpret_cast<unsigned*>(a.state)[(long)mt.x + tS + k] = v;
       }
     }
@@ -272,22 +241,16 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
   float ep_r = 0.f;
   auto env_step = [&](int t) __attribute__((always_inline)) {
     if (es_has) {
-      const unsigned tg = (unsigned)(a.episode * (T + 1) + t);
+      const unsigned tg = env_tg(a.episode, T, t);
       const int L = es_L;
       const bool live = t < L;
       float term = 0.f;
       if (live) {
         const unsigned pre_ = t > 0 ? Pp(K_REWARD, t & 1)[es_el] : hprefix(a.seed, ST_REWARD, (unsigned)(a.env0 + b0 + es_el), tg);
-        term = u01(hfin(pre_, (unsigned)(es_n * A + act[es_el * N + es_n]))) - 0.5f;
+        term = env_reward_term(pre_, (unsigned)(es_n * A + act[es_el * N + es_n]));
       }
-      float acc = 0.f;
-      for (int n0 = 0; n0 < N; n0 += 4) {          // four shuffles in flight; the sum stays in agent order
-        float v[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = __shfl(term, (es_l0 + n0 + k) & 63, 64);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc = n0 + k < N ? acc + v[k] : acc;
-      }
+      float acc;
+      env_agent_sum(term, es_l0, N, acc);
       if (es_n == 0) {
         const long o = (long)(b0 + es_el) * T + t;
         const float rew = live ? acc * (1.0f / (float)N) : 0.f;
@@ -530,8 +493,8 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
         const int navail = __popc(am);
         int arg = em ? __ffs(em) - 1 : (am ? __ffs(am) - 1 : 0);
         const bool explore = ue[rt] < eps;
-        int kk = (int)floorf(up[rt] * (float)navail);
-        if (kk > navail - 1) kk = navail - 1;
+        int kk;
+        env_pick(up[rt], navail, kk);
         unsigned sm = 0u;
 #pragma unroll
         for (int at = 0; at < AC; ++at) {
@@ -556,7 +519,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
     for (int t = 0; t < T; ++t) {
       const float eps = eps_next;
       if (a.eps) { if (t + 1 < T) eps_next = a.eps[t + 1]; }
-      else { eps_d = eps_d > a.eps_min ? eps_d - a.eps_anneal : eps_d; eps_next = (float)eps_d; }
+      else { eps_d = eps_anneal_step(eps_d, a.eps_anneal, a.eps_min); eps_next = (float)eps_d; }
       const unsigned tg = (unsigned)(a.episode * (T + 1) + t);
       // ---- A (beside the recurrence): pre(t+1) from the planes of slot t+1; state + availability of slot t+1 (record, bit masks; slot 1's
       // were made in the prologue)
@@ -592,19 +555,11 @@ static size_t rx6_lds(int rtc, int KI, int A, int epw) {
 // row tiles a workgroup may hold: five / seven fc1 chunks (wide inputs) cost registers and LDS
 static int rx6_max_tiles(int KI) { return KI > 160 ? 3 : KI > 96 ? 4 : 5; }
 
-// environments per workgroup: one workgroup per CU while the batch fits one round (small batches spread over all CUs with partly
-// filled tiles); beyond that as few FULL rounds of 256 workgroups as five row tiles per workgroup allow, evenly filled (0: none fits)
+// environments per workgroup: even rounds of workgroups of up to five row tiles (0: none fits)
 static int rx6_epw(int E, int N, int KI, int A) {
   int epw_max = 16 * rx6_max_tiles(KI) / N;
   while (epw_max > 1 && rx6_lds((epw_max * N + 15) / 16, KI, A, epw_max) > 160 * 1024) --epw_max;
-  if (epw_max < 1) return 0;
-  int epw = (E + 255) / 256;
-  if (epw > epw_max) {
-    const int rounds = (E + 256 * epw_max - 1) / (256 * epw_max);
-    epw = (E + 256 * rounds - 1) / (256 * rounds);
-    if (epw > epw_max) epw = epw_max;
-  }
-  return epw;
+  return epw_max < 1 ? 0 : even_rounds_epw(E, epw_max);
 }
 // which decomposition runs a batch: the round-5 kernel where it holds ONE row tile per workgroup (0.46 against 0.47 ms at 512 envs: a
 // lock-step is a chain of latencies there, and its four short phases carry them better), this file's kernel from two tiles on (1024
@@ -641,21 +596,10 @@ extern "C" int marl_synth_rollout_x6_supported(int N, int O, int A) { return mar
 extern "C" int marl_synth_rollout_x6_plan(int E, int N, int O, int A, int last_action, int reuse_network, int* plan) {
   if (!plan || E <= 0 || !marl_synth_rollout_x6_supported_flags(N, O, A, last_action, reuse_network)) return (int)hipErrorInvalidValue;
   const int I = O + (last_action ? A : 0) + (reuse_network ? N : 0), KI = (I + 31) / 32 * 32;
-  int epw;
-  if (rx6_use_v1(E, N, O, A, last_action, reuse_network)) {
-    const int epw_max = (KI > 96 ? 32 : 48) / N;
-    epw = (E + 255) / 256;
-    if (epw > epw_max) {
-      const int rounds = (E + 256 * epw_max - 1) / (256 * epw_max);
-      epw = (E + 256 * rounds - 1) / (256 * rounds);
-      if (epw > epw_max) epw = epw_max;
-    }
-    plan[0] = 1;
-  } else {
-    epw = rx6_epw(E, N, KI, A);
-    if (epw < 1) return (int)hipErrorInvalidValue;
-    plan[0] = 2;
-  }
+  const bool v1 = rx6_use_v1(E, N, O, A, last_action, reuse_network);
+  const int epw = v1 ? marl_rollout_x6_v1_epw(E, N, KI) : rx6_epw(E, N, KI, A);
+  if (epw < 1) return (int)hipErrorInvalidValue;
+  plan[0] = v1 ? 1 : 2;
   plan[1] = (E + epw - 1) / epw; plan[2] = (epw * N + 15) / 16; plan[3] = epw; plan[4] = KI > 160 ? 7 : KI > 96 ? 5 : 3;
   return 0;
 }
@@ -670,22 +614,13 @@ extern "C" int marl_synth_rollout_x6(const marl_agent_weights_t* w, unsigned see
     return marl_rollout_x6_v1(w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded, length, won,
                               h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network, stream);
   if (E <= 0 || T <= 0) return 0;
-  if (w->H != H || state_ld < S || !marl_synth_rollout_x6_supported_flags(N, O, A, last_action, reuse_network)) return (int)hipErrorInvalidValue;
-  if (reinterpret_cast<uintptr_t>(obs) & 15) return (int)hipErrorInvalidValue;
-  RX6Args a;
-  a.W1 = w->fc1_w; a.b1 = w->fc1_b; a.Wih = w->w_ih; a.Whh = w->w_hh; a.bih = w->b_ih; a.bhh = w->b_hh;
-  a.W2 = w->fc2_w; a.b2 = w->fc2_b;
-  a.eps = eps; a.eps0 = eps0; a.eps_anneal = eps_anneal; a.eps_min = eps_min; a.obs = obs; a.state = state; a.SL = state_ld; a.avail = avail;
-  a.u = u; a.r = r; a.term = term; a.padded = padded; a.length = length; a.won = won; a.h_out = h_out; a.stats = stats;
-  a.seed = seed; a.rseed = rseed; a.env0 = env0; a.episode = episode; a.fixed_len = fixed_len;
-  a.E = E; a.T = T; a.N = N; a.O = O; a.S = S; a.A = A;
-  a.has_act = last_action ? 1 : 0; a.has_id = reuse_network ? 1 : 0;
-  a.I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
-  a.KI = (a.I + 31) / 32 * 32;
-  a.R = (long)E * N;
-  // record offsets are 32-bit element offsets inside the kernel
-  if ((double)E * (T + 1) * N * (O > A ? O : A) >= 2147483648.0 || (double)E * (T + 1) * state_ld >= 2147483648.0)
+  if (!marl_synth_rollout_x6_supported_flags(N, O, A, last_action, reuse_network) || (reinterpret_cast<uintptr_t>(obs) & 15))
     return (int)hipErrorInvalidValue;
+  RX6Args a;
+  if (const int e = rollout_args(a, w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded,
+                                 length, won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network))
+    return e;
+  a.KI = (a.I + 31) / 32 * 32;
   const int nk1 = a.KI > 160 ? 7 : a.KI > 96 ? 5 : 3;
   if (A > 16 && nk1 != 7) return (int)hipErrorInvalidValue;      // only the seven-chunk instantiations carry two action tiles
   const int epw = rx6_epw(E, N, a.KI, A);
@@ -694,7 +629,6 @@ extern "C" int marl_synth_rollout_x6(const marl_agent_weights_t* w, unsigned see
   const int rtc = (epw * N + 15) / 16;
   const size_t lds = rx6_lds(rtc, a.KI, A, epw);
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-  dim3 grid((unsigned)((E + epw - 1) / epw)), block(RNT);
   const void* fn = nullptr;
 #define RX6_PICK(NK_) (rtc == 1 ? (const void*)synth_rollout_x6_kernel<1, NK_> : rtc == 2 ? (const void*)synth_rollout_x6_kernel<2, NK_> \
                        : rtc == 3 ? (const void*)synth_rollout_x6_kernel<3, NK_> : (const void*)synth_rollout_x6_kernel<4, NK_>)
@@ -702,11 +636,5 @@ extern "C" int marl_synth_rollout_x6(const marl_agent_weights_t* w, unsigned see
   else if (nk1 == 5) fn = RX6_PICK(5);
   else fn = rtc == 1 ? (const void*)synth_rollout_x6_kernel<1, 7, 2> : rtc == 2 ? (const void*)synth_rollout_x6_kernel<2, 7, 2> : (const void*)synth_rollout_x6_kernel<3, 7, 2>;
 #undef RX6_PICK
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  void* kargs[] = {(void*)&a};
-  e = hipLaunchKernel(fn, grid, block, kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  MARL_CHECK_LAUNCH();
-  return 0;
+  return launch_rollout(fn, (E + epw - 1) / epw, lds, a, stream);
 }

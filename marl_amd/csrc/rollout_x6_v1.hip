@@ -2,7 +2,7 @@
 // bitwise twin of rollout_x6.hip (same arithmetic, another division of labour: tests/test_gpu_rollout.py compares the two records).
 // Whole-rollout persistent kernel with the agent step as bf16x6 split products (x6.h; args.gemm_mode = "bf16x6"): ONE launch plays all
 // T lock-steps of E synthetic SMAC-shaped environments (reference rollout.py:60-101 + controller/share_params.py:37-72, vectorised).
-// Same environment (synth_hash.h), same epsilon-greedy choice, same episode record as rollout_fused.hip (the fp32 MFMA kernel); the
+// Same environment (synth_env.h), same epsilon-greedy choice, same episode record as rollout_fused.hip (the fp32 MFMA kernel); the
 // agent's products (network/q_network.py:16-21) are six bf16 MFMA products each, fp32 accumulate.
 //
 // Why it is another decomposition and not a variant of rollout_fused.hip: pre-split, a hidden-unit slice's weights are 204 registers,
@@ -21,33 +21,9 @@
 // A workgroup holds whole environments in RTC <= 3 row tiles of 16 (episode, agent) rows (~45 KB of LDS per tile); larger batches
 // run in rounds of workgroups (4096 envs x 5 agents: 512 workgroups of 8 environments = two full rounds).
 #include "x6.h"
-#include "synth_hash.h"
-#include "../../include/marl_hip.h"
+#include "synth_rollout.h"
 
 namespace {
-
-constexpr int H = 64;
-constexpr int RNT = 512;
-constexpr int HP = 72;            // pitch (bf16) of the 64-wide planes
-
-struct RX6Args {
-  const float *W1, *b1, *Wih, *Whh, *bih, *bhh, *W2, *b2;
-  const float* eps;       // [T] epsilon of each lock-step (device), or null: the schedule below
-  double eps0, eps_anneal, eps_min;
-  float* stats;           // [3][E] or null: per episode  sum_t r | won | length
-  float *obs, *state, *avail;   // (E,T+1,N,O) (E,T+1,SL >= S) (E,T+1,N,A)
-  long SL;
-  int* u;                 // (E,T,N)
-  float *r, *term, *padded;     // (E,T)
-  int *length, *won;      // (E)
-  float* h_out;           // (E*N,64) final hidden state or null
-  unsigned seed, rseed;
-  int env0, episode, fixed_len;
-  int E, T, N, O, S, A, I, KI;
-  int EPW;                // whole environments per workgroup
-  int has_act, has_id;
-  long R;
-};
 
 template <int RTC, int NK1>
 __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
@@ -98,7 +74,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
     if (a.fixed_len) L = T;
     elen[e] = L;
     a.length[b] = L;
-    const int won_ = (int)(hkey(a.seed, ST_WON, env, (unsigned)a.episode, 0u) & 1u);
+    const int won_ = env_won(a.seed, env, a.episode);
     a.won[b] = won_;
     if (a.stats && b0 + e < a.E) { a.stats[a.E + b] = (float)won_; a.stats[2L * a.E + b] = (float)L; }
   }
@@ -127,11 +103,11 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
   auto bits = [](float v) { return __builtin_bit_cast(unsigned, v); };
   typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
   auto gen_prefix_obs = [&](int t, int r) {
-    const unsigned tg = (unsigned)(a.episode * (T + 1) + t);
+    const unsigned tg = env_tg(a.episode, T, t);
     pfxO[r] = hprefix(a.seed, ST_OBS, (unsigned)(a.env0 + b0 + rowe[r]), tg);
   };
   auto gen_prefix_rest = [&](int t, int r) {
-    const unsigned tg = (unsigned)(a.episode * (T + 1) + t);
+    const unsigned tg = env_tg(a.episode, T, t);
     pfxA[r] = hprefix(a.seed, ST_AVAIL, (unsigned)(a.env0 + b0 + rowe[r]), tg);
     if (r < nenv_wg) pfxS[r] = hprefix(a.seed, ST_STATE, (unsigned)(a.env0 + b0 + r), tg);
   };
@@ -149,7 +125,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
       const unsigned idx = (unsigned)(mt.w * O + k);
       u32x4 v;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = bits(2.0f * u01(hfin(po, idx + (unsigned)i)) - 1.0f) & lm;
+      for (int i = 0; i < 4; ++i) v[i] = bits(env_value(po, idx + (unsigned)i)) & lm;
       *reinterpret_cast<u32x4*>(a.obs + (long)mt.x + tNO + k) = v;
       if (to_lds) {                              // padded steps feed zeros (rollout.py:122-133); split once, here
         f32x4 w;
@@ -170,7 +146,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
       const int k = e - r * A;
       const int4 mt = rmeta[r];
       const float uu = u01(hfin(pfxA[r], (unsigned)(mt.w * A + k)));
-      const bool on = (t <= mt.z) & ((k == 0) | (uu < 0.7f));
+      const bool on = (t <= mt.z) & env_avail(uu, k);
       const float v = on ? 1.f : 0.f;
       a.avail[(long)mt.y + tNA + k] = v;
       Av[r * A + k] = v;
@@ -184,7 +160,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
         const unsigned lm = t <= mt.y ? 0xffffffffu : 0u;
         u32x4 v;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = bits(2.0f * u01(hfin(ps, (unsigned)(k + i))) - 1.0f) & (k + i < S ? lm : 0u);
+        for (int i = 0; i < 4; ++i) v[i] = bits(env_value(ps, (unsigned)(k + i))) & (k + i < S ? lm : 0u);
         if (mt.z) *reinterpret_cast<u32x4*>(a.state + (long)mt.x + tS + k) = v;
       }
     } else {
@@ -193,7 +169,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
         const int k = e - el * S;
         const int4 mt = emeta[el];
         const unsigned lm = t <= mt.y ? 0xffffffffu : 0u;
-        const unsigned v = bits(2.0f * u01(hfin(pfxS[el], (unsigned)k)) - 1.0f) & lm;
+        const unsigned v = bits(env_value(pfxS[el], (unsigned)k)) & lm;
         if (mt.z) reinterpret_cast<unsigned*>(a.state)[(long)mt.x + tS + k] = v;
       }
     }
@@ -206,7 +182,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
   __syncthreads();
   if (tid < rows) {       // prefixes of slot 1; uniforms of the first choice
     gen_prefix_obs(1, tid); gen_prefix_rest(1, tid);
-    const unsigned env = (unsigned)(a.env0 + b0 + rowe[tid]), tg0 = (unsigned)(a.episode * (T + 1));
+    const unsigned env = (unsigned)(a.env0 + b0 + rowe[tid]), tg0 = env_tg(a.episode, T, 0);
     uex[tid] = u01(hkey(a.rseed, ST_EXPLORE, env, tg0, (unsigned)rown[tid]));
     uex[rows + tid] = u01(hkey(a.rseed, ST_PICK, env, tg0, (unsigned)rown[tid]));
   }
@@ -258,8 +234,8 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
     const int navail = __popc(am);
     int arg = em ? __ffs(em) - 1 : (am ? __ffs(am) - 1 : 0);
     const bool explore = uex[par * 2 * rows + rr] < eps;
-    int kk = (int)floorf(uex[par * 2 * rows + rows + rr] * (float)navail);
-    if (kk > navail - 1) kk = navail - 1;
+    int kk;
+    env_pick(uex[par * 2 * rows + rows + rr], navail, kk);
     const bool sel = explore && on && __popc(am & ((1u << m) - 1u)) == kk;
     const unsigned sm = (unsigned)(__ballot(sel) >> sh) & 0xffffu;
     if (sm) arg = __ffs(sm) - 1;
@@ -273,7 +249,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
   const bool pre_r = 4 * nenv_wg <= rows;
   // the uniforms of step t+1's choice and the hash prefixes of slot t+2, ONE hash per thread of a 256-thread team (index ti)
   auto hashes = [&](int t, int ti) __attribute__((always_inline)) {
-    const unsigned tg = (unsigned)(a.episode * (T + 1) + t);
+    const unsigned tg = env_tg(a.episode, T, t);
     const int kind = ti / rows, r = ti - kind * rows;
     if (kind < 5) {
       const unsigned env = (unsigned)(a.env0 + b0 + rowe[r]), nn_ = (unsigned)rown[r];
@@ -370,7 +346,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
       // step; the uniforms go to the other parity's buffer - team I reads this step's now); the choice of the third row tile
       const float eps = eps_next;
       if (a.eps) { if (t + 1 < T) eps_next = a.eps[t + 1]; }
-      else { eps_d = eps_d > a.eps_min ? eps_d - a.eps_anneal : eps_d; eps_next = (float)eps_d; }
+      else { eps_d = eps_anneal_step(eps_d, a.eps_anneal, a.eps_min); eps_next = (float)eps_d; }
       if (RTC == 3) choose(RTC - 1, t, eps);
       if (t + 1 < T) fc1();
       hashes(t, tid);
@@ -452,7 +428,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
         const unsigned lm = t <= oi_len[j] ? 0xffffffffu : 0u, fm = t < oi_len[j] ? 0xffffffffu : 0u;
         u32x4 v;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) v[i] = bits(2.0f * u01(hfin(po, (unsigned)(oi_idx[j] + i))) - 1.0f) & lm;
+        for (int i = 0; i < 4; ++i) v[i] = bits(env_value(po, (unsigned)(oi_idx[j] + i))) & lm;
         *reinterpret_cast<u32x4*>(a.obs + (long)oi_off[j] + tNO) = v;
         if (to_lds) {
           f32x4 w;
@@ -476,8 +452,8 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
       const int par = t & 1;
       const float eps = eps_next;
       if (a.eps) { if (t + 1 < T) eps_next = a.eps[t + 1]; }
-      else { eps_d = eps_d > a.eps_min ? eps_d - a.eps_anneal : eps_d; eps_next = (float)eps_d; }
-      const unsigned tg = (unsigned)(a.episode * (T + 1) + t);
+      else { eps_d = eps_anneal_step(eps_d, a.eps_anneal, a.eps_min); eps_next = (float)eps_d; }
+      const unsigned tg = env_tg(a.episode, T, t);
       // ---- P1: the observations of slot t+1 -> record, and (steps that feed the network) -> input planes
       gen_obs_items(t + 1, t + 1 < T);
       ST_MARK(0);
@@ -497,7 +473,7 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_x6_kernel(RX6Args a) {
         if (live) {
           const unsigned pre_ = (pre_r && t > 0) ? pfxS[rows / 2 + (t & 1) * (rows / 4) + es_el]
                                                  : hprefix(a.seed, ST_REWARD, (unsigned)(a.env0 + b0 + es_el), tg);
-          term = u01(hfin(pre_, (unsigned)(es_n * A + act[es_el * N + es_n]))) - 0.5f;
+          term = env_reward_term(pre_, (unsigned)(es_n * A + act[es_el * N + es_n]));
         }
         float acc = 0.f;
         for (int n0 = 0; n0 < N; n0 += 4) {          // four shuffles in flight; the sum stays in agent order
@@ -552,52 +528,33 @@ __attribute__((visibility("hidden"))) int marl_rollout_x6_v1_supported(int N, in
   return rx6_lds(KI > 96 ? 2 : 3, KI, A) <= 160 * 1024 ? 1 : 0;
 }
 
+// environments per workgroup: even rounds of workgroups of up to three row tiles (five fc1 chunks: two - registers)
+__attribute__((visibility("hidden"))) int marl_rollout_x6_v1_epw(int E, int N, int KI) {
+  const int epw_max = (KI > 96 ? 32 : 48) / N;
+  return epw_max < 1 ? 0 : even_rounds_epw(E, epw_max);
+}
+
 __attribute__((visibility("hidden"))) int marl_rollout_x6_v1(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
                                      int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
                                      float* r, float* term, float* padded, int* length, int* won, float* h_out,
                                      float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
                                      int O, int S, int A, int last_action, int reuse_network, void* stream) {
   if (E <= 0 || T <= 0) return 0;
-  if (w->H != H || state_ld < S || !marl_rollout_x6_v1_supported(N, O, A)) return (int)hipErrorInvalidValue;
-  if (reinterpret_cast<uintptr_t>(obs) & 15) return (int)hipErrorInvalidValue;
+  if (!marl_rollout_x6_v1_supported(N, O, A) || (reinterpret_cast<uintptr_t>(obs) & 15)) return (int)hipErrorInvalidValue;
   RX6Args a;
-  a.W1 = w->fc1_w; a.b1 = w->fc1_b; a.Wih = w->w_ih; a.Whh = w->w_hh; a.bih = w->b_ih; a.bhh = w->b_hh;
-  a.W2 = w->fc2_w; a.b2 = w->fc2_b;
-  a.eps = eps; a.eps0 = eps0; a.eps_anneal = eps_anneal; a.eps_min = eps_min; a.obs = obs; a.state = state; a.SL = state_ld; a.avail = avail;
-  a.u = u; a.r = r; a.term = term; a.padded = padded; a.length = length; a.won = won; a.h_out = h_out; a.stats = stats;
-  a.seed = seed; a.rseed = rseed; a.env0 = env0; a.episode = episode; a.fixed_len = fixed_len;
-  a.E = E; a.T = T; a.N = N; a.O = O; a.S = S; a.A = A;
-  a.has_act = last_action ? 1 : 0; a.has_id = reuse_network ? 1 : 0;
-  a.I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
+  if (const int e = rollout_args(a, w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded,
+                                 length, won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network))
+    return e;
   a.KI = (a.I + 31) / 32 * 32;
-  a.R = (long)E * N;
-  // record offsets are 32-bit element offsets inside the kernel
-  if ((double)E * (T + 1) * N * (O > A ? O : A) >= 2147483648.0 || (double)E * (T + 1) * state_ld >= 2147483648.0)
-    return (int)hipErrorInvalidValue;
-  // environments per workgroup: one workgroup per CU while the batch fits one round (small batches spread over all CUs with partly
-  // filled tiles); beyond that as few FULL rounds of 256 workgroups as three row tiles per workgroup allow, evenly filled
   const int nk1 = a.KI > 96 ? 5 : 3;
-  const int epw_max = (nk1 == 3 ? 48 : 32) / N;            // (five fc1 chunks: two row tiles per workgroup - registers)
-  if (epw_max < 1) return (int)hipErrorInvalidValue;
-  int epw = (E + 255) / 256;
-  if (epw > epw_max) {
-    const int rounds = (E + 256 * epw_max - 1) / (256 * epw_max);
-    epw = (E + 256 * rounds - 1) / (256 * rounds);
-    if (epw > epw_max) epw = epw_max;
-  }
+  const int epw = marl_rollout_x6_v1_epw(E, N, a.KI);
+  if (epw < 1) return (int)hipErrorInvalidValue;
   a.EPW = epw;
   const int rtc = (epw * N + 15) / 16;
   const size_t lds = rx6_lds(rtc, a.KI, A);
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-  dim3 grid((unsigned)((E + epw - 1) / epw)), block(RNT);
   const void* fn;
   if (nk1 == 3) fn = rtc == 1 ? (const void*)synth_rollout_x6_kernel<1, 3> : rtc == 2 ? (const void*)synth_rollout_x6_kernel<2, 3> : (const void*)synth_rollout_x6_kernel<3, 3>;
   else fn = rtc == 1 ? (const void*)synth_rollout_x6_kernel<1, 5> : (const void*)synth_rollout_x6_kernel<2, 5>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  if (e != hipSuccess) return (int)e;
-  void* kargs[] = {(void*)&a};
-  e = hipLaunchKernel(fn, grid, block, kargs, lds, (hipStream_t)stream);
-  if (e != hipSuccess) return (int)e;
-  MARL_CHECK_LAUNCH();
-  return 0;
+  return launch_rollout(fn, (E + epw - 1) / epw, lds, a, stream);
 }
