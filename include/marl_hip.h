@@ -526,6 +526,36 @@ int marl_synth_rollout_x6(const marl_agent_weights_t* w, unsigned seed, unsigned
                           float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int O, int S,
                           int A, int last_action, int reuse_network, void* stream);
 
+/* ---- RTW reflection head (rtw_head.hip) -------------------------------------------------------
+ * The parts of RTWAgent (network/RTW.py:16-57) beyond the RNNQNet agent, torch layouts, hidden_dim = attn_dim = 64:
+ *   t0 (64, 64+N), t2 (A, 64)      teammate_net.0 / .2
+ *   w0 (64, O+N*A), w2 (O, 64)     world_net.0 / .2
+ *   wq (64, 2O), wk (64, A)        w_q, w_k
+ *   v0 (64, 64+A), v2 (A, 64)      w_v.0 / .2 */
+typedef struct {
+  const float *t0_w, *t0_b, *t2_w, *t2_b;
+  const float *w0_w, *w0_b, *w2_w, *w2_b;
+  const float *wq_w, *wq_b, *wk_w, *wk_b;
+  const float *v0_w, *v0_b, *v2_w, *v2_b;
+} marl_rtw_weights_t;
+/* 1 when the head kernels cover the shape: H = hidden_dim = attn_dim = 64, 1 <= N <= 16, 1 <= A <= 32, 1 <= O <= 256. */
+int marl_rtw_supported(int N, int O, int A, int H, int hidden_dim, int attn_dim);
+/* Act mode (test_mode=True, RTW.py:70-119; RTWMAC.choose_action share_params.py:641-677 for every agent of E envs at once):
+ * q (E*N, A) += the reflection term of each row.  h (E*N, 64) = the GRU output of the step; o of row (e, n) at
+ * obs + (e*obs_bs + obs_t0*N + n)*O and avail of agent j at avail + (e*av_bs + av_t0*N + j)*A (the (ptr, bs, t0) slot
+ * convention of marl_agent_unroll_fwd).  not_self_model as args.not_self_model.  Optional outputs (NULL to skip): a_out
+ * (E*N, N) int32 teammate actions a_j of each row (the self entry included), ohat_out (E*N, O) the world net's o_hat. */
+int marl_rtw_head_act(const marl_rtw_weights_t* w, const float* h, const float* obs, long obs_bs, int obs_t0,
+                      const float* avail, long av_bs, int av_t0, float* q, int* a_out, float* ohat_out, int E, int N,
+                      int O, int A, int not_self_model, void* stream);
+/* Given mode (target=False, RTW.py:121-203; RTWMAC.get_current_q_values share_params.py:730-764) over B episodes x T steps:
+ * q (B,T,N,A) += the reflection term with the taken actions u and the real o_next; the value of teammate j is computed
+ * from hs of row j (RTW.py:122: h_repeat[b,i,j] = h[b,j]).  hs (B,T,N,64) as marl_agent_unroll_fwd writes it; o at
+ * obs + (b*obs_bs + (t+obs_t0)*N + n)*O, o_next likewise, u int32 at u[b*u_bs + (t+u_t0)*N + n] (< 0 reads as 0). */
+int marl_rtw_head_given(const marl_rtw_weights_t* w, const float* hs, const float* obs, long obs_bs, int obs_t0,
+                        const float* obs_next, long on_bs, int on_t0, const int* u, long u_bs, int u_t0, float* q,
+                        int B, int T, int N, int O, int A, int not_self_model, void* stream);
+
 const char* marl_hip_version(void);
 
 /* Experiment switches (A/B measurements, variant tests): one table per process; NO entry point reads the environment.

@@ -47,6 +47,11 @@ class MarlQtranWeights(C.Structure):
                 ("q2_w", C.c_void_p), ("q2_b", C.c_void_p), ("q4_w", C.c_void_p), ("q4_b", C.c_void_p)]
 
 
+class MarlRtwWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("t0_w", "t0_b", "t2_w", "t2_b", "w0_w", "w0_b", "w2_w", "w2_b",
+                                          "wq_w", "wq_b", "wk_w", "wk_b", "v0_w", "v0_b", "v2_w", "v2_b")]
+
+
 class MarlAgentGrads(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p),
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
@@ -64,6 +69,7 @@ AG = C.POINTER(MarlAgentGrads)
 QW = C.POINTER(MarlQmixWeights)
 M3 = C.POINTER(MarlMlp3Weights)
 QT = C.POINTER(MarlQtranWeights)
+RW = C.POINTER(MarlRtwWeights)
 
 # name -> (restype, argtypes); must list every symbol of include/marl_hip.h
 SIGNATURES = {
@@ -148,6 +154,9 @@ SIGNATURES = {
     "marl_synth_rollout_x6_supported_flags": (I, [I, I, I, I, I]),
     "marl_synth_rollout_x6_plan": (I, [I, I, I, I, I, I, P]),
     "marl_synth_rollout_x6": (I, [AW, U, U, I, I, I, P, P, P, L, P, P, P, P, P, P, P, P, P, D, D, D, I, I, I, I, I, I, I, I, P]),
+    "marl_rtw_supported": (I, [I, I, I, I, I, I]),
+    "marl_rtw_head_act": (I, [RW, P, P, L, I, P, L, I, P, P, P, I, I, I, I, I, P]),
+    "marl_rtw_head_given": (I, [RW, P, P, L, I, P, L, I, P, L, I, P, I, I, I, I, I, I, P]),
     "marl_hip_version": (C.c_char_p, []),
     "marl_experiment_set": (I, [C.c_char_p, I]),
     "marl_experiment_get": (I, [C.c_char_p]),

@@ -13,6 +13,7 @@ import torch
 from .. import ops
 from ..hostutil import require_cuda, to_dev, onehot_to_index, flatten_module
 from ..network.q_network import RNNQNet
+from ..network.rtw import RTWAgent
 
 
 class SharedMAC:
@@ -182,5 +183,64 @@ class SharedMACWithState(_Unsupported):
     pass
 
 
-class RTWMAC(_Unsupported):
-    pass
+class RTWMAC(SharedMAC):
+    """reference controller/share_params.py:612-804: SharedMAC over an RTWAgent.  Inference only: choose_action (act mode,
+    :641-677) and get_current_q_values (given mode, :730-764) run the agent unroll followed by the reflection head
+    (csrc/rtw_head.hip).  get_next_q_values fails with the reference's TypeError (RTWAgent.forward target=True), so
+    RTWQLearner.train cannot run - in the reference either."""
+
+    rtw = True
+
+    def _build_agents(self, input_shape):
+        self.agent = RTWAgent(input_shape, self.args)
+
+    def not_self_model(self):
+        return bool(getattr(self.args, "not_self_model", True))
+
+    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
+        """One agent, one env; avail_actions covers EVERY agent (rollout.py:73-74).  Same numpy draw order as SharedMAC."""
+        dev = self.device()
+        N, A, O = self.n_agents, self.n_actions, self.obs_shape
+        avail_all = np.asarray(avail_actions, dtype=np.float32).reshape(N, A)
+        avail_ind = np.nonzero(avail_all[agent_num])[0]
+        la = -1
+        if self.args.last_action:
+            nz = np.nonzero(np.asarray(last_action))[0]
+            la = int(nz[0]) if nz.size else -1
+        obs_full = torch.zeros(1, 1, N, O, device=dev)
+        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
+        ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
+        ufed[0, 0, agent_num] = la
+        q = torch.empty(1, 1, N, A, device=dev)
+        h_in = self.hidden_states.reshape(N, -1).contiguous()
+        h_out = torch.empty_like(h_in)
+        ops.agent_unroll_fwd(self.agent.weights(), obs_full, N, 0, ufed, N, 0, h_in, q, None, h_out, None,
+                             1, 1, N, O, A, self.args.last_action, self.args.reuse_network)
+        # the head reads row agent_num's h and o and every agent's availability; the other rows of the tile are discarded
+        ops.rtw_head_act(self.agent.rtw_weights(), h_out, obs_full, N, 0, to_dev(avail_all, dev), N, 0, q, 1, N, O, A,
+                         self.not_self_model())
+        self.hidden_states[0, agent_num] = h_out[agent_num]
+        q_value = q[0, 0, agent_num].cpu()
+        q_value[torch.as_tensor(avail_all[agent_num]) == 0.0] = -float("inf")
+        if np.random.uniform() < epsilon:
+            return np.random.choice(avail_ind)
+        return torch.argmax(q_value)
+
+    def get_current_q_values(self, batch, max_episode_len):
+        """(q, hs, 0.0, 0.0) - reference :730-764: the unroll, then the given-mode head with the taken actions and o_next."""
+        T = max_episode_len
+        q, hs = self._batch_unroll(batch, T, "cur")
+        dev = q.device
+        N, A, O = self.n_agents, self.n_actions, self.obs_shape
+        B = q.shape[0]
+        o = to_dev(batch["o"][:, :T], dev)
+        on = to_dev(batch["o_next"][:, :T], dev)
+        u = to_dev(batch["u"][:, :T], dev, torch.int32).view(B, T, N)
+        ops.rtw_head_given(self.agent.rtw_weights(), hs, o, T * N, 0, on, T * N, 0, u, T * N, 0, q, B, T, N, O, A,
+                           self.not_self_model())
+        return q, hs, 0.0, 0.0
+
+    def get_next_q_values(self, batch, max_episode_len):
+        """reference :766-789 passes obs_next = None and u = None into RTWAgent.forward, which fails (RTW.py:178)."""
+        raise TypeError("RTWMAC.get_next_q_values: the reference's target pass concatenates obs with obs_next = None "
+                        "(network/RTW.py:178); RTW training is not defined")

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import sys
 
-from .common.arguments import get_common_args, get_mixer_args
+from .common.arguments import get_common_args, get_mixer_args, get_RTW_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .runner import Runner
@@ -21,6 +21,7 @@ MAPS = {"2s3z": (5, 80, 120, 11, 120), "3s5z": (8, 128, 216, 14, 150), "MMM2": (
 def build(argv=None):
     args = get_common_args(argv)
     get_mixer_args(args)
+    get_RTW_args(args)
     if args.env == 'smac':
         args.env = 'synthetic'
     if args.env == 'synthetic':

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
-                   MarlQtranWeights, check)
+                   MarlQtranWeights, MarlRtwWeights, check)
 
 
 def _p(t):
@@ -717,3 +717,40 @@ def qtran_head_bwd(w, hidden, u, d_out, y1, y2, dy1, dy2, de2, dhidden, accumula
                                   _p(_f32(dy1)), _p(_f32(dy2)), _p(_f32(de2)), _p(_f32(dhidden)), 1 if accumulate else 0,
                                   _p(_f32(d_enc0_w)), _p(_f32(d_enc0_b)), _p(_f32(d_enc2_b)), _p(ws), ws.numel() * 4,
                                   BT, N, A, AE, _stream()), "marl_qtran_head_bwd")
+
+
+# ---- RTW reflection head (csrc/rtw_head.hip)
+RTW_KEYS = (("t0", "teammate_net.0"), ("t2", "teammate_net.2"), ("w0", "world_net.0"), ("w2", "world_net.2"),
+            ("wq", "w_q"), ("wk", "w_k"), ("v0", "w_v.0"), ("v2", "w_v.2"))
+
+
+def rtw_supported(N, O, A, H=64, hidden_dim=64, attn_dim=64):
+    return bool(_lib.load().marl_rtw_supported(N, O, A, H, hidden_dim, attn_dim))
+
+
+def rtw_weights(params):
+    """params: dict name -> tensor with RTWAgent keys (network/RTW.py:24-56) -> marl_rtw_weights_t."""
+    w = MarlRtwWeights()
+    for short, name in RTW_KEYS:
+        for suf, key in (("_w", ".weight"), ("_b", ".bias")):
+            t = params[name + key]
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda, name + key
+            setattr(w, short + suf, t.data_ptr())
+    w._keep = params
+    return w
+
+
+def rtw_head_act(w, h, obs, obs_bs, obs_t0, avail, av_bs, av_t0, q, E, N, O, A, not_self_model=True, a_out=None,
+                 ohat_out=None):
+    """q (E*N, A) += the act-mode reflection term (RTWAgent.forward test_mode=True, network/RTW.py:70-119)."""
+    check(_lib.load().marl_rtw_head_act(C.byref(w), _p(_f32(h)), _p(_f32(obs)), obs_bs, obs_t0, _p(_f32(avail)), av_bs, av_t0,
+                                        _p(_f32(q)), _p(_i32(a_out)) if a_out is not None else None,
+                                        _p(_f32(ohat_out)) if ohat_out is not None else None, E, N, O, A,
+                                        1 if not_self_model else 0, _stream()), "marl_rtw_head_act")
+
+
+def rtw_head_given(w, hs, obs, obs_bs, obs_t0, obs_next, on_bs, on_t0, u, u_bs, u_t0, q, B, T, N, O, A, not_self_model=True):
+    """q (B,T,N,A) += the given-mode reflection term (RTWAgent.forward target=False, network/RTW.py:121-203)."""
+    check(_lib.load().marl_rtw_head_given(C.byref(w), _p(_f32(hs)), _p(_f32(obs)), obs_bs, obs_t0, _p(_f32(obs_next)), on_bs,
+                                          on_t0, _p(_i32(u)), u_bs, u_t0, _p(_f32(q)), B, T, N, O, A,
+                                          1 if not_self_model else 0, _stream()), "marl_rtw_head_given")

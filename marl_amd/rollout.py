@@ -6,6 +6,8 @@
   device: per step one observe kernel, one agent-step kernel (the T=1 unroll), one epsilon-greedy
   selection kernel, one env-step kernel; the episode record never leaves HBM.
   Epsilon is annealed once per lock-step (quirk Q7 kept for n_envs = 1).
+  With an RTW controller (RTWMAC) the reflection head (csrc/rtw_head.hip, act mode) runs between the agent step and the
+  selection; such rollouts always take this per-step path (the whole-rollout kernels have no head).
 """
 from __future__ import annotations
 
@@ -151,7 +153,8 @@ class RolloutWorker:
         if a.replay_dir != '' and evaluate:
             env.close()
         mode = getattr(self, "rollout_mode", "whole")      # "whole" | "fused_step" | "unfused" (tests)
-        if mode == "whole" and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
+        rtw = getattr(mac, "rtw", False)
+        if mode == "whole" and not rtw and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
             # the persistent kernel writes every field of the record, so training rollouts can be
             # played straight into the replay ring (record_sink = the ReplayBuffer; zero-copy store)
             sink = getattr(self, "record_sink", None)
@@ -175,12 +178,16 @@ class RolloutWorker:
         if a.epsilon_anneal_scale == 'episode':
             epsilon = epsilon - self.anneal_epsilon if epsilon > self.min_epsilon else epsilon
         w = mac.agent.weights()
+        w_rtw = mac.agent.rtw_weights() if rtw else None
         fused = hasattr(env, "fused_step") and mode != "unfused"
         env.observe(0, rec)
         for t in range(T):
             # agent step = the unroll kernel with T=1 reading slot t of the record in place
             ops.agent_unroll_fwd(w, rec.obs, (T + 1) * N, t, rec.u, T * N, t - 1, h, q, None, h, None,
                                  E, 1, N, O, A, a.last_action, a.reuse_network)
+            if rtw:     # q += the reflection term (RTWMAC.choose_action for every agent, share_params.py:641-677)
+                ops.rtw_head_act(w_rtw, h, rec.obs, (T + 1) * N, t, rec.avail, (T + 1) * N, t, q, E, N, O, A,
+                                 mac.not_self_model())
             if fused:
                 env.fused_step(t, q, epsilon, self.rseed, rec)
             else:
@@ -237,6 +244,8 @@ class RolloutWorker:
         on the CURRENT stream (a side stream in the overlapped runner) and return a handle for finish_episodes().
         ``mac``: the controller whose weights the rollout reads (a snapshot while the learner updates the live one)."""
         env = self.env
+        if getattr(mac if mac is not None else self.mac, "rtw", False):
+            raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no RTW head: use generate_episodes")
         if not (getattr(env, "batched", False) and hasattr(env, "whole_rollout") and env.supports_whole_rollout()):
             raise RuntimeError("launch_episodes needs a batched env with the whole-rollout kernel")
         dev = require_cuda("RolloutWorker")
@@ -296,8 +305,10 @@ class RolloutWorker:
                         while avail_actions[agent_id][action] == 0:
                             action = np.random.randint(0, A - 1)
                     else:
+                        # RTW: every agent's availability (rollout.py:73-76)
                         action = self.mac.choose_action(obs[agent_id], last_actions[agent_id], agent_id,
-                                                        avail_actions[agent_id], epsilon, evaluate)
+                                                        avail_actions if getattr(a, "RTW", False) else avail_actions[agent_id], epsilon,
+                                                        evaluate)
                     onehot = np.zeros(A)
                     onehot[action] = 1
                     actions.append(action)

@@ -9,6 +9,11 @@ of one update - the reference has lag 0, which is why this is off by default), w
 excludes, and the cadence of runner.py:85-98 (store -> train_steps updates -> log -> save) is unchanged.
 ``"lag1_serial"`` runs the same schedule on one stream (the parity check of the overlapped mode: identical losses).
 
+``args.RTW`` (with reuse_network, reference runner.py:20-23,46-49): RTWMAC and RTWQLearner.  Evaluation and rollouts run
+(the per-step path; no overlapped rollouts); training raises the reference's TypeError.  Divergence: the reference pairs
+RTWMAC with the plain QTRANLearner for qtran_base / qtran_alt, which cannot run on an RTW controller; here that
+combination raises NotImplementedError.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -20,19 +25,26 @@ import numpy as np
 import torch
 
 from .rollout import RolloutWorker
-from .controller.share_params import SharedMAC
+from .controller.share_params import SharedMAC, RTWMAC
 from .common.replaybuffer import ReplayBuffer
 from .algorithm.q_learner import QLearner
 from .algorithm.qtran_learner import QTRANLearner
+from .algorithm.rtw_q_learner import RTWQLearner
 from .utils.logging import Logger
 
 
 class Runner:
     def __init__(self, env, logger, args):
         self.env = env
-        if not args.reuse_network or getattr(args, "RTW", False):
-            raise NotImplementedError("only the shared-parameter controller (reuse_network, RTW off) is on the hot path")
-        self.mac = SharedMAC(args)
+        if not args.reuse_network:
+            raise NotImplementedError("only the shared-parameter controller (reuse_network) is on the hot path")
+        rtw = bool(getattr(args, "RTW", False))
+        if rtw and (args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1):
+            raise NotImplementedError("RTW with a QTRAN learner is not supported (the reference's QTRANLearner cannot "
+                                      "drive an RTW controller)")
+        if rtw and getattr(args, "overlap_rollout", False):
+            raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no RTW head")
+        self.mac = RTWMAC(args) if rtw else SharedMAC(args)
         self.rolloutWorker = RolloutWorker(env, self.mac, args)
         self.buffer = ReplayBuffer(args)
         self.rolloutWorker.record_sink = self.buffer   # batched rollouts write into the replay ring in place
@@ -47,7 +59,7 @@ class Runner:
         logger.setup_tb(self.save_path + '/tb/other')
         self.logger = logger
         if any(args.alg.find(a) > -1 for a in ('vdn', 'qmix', 'qplex')):
-            self.learner = QLearner(self.mac, args)
+            self.learner = RTWQLearner(self.mac, logger, args) if rtw else QLearner(self.mac, args)
         elif args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1:
             self.learner = QTRANLearner(self.mac, args)
         else:
