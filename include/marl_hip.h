@@ -556,6 +556,46 @@ int marl_rtw_head_given(const marl_rtw_weights_t* w, const float* hs, const floa
                         const float* obs_next, long on_bs, int on_t0, const int* u, long u_bs, int u_t0, float* q,
                         int B, int T, int N, int O, int A, int not_self_model, void* stream);
 
+/* ---- world-model head (world_head.hip) --------------------------------------------------------
+ * The WorldModel of network/world_model.py:7-41 (the part of world_model.Agent beyond the RNNQNet agent), torch layouts,
+ * rnn_hidden_dim = 64:  h0 (64,64), h2 (64,64) world.hidden_embd.0 / .2;  r (A,64) world.r_out;  o (O,64) world.o_out;
+ * t (2,64) world.terminate_out.  e = relu(h2 relu(h0 h + b) + b) (:33), r = r_out(e), o_hat = o_out(e), tau = terminate_out(e). */
+typedef struct {
+  const float *h0_w, *h0_b, *h2_w, *h2_b;
+  const float *r_w, *r_b, *o_w, *o_b, *t_w, *t_b;
+} marl_world_weights_t;
+/* Gradient destinations of the same layers (accumulated into; terminate_out gets none: tau never reaches a loss). */
+typedef struct {
+  float *h0_w, *h0_b, *h2_w, *h2_b;
+  float *r_w, *r_b, *o_w, *o_b;
+} marl_world_grads_t;
+/* 1 when the head kernels cover the shape: H = 64, 1 <= N <= 16, 1 <= A <= 32, 1 <= O <= 256. */
+int marl_world_supported(int N, int O, int A, int H);
+/* Forward over R = B*T*N rows (world_model.py:44-75 after the GRU; SharedMACWithState.get_current_q_values /
+ * get_next_q_values share_params.py:303-375, choose_action :214-260 with B = E environments and T = 1):
+ *   h (R,64): the hs plane marl_agent_unroll_fwd writes, or the (E*N,64) state of a rollout step
+ *   q (R,A) += r (world_model.py:71: q = fc2(h) + r), or NULL; optional outputs r_out (R,A), ohat_out (R,O), tau_out (R,2)
+ *   Act mode: loss == NULL.  Train mode (loss != NULL): loss[0] += sum over the rows of (o_hat - o_next)^2
+ *   (q_learner_state.py:175-181 before the mean; unmasked).  o_next of row (b,t,n) is read with the unroll's addressing:
+ *   obs + ((m(b)*obs_bs) + (t+obs_t0)*N + n)*O with m(b) = ep_map ? ep_map[b] : b; steps t >= ep_len[b] read as zeros
+ *   (ep_len may be NULL).  ws: marl_world_fwd_workspace() bytes of per-workgroup partials, summed in a fixed order. */
+size_t marl_world_fwd_workspace(int B, int T, int N);
+int marl_world_head_fwd(const marl_world_weights_t* w, const float* h, float* q, float* r_out, float* ohat_out,
+                        float* tau_out, const float* obs, long obs_bs, int obs_t0, const int* ep_len, const int* ep_map,
+                        float* loss, float* ws, size_t ws_bytes, int B, int T, int N, int O, int A, void* stream);
+/* Backward of the train-mode forward (autograd of q_learner_state.py:100-181 through the head, loss.backward() :184):
+ *   dr = the sparse pair (dq_idx, dq_val) per row that marl_agent_unroll_bwd also receives (dr = dq; dq_idx NULL: none)
+ *   d_o_hat = dscale * den[0] * (o_hat - o_next), o_next addressed as in the forward (den NULL: 1).  With dscale = 2 / K,
+ *   K = B*T*N*O and den = sum(mask) the optimizer's division by den (marl_rmsprop_step / marl_adam_step) leaves d mean / d o_hat.
+ *   dhs (R,64) = the gradient on hs (written), for marl_agent_unroll_bwd's dhs input; the weight and bias gradients of
+ *   h0, h2, r, o are accumulated into g by fixed-order reductions (marl_linear_wgrad).  Activations are recomputed from hs.
+ *   ws: marl_world_bwd_workspace() bytes. */
+size_t marl_world_bwd_workspace(int B, int T, int N, int O, int A);
+int marl_world_head_bwd(const marl_world_weights_t* w, const marl_world_grads_t* g, const float* hs, const int* dq_idx,
+                        const float* dq_val, const float* obs, long obs_bs, int obs_t0, const int* ep_len, const int* ep_map,
+                        const float* den, float dscale, float* dhs, float* ws, size_t ws_bytes, int B, int T, int N, int O,
+                        int A, void* stream);
+
 const char* marl_hip_version(void);
 
 /* Experiment switches (A/B measurements, variant tests): one table per process; NO entry point reads the environment.

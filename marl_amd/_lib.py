@@ -52,6 +52,14 @@ class MarlRtwWeights(C.Structure):
                                           "wq_w", "wq_b", "wk_w", "wk_b", "v0_w", "v0_b", "v2_w", "v2_b")]
 
 
+class MarlWorldWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("h0_w", "h0_b", "h2_w", "h2_b", "r_w", "r_b", "o_w", "o_b", "t_w", "t_b")]
+
+
+class MarlWorldGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("h0_w", "h0_b", "h2_w", "h2_b", "r_w", "r_b", "o_w", "o_b")]
+
+
 class MarlAgentGrads(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p),
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
@@ -70,6 +78,7 @@ QW = C.POINTER(MarlQmixWeights)
 M3 = C.POINTER(MarlMlp3Weights)
 QT = C.POINTER(MarlQtranWeights)
 RW = C.POINTER(MarlRtwWeights)
+WW, WG = C.POINTER(MarlWorldWeights), C.POINTER(MarlWorldGrads)
 
 # name -> (restype, argtypes); must list every symbol of include/marl_hip.h
 SIGNATURES = {
@@ -157,6 +166,11 @@ SIGNATURES = {
     "marl_rtw_supported": (I, [I, I, I, I, I, I]),
     "marl_rtw_head_act": (I, [RW, P, P, L, I, P, L, I, P, P, P, I, I, I, I, I, P]),
     "marl_rtw_head_given": (I, [RW, P, P, L, I, P, L, I, P, L, I, P, I, I, I, I, I, I, P]),
+    "marl_world_supported": (I, [I, I, I, I]),
+    "marl_world_fwd_workspace": (SZ, [I, I, I]),
+    "marl_world_head_fwd": (I, [WW, P, P, P, P, P, P, L, I, P, P, P, P, SZ, I, I, I, I, I, P]),
+    "marl_world_bwd_workspace": (SZ, [I, I, I, I, I]),
+    "marl_world_head_bwd": (I, [WW, WG, P, P, P, P, L, I, P, P, P, F, P, P, SZ, I, I, I, I, I, P]),
     "marl_hip_version": (C.c_char_p, []),
     "marl_experiment_set": (I, [C.c_char_p, I]),
     "marl_experiment_get": (I, [C.c_char_p]),

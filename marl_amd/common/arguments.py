@@ -14,6 +14,8 @@ def _bool(v):
 def get_common_args(argv=None):
     p = argparse.ArgumentParser()
     p.add_argument('--RTW', type=_bool, default=False)
+    # not in the reference's parser (its runner never builds SharedMACWithState + QLearnerWithState): the world-model agent
+    p.add_argument('--world_model', type=_bool, default=False)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')

@@ -14,6 +14,7 @@ from .. import ops
 from ..hostutil import require_cuda, to_dev, onehot_to_index, flatten_module
 from ..network.q_network import RNNQNet
 from ..network.rtw import RTWAgent
+from ..network.world_model import Agent as WorldAgent
 
 
 class SharedMAC:
@@ -179,8 +180,65 @@ class SeparatedMAC(_Unsupported):
     """name kept for `from controller.share_params import ...` (reference runner.py:4); the reference class is broken."""
 
 
-class SharedMACWithState(_Unsupported):
-    pass
+class SharedMACWithState(SharedMAC):
+    """reference controller/share_params.py:185-387: SharedMAC over a world_model.Agent, whose Q values include the world
+    head's r (network/world_model.py:71).  Every pass is the agent unroll followed by the head (csrc/world_head.hip)."""
+
+    world = True
+
+    def _build_agents(self, input_shape):
+        self.agent = WorldAgent(input_shape, self.args)
+
+    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
+        """One agent, one env (reference :214-260): SharedMAC's with q + r, same numpy draw order."""
+        dev = self.device()
+        N, A, O = self.n_agents, self.n_actions, self.obs_shape
+        avail = np.asarray(avail_actions)
+        avail_ind = np.nonzero(avail)[0]
+        la = -1
+        if self.args.last_action:
+            nz = np.nonzero(np.asarray(last_action))[0]
+            la = int(nz[0]) if nz.size else -1
+        obs_full = torch.zeros(1, 1, N, O, device=dev)
+        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
+        ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
+        ufed[0, 0, agent_num] = la
+        q = torch.empty(1, 1, N, A, device=dev)
+        h_in = self.hidden_states.reshape(N, -1).contiguous()
+        h_out = torch.empty_like(h_in)
+        ops.agent_unroll_fwd(self.agent.weights(), obs_full, N, 0, ufed, N, 0, h_in, q, None, h_out, None,
+                             1, 1, N, O, A, self.args.last_action, self.args.reuse_network)
+        ops.world_head_fwd(self.agent.world_weights(), h_out, q, 1, 1, N, O, A)
+        self.hidden_states[0, agent_num] = h_out[agent_num]
+        q_value = q[0, 0, agent_num].cpu()
+        q_value[torch.as_tensor(avail, dtype=torch.float32) == 0.0] = -float("inf")
+        if np.random.uniform() < epsilon:
+            return np.random.choice(avail_ind)
+        return torch.argmax(q_value)
+
+    def head(self, hs, q, B, T, with_ohat=True, with_tau=True):
+        """q (B,T,N,A) += r from hs (B,T,N,64); returns the reference's `returns` dict (:303-375) without ep_hidden_states"""
+        dev = hs.device
+        N, A, O = self.n_agents, self.n_actions, self.obs_shape
+        r = torch.empty(B, T, N, A, device=dev)
+        ohat = torch.empty(B, T, N, O, device=dev) if with_ohat else None
+        tau = torch.empty(B, T, N, 2, device=dev) if with_tau else None
+        ops.world_head_fwd(self.agent.world_weights(), hs, q, B, T, N, O, A, r_out=r, ohat_out=ohat, tau_out=tau)
+        return {"r": r, "o_next": ohat, "terminated": tau}
+
+    def _world_q_values(self, batch, T, which):
+        q, hs = self._batch_unroll(batch, T, which)
+        returns = {"ep_hidden_states": hs}
+        returns.update(self.head(hs, q, q.shape[0], T))
+        return q, returns
+
+    def get_current_q_values(self, batch, max_episode_len):
+        """(q + r, returns{ep_hidden_states, r, o_next, terminated}) - reference :303-338"""
+        return self._world_q_values(batch, max_episode_len, "cur")
+
+    def get_next_q_values(self, batch, max_episode_len):
+        """reference :340-375 (inputs o_next, u_onehot[t])"""
+        return self._world_q_values(batch, max_episode_len, "next")
 
 
 class RTWMAC(SharedMAC):

@@ -1,6 +1,2 @@
-"""Name kept for reference runner.py:10; never constructed by the reference runner."""
-
-
-class QLearnerWithState:
-    def __init__(self, *a, **k):
-        raise NotImplementedError("QLearnerWithState is out of scope")
+"""`from algorithm.q_learner_state import QLearnerWithState` (reference runner.py:10) resolves to the product class."""
+from marl_amd.algorithm.q_learner_state import QLearnerWithState  # noqa: F401

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
-                   MarlQtranWeights, MarlRtwWeights, check)
+                   MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, check)
 
 
 def _p(t):
@@ -754,3 +754,61 @@ def rtw_head_given(w, hs, obs, obs_bs, obs_t0, obs_next, on_bs, on_t0, u, u_bs, 
     check(_lib.load().marl_rtw_head_given(C.byref(w), _p(_f32(hs)), _p(_f32(obs)), obs_bs, obs_t0, _p(_f32(obs_next)), on_bs,
                                           on_t0, _p(_i32(u)), u_bs, u_t0, _p(_f32(q)), B, T, N, O, A,
                                           1 if not_self_model else 0, _stream()), "marl_rtw_head_given")
+
+
+# ---- world-model head (csrc/world_head.hip)
+WORLD_KEYS = (("h0", "world.hidden_embd.0"), ("h2", "world.hidden_embd.2"), ("r", "world.r_out"), ("o", "world.o_out"),
+              ("t", "world.terminate_out"))
+
+
+def world_supported(N, O, A, H=64):
+    return bool(_lib.load().marl_world_supported(N, O, A, H))
+
+
+def _world_struct(cls, params, keys):
+    w = cls()
+    for short, name in keys:
+        for suf, key in (("_w", ".weight"), ("_b", ".bias")):
+            t = params[name + key]
+            assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda, name + key
+            setattr(w, short + suf, t.data_ptr())
+    w._keep = params
+    return w
+
+
+def world_weights(params):
+    """params: dict name -> tensor with world_model.Agent keys (network/world_model.py:12-19) -> marl_world_weights_t."""
+    return _world_struct(MarlWorldWeights, params, WORLD_KEYS)
+
+
+def world_grads(grads):
+    """grads: dict name -> gradient tensor with the same keys (terminate_out not needed) -> marl_world_grads_t."""
+    return _world_struct(MarlWorldGrads, grads, WORLD_KEYS[:4])
+
+
+def world_head_fwd(w, h, q, B, T, N, O, A, r_out=None, ohat_out=None, tau_out=None, obs=None, obs_bs=0, obs_t0=0,
+                   ep_len=None, ep_map=None, loss=None):
+    """q (B*T*N, A) += r (network/world_model.py:71; q may be None).  With `loss` (a one-float device view, e.g. a slot of the
+    loss statistics): train mode, loss += sum (o_hat - o_next)^2 with o_next read through (obs, obs_bs, obs_t0, ep_len, ep_map)."""
+    lib = _lib.load()
+    ws = None
+    if loss is not None:
+        ws = WS.get("world_fwd", lib.marl_world_fwd_workspace(B, T, N), h.device)
+    check(lib.marl_world_head_fwd(C.byref(w), _p(_f32(h)), _p(_f32(q)) if q is not None else None, _p(r_out), _p(ohat_out),
+                                  _p(tau_out), _p(_f32(obs)) if obs is not None else None, obs_bs, obs_t0,
+                                  _p(_i32(ep_len)) if ep_len is not None else None,
+                                  _p(_i32(ep_map)) if ep_map is not None else None, _p(_f32(loss)) if loss is not None else None,
+                                  _p(ws), 0 if ws is None else ws.numel() * 4, B, T, N, O, A, _stream()),
+          "marl_world_head_fwd")
+
+
+def world_head_bwd(w, g, hs, dq_idx, dq_val, obs, obs_bs, obs_t0, den, dscale, dhs, B, T, N, O, A, ep_len=None, ep_map=None):
+    """dhs (B*T*N, 64) = gradient on hs; the head's weight gradients accumulate into `g` (marl_world_grads_t)."""
+    lib = _lib.load()
+    ws = WS.get("world_bwd", lib.marl_world_bwd_workspace(B, T, N, O, A), hs.device)
+    check(lib.marl_world_head_bwd(C.byref(w), C.byref(g), _p(_f32(hs)), _p(_i32(dq_idx)) if dq_idx is not None else None,
+                                  _p(_f32(dq_val)) if dq_val is not None else None, _p(_f32(obs)), obs_bs, obs_t0,
+                                  _p(_i32(ep_len)) if ep_len is not None else None,
+                                  _p(_i32(ep_map)) if ep_map is not None else None, _p(_f32(den)) if den is not None else None,
+                                  float(dscale), _p(_f32(dhs)), _p(ws), ws.numel() * 4, B, T, N, O, A, _stream()),
+          "marl_world_head_bwd")

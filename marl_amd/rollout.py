@@ -154,7 +154,8 @@ class RolloutWorker:
             env.close()
         mode = getattr(self, "rollout_mode", "whole")      # "whole" | "fused_step" | "unfused" (tests)
         rtw = getattr(mac, "rtw", False)
-        if mode == "whole" and not rtw and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
+        world = getattr(mac, "world", False)
+        if mode == "whole" and not rtw and not world and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
             # the persistent kernel writes every field of the record, so training rollouts can be
             # played straight into the replay ring (record_sink = the ReplayBuffer; zero-copy store)
             sink = getattr(self, "record_sink", None)
@@ -179,6 +180,7 @@ class RolloutWorker:
             epsilon = epsilon - self.anneal_epsilon if epsilon > self.min_epsilon else epsilon
         w = mac.agent.weights()
         w_rtw = mac.agent.rtw_weights() if rtw else None
+        w_world = mac.agent.world_weights() if world else None
         fused = hasattr(env, "fused_step") and mode != "unfused"
         env.observe(0, rec)
         for t in range(T):
@@ -188,6 +190,8 @@ class RolloutWorker:
             if rtw:     # q += the reflection term (RTWMAC.choose_action for every agent, share_params.py:641-677)
                 ops.rtw_head_act(w_rtw, h, rec.obs, (T + 1) * N, t, rec.avail, (T + 1) * N, t, q, E, N, O, A,
                                  mac.not_self_model())
+            if world:   # q += r (SharedMACWithState.choose_action for every agent, share_params.py:214-260)
+                ops.world_head_fwd(w_world, h, q, E, 1, N, O, A)
             if fused:
                 env.fused_step(t, q, epsilon, self.rseed, rec)
             else:
@@ -246,6 +250,8 @@ class RolloutWorker:
         env = self.env
         if getattr(mac if mac is not None else self.mac, "rtw", False):
             raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no RTW head: use generate_episodes")
+        if getattr(mac if mac is not None else self.mac, "world", False):
+            raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no world-model head: use generate_episodes")
         if not (getattr(env, "batched", False) and hasattr(env, "whole_rollout") and env.supports_whole_rollout()):
             raise RuntimeError("launch_episodes needs a batched env with the whole-rollout kernel")
         dev = require_cuda("RolloutWorker")

@@ -14,6 +14,11 @@ excludes, and the cadence of runner.py:85-98 (store -> train_steps updates -> lo
 RTWMAC with the plain QTRANLearner for qtran_base / qtran_alt, which cannot run on an RTW controller; here that
 combination raises NotImplementedError.
 
+``args.world_model`` (a switch of this project; the reference runner never builds the pair): SharedMACWithState and
+QLearnerWithState (reference controller/share_params.py:185-387, algorithm/q_learner_state.py) for vdn / qmix / qplex.
+Rollouts take the per-step path.  With RTW it raises ValueError, with qtran_* the reference's ValueError, with overlapped
+rollouts NotImplementedError.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -25,11 +30,12 @@ import numpy as np
 import torch
 
 from .rollout import RolloutWorker
-from .controller.share_params import SharedMAC, RTWMAC
+from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC
 from .common.replaybuffer import ReplayBuffer
 from .algorithm.q_learner import QLearner
 from .algorithm.qtran_learner import QTRANLearner
 from .algorithm.rtw_q_learner import RTWQLearner
+from .algorithm.q_learner_state import QLearnerWithState
 from .utils.logging import Logger
 
 
@@ -44,7 +50,14 @@ class Runner:
                                       "drive an RTW controller)")
         if rtw and getattr(args, "overlap_rollout", False):
             raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no RTW head")
-        self.mac = RTWMAC(args) if rtw else SharedMAC(args)
+        world = bool(getattr(args, "world_model", False))
+        if world and rtw:
+            raise ValueError("world_model and RTW are two different agents: choose one")
+        if world and not any(args.alg.find(a) > -1 for a in ('vdn', 'qmix', 'qplex')):
+            raise ValueError("Mixer {} not recognised.".format(args.alg))     # QLearnerWithState (q_learner_state.py:32)
+        if world and getattr(args, "overlap_rollout", False):
+            raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no world-model head")
+        self.mac = RTWMAC(args) if rtw else SharedMACWithState(args) if world else SharedMAC(args)
         self.rolloutWorker = RolloutWorker(env, self.mac, args)
         self.buffer = ReplayBuffer(args)
         self.rolloutWorker.record_sink = self.buffer   # batched rollouts write into the replay ring in place
@@ -59,7 +72,8 @@ class Runner:
         logger.setup_tb(self.save_path + '/tb/other')
         self.logger = logger
         if any(args.alg.find(a) > -1 for a in ('vdn', 'qmix', 'qplex')):
-            self.learner = RTWQLearner(self.mac, logger, args) if rtw else QLearner(self.mac, args)
+            self.learner = RTWQLearner(self.mac, logger, args) if rtw else \
+                QLearnerWithState(self.mac, args) if world else QLearner(self.mac, args)
         elif args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1:
             self.learner = QTRANLearner(self.mac, args)
         else:
