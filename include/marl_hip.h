@@ -596,6 +596,44 @@ int marl_world_head_bwd(const marl_world_weights_t* w, const marl_world_grads_t*
                         const float* den, float dscale, float* dhs, float* ws, size_t ws_bytes, int B, int T, int N, int O,
                         int A, void* stream);
 
+/* ---- MAIC message head (maic_head.hip) ----------------------------------------------------------
+ * The parts of MAICAgent (network/MAIC.py:19-47) that its forward evaluates beyond the RNNQNet agent, torch layouts, with
+ * rnn_hidden_dim = nn_hidden_size = 64, latent_dim L = 8, attention_dim D = 32 (inference_net only feeds the MI loss):
+ *   e0 (64,64), bn (64) weight / bias / running_mean / running_var / num_batches_tracked (int64), e3 (2*N*L, 64)
+ *                                       embed_net.0 / .1 / .3
+ *   m0 (64, 64+L), m2 (A, 64)           msg_net.0 / .2
+ *   k (D, 64), q (D, L)                 w_key, w_query
+ * bn_rm / bn_rv / bn_nbt are read in eval mode and UPDATED in batch-statistics mode (bn_nbt may be NULL). */
+typedef struct {
+  const float *e0_w, *e0_b, *bn_w, *bn_b;
+  float *bn_rm, *bn_rv;
+  long long* bn_nbt;
+  const float *e3_w, *e3_b, *m0_w, *m0_b, *m2_w, *m2_b, *k_w, *k_b, *q_w, *q_b;
+} marl_maic_weights_t;
+/* 1 when the head kernels cover the shape: H = NH = 64, L = 8, D = 32, 1 <= N <= 16, 1 <= A <= 32 (O only has to be positive:
+ * the head does not read observations). */
+int marl_maic_supported(int N, int O, int A, int H, int NH, int L, int D);
+/* Bytes of scratch the batch-statistics mode needs for bs environments of N agents (eval mode needs none). */
+size_t marl_maic_workspace(int bs, int N);
+/* MAICAgent.forward after fc2 (MAIC.py:58-87) over bs environments x N agents, rows b*N + agent:
+ *   h (bs*N, 64) the GRU output, q (bs*N, A) = fc2(h) on entry, q[b, j] += sum_i alpha[b,i,j] msg[b,i,j] on return (:85).
+ *   test_mode: latent = the means and alpha < 0.25 / N is set to 0 (:63-64, :81-82); otherwise latent = mean + sqrt(var) eps
+ *   with eps (bs*N, N*L) supplied by the caller (:66-68, rsample's noise) and no gate.  var = max(exp(.), var_floor) (:59-61).
+ *   bn_batch 0: BatchNorm1d in eval mode (running statistics), one launch.  bn_batch 1: training mode - statistics of the
+ *   batch over all bs*N rows (biased variance), running_mean / running_var (unbiased) moved by bn_momentum and
+ *   num_batches_tracked += 1; three launches, partial statistics merged in a fixed order (two calls give the same bits);
+ *   needs bs*N >= 2 and ws of marl_maic_workspace() bytes.
+ *   Optional outputs (NULL to skip): mean_out / var_out / lat_out (bs*N, N*L), alpha_out (bs*N, N) after the gate,
+ *   msg_out (bs*N*N, A) with pair row (b*N + i)*N + j (:72). */
+int marl_maic_head_fwd(const marl_maic_weights_t* w, const float* h, float* q, const float* eps, float* mean_out,
+                       float* var_out, float* lat_out, float* alpha_out, float* msg_out, float* ws, size_t ws_bytes, int bs,
+                       int N, int A, int test_mode, int bn_batch, float var_floor, float bn_eps, float bn_momentum,
+                       void* stream);
+/* eps (E*N, N*8) of a sampled-latent rollout step (replaces the torch generator behind rsample, MAIC.py:68): element (n, c) of
+ * environment env0 + e is sqrt(-2 ln(1 - u1)) cos(2 pi u2) with u1, u2 the counter-hash draws 2k, 2k + 1 (k = n*N*8 + c) of
+ * stream 8 keyed by (rseed, env, tg = the global step), as marl_select_actions draws its own. */
+int marl_maic_noise(unsigned rseed, int env0, unsigned tg, float* eps, int E, int N, void* stream);
+
 const char* marl_hip_version(void);
 
 /* Experiment switches (A/B measurements, variant tests): one table per process; NO entry point reads the environment.

@@ -16,6 +16,8 @@ def get_common_args(argv=None):
     p.add_argument('--RTW', type=_bool, default=False)
     # not in the reference's parser (its runner never builds SharedMACWithState + QLearnerWithState): the world-model agent
     p.add_argument('--world_model', type=_bool, default=False)
+    # the reference's parser has no switch for its MAIC agent (network/MAIC.py) either: MAICMAC, inference and rollouts only
+    p.add_argument('--MAIC', type=_bool, default=False)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')
@@ -92,6 +94,16 @@ def _assign(args, table):
 def get_RTW_args(args):
     """reference :48-53 (returns None there as well)"""
     _assign(args, dict(world_loss_weight=1, teammate_loss_weight=1, hidden_dim=64, attn_dim=64, not_self_model=True))
+
+
+def get_maic_args(args):
+    """The MAIC agent's sizes (network/MAIC.py:13-17,59-61 reads them from args).  The reference's arguments.py sets only
+    attention_dim = 32 (:215, get_g2anet_args); latent_dim 8, nn_hidden_size 64 and var_floor 0.002 are the MAIC paper's
+    defaults.  Values the caller already set are kept."""
+    for k, v in dict(latent_dim=8, nn_hidden_size=64, var_floor=0.002, attention_dim=32).items():
+        if not hasattr(args, k):
+            setattr(args, k, v)
+    return args
 
 
 def get_coma_args(args):

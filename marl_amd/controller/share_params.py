@@ -15,6 +15,7 @@ from ..hostutil import require_cuda, to_dev, onehot_to_index, flatten_module
 from ..network.q_network import RNNQNet
 from ..network.rtw import RTWAgent
 from ..network.world_model import Agent as WorldAgent
+from ..network.maic import MAICAgent
 
 
 class SharedMAC:
@@ -302,3 +303,83 @@ class RTWMAC(SharedMAC):
         """reference :766-789 passes obs_next = None and u = None into RTWAgent.forward, which fails (RTW.py:178)."""
         raise TypeError("RTWMAC.get_next_q_values: the reference's target pass concatenates obs with obs_next = None "
                         "(network/RTW.py:178); RTW training is not defined")
+
+
+class MAICMAC(SharedMAC):
+    """SharedMAC over a MAICAgent (reference network/MAIC.py).  The reference ships the agent without a controller, so this
+    class is the project's own, shaped like RTWMAC / SharedMACWithState.  Inference only: every pass is the agent unroll
+    followed by the message head (csrc/maic_head.hip); training belongs to a later change (MAICQLearner.train raises).
+
+    BatchNorm follows ``self.agent.training``.  ``self.agent.eval()``: running statistics, every environment on its own.
+    Training mode (a freshly built agent; the reference never leaves it): the statistics of ALL rows of a head call and
+    the running statistics move with every call, so the environments of a call are coupled - a batched rollout of E
+    environments is NOT E serial rollouts, and ``get_current_q_values`` evaluates the head once per transition index t (the
+    rows a reference-shaped loop would hand to one MAICAgent.forward call) instead of once for all t."""
+
+    maic = True
+
+    def _build_agents(self, input_shape):
+        self.agent = MAICAgent(input_shape, self.args)
+        self._step_q = None
+
+    def load_state(self, other_mac):
+        """parameters as SharedMAC, plus the BatchNorm buffers (not part of the flat parameter buffer)"""
+        SharedMAC.load_state(self, other_mac)
+        src = dict(other_mac.agent.named_buffers())
+        for k, b in self.agent.named_buffers():
+            b.copy_(src[k])
+
+    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
+        """One agent of one env, but ``obs`` (N, O), ``last_action`` (N, A) and ``avail_actions`` (N, A) cover EVERY agent
+        (rollout.py passes them whole for this controller): agent j's Q values need the hidden state of every agent of the
+        step.  The step is evaluated once, when agent 0 asks (test_mode = evaluate); agents 1 .. N-1 are served from it.
+        Same numpy draw order as SharedMAC: one uniform per call, one choice only when exploring."""
+        dev = self.device()
+        N, A, O = self.n_agents, self.n_actions, self.obs_shape
+        avail_all = np.asarray(avail_actions, dtype=np.float32).reshape(N, A)
+        if agent_num == 0:
+            obs_full = to_dev(np.asarray(obs, dtype=np.float32).reshape(1, 1, N, O), dev)
+            ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
+            if self.args.last_action:
+                la = np.asarray(last_action, dtype=np.float32).reshape(N, A)
+                idx = np.where(la.any(axis=1), la.argmax(axis=1), -1).astype(np.int32)
+                ufed[0, 0] = to_dev(idx, dev, torch.int32)
+            q = torch.empty(1, 1, N, A, device=dev)
+            h_in = self.hidden_states.reshape(N, -1).contiguous()
+            h_out = torch.empty_like(h_in)
+            ops.agent_unroll_fwd(self.agent.weights(), obs_full, N, 0, ufed, N, 0, h_in, q, None, h_out, None,
+                                 1, 1, N, O, A, self.args.last_action, self.args.reuse_network)
+            self.agent.head(h_out, q.view(N, A), 1, bool(evaluate))
+            self.hidden_states = h_out.view(1, N, -1)
+            self._step_q = q.view(N, A).cpu()
+        q_value = self._step_q[agent_num].clone()
+        q_value[torch.as_tensor(avail_all[agent_num]) == 0.0] = -float("inf")
+        if np.random.uniform() < epsilon:
+            return np.random.choice(np.nonzero(avail_all[agent_num])[0])
+        return torch.argmax(q_value)
+
+    def _maic_q_values(self, batch, T, which, test_mode, eps):
+        q, hs = self._batch_unroll(batch, T, which)
+        B, N, A = q.shape[0], self.n_agents, self.n_actions
+        NL = N * self.args.latent_dim
+        if eps is not None:
+            eps = to_dev(eps, q.device).view(B, T, N, NL)
+        if not self.agent.training:
+            self.agent.head(hs.view(B * T * N, -1), q.view(B * T * N, A), B * T, test_mode,
+                            None if eps is None else eps.view(B * T * N, NL))
+            return q, hs, {}
+        for t in range(T):       # batch statistics are per call: one call per transition index
+            qt = q[:, t].contiguous()
+            self.agent.head(hs[:, t].contiguous().view(B * N, -1), qt.view(B * N, A), B, test_mode,
+                            None if eps is None else eps[:, t].contiguous().view(B * N, NL))
+            q[:, t] = qt
+        return q, hs, {}
+
+    def get_current_q_values(self, batch, max_episode_len, test_mode=False, eps=None):
+        """(q (B,T,N,A) with the gated messages added, hs (B,T,N,H), {}): the unroll, then the head over all B*T*N rows.
+        ``eps`` (B,T,N,N*latent_dim): the noise of the sampled latents (test_mode False); drawn with torch.randn if absent."""
+        return self._maic_q_values(batch, max_episode_len, "cur", bool(test_mode), eps)
+
+    def get_next_q_values(self, batch, max_episode_len, test_mode=False, eps=None):
+        """as get_current_q_values on (o_next, u_onehot[t])"""
+        return self._maic_q_values(batch, max_episode_len, "next", bool(test_mode), eps)

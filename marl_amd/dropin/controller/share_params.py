@@ -1,1 +1,1 @@
-from marl_amd.controller.share_params import SharedMAC, SeparatedMAC, SharedMACWithState, RTWMAC  # noqa: F401
+from marl_amd.controller.share_params import SharedMAC, SeparatedMAC, SharedMACWithState, RTWMAC, MAICMAC  # noqa: F401

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
-                   MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, check)
+                   MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, check)
 
 
 def _p(t):
@@ -812,3 +812,58 @@ def world_head_bwd(w, g, hs, dq_idx, dq_val, obs, obs_bs, obs_t0, den, dscale, d
                                   _p(_i32(ep_map)) if ep_map is not None else None, _p(_f32(den)) if den is not None else None,
                                   float(dscale), _p(_f32(dhs)), _p(ws), ws.numel() * 4, B, T, N, O, A, _stream()),
           "marl_world_head_bwd")
+
+
+# ---- MAIC message head (csrc/maic_head.hip)
+MAIC_KEYS = (("e0", "embed_net.0"), ("e3", "embed_net.3"), ("m0", "msg_net.0"), ("m2", "msg_net.2"), ("k", "w_key"),
+             ("q", "w_query"))
+MAIC_BN = (("bn_w", "embed_net.1.weight", torch.float32), ("bn_b", "embed_net.1.bias", torch.float32),
+           ("bn_rm", "embed_net.1.running_mean", torch.float32), ("bn_rv", "embed_net.1.running_var", torch.float32),
+           ("bn_nbt", "embed_net.1.num_batches_tracked", torch.int64))
+
+
+def maic_supported(N, O, A, H=64, NH=64, L=8, D=32):
+    return bool(_lib.load().marl_maic_supported(N, O, A, H, NH, L, D))
+
+
+def maic_weights(tensors):
+    """tensors: dict name -> tensor with MAICAgent's parameter and buffer keys (network/MAIC.py:19-47) -> marl_maic_weights_t."""
+    w = MarlMaicWeights()
+    names = [(short + suf, name + key, torch.float32) for short, name in MAIC_KEYS for suf, key in (("_w", ".weight"), ("_b", ".bias"))]
+    for field, name, dt in names + list(MAIC_BN):
+        t = tensors[name]
+        assert t.is_contiguous() and t.dtype == dt and t.is_cuda, name
+        setattr(w, field, t.data_ptr())
+    w._keep = tensors
+    return w
+
+
+def maic_head_fwd(w, h, q, bs, N, A, test_mode=True, bn_batch=False, eps=None, var_floor=0.002, bn_eps=1e-5, bn_momentum=0.1,
+                  mean_out=None, var_out=None, lat_out=None, alpha_out=None, msg_out=None):
+    """q (bs*N, A) += the gated messages of MAICAgent.forward (network/MAIC.py:58-87) from h (bs*N, 64).  ``eps`` (bs*N, N*8):
+    the noise of the sampled latents (test_mode False).  ``bn_batch``: BatchNorm on the statistics of this call's rows, with
+    the running statistics in ``w`` updated, instead of on the running statistics."""
+    lib = _lib.load()
+    if not lib.marl_maic_supported(N, 1, A, 64, 64, 8, 32):
+        raise ValueError("the gfx950 MAIC head covers N <= 16 and A <= 32 (N %d, A %d)" % (N, A))
+    if not test_mode and eps is None:
+        raise ValueError("sampled latents (test_mode=False) need eps")
+    if bn_batch and bs * N < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got %d row(s)" % (bs * N))
+    for t, cols in ((h, 64), (q, A)):
+        assert t.is_contiguous() and t.numel() == bs * N * cols
+    if eps is not None:
+        assert eps.is_contiguous() and eps.numel() == bs * N * N * 8
+    ws = WS.get("maic", lib.marl_maic_workspace(bs, N), h.device) if bn_batch else None
+    opt = [None if t is None else _p(_f32(t)) for t in (mean_out, var_out, lat_out, alpha_out, msg_out)]
+    check(lib.marl_maic_head_fwd(C.byref(w), _p(_f32(h)), _p(_f32(q)), _p(_f32(eps)) if eps is not None else None, *opt,
+                                 _p(ws), 0 if ws is None else ws.numel() * 4, bs, N, A, 1 if test_mode else 0,
+                                 1 if bn_batch else 0, float(var_floor), float(bn_eps), float(bn_momentum), _stream()),
+          "marl_maic_head_fwd")
+
+
+def maic_noise(rseed, env0, tg, eps, E, N):
+    """eps (E*N, N*8) <- the standard-normal draws of lock-step ``tg`` (counter hash + Box-Muller, csrc/maic_head.hip)"""
+    assert eps.is_contiguous() and eps.numel() == E * N * N * 8
+    check(_lib.load().marl_maic_noise(rseed & 0xFFFFFFFF, env0, tg & 0xFFFFFFFF, _p(_f32(eps)), E, N, _stream()),
+          "marl_maic_noise")

@@ -7,7 +7,10 @@
   selection kernel, one env-step kernel; the episode record never leaves HBM.
   Epsilon is annealed once per lock-step (quirk Q7 kept for n_envs = 1).
   With an RTW controller (RTWMAC) the reflection head (csrc/rtw_head.hip, act mode) runs between the agent step and the
-  selection; such rollouts always take this per-step path (the whole-rollout kernels have no head).
+  selection; such rollouts always take this per-step path (the whole-rollout kernels have no head).  The world-model head
+  (SharedMACWithState) and the MAIC message head (MAICMAC, csrc/maic_head.hip; test mode = ``evaluate``) run at the same place.
+  MAIC's sampled latents (training rollouts) take their noise from the counter hash keyed by (rseed, env, global step, agent,
+  column) through a Box-Muller transform (ops.maic_noise), so a rollout is a pure function of its seeds.
 """
 from __future__ import annotations
 
@@ -155,7 +158,8 @@ class RolloutWorker:
         mode = getattr(self, "rollout_mode", "whole")      # "whole" | "fused_step" | "unfused" (tests)
         rtw = getattr(mac, "rtw", False)
         world = getattr(mac, "world", False)
-        if mode == "whole" and not rtw and not world and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
+        maic = getattr(mac, "maic", False)
+        if mode == "whole" and not rtw and not world and not maic and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
             # the persistent kernel writes every field of the record, so training rollouts can be
             # played straight into the replay ring (record_sink = the ReplayBuffer; zero-copy store)
             sink = getattr(self, "record_sink", None)
@@ -181,6 +185,7 @@ class RolloutWorker:
         w = mac.agent.weights()
         w_rtw = mac.agent.rtw_weights() if rtw else None
         w_world = mac.agent.world_weights() if world else None
+        maic_eps = torch.empty(E * N, N * a.latent_dim, device=dev) if maic and not evaluate else None
         fused = hasattr(env, "fused_step") and mode != "unfused"
         env.observe(0, rec)
         for t in range(T):
@@ -192,6 +197,10 @@ class RolloutWorker:
                                  mac.not_self_model())
             if world:   # q += r (SharedMACWithState.choose_action for every agent, share_params.py:214-260)
                 ops.world_head_fwd(w_world, h, q, E, 1, N, O, A)
+            if maic:    # q += the gated messages (MAICMAC.choose_action for every agent of every env)
+                if maic_eps is not None:
+                    ops.maic_noise(self.rseed, env.env0, env.global_step(t), maic_eps, E, N)
+                mac.agent.head(h, q.view(E * N, A), E, bool(evaluate), maic_eps)
             if fused:
                 env.fused_step(t, q, epsilon, self.rseed, rec)
             else:
@@ -252,6 +261,8 @@ class RolloutWorker:
             raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no RTW head: use generate_episodes")
         if getattr(mac if mac is not None else self.mac, "world", False):
             raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no world-model head: use generate_episodes")
+        if getattr(mac if mac is not None else self.mac, "maic", False):
+            raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no MAIC head: use generate_episodes")
         if not (getattr(env, "batched", False) and hasattr(env, "whole_rollout") and env.supports_whole_rollout()):
             raise RuntimeError("launch_episodes needs a batched env with the whole-rollout kernel")
         dev = require_cuda("RolloutWorker")
@@ -312,9 +323,12 @@ class RolloutWorker:
                             action = np.random.randint(0, A - 1)
                     else:
                         # RTW: every agent's availability (rollout.py:73-76)
-                        action = self.mac.choose_action(obs[agent_id], last_actions[agent_id], agent_id,
-                                                        avail_actions if getattr(a, "RTW", False) else avail_actions[agent_id], epsilon,
-                                                        evaluate)
+                        if getattr(self.mac, "maic", False):      # every agent's observation, last action and availability
+                            action = self.mac.choose_action(obs, last_actions, agent_id, avail_actions, epsilon, evaluate)
+                        else:
+                            action = self.mac.choose_action(obs[agent_id], last_actions[agent_id], agent_id,
+                                                            avail_actions if getattr(a, "RTW", False) else avail_actions[agent_id], epsilon,
+                                                            evaluate)
                     onehot = np.zeros(A)
                     onehot[action] = 1
                     actions.append(action)

@@ -19,6 +19,11 @@ QLearnerWithState (reference controller/share_params.py:185-387, algorithm/q_lea
 Rollouts take the per-step path.  With RTW it raises ValueError, with qtran_* the reference's ValueError, with overlapped
 rollouts NotImplementedError.
 
+``args.MAIC`` (a switch of this project; the reference ships network/MAIC.py without a controller or a learner): MAICMAC and
+MAICQLearner for vdn / qmix / qplex.  Evaluation and rollouts run (the per-step path); ``learner.train`` raises
+NotImplementedError and touches nothing.  With RTW or world_model it raises ValueError, with qtran_* or overlapped rollouts
+NotImplementedError - all before anything is built.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -30,12 +35,13 @@ import numpy as np
 import torch
 
 from .rollout import RolloutWorker
-from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC
+from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC, MAICMAC
 from .common.replaybuffer import ReplayBuffer
 from .algorithm.q_learner import QLearner
 from .algorithm.qtran_learner import QTRANLearner
 from .algorithm.rtw_q_learner import RTWQLearner
 from .algorithm.q_learner_state import QLearnerWithState
+from .algorithm.maic_q_learner import MAICQLearner
 from .utils.logging import Logger
 
 
@@ -57,7 +63,17 @@ class Runner:
             raise ValueError("Mixer {} not recognised.".format(args.alg))     # QLearnerWithState (q_learner_state.py:32)
         if world and getattr(args, "overlap_rollout", False):
             raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no world-model head")
-        self.mac = RTWMAC(args) if rtw else SharedMACWithState(args) if world else SharedMAC(args)
+        maic = bool(getattr(args, "MAIC", False))
+        if maic and (rtw or world):
+            raise ValueError("MAIC, RTW and world_model are three different agents: choose one")
+        if maic and (args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1):
+            raise NotImplementedError("MAIC with a QTRAN learner is not supported")
+        if maic and getattr(args, "overlap_rollout", False):
+            raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no MAIC head")
+        if maic:
+            from .common.arguments import get_maic_args
+            get_maic_args(args)
+        self.mac = RTWMAC(args) if rtw else SharedMACWithState(args) if world else MAICMAC(args) if maic else SharedMAC(args)
         self.rolloutWorker = RolloutWorker(env, self.mac, args)
         self.buffer = ReplayBuffer(args)
         self.rolloutWorker.record_sink = self.buffer   # batched rollouts write into the replay ring in place
@@ -73,7 +89,7 @@ class Runner:
         self.logger = logger
         if any(args.alg.find(a) > -1 for a in ('vdn', 'qmix', 'qplex')):
             self.learner = RTWQLearner(self.mac, logger, args) if rtw else \
-                QLearnerWithState(self.mac, args) if world else QLearner(self.mac, args)
+                QLearnerWithState(self.mac, args) if world else MAICQLearner(self.mac, args) if maic else QLearner(self.mac, args)
         elif args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1:
             self.learner = QTRANLearner(self.mac, args)
         else:

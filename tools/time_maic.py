@@ -1,0 +1,76 @@
+#!/usr/bin/env python3
+"""Cost of the MAIC message head (csrc/maic_head.hip) in the per-step rollout: HIP-event ms per lock-step of the fused_step
+rollout with a MAICMAC (agent step + head + env step) and with the plain controller (no head), and the head launch alone, with
+BatchNorm in eval mode (one launch) and in batch-statistics mode (three launches).  Evaluation rollouts: test-mode latents.
+    python tools/time_maic.py [--shape 2s3z|MMM2] [--envs 512 4096 ...]
+tools/time_rtw.py with the same arguments is the yardstick next to it."""
+import argparse
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from oracle import seeded  # noqa: E402
+from marl_amd.common.arguments import get_maic_args  # noqa: E402
+from marl_amd.controller.share_params import SharedMAC, MAICMAC  # noqa: E402
+from marl_amd.rollout import RolloutWorker  # noqa: E402
+from marl_amd.env.synthetic_smac import SyntheticSMACEnv  # noqa: E402
+
+
+def rollout_ms(mac_cls, args, E, train=False):
+    torch.manual_seed(0)
+    mac = mac_cls(args)
+    mac.cuda()
+    mac.agent.train(train)
+    env = SyntheticSMACEnv(E, args.n_agents, args.obs_shape, args.state_shape, args.n_actions, args.episode_limit, seed=1,
+                           fixed_length=True)
+    w = RolloutWorker(env, mac, args)
+    w.rollout_mode = "fused_step"
+    w.generate_episodes(E, evaluate=True)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(3):
+        w.generate_episodes(E, evaluate=True)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / 3 / args.episode_limit, mac
+
+
+def head_ms(mac, args, E, train):
+    N, A = args.n_agents, args.n_actions
+    dev = torch.device("cuda")
+    h = torch.randn(E * N, 64, device=dev)
+    q = torch.zeros(E * N, A, device=dev)
+    mac.agent.train(train)
+    for _ in range(3):
+        mac.agent.head(h, q, E, True)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    torch.cuda.synchronize()
+    e0.record()
+    for _ in range(50):
+        mac.agent.head(h, q, E, True)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / 50
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shape", default="2s3z", choices=["2s3z", "MMM2"])
+    ap.add_argument("--envs", type=int, nargs="+", default=[512, 4096])
+    ap.add_argument("--T", type=int, default=20, help="lock-steps per timed rollout")
+    o = ap.parse_args()
+    for E in o.envs:
+        args = get_maic_args(seeded.make_args(o.shape, "qmix", episode_limit=o.T, seed=1))
+        base, _ = rollout_ms(SharedMAC, args, E)
+        for train in (False, True):
+            step, mac = rollout_ms(MAICMAC, args, E, train)
+            print("%-5s envs %5d  BatchNorm %-5s per lock-step: no head %.3f ms  with head %.3f ms  (+%.3f)   head launch alone "
+                  "%.3f ms" % (o.shape, E, "batch" if train else "eval", base, step, step - base, head_ms(mac, args, E, train)),
+                  flush=True)
+
+
+if __name__ == "__main__":
+    main()
