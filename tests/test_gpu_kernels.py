@@ -1228,7 +1228,8 @@ def test_qmix_mix(dev):
                                    (8200, 5, 124)])
 def test_qmix_fused(dev, R, N, S, x6):
     """fused hypernet + mixing kernels (forward, dq, hypernet weight gradients; fp32 MFMA and the bf16x6 split variant) vs torch-CPU
-    autograd of the restated QMixMixer.forward (reference network/mixer.py:57-80); S not a multiple of 4 falls back."""
+    autograd of the restated QMixMixer.forward (reference network/mixer.py:57-80); S not a multiple of 4 falls back.
+    The LOSS variants of these kernels (marl_qmix_fused_loss_bwd / _x6) are tested in tests/test_gpu_qmix_loss.py."""
     from marl_amd import ops
     E = 32
     assert ops.qmix_fused_supported(N, S, E)
@@ -1897,7 +1898,8 @@ def test_qmix_wide(dev, R, N, S, bf16):
     rounded to bf16 - an EXTERNAL reference for the reduced-precision mode, so the tolerance stays tight (products of
     bf16 values are exact in fp32; only the accumulation order differs); the weight gradient uses the unrounded states
     (straight-through), compared at 2e-2 of its scale.  bf16 = "fwd": bf16 operands in the hypernet GEMM only (flags = 1 of the
-    C-ABI, without the weight-gradient bit): the weight-gradient GEMM is fp32 on the unrounded states, held to 1e-4."""
+    C-ABI, without the weight-gradient bit): the weight-gradient GEMM is fp32 on the unrounded states, held to 1e-4.
+    The LOSS variant (marl_qmix_wide_loss_bwd) is tested in tests/test_gpu_qmix_loss.py."""
     from marl_amd import ops
     E = 32
     wg32 = bf16 == "fwd"
