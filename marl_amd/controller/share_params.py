@@ -19,6 +19,12 @@ from ..network.maic import MAICAgent
 
 
 class SharedMAC:
+    # the head seam: a subclass whose Q values are "the unroll, then a head kernel that adds a term to q" overrides these two
+    # attributes, _step_head (serial choose_action) and rollout_head (batched lock-step)
+    head_name = None                  # as error texts name the head; None: the whole-rollout kernels may run
+    choose_action_inputs = "agent"    # what the serial rollout hands choose_action: "agent" the agent's own row of obs /
+                                      # last action / availability, "avail_all" every agent's availability, "all" all three whole
+
     def __init__(self, args):
         self.n_actions = args.n_actions
         self.n_agents = args.n_agents
@@ -80,33 +86,50 @@ class SharedMAC:
 
     # ------------------------------------------------------------------ serial action choice
     def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
-        """One agent, one env (reference :37-72), same numpy RNG draw order:
-        one uniform per call, one choice only when exploring."""
+        """One agent, one env (reference :37-72), same numpy RNG draw order: one uniform per call, one choice only when
+        exploring.  ``avail_actions``: the agent's row, or every agent's (choose_action_inputs = "avail_all")."""
         dev = self.device()
-        N, A, O = self.n_agents, self.n_actions, self.obs_shape
-        avail = np.asarray(avail_actions)
-        avail_ind = np.nonzero(avail)[0]
+        N, O = self.n_agents, self.obs_shape
+        avail = np.asarray(avail_actions, dtype=np.float32)
+        if self.choose_action_inputs == "avail_all":
+            avail = avail.reshape(N, self.n_actions)
         la = -1
         if self.args.last_action:
             nz = np.nonzero(np.asarray(last_action))[0]
             la = int(nz[0]) if nz.size else -1
-        obs_t = to_dev(np.asarray(obs, dtype=np.float32).reshape(1, O), dev)
         # run row `agent_num` of a 1-episode batch: pad the agent axis so the id block matches
         obs_full = torch.zeros(1, 1, N, O, device=dev)
-        obs_full[0, 0, agent_num] = obs_t[0]
+        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
         ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
         ufed[0, 0, agent_num] = la
-        q = torch.empty(1, 1, N, A, device=dev)
+        q, h_out = self._agent_step_one(obs_full, ufed)
+        self._step_head(h_out, q, obs_full, avail, evaluate)
+        self.hidden_states[0, agent_num] = h_out[agent_num]
+        return self._draw(q[0, 0, agent_num].cpu(), avail if avail.ndim == 1 else avail[agent_num], epsilon)
+
+    def _agent_step_one(self, obs_full, ufed):
+        """the T = 1 unroll of one environment from self.hidden_states: (q (1,1,N,A), h_out (N,H))"""
+        N, A, O = self.n_agents, self.n_actions, self.obs_shape
+        q = torch.empty(1, 1, N, A, device=obs_full.device)
         h_in = self.hidden_states.reshape(N, -1).contiguous()
         h_out = torch.empty_like(h_in)
         ops.agent_unroll_fwd(self.agent.weights(), obs_full, N, 0, ufed, N, 0, h_in, q, None, h_out, None,
                              1, 1, N, O, A, self.args.last_action, self.args.reuse_network)
-        self.hidden_states[0, agent_num] = h_out[agent_num]
-        q_value = q[0, 0, agent_num].cpu()
-        q_value[torch.as_tensor(avail, dtype=torch.float32) == 0.0] = -float("inf")
+        return q, h_out
+
+    def _step_head(self, h_out, q, obs_full, avail, evaluate):
+        """q (1,1,N,A) += the head's term for one environment; ``avail`` as choose_action received it"""
+
+    @staticmethod
+    def _draw(q_row, avail_row, epsilon):
+        """epsilon-greedy over the available actions: one uniform, one choice only when exploring"""
+        q_row[torch.as_tensor(avail_row, dtype=torch.float32) == 0.0] = -float("inf")
         if np.random.uniform() < epsilon:
-            return np.random.choice(avail_ind)
-        return torch.argmax(q_value)
+            return np.random.choice(np.nonzero(avail_row)[0])
+        return torch.argmax(q_row)
+
+    def rollout_head(self, h, q, rec, t, E, evaluate, rseed, env):
+        """q (E,1,N,A) += the head's term at lock-step t of a batched rollout (h (E*N,H): the step's GRU output)"""
 
     # ------------------------------------------------------------------ batched primitives
     def unroll_x6(self, B, T, obs=None):
@@ -185,37 +208,19 @@ class SharedMACWithState(SharedMAC):
     """reference controller/share_params.py:185-387: SharedMAC over a world_model.Agent, whose Q values include the world
     head's r (network/world_model.py:71).  Every pass is the agent unroll followed by the head (csrc/world_head.hip)."""
 
-    world = True
+    world = True                      # QLearnerWithState asks for it
+    head_name = "world-model"
 
     def _build_agents(self, input_shape):
         self.agent = WorldAgent(input_shape, self.args)
 
-    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
-        """One agent, one env (reference :214-260): SharedMAC's with q + r, same numpy draw order."""
-        dev = self.device()
-        N, A, O = self.n_agents, self.n_actions, self.obs_shape
-        avail = np.asarray(avail_actions)
-        avail_ind = np.nonzero(avail)[0]
-        la = -1
-        if self.args.last_action:
-            nz = np.nonzero(np.asarray(last_action))[0]
-            la = int(nz[0]) if nz.size else -1
-        obs_full = torch.zeros(1, 1, N, O, device=dev)
-        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
-        ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
-        ufed[0, 0, agent_num] = la
-        q = torch.empty(1, 1, N, A, device=dev)
-        h_in = self.hidden_states.reshape(N, -1).contiguous()
-        h_out = torch.empty_like(h_in)
-        ops.agent_unroll_fwd(self.agent.weights(), obs_full, N, 0, ufed, N, 0, h_in, q, None, h_out, None,
-                             1, 1, N, O, A, self.args.last_action, self.args.reuse_network)
-        ops.world_head_fwd(self.agent.world_weights(), h_out, q, 1, 1, N, O, A)
-        self.hidden_states[0, agent_num] = h_out[agent_num]
-        q_value = q[0, 0, agent_num].cpu()
-        q_value[torch.as_tensor(avail, dtype=torch.float32) == 0.0] = -float("inf")
-        if np.random.uniform() < epsilon:
-            return np.random.choice(avail_ind)
-        return torch.argmax(q_value)
+    def _step_head(self, h_out, q, obs_full, avail, evaluate):
+        """q += r (reference :214-260)"""
+        ops.world_head_fwd(self.agent.world_weights(), h_out, q, 1, 1, self.n_agents, self.obs_shape, self.n_actions)
+
+    def rollout_head(self, h, q, rec, t, E, evaluate, rseed, env):
+        """q += r: choose_action for every agent of every environment"""
+        ops.world_head_fwd(self.agent.world_weights(), h, q, E, 1, self.n_agents, self.obs_shape, self.n_actions)
 
     def head(self, hs, q, B, T, with_ohat=True, with_tau=True):
         """q (B,T,N,A) += r from hs (B,T,N,64); returns the reference's `returns` dict (:303-375) without ep_hidden_states"""
@@ -248,7 +253,8 @@ class RTWMAC(SharedMAC):
     (csrc/rtw_head.hip).  get_next_q_values fails with the reference's TypeError (RTWAgent.forward target=True), so
     RTWQLearner.train cannot run - in the reference either."""
 
-    rtw = True
+    head_name = "RTW"
+    choose_action_inputs = "avail_all"
 
     def _build_agents(self, input_shape):
         self.agent = RTWAgent(input_shape, self.args)
@@ -256,34 +262,18 @@ class RTWMAC(SharedMAC):
     def not_self_model(self):
         return bool(getattr(self.args, "not_self_model", True))
 
-    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
-        """One agent, one env; avail_actions covers EVERY agent (rollout.py:73-74).  Same numpy draw order as SharedMAC."""
-        dev = self.device()
+    def _step_head(self, h_out, q, obs_full, avail, evaluate):
+        """q += the reflection term (reference :641-677).  The head reads row agent_num's h and o and every agent's
+        availability (rollout.py:73-74); the other rows of the tile are discarded."""
         N, A, O = self.n_agents, self.n_actions, self.obs_shape
-        avail_all = np.asarray(avail_actions, dtype=np.float32).reshape(N, A)
-        avail_ind = np.nonzero(avail_all[agent_num])[0]
-        la = -1
-        if self.args.last_action:
-            nz = np.nonzero(np.asarray(last_action))[0]
-            la = int(nz[0]) if nz.size else -1
-        obs_full = torch.zeros(1, 1, N, O, device=dev)
-        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
-        ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
-        ufed[0, 0, agent_num] = la
-        q = torch.empty(1, 1, N, A, device=dev)
-        h_in = self.hidden_states.reshape(N, -1).contiguous()
-        h_out = torch.empty_like(h_in)
-        ops.agent_unroll_fwd(self.agent.weights(), obs_full, N, 0, ufed, N, 0, h_in, q, None, h_out, None,
-                             1, 1, N, O, A, self.args.last_action, self.args.reuse_network)
-        # the head reads row agent_num's h and o and every agent's availability; the other rows of the tile are discarded
-        ops.rtw_head_act(self.agent.rtw_weights(), h_out, obs_full, N, 0, to_dev(avail_all, dev), N, 0, q, 1, N, O, A,
+        ops.rtw_head_act(self.agent.rtw_weights(), h_out, obs_full, N, 0, to_dev(avail, h_out.device), N, 0, q,
+                         1, N, O, A, self.not_self_model())
+
+    def rollout_head(self, h, q, rec, t, E, evaluate, rseed, env):
+        """q += the reflection term from slot t of the record: choose_action for every agent of every environment"""
+        N, A, O, T = self.n_agents, self.n_actions, self.obs_shape, rec.T
+        ops.rtw_head_act(self.agent.rtw_weights(), h, rec.obs, (T + 1) * N, t, rec.avail, (T + 1) * N, t, q, E, N, O, A,
                          self.not_self_model())
-        self.hidden_states[0, agent_num] = h_out[agent_num]
-        q_value = q[0, 0, agent_num].cpu()
-        q_value[torch.as_tensor(avail_all[agent_num]) == 0.0] = -float("inf")
-        if np.random.uniform() < epsilon:
-            return np.random.choice(avail_ind)
-        return torch.argmax(q_value)
 
     def get_current_q_values(self, batch, max_episode_len):
         """(q, hs, 0.0, 0.0) - reference :730-764: the unroll, then the given-mode head with the taken actions and o_next."""
@@ -316,11 +306,13 @@ class MAICMAC(SharedMAC):
     environments is NOT E serial rollouts, and ``get_current_q_values`` evaluates the head once per transition index t (the
     rows a reference-shaped loop would hand to one MAICAgent.forward call) instead of once for all t."""
 
-    maic = True
+    head_name = "MAIC"
+    choose_action_inputs = "all"
 
     def _build_agents(self, input_shape):
         self.agent = MAICAgent(input_shape, self.args)
         self._step_q = None
+        self._eps = None              # the batched rollout's noise buffer, kept per E
 
     def load_state(self, other_mac):
         """parameters as SharedMAC, plus the BatchNorm buffers (not part of the flat parameter buffer)"""
@@ -344,19 +336,26 @@ class MAICMAC(SharedMAC):
                 la = np.asarray(last_action, dtype=np.float32).reshape(N, A)
                 idx = np.where(la.any(axis=1), la.argmax(axis=1), -1).astype(np.int32)
                 ufed[0, 0] = to_dev(idx, dev, torch.int32)
-            q = torch.empty(1, 1, N, A, device=dev)
-            h_in = self.hidden_states.reshape(N, -1).contiguous()
-            h_out = torch.empty_like(h_in)
-            ops.agent_unroll_fwd(self.agent.weights(), obs_full, N, 0, ufed, N, 0, h_in, q, None, h_out, None,
-                                 1, 1, N, O, A, self.args.last_action, self.args.reuse_network)
-            self.agent.head(h_out, q.view(N, A), 1, bool(evaluate))
+            q, h_out = self._agent_step_one(obs_full, ufed)
+            self._step_head(h_out, q, obs_full, avail_all, evaluate)
             self.hidden_states = h_out.view(1, N, -1)
             self._step_q = q.view(N, A).cpu()
-        q_value = self._step_q[agent_num].clone()
-        q_value[torch.as_tensor(avail_all[agent_num]) == 0.0] = -float("inf")
-        if np.random.uniform() < epsilon:
-            return np.random.choice(np.nonzero(avail_all[agent_num])[0])
-        return torch.argmax(q_value)
+        return self._draw(self._step_q[agent_num].clone(), avail_all[agent_num], epsilon)
+
+    def _step_head(self, h_out, q, obs_full, avail, evaluate):
+        self.agent.head(h_out, q.view(self.n_agents, self.n_actions), 1, bool(evaluate))
+
+    def rollout_head(self, h, q, rec, t, E, evaluate, rseed, env):
+        """q += the gated messages: choose_action for every agent of every environment; exploring, the latents' noise is
+        the counter hash of (rseed, environment, global step)"""
+        N, A = self.n_agents, self.n_actions
+        eps = None
+        if not evaluate:
+            if self._eps is None or self._eps.shape[0] != E * N:
+                self._eps = torch.empty(E * N, N * self.args.latent_dim, device=h.device)
+            eps = self._eps
+            ops.maic_noise(rseed, env.env0, env.global_step(t), eps, E, N)
+        self.agent.head(h, q.view(E * N, A), E, bool(evaluate), eps)
 
     def _maic_q_values(self, batch, T, which, test_mode, eps):
         q, hs = self._batch_unroll(batch, T, which)

@@ -16,7 +16,8 @@
 //     exactly the B operand of the K-permuted 16 x 16 x 16 step (register i <-> row 4 q + i), so sum_i alpha_ij T_ij is a second
 //     MFMA with the gated alphas scattered into the A operand - no LDS round trip, no cross-lane sum.
 //   * key . (Wq latent + bq) = (Wq^T key) . latent + key . bq: eight numbers per row instead of a D-wide query per pair.
-// Dense products are fp32 MFMA (v_mfma_f32_16x16x4_f32) with the weights read through L2, as rtw_head.hip / world_head.hip.
+// Dense products are fp32 MFMA (v_mfma_f32_16x16x4_f32) with the weights read through L2: the tile product of
+// csrc/head_tile.h.
 //
 // BatchNorm: eval mode is an affine map folded per column in the one launch.  Batch-statistics mode (a module in training
 // mode) needs the column statistics of y over ALL rows first: launch 1 writes y and one (mean, M2) pair per workgroup and
@@ -24,9 +25,12 @@
 // float atomics, the same bits on every run), writes scale / shift and updates running_mean / running_var /
 // num_batches_tracked, launch 3 is the head reading y back.
 #include "synth_env.h"
+#include "head_tile.h"
 #include "../../include/marl_hip.h"
 
 namespace {
+
+using head_tile::drow;
 
 constexpr int MC_H = 64;             // rnn_hidden_dim
 constexpr int MC_NH = 64;            // nn_hidden_size
@@ -55,32 +59,14 @@ struct MaicArgs {
   float var_floor, bn_eps, bn_mom;
 };
 
-__host__ __device__ inline long mc_pad(long n) { return (n + 63) / 64 * 64; }
 __host__ __device__ inline int mc_envs_per_tile(int N) { return N >= 16 ? 1 : 16 / N; }
 
-// acc[16 x 16 column tile n0] += X[16 x K] W^T: W row-major (nvalid rows of ldw floats), X in LDS (row pitch ldx), K % 16 == 0.
-// K-permuted as rtw_head.hip: at step i lane quarter q supplies k0 + 4q + i for both operands.
+// every dense product here starts from zero, has K = 64 and a zero-padded X: the unguarded flavour
 __device__ __forceinline__ f32x4 mc_gemm(const float* X, int ldx, int K, const float* __restrict__ W, long ldw, int n0,
                                          int nvalid) {
-  const int l = threadIdx.x, m = l & 15, q4 = (l >> 4) * 4;
-  const int n = n0 + m;
-  const bool nok = n < nvalid;
-  const float* wr = W + (long)(nok ? n : 0) * ldw;
-  f32x4 acc = {0, 0, 0, 0};
-  for (int k0 = 0; k0 < K; k0 += 16) {
-    const int k = k0 + q4;
-    f32x4 a, b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      a[i] = X[m * ldx + k + i];
-      b[i] = nok ? __ldg(wr + k + i) : 0.0f;
-    }
-    acc = mfma16x4(a, b, acc);
-  }
-  return acc;
+  return head_tile::tile_gemm<false>(f32x4{0, 0, 0, 0}, X, ldx, K, W, ldw, 0, n0, nvalid);
 }
 
-__device__ __forceinline__ int drow(int r) { return 4 * (threadIdx.x >> 4) + r; }
 __device__ __forceinline__ float leaky(float t) { return t > 0.0f ? t : 0.01f * t; }
 
 // rows of this workgroup's tile that exist
@@ -90,20 +76,13 @@ __device__ __forceinline__ int tile_rows(const MaicArgs& p, long row0) {
   return left < rw ? (int)left : rw;
 }
 
-__device__ __forceinline__ void load_h(const MaicArgs& p, long row0, int nv, float* sh_h) {
-  for (int idx = threadIdx.x; idx < 16 * MC_H; idx += 64) {
-    const int r = idx / MC_H, c = idx % MC_H;
-    sh_h[r * MC_LDH + c] = r < nv ? p.h[(row0 + r) * MC_H + c] : 0.0f;
-  }
-}
-
 // ---- batch statistics, launch 1: y = embed_net.0 h of the tile and the tile's (mean, M2) per column
 __global__ __launch_bounds__(64) void maic_embed_stats_kernel(MaicArgs p) {
   __shared__ float sh_h[16 * MC_LDH], sh_y[16 * MC_LDH];
   const long row0 = (long)blockIdx.x * p.G * p.N;
   const int nv = tile_rows(p, row0);
   const int l = threadIdx.x, m = l & 15;
-  load_h(p, row0, nv, sh_h);
+  head_tile::load_h(sh_h, MC_LDH, p.h, row0, [&](int r) { return r < nv; });
   __syncthreads();
   for (int n0 = 0; n0 < MC_NH; n0 += 16) {
     const f32x4 acc = mc_gemm(sh_h, MC_LDH, MC_H, p.w.e0_w, MC_H, n0, MC_NH);
@@ -174,7 +153,7 @@ __global__ __launch_bounds__(64) void maic_head_kernel(MaicArgs p) {
   const long row0 = (long)blockIdx.x * RW;
   const int nv = tile_rows(p, row0);
   const int l = threadIdx.x, m = l & 15, qd = l >> 4;
-  load_h(p, row0, nv, sh_h);
+  head_tile::load_h(sh_h, MC_LDH, p.h, row0, [&](int r) { return r < nv; });
   __syncthreads();
   // ---- z = LeakyReLU(BatchNorm(embed_net.0 h)); U = msg_net.0[:, :64] h + b; key = w_key h + b
   for (int n0 = 0; n0 < MC_NH; n0 += 16) {
@@ -379,7 +358,7 @@ WsLayout ws_layout(int bs, int N) {
   const int G = mc_envs_per_tile(N);
   L.nblk = (bs + G - 1) / G;
   L.y = 0;
-  L.part = mc_pad((long)bs * N * MC_NH);
+  L.part = head_tile::pad64((long)bs * N * MC_NH);
   L.ss = L.part + (long)L.nblk * 128;
   L.total = L.ss + 128;
   return L;

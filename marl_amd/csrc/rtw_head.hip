@@ -6,13 +6,17 @@
 //
 // Dense products run on the fp32 matrix cores (v_mfma_f32_16x16x4_f32) over the 16-row tile, with the weights read through
 // L2 (140 KB at 2s3z, 280 KB at MMM2: more than a workgroup's LDS, and every phase reads each weight once per tile).
+// The tile product and its K-permutation are csrc/head_tile.h.
 // One-hot blocks are never multiplied: each becomes a gathered weight column added to the pre-activation
 // (T0[:, 64 + j], W0[:, O + j A + a_j], Wk[:, a_j], V0[:, 64 + a_j]).  The value net's second layer is applied once to
 // g = sum_j p_j relu(V0 [h ; m_j] + b) (plus bv2 * sum_j p_j) instead of to each v_j.  Argmax and softmax are on the VALU.
-#include "common.h"
+#include "head_tile.h"
 #include "../../include/marl_hip.h"
 
 namespace {
+
+using head_tile::drow;
+using head_tile::tile_gemm;    // K-guarded here: O is any width
 
 constexpr int RTW_H = 64;          // rnn_hidden_dim = hidden_dim = attn_dim
 constexpr int RTW_LDH = RTW_H + 4;
@@ -35,32 +39,6 @@ struct RtwArgs {
 
 __host__ __device__ inline int rtw_op(int O) { return (O + 15) / 16 * 16; }
 
-// acc[16 x 16 column tile n0] += X[16 x K] * W[n0.., coff + k]^T over k < K.  X in LDS (row pitch ldx, zero-padded to a
-// multiple of 16 columns), W row-major with row stride ldw; columns n >= nvalid read as 0.  K-permuted: at step i lane
-// quarter q supplies k0 + 4q + i for both operands.
-__device__ __forceinline__ f32x4 tile_gemm(f32x4 acc, const float* X, int ldx, int K, const float* __restrict__ W, long ldw,
-                                           int coff, int n0, int nvalid) {
-  const int l = threadIdx.x, m = l & 15, q4 = (l >> 4) * 4;
-  const int n = n0 + m;
-  const bool nok = n < nvalid;
-  const float* wr = W + (long)(nok ? n : 0) * ldw + coff;
-  for (int k0 = 0; k0 < K; k0 += 16) {
-    const int k = k0 + q4;
-    f32x4 a, b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool kok = k + i < K;
-      a[i] = kok ? X[m * ldx + k + i] : 0.0f;
-      b[i] = (kok && nok) ? __ldg(wr + k + i) : 0.0f;
-    }
-    acc = mfma16x4(a, b, acc);
-  }
-  return acc;
-}
-
-// row of D reg r for lane l, column (l & 15)
-__device__ __forceinline__ int drow(int r) { return 4 * (threadIdx.x >> 4) + r; }
-
 template <bool GIVEN, bool NOT_SELF>
 __global__ __launch_bounds__(64) void rtw_head_kernel(RtwArgs p) {
   extern __shared__ float smem[];
@@ -78,7 +56,8 @@ __global__ __launch_bounds__(64) void rtw_head_kernel(RtwArgs p) {
   float* sh_ps = sh_p + 16 * RTW_NMAX;      // [16] sum_j p_j
   int* sh_a = (int*)(sh_ps + 16);           // [16][NMAX] a_j (act) / u_j (given); -1 = masked one-hot block
 
-  // ---- load the tile: h, o (and o_next); rows past the tile / past G are zeros and never stored
+  // ---- load the tile: h, o (and o_next); rows past the tile / past G are zeros and never stored.  Every load here addresses
+  // a row as (environment g, agent r % N), h included: head_tile::load_h has the other heads' flat row addressing
   for (int idx = l; idx < 16 * RTW_H; idx += 64) {
     const int r = idx / RTW_H, c = idx % RTW_H, g = g0 + r / N;
     sh_h[r * RTW_LDH + c] = (r < R && g < p.G) ? p.h[((long)g * N + r % N) * RTW_H + c] : 0.0f;
@@ -109,7 +88,7 @@ __global__ __launch_bounds__(64) void rtw_head_kernel(RtwArgs p) {
     // ---- teammate net: P = h T0[:, :64]^T + b0 (shared by every j)
     const int ldt0 = RTW_H + N;
     for (int n0 = 0; n0 < RTW_H; n0 += 16) {
-      f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_h, RTW_LDH, RTW_H, w.t0_w, ldt0, 0, n0, RTW_H);
+      f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_h, RTW_LDH, RTW_H, w.t0_w, ldt0, 0, n0, RTW_H);
 #pragma unroll
       for (int r = 0; r < 4; ++r) sh_P[drow(r) * RTW_LDH + n0 + m] = acc[r] + w.t0_b[n0 + m];
     }
@@ -123,7 +102,7 @@ __global__ __launch_bounds__(64) void rtw_head_kernel(RtwArgs p) {
       }
       __syncthreads();
       for (int n0 = 0; n0 < A; n0 += 16) {
-        f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_x, RTW_LDH, RTW_H, w.t2_w, RTW_H, 0, n0, A);
+        f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_x, RTW_LDH, RTW_H, w.t2_w, RTW_H, 0, n0, A);
         if (n0 + m < A) {
 #pragma unroll
           for (int r = 0; r < 4; ++r) sh_t[drow(r) * (RTW_AMAX + 1) + n0 + m] = acc[r] + w.t2_b[n0 + m];
@@ -151,7 +130,7 @@ __global__ __launch_bounds__(64) void rtw_head_kernel(RtwArgs p) {
     // ---- world net: o_hat = W2 relu(W0 [o ; m_0 .. m_{N-1}] + b0) + b2
     const int ldw0 = O + N * A;
     for (int n0 = 0; n0 < RTW_H; n0 += 16) {
-      f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_o, ldo, O, w.w0_w, ldw0, 0, n0, RTW_H);
+      f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_o, ldo, O, w.w0_w, ldw0, 0, n0, RTW_H);
       const int c = n0 + m;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -166,7 +145,7 @@ __global__ __launch_bounds__(64) void rtw_head_kernel(RtwArgs p) {
     }
     __syncthreads();
     for (int n0 = 0; n0 < OP; n0 += 16) {
-      f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_x, RTW_LDH, RTW_H, w.w2_w, RTW_H, 0, n0, O);
+      f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_x, RTW_LDH, RTW_H, w.w2_w, RTW_H, 0, n0, O);
       const int c = n0 + m;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -181,14 +160,14 @@ __global__ __launch_bounds__(64) void rtw_head_kernel(RtwArgs p) {
 
   // ---- query = Wq [o ; o_next or o_hat] + bq, scaled by 1 / sqrt(attn_dim) = 1/8 as the score uses it (RTW.py:111)
   for (int n0 = 0; n0 < RTW_H; n0 += 16) {
-    f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_o, ldo, O, w.wq_w, 2 * O, 0, n0, RTW_H);
-    acc = tile_gemm(acc, sh_on, ldo, O, w.wq_w, 2 * O, O, n0, RTW_H);
+    f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_o, ldo, O, w.wq_w, 2 * O, 0, n0, RTW_H);
+    acc = tile_gemm<true>(acc, sh_on, ldo, O, w.wq_w, 2 * O, O, n0, RTW_H);
 #pragma unroll
     for (int r = 0; r < 4; ++r) sh_x[drow(r) * RTW_LDH + n0 + m] = (acc[r] + w.wq_b[n0 + m]) / 8.0f;
   }
   // ---- value pre-activation V0[:, :64] h + bv0 of every row of the tile
   for (int n0 = 0; n0 < RTW_H; n0 += 16) {
-    f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_h, RTW_LDH, RTW_H, w.v0_w, RTW_H + A, 0, n0, RTW_H);
+    f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_h, RTW_LDH, RTW_H, w.v0_w, RTW_H + A, 0, n0, RTW_H);
 #pragma unroll
     for (int r = 0; r < 4; ++r) sh_P[drow(r) * RTW_LDH + n0 + m] = acc[r] + w.v0_b[n0 + m];
   }
@@ -238,7 +217,7 @@ __global__ __launch_bounds__(64) void rtw_head_kernel(RtwArgs p) {
   __syncthreads();
   // ---- q += V2 g + bv2 * sum_j p_j
   for (int n0 = 0; n0 < A; n0 += 16) {
-    f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_x, RTW_LDH, RTW_H, w.v2_w, RTW_H, 0, n0, A);
+    f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_x, RTW_LDH, RTW_H, w.v2_w, RTW_H, 0, n0, A);
     const int c = n0 + m;
     if (c < A) {
 #pragma unroll

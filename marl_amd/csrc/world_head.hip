@@ -6,7 +6,7 @@
 //   r = Wr e + br  (A)   -> q += r                     world_model.py:71
 //   o_hat = Wo e + bo (O), tau = Wt e + bt (2)          tau never reaches a loss; computed on request only
 // Dense products run on the fp32 matrix cores (v_mfma_f32_16x16x4_f32) over the tile with the weights read through L2
-// (W1, W2: 16 KB each, Wr / Wo: A / O rows of 256 B - 99 KB at 2s3z, 129 KB at MMM2), as csrc/rtw_head.hip does.
+// (W1, W2: 16 KB each, Wr / Wo: A / O rows of 256 B - 99 KB at 2s3z, 129 KB at MMM2): the tile product of csrc/head_tile.h.
 //
 // Train mode adds sum (o_hat - o_next)^2 of the tile into one partial per workgroup; a one-workgroup kernel sums the partials in
 // a fixed order and adds the total into the loss slot - no float atomics, the same bits on every run.
@@ -18,10 +18,14 @@
 // and stores z, e, dZ, dE, dR (dense), d_o for the weight gradients: four marl_linear_wgrad reductions (partial slabs, fixed-order
 // reduce) accumulate them into the caller's gradient buffer.  Traffic per row: hs read twice (fwd + bwd) and once more by the
 // W1 reduction; 4 x 64 + A + O floats written and read back once by the reductions.
-#include "common.h"
+#include "head_tile.h"
 #include "../../include/marl_hip.h"
 
 namespace {
+
+using head_tile::drow;
+using head_tile::tile_gemm;    // K-guarded here: O is any width
+using head_tile::tile_gemm_t;
 
 constexpr int WM_H = 64;            // rnn_hidden_dim
 constexpr int WM_LDH = WM_H + 4;
@@ -44,55 +48,6 @@ struct WorldArgs {
   long R; int T, N, O, A;
 };
 
-__host__ __device__ inline long wm_pad(long n) { return (n + 63) / 64 * 64; }
-__host__ __device__ inline int wm_ld4(int n) { return (n + 3) / 4 * 4; }
-
-// acc[16 x 16 column tile n0] += X[16 x K] W^T: W row-major (nvalid rows of ldw floats), X in LDS (row pitch ldx).
-// K-permuted as rtw_head.hip: at step i lane quarter q supplies k0 + 4q + i for both operands.
-__device__ __forceinline__ f32x4 tile_gemm(f32x4 acc, const float* X, int ldx, int K, const float* __restrict__ W, long ldw,
-                                           int n0, int nvalid) {
-  const int l = threadIdx.x, m = l & 15, q4 = (l >> 4) * 4;
-  const int n = n0 + m;
-  const bool nok = n < nvalid;
-  const float* wr = W + (long)(nok ? n : 0) * ldw;
-  for (int k0 = 0; k0 < K; k0 += 16) {
-    const int k = k0 + q4;
-    f32x4 a, b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool kok = k + i < K;
-      a[i] = kok ? X[m * ldx + k + i] : 0.0f;
-      b[i] = (kok && nok) ? __ldg(wr + k + i) : 0.0f;
-    }
-    acc = mfma16x4(a, b, acc);
-  }
-  return acc;
-}
-
-// acc[16 x 16 column tile n0] += X[16 x K] W: W row-major (K rows of ldw floats, columns n < nvalid) - the input gradient of
-// a Linear layer whose weight is W.
-__device__ __forceinline__ f32x4 tile_gemm_t(f32x4 acc, const float* X, int ldx, int K, const float* __restrict__ W, long ldw,
-                                             int n0, int nvalid) {
-  const int l = threadIdx.x, m = l & 15, q4 = (l >> 4) * 4;
-  const int n = n0 + m;
-  const bool nok = n < nvalid;
-  for (int k0 = 0; k0 < K; k0 += 16) {
-    const int k = k0 + q4;
-    f32x4 a, b;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const bool kok = k + i < K;
-      a[i] = kok ? X[m * ldx + k + i] : 0.0f;
-      b[i] = (kok && nok) ? __ldg(W + (long)(k + i) * ldw + n) : 0.0f;
-    }
-    acc = mfma16x4(a, b, acc);
-  }
-  return acc;
-}
-
-// row of D reg r for this lane; its column is n0 + (lane & 15)
-__device__ __forceinline__ int drow(int r) { return 4 * (threadIdx.x >> 4) + r; }
-
 // o_next of row g, column c (c < O): the unroll's addressing (marl_agent_unroll_fwd), steps t >= ep_len read as zeros
 __device__ __forceinline__ float onext_at(const WorldArgs& p, long g, int c) {
   const long tn = (long)p.T * p.N;
@@ -106,13 +61,10 @@ __device__ __forceinline__ float onext_at(const WorldArgs& p, long g, int c) {
 // h of the tile -> sh_h, z -> sh_z, e -> sh_e (rows past R are zeros); optionally stores z and e
 __device__ __forceinline__ void embed(const WorldArgs& p, long row0, float* sh_h, float* sh_z, float* sh_e, bool store) {
   const int l = threadIdx.x, m = l & 15;
-  for (int idx = l; idx < 16 * WM_H; idx += 64) {
-    const int r = idx / WM_H, c = idx % WM_H;
-    sh_h[r * WM_LDH + c] = row0 + r < p.R ? p.h[(row0 + r) * WM_H + c] : 0.0f;
-  }
+  head_tile::load_h(sh_h, WM_LDH, p.h, row0, [&](int r) { return row0 + r < p.R; });
   __syncthreads();
   for (int n0 = 0; n0 < WM_H; n0 += 16) {
-    const f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_h, WM_LDH, WM_H, p.w.h0_w, WM_H, n0, WM_H);
+    const f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_h, WM_LDH, WM_H, p.w.h0_w, WM_H, 0, n0, WM_H);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float v = fmaxf(acc[r] + p.w.h0_b[n0 + m], 0.0f);
@@ -122,7 +74,7 @@ __device__ __forceinline__ void embed(const WorldArgs& p, long row0, float* sh_h
   }
   __syncthreads();
   for (int n0 = 0; n0 < WM_H; n0 += 16) {
-    const f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_z, WM_LDH, WM_H, p.w.h2_w, WM_H, n0, WM_H);
+    const f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_z, WM_LDH, WM_H, p.w.h2_w, WM_H, 0, n0, WM_H);
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const float v = fmaxf(acc[r] + p.w.h2_b[n0 + m], 0.0f);
@@ -142,7 +94,7 @@ __global__ __launch_bounds__(64) void world_fwd_kernel(WorldArgs p) {
   const marl_world_weights_t& w = p.w;
   // ---- r: q += r
   for (int n0 = 0; n0 < p.A; n0 += 16) {
-    const f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_e, WM_LDH, WM_H, w.r_w, WM_H, n0, p.A);
+    const f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_e, WM_LDH, WM_H, w.r_w, WM_H, 0, n0, p.A);
     const int c = n0 + m;
     if (c < p.A) {
 #pragma unroll
@@ -160,7 +112,7 @@ __global__ __launch_bounds__(64) void world_fwd_kernel(WorldArgs p) {
   float lsum = 0.0f;
   if (TRAIN || p.ohat_out) {
     for (int n0 = 0; n0 < p.O; n0 += 16) {
-      const f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_e, WM_LDH, WM_H, w.o_w, WM_H, n0, p.O);
+      const f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_e, WM_LDH, WM_H, w.o_w, WM_H, 0, n0, p.O);
       const int c = n0 + m;
       if (c < p.O) {
 #pragma unroll
@@ -180,7 +132,7 @@ __global__ __launch_bounds__(64) void world_fwd_kernel(WorldArgs p) {
   }
   // ---- tau (terminate_out), on request
   if (p.tau_out) {
-    const f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_e, WM_LDH, WM_H, w.t_w, WM_H, 0, 2);
+    const f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_e, WM_LDH, WM_H, w.t_w, WM_H, 0, 0, 2);
     if (m < 2) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
@@ -241,7 +193,7 @@ __global__ __launch_bounds__(64) void world_bwd_kernel(WorldArgs p) {
   }
   const int OP = (O + 15) / 16 * 16;
   for (int n0 = 0; n0 < OP; n0 += 16) {
-    const f32x4 acc = tile_gemm(f32x4{0, 0, 0, 0}, sh_e, WM_LDH, WM_H, w.o_w, WM_H, n0, O);
+    const f32x4 acc = tile_gemm<true>(f32x4{0, 0, 0, 0}, sh_e, WM_LDH, WM_H, w.o_w, WM_H, 0, n0, O);
     const int c = n0 + m;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -316,10 +268,10 @@ struct BwdLayout {
 
 BwdLayout bwd_layout(long R, int O, int A) {
   BwdLayout L;
-  const long p64 = wm_pad(R * WM_H);
+  const long p64 = head_tile::pad64(R * WM_H);
   L.zs = 0; L.es = p64; L.dz = 2 * p64; L.de = 3 * p64; L.dr = 4 * p64;
-  L.dov = L.dr + wm_pad(R * wm_ld4(A));
-  L.wg = L.dov + wm_pad(R * wm_ld4(O));
+  L.dov = L.dr + head_tile::pad64(R * head_tile::round4(A));
+  L.wg = L.dov + head_tile::pad64(R * head_tile::round4(O));
   size_t wg = 0;
   const int M = R > 0x7fffffff ? 0x7fffffff : (int)R;
   const size_t cand[] = {marl_linear_wgrad_workspace(M, WM_H, WM_H, 1), marl_linear_wgrad_workspace(M, A, WM_H, 1),
@@ -396,7 +348,7 @@ extern "C" int marl_world_head_bwd(const marl_world_weights_t* w, const marl_wor
   a.dq_idx = dq_idx; a.dq_val = dq_val; a.den = den; a.dscale = dscale;
   a.dhs = dhs;
   a.zs = ws + L.zs; a.es = ws + L.es; a.dz = ws + L.dz; a.de = ws + L.de; a.dr = ws + L.dr; a.dov = ws + L.dov;
-  a.lda = wm_ld4(A); a.ldo = wm_ld4(O);
+  a.lda = head_tile::round4(A); a.ldo = head_tile::round4(O);
   a.R = R; a.T = T; a.N = N; a.O = O; a.A = A;
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(world_bwd_kernel, dim3((unsigned)((R + 15) / 16)), dim3(64), 0, s, a);

@@ -9,16 +9,12 @@ BatchNorm follows the module's ``training`` flag as torch does: ``eval()`` norma
 mode - the state of a freshly built module, and the reference never calls ``.eval()`` - with the statistics of all bs * N rows
 of the call, and the running statistics move.  In that mode the rows of one call are coupled.
 """
-import weakref
-
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..hostutil import require_cuda
-from .q_network import RNNQNet
-
-_MAIC_WEIGHTS = weakref.WeakKeyDictionary()
+from .q_network import RNNQNet, cached_struct
 
 
 class MAICAgent(RNNQNet):
@@ -49,22 +45,7 @@ class MAICAgent(RNNQNet):
 
     def maic_weights(self):
         """marl_maic_weights_t over the current parameter and buffer storage (rebuilt only when one moved, as weights())."""
-        c = _MAIC_WEIGHTS.get(self)
-        if c is not None:
-            tlist, ptrs, w = c
-            if all(q.data_ptr() == o and q.is_cuda for q, o in zip(tlist, ptrs)):
-                return w
-        self.weights()                      # moves the module to the device if needed
-        t = dict(self.named_parameters())
-        for v in t.values():
-            if not v.data.is_contiguous():
-                v.data = v.data.contiguous()
-        t = {k: v.data for k, v in t.items()}
-        t.update({k: v for k, v in self.named_buffers()})
-        w = ops.maic_weights(t)
-        tlist = list(t.values())
-        _MAIC_WEIGHTS[self] = (tlist, [q.data_ptr() for q in tlist], w)
-        return w
+        return cached_struct(self, "maic", ops.maic_weights, buffers=True)
 
     def head(self, h, q, bs, test_mode, eps=None, **outs):
         """q (bs*N, A) += the gated messages from h (bs*N, 64), BatchNorm in this module's mode (csrc/maic_head.hip)"""

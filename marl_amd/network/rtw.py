@@ -6,16 +6,12 @@ so the shipped model/qmix/2s3z/*rnn_net_params.pkl files load strictly.  The age
 target=False).  Training-time losses are the constant 0 the reference returns (RTW.py:147-150,167-171); its target pass
 (target=True) fails with a TypeError there, and raises the same error here.
 """
-import weakref
-
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..hostutil import require_cuda
-from .q_network import RNNQNet
-
-_RTW_WEIGHTS = weakref.WeakKeyDictionary()
+from .q_network import RNNQNet, cached_struct
 
 
 class RTWAgent(RNNQNet):
@@ -36,20 +32,7 @@ class RTWAgent(RNNQNet):
 
     def rtw_weights(self):
         """marl_rtw_weights_t over the current parameter storage (rebuilt only when a parameter moved, as weights())."""
-        c = _RTW_WEIGHTS.get(self)
-        if c is not None:
-            plist, ptrs, w = c
-            if all(q.data_ptr() == o and q.is_cuda for q, o in zip(plist, ptrs)):
-                return w
-        self.weights()                      # moves the module to the device if needed
-        p = dict(self.named_parameters())
-        for v in p.values():
-            if not v.data.is_contiguous():
-                v.data = v.data.contiguous()
-        w = ops.rtw_weights({k: v.data for k, v in p.items()})
-        plist = list(p.values())
-        _RTW_WEIGHTS[self] = (plist, [q.data_ptr() for q in plist], w)
-        return w
+        return cached_struct(self, "rtw", ops.rtw_weights)
 
     def forward(self, inputs, hidden_state, obs, obs_next, u, avail_u, target=False, test_mode=False, agent_num=0):
         """reference RTW.py:59-203: (q, h) with test_mode, else (q, h, loss_t, loss_w) with both losses 0."""

@@ -5,16 +5,12 @@ world.o_out, world.terminate_out), so reference state dicts load strictly and th
 learner's flat buffer - is the reference's ``list(mac.parameters())``.  The agent part is the HIP unroll kernel
 (csrc/agent.hip) as in RNNQNet; the head is csrc/world_head.hip: q = fc2(h) + r (world_model.py:71).
 """
-import weakref
-
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..hostutil import require_cuda
-from .q_network import RNNQNet
-
-_WORLD_WEIGHTS = weakref.WeakKeyDictionary()
+from .q_network import RNNQNet, cached_struct
 
 
 class WorldModel(nn.Module):
@@ -40,20 +36,7 @@ class Agent(RNNQNet):
 
     def world_weights(self):
         """marl_world_weights_t over the current parameter storage (rebuilt only when a parameter moved, as weights())."""
-        c = _WORLD_WEIGHTS.get(self)
-        if c is not None:
-            plist, ptrs, w = c
-            if all(q.data_ptr() == o and q.is_cuda for q, o in zip(plist, ptrs)):
-                return w
-        self.weights()                      # moves the module to the device if needed
-        p = dict(self.named_parameters())
-        for v in p.values():
-            if not v.data.is_contiguous():
-                v.data = v.data.contiguous()
-        w = ops.world_weights({k: v.data for k, v in p.items()})
-        plist = list(p.values())
-        _WORLD_WEIGHTS[self] = (plist, [q.data_ptr() for q in plist], w)
-        return w
+        return cached_struct(self, "world", ops.world_weights)
 
     def world_grads(self):
         """marl_world_grads_t over the parameters' .grad views (the learner's flat gradient buffer)."""

@@ -728,16 +728,24 @@ def rtw_supported(N, O, A, H=64, hidden_dim=64, attn_dim=64):
     return bool(_lib.load().marl_rtw_supported(N, O, A, H, hidden_dim, attn_dim))
 
 
+def _linear_fields(keys):
+    return [(short + suf, name + key, torch.float32) for short, name in keys for suf, key in (("_w", ".weight"), ("_b", ".bias"))]
+
+
+def _fill_struct(cls, tensors, fields):
+    """cls() with every (field, tensor name, dtype) of `fields` set to the data pointer of tensors[name]"""
+    w = cls()
+    for field, name, dt in fields:
+        t = tensors[name]
+        assert t.is_contiguous() and t.dtype == dt and t.is_cuda, name
+        setattr(w, field, t.data_ptr())
+    w._keep = tensors
+    return w
+
+
 def rtw_weights(params):
     """params: dict name -> tensor with RTWAgent keys (network/RTW.py:24-56) -> marl_rtw_weights_t."""
-    w = MarlRtwWeights()
-    for short, name in RTW_KEYS:
-        for suf, key in (("_w", ".weight"), ("_b", ".bias")):
-            t = params[name + key]
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda, name + key
-            setattr(w, short + suf, t.data_ptr())
-    w._keep = params
-    return w
+    return _fill_struct(MarlRtwWeights, params, _linear_fields(RTW_KEYS))
 
 
 def rtw_head_act(w, h, obs, obs_bs, obs_t0, avail, av_bs, av_t0, q, E, N, O, A, not_self_model=True, a_out=None,
@@ -765,25 +773,14 @@ def world_supported(N, O, A, H=64):
     return bool(_lib.load().marl_world_supported(N, O, A, H))
 
 
-def _world_struct(cls, params, keys):
-    w = cls()
-    for short, name in keys:
-        for suf, key in (("_w", ".weight"), ("_b", ".bias")):
-            t = params[name + key]
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda, name + key
-            setattr(w, short + suf, t.data_ptr())
-    w._keep = params
-    return w
-
-
 def world_weights(params):
     """params: dict name -> tensor with world_model.Agent keys (network/world_model.py:12-19) -> marl_world_weights_t."""
-    return _world_struct(MarlWorldWeights, params, WORLD_KEYS)
+    return _fill_struct(MarlWorldWeights, params, _linear_fields(WORLD_KEYS))
 
 
 def world_grads(grads):
     """grads: dict name -> gradient tensor with the same keys (terminate_out not needed) -> marl_world_grads_t."""
-    return _world_struct(MarlWorldGrads, grads, WORLD_KEYS[:4])
+    return _fill_struct(MarlWorldGrads, grads, _linear_fields(WORLD_KEYS[:4]))
 
 
 def world_head_fwd(w, h, q, B, T, N, O, A, r_out=None, ohat_out=None, tau_out=None, obs=None, obs_bs=0, obs_t0=0,
@@ -828,14 +825,7 @@ def maic_supported(N, O, A, H=64, NH=64, L=8, D=32):
 
 def maic_weights(tensors):
     """tensors: dict name -> tensor with MAICAgent's parameter and buffer keys (network/MAIC.py:19-47) -> marl_maic_weights_t."""
-    w = MarlMaicWeights()
-    names = [(short + suf, name + key, torch.float32) for short, name in MAIC_KEYS for suf, key in (("_w", ".weight"), ("_b", ".bias"))]
-    for field, name, dt in names + list(MAIC_BN):
-        t = tensors[name]
-        assert t.is_contiguous() and t.dtype == dt and t.is_cuda, name
-        setattr(w, field, t.data_ptr())
-    w._keep = tensors
-    return w
+    return _fill_struct(MarlMaicWeights, tensors, _linear_fields(MAIC_KEYS) + list(MAIC_BN))
 
 
 def maic_head_fwd(w, h, q, bs, N, A, test_mode=True, bn_batch=False, eps=None, var_floor=0.002, bn_eps=1e-5, bn_momentum=0.1,

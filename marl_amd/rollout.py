@@ -156,10 +156,7 @@ class RolloutWorker:
         if a.replay_dir != '' and evaluate:
             env.close()
         mode = getattr(self, "rollout_mode", "whole")      # "whole" | "fused_step" | "unfused" (tests)
-        rtw = getattr(mac, "rtw", False)
-        world = getattr(mac, "world", False)
-        maic = getattr(mac, "maic", False)
-        if mode == "whole" and not rtw and not world and not maic and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
+        if mode == "whole" and mac.head_name is None and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
             # the persistent kernel writes every field of the record, so training rollouts can be
             # played straight into the replay ring (record_sink = the ReplayBuffer; zero-copy store)
             sink = getattr(self, "record_sink", None)
@@ -183,24 +180,13 @@ class RolloutWorker:
         if a.epsilon_anneal_scale == 'episode':
             epsilon = epsilon - self.anneal_epsilon if epsilon > self.min_epsilon else epsilon
         w = mac.agent.weights()
-        w_rtw = mac.agent.rtw_weights() if rtw else None
-        w_world = mac.agent.world_weights() if world else None
-        maic_eps = torch.empty(E * N, N * a.latent_dim, device=dev) if maic and not evaluate else None
         fused = hasattr(env, "fused_step") and mode != "unfused"
         env.observe(0, rec)
         for t in range(T):
             # agent step = the unroll kernel with T=1 reading slot t of the record in place
             ops.agent_unroll_fwd(w, rec.obs, (T + 1) * N, t, rec.u, T * N, t - 1, h, q, None, h, None,
                                  E, 1, N, O, A, a.last_action, a.reuse_network)
-            if rtw:     # q += the reflection term (RTWMAC.choose_action for every agent, share_params.py:641-677)
-                ops.rtw_head_act(w_rtw, h, rec.obs, (T + 1) * N, t, rec.avail, (T + 1) * N, t, q, E, N, O, A,
-                                 mac.not_self_model())
-            if world:   # q += r (SharedMACWithState.choose_action for every agent, share_params.py:214-260)
-                ops.world_head_fwd(w_world, h, q, E, 1, N, O, A)
-            if maic:    # q += the gated messages (MAICMAC.choose_action for every agent of every env)
-                if maic_eps is not None:
-                    ops.maic_noise(self.rseed, env.env0, env.global_step(t), maic_eps, E, N)
-                mac.agent.head(h, q.view(E * N, A), E, bool(evaluate), maic_eps)
+            mac.rollout_head(h, q, rec, t, E, evaluate, self.rseed, env)     # q += the controller's head term, if it has one
             if fused:
                 env.fused_step(t, q, epsilon, self.rseed, rec)
             else:
@@ -257,12 +243,10 @@ class RolloutWorker:
         on the CURRENT stream (a side stream in the overlapped runner) and return a handle for finish_episodes().
         ``mac``: the controller whose weights the rollout reads (a snapshot while the learner updates the live one)."""
         env = self.env
-        if getattr(mac if mac is not None else self.mac, "rtw", False):
-            raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no RTW head: use generate_episodes")
-        if getattr(mac if mac is not None else self.mac, "world", False):
-            raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no world-model head: use generate_episodes")
-        if getattr(mac if mac is not None else self.mac, "maic", False):
-            raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no MAIC head: use generate_episodes")
+        mac = mac if mac is not None else self.mac
+        if mac.head_name is not None:
+            raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no %s head: use generate_episodes"
+                               % mac.head_name)
         if not (getattr(env, "batched", False) and hasattr(env, "whole_rollout") and env.supports_whole_rollout()):
             raise RuntimeError("launch_episodes needs a batched env with the whole-rollout kernel")
         dev = require_cuda("RolloutWorker")
@@ -273,7 +257,7 @@ class RolloutWorker:
                                         self.n_actions, dev)
         if rec is None:
             rec = env.new_record()
-        return self._launch_whole(rec, evaluate, mac if mac is not None else self.mac)
+        return self._launch_whole(rec, evaluate, mac)
 
     def finish_episodes(self, pending, lazy=False):
         """(episodes, rewards, win_tags, steps) of a launched rollout: the one device-to-host copy (and sync).
@@ -322,13 +306,15 @@ class RolloutWorker:
                         while avail_actions[agent_id][action] == 0:
                             action = np.random.randint(0, A - 1)
                     else:
-                        # RTW: every agent's availability (rollout.py:73-76)
-                        if getattr(self.mac, "maic", False):      # every agent's observation, last action and availability
+                        # what the controller asks for: the agent's own rows, every agent's availability (RTW,
+                        # rollout.py:73-76), or every agent's observation, last action and availability (MAIC)
+                        inputs = self.mac.choose_action_inputs
+                        if inputs == "all":
                             action = self.mac.choose_action(obs, last_actions, agent_id, avail_actions, epsilon, evaluate)
                         else:
                             action = self.mac.choose_action(obs[agent_id], last_actions[agent_id], agent_id,
-                                                            avail_actions if getattr(a, "RTW", False) else avail_actions[agent_id], epsilon,
-                                                            evaluate)
+                                                            avail_actions if inputs == "avail_all" else avail_actions[agent_id],
+                                                            epsilon, evaluate)
                     onehot = np.zeros(A)
                     onehot[action] = 1
                     actions.append(action)

@@ -28,6 +28,7 @@ Full resume: ``save_resume`` / ``load_resume`` carry what the refe
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
 
+import collections
 import copy
 import os
 
@@ -45,35 +46,52 @@ from .algorithm.maic_q_learner import MAICQLearner
 from .utils.logging import Logger
 
 
+def _qtran(args):
+    return args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1
+
+
+def _value_mixer(args):
+    return any(args.alg.find(a) > -1 for a in ('vdn', 'qmix', 'qplex'))
+
+
+# One row per agent switch: the controller, the learner, and its refusals as (exception type, text) - combined with a
+# switch of an earlier row, with a learner it cannot drive, with overlapped rollouts.  The rows and a row's checks run in
+# this order, before anything is built; the types differ per row on purpose (module docstring).
+_Switch = collections.namedtuple("_Switch", "name mac learner combined alg_refused alg overlap")
+_AGENT_SWITCHES = (
+    _Switch("RTW", RTWMAC, lambda mac, logger, args: RTWQLearner(mac, logger, args),
+            None,
+            _qtran, (NotImplementedError, "RTW with a QTRAN learner is not supported (the reference's QTRANLearner cannot "
+                                          "drive an RTW controller)"),
+            (NotImplementedError, "overlapped rollouts use the whole-rollout kernel, which has no RTW head")),
+    _Switch("world_model", SharedMACWithState, lambda mac, logger, args: QLearnerWithState(mac, args),
+            (ValueError, "world_model and RTW are two different agents: choose one"),
+            lambda args: not _value_mixer(args), (ValueError, "Mixer {} not recognised."),     # q_learner_state.py:32
+            (NotImplementedError, "overlapped rollouts use the whole-rollout kernel, which has no world-model head")),
+    _Switch("MAIC", MAICMAC, lambda mac, logger, args: MAICQLearner(mac, args),
+            (ValueError, "MAIC, RTW and world_model are three different agents: choose one"),
+            _qtran, (NotImplementedError, "MAIC with a QTRAN learner is not supported"),
+            (NotImplementedError, "overlapped rollouts use the whole-rollout kernel, which has no MAIC head")),
+)
+
+
 class Runner:
     def __init__(self, env, logger, args):
         self.env = env
         if not args.reuse_network:
             raise NotImplementedError("only the shared-parameter controller (reuse_network) is on the hot path")
-        rtw = bool(getattr(args, "RTW", False))
-        if rtw and (args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1):
-            raise NotImplementedError("RTW with a QTRAN learner is not supported (the reference's QTRANLearner cannot "
-                                      "drive an RTW controller)")
-        if rtw and getattr(args, "overlap_rollout", False):
-            raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no RTW head")
-        world = bool(getattr(args, "world_model", False))
-        if world and rtw:
-            raise ValueError("world_model and RTW are two different agents: choose one")
-        if world and not any(args.alg.find(a) > -1 for a in ('vdn', 'qmix', 'qplex')):
-            raise ValueError("Mixer {} not recognised.".format(args.alg))     # QLearnerWithState (q_learner_state.py:32)
-        if world and getattr(args, "overlap_rollout", False):
-            raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no world-model head")
-        maic = bool(getattr(args, "MAIC", False))
-        if maic and (rtw or world):
-            raise ValueError("MAIC, RTW and world_model are three different agents: choose one")
-        if maic and (args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1):
-            raise NotImplementedError("MAIC with a QTRAN learner is not supported")
-        if maic and getattr(args, "overlap_rollout", False):
-            raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no MAIC head")
-        if maic:
+        mac_cls, make_learner = SharedMAC, lambda mac, logger, args: QLearner(mac, args)
+        on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
+        for sw in on:
+            for hit, refusal in ((sw is not on[0], sw.combined), (sw.alg_refused(args), sw.alg),
+                                 (getattr(args, "overlap_rollout", False), sw.overlap)):
+                if hit:
+                    raise refusal[0](refusal[1].format(args.alg))
+            mac_cls, make_learner = sw.mac, sw.learner
+        if mac_cls is MAICMAC:
             from .common.arguments import get_maic_args
             get_maic_args(args)
-        self.mac = RTWMAC(args) if rtw else SharedMACWithState(args) if world else MAICMAC(args) if maic else SharedMAC(args)
+        self.mac = mac_cls(args)
         self.rolloutWorker = RolloutWorker(env, self.mac, args)
         self.buffer = ReplayBuffer(args)
         self.rolloutWorker.record_sink = self.buffer   # batched rollouts write into the replay ring in place
@@ -87,10 +105,9 @@ class Runner:
         os.makedirs(self.save_path, exist_ok=True)
         logger.setup_tb(self.save_path + '/tb/other')
         self.logger = logger
-        if any(args.alg.find(a) > -1 for a in ('vdn', 'qmix', 'qplex')):
-            self.learner = RTWQLearner(self.mac, logger, args) if rtw else \
-                QLearnerWithState(self.mac, args) if world else MAICQLearner(self.mac, args) if maic else QLearner(self.mac, args)
-        elif args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1:
+        if _value_mixer(args):
+            self.learner = make_learner(self.mac, logger, args)
+        elif _qtran(args):
             self.learner = QTRANLearner(self.mac, args)
         else:
             raise ValueError('learner {} cannot find!'.format(args.alg))

@@ -4,6 +4,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 import torch
 
 from oracle import seeded, learners
@@ -217,3 +218,61 @@ def test_launcher_vectorises_an_importable_smac(tmp_path, monkeypatch):
     assert se.StarCraft2Env is not real and se.StarCraft2Env._marl_real is real
     assert vectorise_real_smac(8) is True and se.StarCraft2Env._marl_real is real      # idempotent
     _forget_dropin_modules()
+
+
+_OVERLAP = "overlapped rollouts use the whole-rollout kernel, which has no %s head"
+_RUNNER_REFUSALS = [
+    (dict(RTW=True, alg="qtran_base"), NotImplementedError,
+     "RTW with a QTRAN learner is not supported (the reference's QTRANLearner cannot drive an RTW controller)"),
+    (dict(RTW=True, alg="qtran_alt"), NotImplementedError,
+     "RTW with a QTRAN learner is not supported (the reference's QTRANLearner cannot drive an RTW controller)"),
+    (dict(RTW=True, overlap_rollout=True), NotImplementedError, _OVERLAP % "RTW"),
+    (dict(world_model=True, RTW=True), ValueError, "world_model and RTW are two different agents: choose one"),
+    (dict(world_model=True, alg="qtran_base"), ValueError, "Mixer qtran_base not recognised."),
+    (dict(world_model=True, alg="qtran_alt"), ValueError, "Mixer qtran_alt not recognised."),
+    (dict(world_model=True, alg="iql"), ValueError, "Mixer iql not recognised."),
+    (dict(world_model=True, overlap_rollout=True), NotImplementedError, _OVERLAP % "world-model"),
+    (dict(MAIC=True, RTW=True), ValueError, "MAIC, RTW and world_model are three different agents: choose one"),
+    (dict(MAIC=True, world_model=True), ValueError, "MAIC, RTW and world_model are three different agents: choose one"),
+    (dict(MAIC=True, alg="qtran_base"), NotImplementedError, "MAIC with a QTRAN learner is not supported"),
+    (dict(MAIC=True, alg="qtran_alt"), NotImplementedError, "MAIC with a QTRAN learner is not supported"),
+    (dict(MAIC=True, overlap_rollout=True), NotImplementedError, _OVERLAP % "MAIC"),
+    # the first check that fires wins: the RTW row runs before the world-model row, world-model's before MAIC's
+    (dict(RTW=True, world_model=True, alg="qtran_base"), NotImplementedError,
+     "RTW with a QTRAN learner is not supported (the reference's QTRANLearner cannot drive an RTW controller)"),
+    (dict(RTW=True, world_model=True, overlap_rollout=True), NotImplementedError, _OVERLAP % "RTW"),
+    (dict(world_model=True, MAIC=True, alg="qtran_alt"), ValueError, "Mixer qtran_alt not recognised."),
+    (dict(world_model=True, MAIC=True, overlap_rollout=True), NotImplementedError, _OVERLAP % "world-model"),
+]
+
+
+@pytest.mark.parametrize("over,exc,text", _RUNNER_REFUSALS, ids=["+".join("%s=%s" % kv for kv in o.items())
+                                                                 for o, _, _ in _RUNNER_REFUSALS])
+def test_runner_refusals_keep_type_and_text(over, exc, text, monkeypatch):
+    """every refusal of an agent switch (runner.py's module docstring) with its exact exception type and text, raised
+    before a controller, a rollout worker or a replay buffer is built"""
+    from marl_amd import runner
+    built = []
+    for name in ("RolloutWorker", "ReplayBuffer"):
+        monkeypatch.setattr(runner, name, lambda *a, _n=name, **k: built.append(_n))
+    args = seeded.make_args("2s3z", "qmix")
+    args.__dict__.update(over)
+    with pytest.raises(exc) as info:
+        runner.Runner(None, None, args)
+    assert type(info.value) is exc and str(info.value) == text
+    assert built == []
+
+
+@pytest.mark.parametrize("cls,head", [("RTWMAC", "RTW"), ("SharedMACWithState", "world-model"), ("MAICMAC", "MAIC")])
+def test_launch_episodes_refuses_a_controller_with_a_head(cls, head):
+    from marl_amd.controller import share_params
+    from marl_amd.rollout import RolloutWorker
+    worker = RolloutWorker.__new__(RolloutWorker)
+    worker.env, worker.mac = None, None
+    mac_cls = getattr(share_params, cls)
+    text = "launch_episodes runs the whole-rollout kernel, which has no %s head: use generate_episodes" % head
+    for kw in (dict(mac=mac_cls.__new__(mac_cls)), dict()):
+        worker.mac = None if kw else mac_cls.__new__(mac_cls)
+        with pytest.raises(RuntimeError) as info:
+            worker.launch_episodes(**kw)
+        assert str(info.value) == text
