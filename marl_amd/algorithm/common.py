@@ -2,13 +2,18 @@
 tail, the fused clip+optimizer wrapper, the agent backward pass and data-parallel reduction."""
 from __future__ import annotations
 
+import copy
+import os
 import warnings
 import weakref
 
+import numpy as np
 import torch
 
 from .. import ops, experiments
-from ..hostutil import FlatParams
+from ..hostutil import FlatParams, DeviceBatch, AsyncInt, require_cuda
+from ..network.mixer import x6_mode
+from ..rollout import EpisodeBatch
 
 MASK_BIG = -9999999.0        # reference algorithm/q_learner.py:105,112,126 ; qtran_learner.py:106
 MASK_QTRAN_EVAL = -999999.0  # reference algorithm/qtran_learner.py:105
@@ -158,9 +163,58 @@ class LossReadback:
         return LossReadback.Handle(buf, ev, fn)
 
 
-class SpeculativeBatchMixin:
-    """Learners with `_forward_backward(db)`, `args`, `reducer`, `max_episode_len`."""
+class Learner(ResumeMixin):
+    """The frame of QLearner and QTRANLearner: construction around the learner's own mixers, the batch intake of ``train``,
+    the loss tail, the target copies and the model files.  A learner provides ``_forward_backward(db)``, ``cuda()``,
+    ``sync_replicas()`` and the three items of the loss tail: how many statistics slots it reads, which of them is the
+    denominator, and ``_loss_fn()``."""
     _full_len_streak = 0      # consecutive updates whose max_episode_len was the record's full length
+    n_stats, den_slot = 2, 1  # the loss tail reads stats[:n_stats]; the optimizer divides by stats[den_slot]
+    extra_nets = ()           # attributes of further modules with a <name>_net_params.pkl file of their own
+
+    def _begin(self, mac, args, name):
+        """constructor preamble; the learner then builds mixer / target_mixer / params and calls cuda() and _ready()"""
+        self.max_episode_len = args.episode_limit
+        self.gamma = args.gamma
+        self.lr = args.lr
+        self.model_dir = args.model_dir + '/' + args.alg + '/' + args.map
+        self.args = args
+        self.device = require_cuda(name)
+
+        self.eval_net = mac
+        self.eval_net.cuda()
+        self.target_net = copy.deepcopy(mac)
+
+    def _ready(self, needs_avail):
+        """constructor postamble.  needs_avail: the update reads the current-step availability"""
+        args = self.args
+        self.optimizer = FusedOptimizer(self._flat, args.optimizer, self.lr, args.grad_norm_clip)
+        self._buf = Scratch()
+        self.reducer = GradReducer()
+        self.pair = PairedUnroll(x6=x6_mode(args))
+        self.loss_readback = LossReadback(args)
+        self.graphs = GraphedUpdate.from_args(args)
+        self.needs_avail = needs_avail
+        self.last_stats = None
+        self.sync_replicas()
+
+    def _update_targets(self):
+        """reference q_learner.py:181-184 - two device copies (one for a mixer without parameters: VDN)."""
+        self.target_net.agent._flat.flat.copy_(self.eval_net.agent._flat.flat)
+        if self.mixer is not None and self.mixer._flat.n:
+            self.target_mixer._flat.flat.copy_(self.mixer._flat.flat)
+
+    def _g(self, name, shape, dt=torch.float32):
+        """scratch buffer of the update pass, one per (name, shape, dtype)"""
+        return self._buf.get(name, shape, self.device, dt)
+
+    # ------------------------------------------------------------------ the hot path
+    def get_max_episode_len(self, batch):
+        """reference q_learner.py:49-66 (quirk Q2); returns the batch cut to [:, :T] and T."""
+        T = DeviceBatch.first_terminated_len(torch.as_tensor(np.asarray(batch['terminated'])), self.args.episode_limit)
+        for key in batch.keys():
+            batch[key] = batch[key][:, :T]
+        return batch, T
 
     def _device_batch(self, rec, index, small):
         """DeviceBatch of a device record with max_episode_len agreed.  While the last updates all ran at the record's
@@ -169,7 +223,6 @@ class SpeculativeBatchMixin:
         never waits for the host's first launches after the sync.  A different length - every episode of the batch ended
         early - redoes the pass (forward / backward overwrite their outputs and zero the gradient buffer themselves).
         Returns None when the pass has already been launched."""
-        from ..hostutil import DeviceBatch
         term = (small if small is not None else rec).term
         if not (term.is_cuda and term.dtype == torch.float32 and term.shape[0] > 0) or self._full_len_streak < 2:
             db = DeviceBatch.from_record_auto(rec, self.args, reducer=self.reducer, index=index, small=small)
@@ -184,6 +237,70 @@ class SpeculativeBatchMixin:
             return None
         self._full_len_streak = 0
         return DeviceBatch.from_record(rec, self.args, T=T, index=index, small=small)
+
+    def train(self, batch, train_step):
+        ring = batch.ring if isinstance(batch, EpisodeBatch) else None
+        if self.graphs is not None and ring is not None and self.graphs.run(self, ring, batch.index):
+            db = None                        # forward / backward done (hipGraph replay on the static buffers)
+        elif isinstance(batch, DeviceBatch):
+            db = batch
+        elif ring is not None:
+            # replay sample: big arrays are read in place from the ring through the episode index
+            prep = self.graphs.prepared if self.graphs is not None else None
+            if prep is not None:             # the graph path already gathered the small arrays and agreed on T
+                self.graphs.prepared = None
+                db = DeviceBatch.from_record(ring, self.args, T=prep[1], index=batch.index, small=prep[0])
+            else:
+                small = ring.select_small(batch.index, avail_cur=self.needs_avail)
+                db = self._device_batch(ring, batch.index, small)
+        elif isinstance(batch, EpisodeBatch) and batch.record is not None:
+            db = self._device_batch(batch.record, None, None)
+        else:
+            T = None
+            if self.reducer.enabled:         # shards must agree on T
+                T = DeviceBatch.first_terminated_len(torch.as_tensor(np.asarray(batch['terminated'])),
+                                                     self.args.episode_limit, reducer=self.reducer)
+            db = DeviceBatch.from_dict(batch, self.args, self.device, T=T)
+        if db is not None:                   # (None: _device_batch already launched the pass for the record's full length)
+            self.max_episode_len = db.T
+            self._forward_backward(db)
+        return self._finish_update(train_step)
+
+    def _loss_fn(self):
+        """host statistics stats[:n_stats] -> the loss value"""
+        return lambda s: s[0] / s[1]
+
+    def _finish_update(self, train_step):
+        """gradient all-reduce, clip + optimizer, target sync, loss readback (reference q_learner.py:168-179)"""
+        self.reducer.allreduce_(self._flat.gradx)
+        stats = self._flat.stats
+        self.optimizer.step(den=stats[self.den_slot:self.den_slot + 1])
+        if train_step > 0 and train_step % self.args.target_update_cycle == 0:
+            self._update_targets()
+        self.last_stats = stats
+        return self.loss_readback.read(stats[:self.n_stats], self._loss_fn())
+
+    # ------------------------------------------------------------------ checkpoints (reference q_learner.py:193-209)
+    def save_models(self, train_step):
+        num = str(train_step // self.args.save_cycle)
+        if not os.path.exists(self.model_dir):
+            os.makedirs(self.model_dir)
+        self.eval_net.save_models(self.model_dir + '/' + num + '_rnn_net_params.pkl')
+        for name in ("mixer",) + self.extra_nets:
+            torch.save({k: v.detach().cpu() for k, v in getattr(self, name).state_dict().items()},
+                       self.model_dir + '/' + num + '_' + name + '_net_params.pkl')
+
+    def load_models(self):
+        if os.path.exists(self.model_dir + '/rnn_net_params.pkl'):
+            path_rnn = self.model_dir + '/rnn_net_params.pkl'
+            path_mix = self.model_dir + '/mixer_net_params.pkl'
+            self.eval_net.load_models(path_rnn)
+            for name in ("mixer",) + self.extra_nets:
+                getattr(self, name).load_state_dict(torch.load(self.model_dir + '/' + name + '_net_params.pkl', map_location='cpu'))
+            self.sync_replicas()
+            print('Successfully load the model: {} and {}'.format(path_rnn, path_mix))
+        else:
+            raise Exception("No model!")
 
 
 class Scratch:
@@ -216,8 +333,7 @@ def agent_backward(mac, db, which, saved, hs, dq, dhs, buf, dq_idx=None, dq_val=
              "fc2.weight": ag.fc2.weight.grad, "fc2.bias": ag.fc2.bias.grad}
     # opt-in args.gemm_mode = "bf16x6": the split BPTT kernel (csrc/agent_bwd_x6.hip; one workgroup per 16 rows up to 256 row tiles,
     # per 32 rows beyond) - faster than the fp32 kernels at every size measured (profiles/archive/r04_unroll_x6_times.txt)
-    from ..network import mixer as _mixer
-    x6 = (getattr(args, "gemm_mode", _mixer.DEFAULT_GEMM_MODE) == "bf16x6" and dq is None and dq_idx is not None
+    x6 = (x6_mode(args) and dq is None and dq_idx is not None
           and (B * N + 31) // 32 >= experiments.get("x6_bwd_min_wg") and ops.agent_unroll_bwd_x6_supported(B, T, N, A))
     ops.agent_unroll_bwd(w, dq, dhs, saved, hs, dxp, None, grads, B, T, N, A, dq_idx=dq_idx, dq_val=dq_val,
                          dq_idx2=dq_idx2, dq_val2=dq_val2, dq_gdiv=dq_gdiv, x6=x6)
@@ -396,12 +512,10 @@ class GraphedUpdate:
     def _schedule_key(args):
         """what a captured schedule froze besides shapes and pointers: the generation of the experiments table (every
         experiments.set() bumps it) and the args fields the launch sequence reads"""
-        from .. import experiments
         return (experiments.generation,) + tuple(repr(getattr(args, k, None)) for k in GraphedUpdate.SCHEDULE_ARGS)
 
     def run(self, learner, ring, index):
         """Returns True when the update's forward/backward was done here (static buffers + graph), else False."""
-        from ..hostutil import DeviceBatch, AsyncInt
         self.prepared = None
         if self.disabled:
             return False

@@ -10,31 +10,19 @@ Q6 (target sync rule) are reproduced.
 from __future__ import annotations
 
 import copy
-import os
 
 import numpy as np
 import torch
 
-from .. import ops
-from ..hostutil import require_cuda, DeviceBatch, flatten_module
-from ..rollout import EpisodeBatch
+from .. import ops, experiments
+from ..hostutil import flatten_module
 from ..network.mixer import VDNMixer, QMixMixer, DMAQer
-from .common import (MASK_BIG, LearnerParams, FlatView, FusedOptimizer, Scratch, agent_backward, GradReducer, PairedUnroll, ResumeMixin, LossReadback, SpeculativeBatchMixin,
-                     GraphedUpdate)
+from .common import MASK_BIG, LearnerParams, FlatView, Learner, agent_backward
 
 
-class QLearner(ResumeMixin, SpeculativeBatchMixin):
+class QLearner(Learner):
     def __init__(self, mac, args):
-        self.max_episode_len = args.episode_limit
-        self.gamma = args.gamma
-        self.lr = args.lr
-        self.model_dir = args.model_dir + '/' + args.alg + '/' + args.map
-        self.args = args
-        self.device = require_cuda("QLearner")
-
-        self.eval_net = mac
-        self.eval_net.cuda()
-        self.target_net = copy.deepcopy(mac)
+        self._begin(mac, args, "QLearner")
         if args.alg == 'vdn':
             self.mixer = VDNMixer(args)
         elif args.alg == 'qmix':
@@ -46,17 +34,7 @@ class QLearner(ResumeMixin, SpeculativeBatchMixin):
         self.target_mixer = copy.deepcopy(self.mixer)
         self.params = list(mac.parameters()) + list(self.mixer.parameters())
         self.cuda()
-
-        self.optimizer = FusedOptimizer(self._flat, args.optimizer, self.lr, args.grad_norm_clip)
-        self._buf = Scratch()
-        self.reducer = GradReducer()
-        from ..network import mixer as _mixer
-        self.pair = PairedUnroll(x6=getattr(args, "gemm_mode", _mixer.DEFAULT_GEMM_MODE) == "bf16x6")
-        self.loss_readback = LossReadback(args)
-        self.graphs = GraphedUpdate.from_args(args)
-        self.needs_avail = args.alg == 'qplex'       # the current-step availability masks the greedy action (:135-140)
-        self.last_stats = None
-        self.sync_replicas()
+        self._ready(needs_avail=args.alg == 'qplex')     # the current-step availability masks the greedy action (:135-140)
 
     def sync_replicas(self):
         """Data-parallel replicas start from rank 0's parameters, targets and optimizer state (called after
@@ -81,67 +59,70 @@ class QLearner(ResumeMixin, SpeculativeBatchMixin):
         flatten_module(self.target_net.agent, dev)
         flatten_module(self.target_mixer, dev)
 
-    def _update_targets(self):
-        """reference :181-184 - two device copies."""
-        self.target_net.agent._flat.flat.copy_(self.eval_net.agent._flat.flat)
-        if self.mixer is not None and self.mixer._flat.n:
-            self.target_mixer._flat.flat.copy_(self.mixer._flat.flat)
-
-    # ------------------------------------------------------------------ the hot path
-    def get_max_episode_len(self, batch):
-        """reference :49-66 (quirk Q2); returns the batch cut to [:, :T] and T."""
-        T = DeviceBatch.first_terminated_len(torch.as_tensor(np.asarray(batch['terminated'])), self.args.episode_limit)
-        for key in batch.keys():
-            batch[key] = batch[key][:, :T]
-        return batch, T
-
-    def _forward_backward(self, db):
-        a = self.args
-        dev = self.device
+    # ------------------------------------------------------------------ the hot path: the stages of one update pass
+    def _unrolls(self, db, keep_hs=False):
+        """The three agent unrolls: eval current-Q (keeps activations), its double-Q continuation, target next-Q.
+        keep_hs: each also writes its per-step hidden states (B,T,N,H).  Without it none does: the Q-learning losses do
+        not read them and BPTT finds h(t) in `saved`.  Returns q_evals, q_en, q_tgt, saved, (hs, hs_en, hs_tgt)."""
+        a, g = self.args, self._g
         B, T, N, A, H = db.B, db.T, db.N, db.A, a.rnn_hidden_dim
-        R, BT = B * T * N, B * T
-        g = lambda name, shape, dt=torch.float32: self._buf.get(name, shape, dev, dt)
-        # (no (B,T,N,H) hidden-state output: the Q-learning losses do not read it and BPTT finds h(t) in `saved`)
-        q_evals, hs, saved = g("q_evals", (B, T, N, A)), None, g("saved", ops.saved_shape(T, B, N))
+        q_evals, saved = g("q_evals", (B, T, N, A)), g("saved", ops.saved_shape(T, B, N))
         h_last, h_scr = g("h_last", (B * N, H)), g("h_scr", (B * N, H))
         q_tgt, q_en = g("q_tgt", (B, T, N, A)), g("q_en", (B, T, N, A))
-        q_chosen, q_tgt_chosen = g("q_chosen", (R,)), g("q_tgt_chosen", (R,))
+        hs = hs_en = hs_tgt = None
+        if keep_hs:
+            hs, hs_tgt = g("hs", (B, T, N, H)), g("hs_tgt", (B, T, N, H))
+            hs_en = g("hs_en", (B, T, N, H)) if a.double_q else None
         (oc, oc_bs, oc_t0), (on, on_bs, on_t0) = db.o_cur, db.o_next
-        u_act = db.u_act.reshape(-1)
 
-        # eval current-Q unroll (keeps activations), target next-Q unroll
-        # (independent of each other: on small shards they run side by side on two streams, half of the CUs each)
+        # the eval and the target unroll are independent of each other: on small shards they run side by side on two
+        # streams, a share of the CUs each
         emap = getattr(db, 'o_map', None)
         # quirk Q1: no init_hidden between the two eval passes (reference :96-110) - the double-Q pass continues the eval chain.
         # Its inputs at steps 0..T-2 are the eval pass's inputs at steps 1..T-1 (same observations, same last actions, same
-        # weights): fc1 and the input-side gate sums stored there are reused (gi), where the kernels of this shape can
+        # weights): fc1 and the input-side gate sums stored there are reused (gi), where the kernels of this shape can.
+        # Every unroll kernel stores hs when given it, the gi_in continuation included; the bf16x6 entry then runs hs-writing
+        # launches on csrc/agent_x6.hip (never the non-saving agent_x6p.hip path), so the gate sums pair up either way
         cont, gi = None, None
         if a.double_q:
             shifted = on is oc and on_bs == oc_bs and on_t0 == oc_t0 + 1
             split = self.pair.chain_split(B * N, T, a.obs_shape)
-            from .. import experiments
             # (the continuation keeps reading the eval pass's input-side gate sums at every batch size: 0.55 ms at 4096 envs against
             # 0.97 ms for a plain unroll in the round-6 decomposition, csrc/agent_x6p.hip - which the TARGET unroll below runs on)
             if shifted and ((self.eval_net.unroll_x6(B, T, oc) and experiments.get("fwd_xs") != 0) or
                             ops.agent_unroll_reuse_supported(B, T, N, a.obs_shape, A, split[0] if split else 256)):
                 gi = g("gi", ops.saved_shape(T, B, N, planes=3))
-            cont = lambda cu: self.eval_net.unroll(on, on_bs, on_t0, db.u_fed, db.u_bs, 0, B, T, q_en, None, h_scr, None, h0=h_last,
+            cont = lambda cu: self.eval_net.unroll(on, on_bs, on_t0, db.u_fed, db.u_bs, 0, B, T, q_en, hs_en, h_scr, None, h0=h_last,
                                                    ep_len=db.ep_len, ep_map=emap, cu_budget=cu, gi_in=gi)
         self.pair.run_chain(B * N, T, a.obs_shape,
                             lambda cu: self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, q_evals, hs, h_last, saved,
                                                             h0=None, ep_len=db.ep_len, ep_map=emap, cu_budget=cu, gi_out=gi),
                             cont,
-                            lambda cu: self.target_net.unroll(on, on_bs, on_t0, db.u_fed, db.u_bs, 0, B, T, q_tgt, None, None, None,
+                            lambda cu: self.target_net.unroll(on, on_bs, on_t0, db.u_fed, db.u_bs, 0, B, T, q_tgt, hs_tgt, None, None,
                                                               h0=None, ep_len=db.ep_len, ep_map=emap, cu_budget=cu))
-        ops.q_gather(q_evals, u_act, q_chosen, R, A)
+        return q_evals, q_en, q_tgt, saved, (hs, hs_en, hs_tgt)
+
+    def _select(self, db, q_evals, q_en, q_tgt):
+        """Q of the taken actions and the target Q of the greedy next actions (double-Q: greedy by the continuation's Qs).
+        Returns q_chosen, q_tgt_chosen (R,) and cur_max, the double-Q greedy actions (else None)."""
+        R, A, g = db.B * db.T * db.N, db.A, self._g
+        q_chosen, q_tgt_chosen = g("q_chosen", (R,)), g("q_tgt_chosen", (R,))
+        ops.q_gather(q_evals, db.u_act.reshape(-1), q_chosen, R, A)
         cur_max = None
-        if a.double_q:
+        if self.args.double_q:
             cur_max = g("cur_max", (R,), torch.int32)
             ops.q_double_select(q_en, q_tgt, db.avail_next, MASK_BIG, q_tgt_chosen, cur_max, R, A)
         else:
             ops.q_masked_max(q_tgt, db.avail_next, MASK_BIG, q_tgt_chosen, None, R, A)
+        return q_chosen, q_tgt_chosen, cur_max
 
-        ctx = {}
+    def _mix(self, db, q_evals, q_tgt, q_chosen, q_tgt_chosen, cur_max):
+        """Eval and target mixer forwards.  Returns q_tot, q_tot_tgt, the eval mixer's ctx and `fold`: QMIX's eval forward
+        is left to the loss stage, where it is one launch with the TD loss and the mixer backward."""
+        a, g = self.args, self._g
+        N, BT, A = db.N, db.B * db.T, db.A
+        R = BT * N
+        ctx, fold = {}, False
         qc, qtc = q_chosen.view(BT, N), q_tgt_chosen.view(BT, N)
         if a.alg == 'qplex':
             max_q = g("max_q", (R,))
@@ -162,84 +143,31 @@ class QLearner(ResumeMixin, SpeculativeBatchMixin):
                 self.mixer.loss_backward_fused(db.s) and not getattr(a, "no_loss_fold", False)
             q_tot = g("q_tot", (BT,)) if fold else self.mixer.hip_forward(qc, db.s, BT, ctx=ctx)
             q_tot_tgt = self.target_mixer.hip_forward(qtc, db.s_next, BT, tag="t")
+        return q_tot, q_tot_tgt, ctx, fold
 
-        # TD loss (un-normalised numerator + sum(mask) land in the tail of the gradient buffer)
-        self._flat.zero_grad()
-        if a.alg != 'qplex' and fold:
+    def _loss_backward(self, db, q_chosen, q_tot, q_tot_tgt, ctx, fold):
+        """TD loss (un-normalised numerator + sum(mask) land in the tail of the gradient buffer, zeroed before) and the
+        mixer backward.  Returns dq_chosen, the gradient on the taken actions' Qs."""
+        BT = db.B * db.T
+        if fold:
             # fused QMIX: eval-mixer forward, TD loss and mixer backward are ONE launch (the backward recomputes q_tot anyway)
-            dq_chosen = self.mixer.hip_loss_backward(qc, db.s, BT, q_tot_tgt, db.r, db.term, db.padded, self.gamma,
-                                                     self._flat.stats[:2], q_tot=q_tot)
-        else:
-            dq_tot = g("dq_tot", (BT,))
-            ops.td_loss(q_tot, q_tot_tgt, db.r, db.term, db.padded, self.gamma, dq_tot, self._flat.stats[:2], BT)
-            # backward: mixer, gather, BPTT
-            dq_chosen = self.mixer.hip_backward(ctx, dq_tot, BT)
+            return self.mixer.hip_loss_backward(q_chosen.view(BT, db.N), db.s, BT, q_tot_tgt, db.r, db.term, db.padded, self.gamma,
+                                                self._flat.stats[:2], q_tot=q_tot)
+        dq_tot = self._g("dq_tot", (BT,))
+        ops.td_loss(q_tot, q_tot_tgt, db.r, db.term, db.padded, self.gamma, dq_tot, self._flat.stats[:2], BT)
+        return self.mixer.hip_backward(ctx, dq_tot, BT)
+
+    def _forward_backward(self, db):
+        q_evals, q_en, q_tgt, saved, _ = self._unrolls(db)
+        q_chosen, q_tgt_chosen, cur_max = self._select(db, q_evals, q_en, q_tgt)
+        q_tot, q_tot_tgt, ctx, fold = self._mix(db, q_evals, q_tgt, q_chosen, q_tgt_chosen, cur_max)
+        self._flat.zero_grad()
+        dq_chosen = self._loss_backward(db, q_chosen, q_tot, q_tot_tgt, ctx, fold)
         # the loss reaches q_evals only through the gather above: hand BPTT the sparse (action, gradient) pairs
         # instead of scattering them into a dense (B,T,N,A) tensor
-        agent_backward(self.eval_net, db, "cur", saved, hs, None, None, self._buf,
-                       dq_idx=u_act, dq_val=dq_chosen.reshape(-1).contiguous())
+        agent_backward(self.eval_net, db, "cur", saved, None, None, None, self._buf,
+                       dq_idx=db.u_act.reshape(-1), dq_val=dq_chosen.reshape(-1).contiguous())
         self._dbg = dict(q_evals=q_evals, q_targets=q_tgt, q_tot=q_tot, q_tot_target=q_tot_tgt)
-
-    def train(self, batch, train_step):
-        if self.graphs is not None and isinstance(batch, EpisodeBatch) and batch.ring is not None and \
-                self.graphs.run(self, batch.ring, batch.index):
-            return self._finish_update(train_step)
-        if isinstance(batch, DeviceBatch):
-            db = batch
-        elif isinstance(batch, EpisodeBatch) and batch.ring is not None:
-            # replay sample: big arrays are read in place from the ring through the episode index
-            prep = self.graphs.prepared if self.graphs is not None else None
-            if prep is not None:             # the graph path already gathered the small arrays and agreed on T
-                self.graphs.prepared = None
-                db = DeviceBatch.from_record(batch.ring, self.args, T=prep[1], index=batch.index, small=prep[0])
-            else:
-                small = batch.ring.select_small(batch.index, avail_cur=self.needs_avail)
-                db = self._device_batch(batch.ring, batch.index, small)
-                if db is None:
-                    return self._finish_update(train_step)
-        elif isinstance(batch, EpisodeBatch) and batch.record is not None:
-            db = self._device_batch(batch.record, None, None)
-            if db is None:
-                return self._finish_update(train_step)
-        else:
-            T = None
-            if self.reducer.enabled:   # shards must agree on T
-                T = DeviceBatch.first_terminated_len(torch.as_tensor(np.asarray(batch['terminated'])),
-                                                     self.args.episode_limit, reducer=self.reducer)
-            db = DeviceBatch.from_dict(batch, self.args, self.device, T=T)
-        self.max_episode_len = db.T
-        self._forward_backward(db)
-        return self._finish_update(train_step)
-
-    def _finish_update(self, train_step):
-        """gradient all-reduce, clip + optimizer, target sync, loss readback (reference :168-179)"""
-        self.reducer.allreduce_(self._flat.gradx)
-        stats = self._flat.stats
-        self.optimizer.step(den=stats[1:2])
-        if train_step > 0 and train_step % self.args.target_update_cycle == 0:
-            self._update_targets()
-        self.last_stats = stats
-        return self.loss_readback.read(stats[:2], lambda s: s[0] / s[1])
-
-    # ------------------------------------------------------------------ checkpoints (reference :193-209)
-    def save_models(self, train_step):
-        num = str(train_step // self.args.save_cycle)
-        if not os.path.exists(self.model_dir):
-            os.makedirs(self.model_dir)
-        self.eval_net.save_models(self.model_dir + '/' + num + '_rnn_net_params.pkl')
-        torch.save({k: v.detach().cpu() for k, v in self.mixer.state_dict().items()},
-                   self.model_dir + '/' + num + '_mixer_net_params.pkl')
-
-    def load_models(self):
-        if os.path.exists(self.model_dir + '/rnn_net_params.pkl'):
-            path_rnn = self.model_dir + '/rnn_net_params.pkl'
-            path_mix = self.model_dir + '/mixer_net_params.pkl'
-            self.eval_net.load_models(path_rnn)
-            self.mixer.load_state_dict(torch.load(path_mix, map_location='cpu'))
-            self.sync_replicas()
-            print('Successfully load the model: {} and {}'.format(path_rnn, path_mix))
-        else:
-            raise Exception("No model!")
 
     def get_q_and_q_tot_table(self):
         """Matrix-game diagnostic (reference :211-262): 3x3 q_tot table + per-agent Q rows with

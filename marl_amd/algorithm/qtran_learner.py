@@ -9,31 +9,22 @@ optimizer state layout matches; its gradient is identically zero.
 from __future__ import annotations
 
 import copy
-import os
 
 import numpy as np
 import torch
 
 from .. import ops
-from ..hostutil import require_cuda, DeviceBatch, flatten_module
-from ..rollout import EpisodeBatch
+from ..hostutil import flatten_module
 from ..network.mixer import QtranQBase, QtranQAlt, QtranV, QMixMixer
-from .common import (MASK_BIG, MASK_QTRAN_EVAL, LearnerParams, FlatView, FusedOptimizer, Scratch, agent_backward,
-                     GradReducer, PairedUnroll, ResumeMixin, LossReadback, SpeculativeBatchMixin, GraphedUpdate)
+from .common import MASK_BIG, MASK_QTRAN_EVAL, LearnerParams, FlatView, Learner, agent_backward
 
 
-class QTRANLearner(ResumeMixin, SpeculativeBatchMixin):
+class QTRANLearner(Learner):
+    n_stats, den_slot = 4, 3  # L_td, L_opt, L_nopt numerators, sum(mask)
+    extra_nets = ("v",)
+
     def __init__(self, mac, args):
-        self.max_episode_len = args.episode_limit
-        self.gamma = args.gamma
-        self.lr = args.lr
-        self.model_dir = args.model_dir + '/' + args.alg + '/' + args.map
-        self.args = args
-        self.device = require_cuda("QTRANLearner")
-
-        self.eval_net = mac
-        self.eval_net.cuda()
-        self.target_net = copy.deepcopy(mac)
+        self._begin(mac, args, "QTRANLearner")
         if args.alg == 'qtran_base':
             self.mixer = QtranQBase(args)
         elif args.alg == 'qtran_alt':
@@ -47,16 +38,7 @@ class QTRANLearner(ResumeMixin, SpeculativeBatchMixin):
         self.q_sum_mixer = QMixMixer(args)
         self.params += list(self.q_sum_mixer.parameters())
         self.cuda()
-        self.optimizer = FusedOptimizer(self._flat, args.optimizer, self.lr, args.grad_norm_clip)
-        self._buf = Scratch()
-        self.reducer = GradReducer()
-        from ..network import mixer as _mixer
-        self.pair = PairedUnroll(x6=getattr(args, "gemm_mode", _mixer.DEFAULT_GEMM_MODE) == "bf16x6")
-        self.loss_readback = LossReadback(args)
-        self.graphs = GraphedUpdate.from_args(args)
-        self.needs_avail = True                      # local greedy actions are masked with the current availability (:103-108)
-        self.last_stats = None
-        self.sync_replicas()
+        self._ready(needs_avail=True)                # local greedy actions are masked with the current availability (:103-108)
 
     def sync_replicas(self):
         """replicas start from rank 0's parameters, targets and optimizer state (see QLearner.sync_replicas)"""
@@ -77,22 +59,10 @@ class QTRANLearner(ResumeMixin, SpeculativeBatchMixin):
         flatten_module(self.target_net.agent, dev)
         flatten_module(self.target_mixer, dev)
 
-    def _update_targets(self):
-        self.target_net.agent._flat.flat.copy_(self.eval_net.agent._flat.flat)
-        self.target_mixer._flat.flat.copy_(self.mixer._flat.flat)
-
-    def get_max_episode_len(self, batch):
-        T = DeviceBatch.first_terminated_len(torch.as_tensor(np.asarray(batch['terminated'])), self.args.episode_limit)
-        for key in batch.keys():
-            batch[key] = batch[key][:, :T]
-        return batch, T
-
     def _forward_backward(self, db):
-        a = self.args
-        dev = self.device
+        a, g = self.args, self._g
         B, T, N, A, H = db.B, db.T, db.N, db.A, a.rnn_hidden_dim
         R, BT = B * T * N, B * T
-        g = lambda name, shape, dt=torch.float32: self._buf.get(name, shape, dev, dt)
         q_evals, hs, saved = g("q_evals", (B, T, N, A)), g("hs", (B, T, N, H)), g("saved", ops.saved_shape(T, B, N))
         q_tgt, hs_tgt = g("q_tgt", (B, T, N, A)), g("hs_tgt", (B, T, N, H))
         (oc, oc_bs, oc_t0), (on, on_bs, on_t0) = db.o_cur, db.o_next
@@ -151,62 +121,9 @@ class QTRANLearner(ResumeMixin, SpeculativeBatchMixin):
         self._dbg = dict(q_evals=q_evals, hs=hs, joint_q=joint_q, joint_q_targets=joint_q_tgt, v=v,
                          joint_q_hat=joint_q_hat)
 
-    def train(self, batch, train_step):
-        if self.graphs is not None and isinstance(batch, EpisodeBatch) and batch.ring is not None and \
-                self.graphs.run(self, batch.ring, batch.index):
-            db = None                    # forward / backward done (hipGraph replay on the static buffers)
-        elif isinstance(batch, DeviceBatch):
-            db = batch
-        elif isinstance(batch, EpisodeBatch) and batch.ring is not None:
-            # replay sample: big arrays are read in place from the ring through the episode index
-            prep = self.graphs.prepared if self.graphs is not None else None
-            if prep is not None:             # the graph path already gathered the small arrays and agreed on T
-                self.graphs.prepared = None
-                db = DeviceBatch.from_record(batch.ring, self.args, T=prep[1], index=batch.index, small=prep[0])
-            else:
-                small = batch.ring.select_small(batch.index, avail_cur=self.needs_avail)
-                db = self._device_batch(batch.ring, batch.index, small)
-        elif isinstance(batch, EpisodeBatch) and batch.record is not None:
-            db = self._device_batch(batch.record, None, None)
-        else:
-            T = None
-            if self.reducer.enabled:
-                T = DeviceBatch.first_terminated_len(torch.as_tensor(np.asarray(batch['terminated'])),
-                                                     self.args.episode_limit, reducer=self.reducer)
-            db = DeviceBatch.from_dict(batch, self.args, self.device, T=T)
-        if db is not None:               # (None: _device_batch already launched the pass for the record's full length)
-            self.max_episode_len = db.T
-            self._forward_backward(db)
-        self.reducer.allreduce_(self._flat.gradx)
-        st = self._flat.stats
-        self.optimizer.step(den=st[3:4])
-        if train_step > 0 and train_step % self.args.target_update_cycle == 0:
-            self._update_targets()
-        self.last_stats = st
+    def _loss_fn(self):
         lo, ln = self.args.lambda_opt, self.args.lambda_nopt
-        return self.loss_readback.read(st[:4], lambda s: (s[0] + lo * s[1] + ln * s[2]) / s[3])
-
-    def save_models(self, train_step):
-        num = str(train_step // self.args.save_cycle)
-        if not os.path.exists(self.model_dir):
-            os.makedirs(self.model_dir)
-        cpu = lambda m: {k: v.detach().cpu() for k, v in m.state_dict().items()}
-        self.eval_net.save_models(self.model_dir + '/' + num + '_rnn_net_params.pkl')
-        torch.save(cpu(self.mixer), self.model_dir + '/' + num + '_mixer_net_params.pkl')
-        torch.save(cpu(self.v), self.model_dir + '/' + num + '_v_net_params.pkl')
-
-    def load_models(self):
-        if os.path.exists(self.model_dir + '/rnn_net_params.pkl'):
-            path_rnn = self.model_dir + '/rnn_net_params.pkl'
-            path_mix = self.model_dir + '/mixer_net_params.pkl'
-            path_v = self.model_dir + '/v_net_params.pkl'
-            self.eval_net.load_models(path_rnn)
-            self.mixer.load_state_dict(torch.load(path_mix, map_location='cpu'))
-            self.v.load_state_dict(torch.load(path_v, map_location='cpu'))
-            self.sync_replicas()
-            print('Successfully load the model: {} and {}'.format(path_rnn, path_mix))
-        else:
-            raise Exception("No model!")
+        return lambda s: (s[0] + lo * s[1] + ln * s[2]) / s[3]
 
     def get_q_and_q_tot_table(self):
         """reference :237-272 - note the reference accumulates the one-hot across (i,j) iterations

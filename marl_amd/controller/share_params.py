@@ -12,6 +12,7 @@ import torch
 
 from .. import ops
 from ..hostutil import require_cuda, to_dev, onehot_to_index, flatten_module
+from ..network.mixer import x6_mode
 from ..network.q_network import RNNQNet
 from ..network.rtw import RTWAgent
 from ..network.world_model import Agent as WorldAgent
@@ -136,8 +137,7 @@ class SharedMAC:
         """True when a T-step unroll over B episodes runs on the bf16x6 split kernel (args.gemm_mode = "bf16x6", a shape
         csrc/agent_x6.hip covers and - when given - an observation tensor on a 16-byte boundary: a misaligned view takes the
         fp32 kernels instead of failing in the entry point)."""
-        from ..network import mixer as _mixer
-        return (T >= 4 and getattr(self.args, "gemm_mode", _mixer.DEFAULT_GEMM_MODE) == "bf16x6"
+        return (T >= 4 and x6_mode(self.args)
                 and (obs is None or obs.data_ptr() % 16 == 0)
                 and ops.agent_unroll_x6_supported(B, T, self.n_agents, self.obs_shape, self.n_actions, self.args.last_action,
                                                   self.args.reuse_network))

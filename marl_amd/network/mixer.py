@@ -63,7 +63,7 @@ class _Precision:
 
     def _x6mode(self):
         """args.gemm_mode = "bf16x6": the mixer's dense products as bf16x6 splits where a split kernel exists"""
-        return getattr(self.args, "gemm_mode", DEFAULT_GEMM_MODE) == "bf16x6"
+        return x6_mode(self.args)
 
     def _wgrad_bf16(self):
         """with mixer_dtype "bf16" the wide-state mixer's weight-gradient GEMM takes bf16 operands too (its own flag bit of
@@ -378,6 +378,11 @@ class DMAQ_SI_Weight(nn.Module):
 DEFAULT_GEMM_MODE = "f32"
 
 
+def x6_mode(args):
+    """args.gemm_mode is "bf16x6"; args without one take DEFAULT_GEMM_MODE as it stands at the time of the call"""
+    return getattr(args, "gemm_mode", DEFAULT_GEMM_MODE) == "bf16x6"
+
+
 def _keep_hidden():
     """the fused head families keep their hidden activations for the backward (MARL_MLP3_KEEP=0: recompute them there)"""
     from .. import experiments
@@ -448,7 +453,7 @@ class DMAQer(_Precision, nn.Module):
     def _x6(self, x_in, K1, nout, groups):
         """the family runs on the bf16x6 split kernels (csrc/mlp3_x6.hip): opt-in args.gemm_mode = "bf16x6" - fp32-accurate
         products on the bf16 matrix cores; the default "f32" keeps v_mfma_f32_16x16x4_f32"""
-        return (getattr(self.args, "gemm_mode", DEFAULT_GEMM_MODE) == "bf16x6" and _keep_hidden()
+        return (x6_mode(self.args) and _keep_hidden()
                 and ops.mlp3_x6_supported(x_in, K1, 64, 64, nout, groups))
 
     def _kept(self, name, rows, three, groups, dev):

@@ -19,6 +19,7 @@ import torch
 
 from . import ops
 from .hostutil import h2d_async, require_cuda
+from .network.mixer import x6_mode
 
 
 class EpisodeBatch(dict):
@@ -230,8 +231,7 @@ class RolloutWorker:
             for t in range(T):
                 epsilon = epsilon - self.anneal_epsilon if epsilon > self.min_epsilon else epsilon
         mac.init_hidden(E)
-        from .network import mixer as _mixer
-        x6 = getattr(a, "gemm_mode", _mixer.DEFAULT_GEMM_MODE) == "bf16x6"      # the agent step as split products (csrc/rollout_x6.hip)
+        x6 = x6_mode(a)      # the agent step as split products (csrc/rollout_x6.hip)
         env.whole_rollout(mac.agent.weights(), None, self.rseed, rec, a.last_action, a.reuse_network,
                           h_out=mac.hidden_states.view(E * N, H), eps_sched=sched, x6=x6)
         if not evaluate:
