@@ -983,8 +983,8 @@ def test_agent_unroll_bwd_from_x6_saved(dev, B, T):
 def test_agent_unroll_bwd_x6_split(dev, shape, B, T, pairs, with_dhs, la=1, rn=1):
     """BPTT on the bf16x6 split kernels (csrc/agent_bwd_x6.hip, opt-in gemm_mode): one or two sparse (action, value) pairs per row
     (the second pair with one value per (episode, step) shared by its agents, as QTRAN uses it), an optional external gradient on
-    hs, one row tile per workgroup (up to 256 tiles) and two (beyond; row counts that leave the last workgroup with a partial or a
-    missing second tile) - every gradient and dxp against
+    hs, one row tile per workgroup (up to 256 tiles) and two (beyond; row counts that leave the last workgroup with a partial
+    second tile - a missing one and the mixed plan's second launch are in tests/test_gpu_bptt.py) - every gradient and dxp against
     torch autograd of the oracle unroll at the bounds of test_agent_unroll_bwd, beside the fp32 MFMA kernel on the same inputs."""
     from marl_amd import ops
     args, p_np, obs, ufed, h0 = _agent_case(shape, B, T, dev, seed=3, la=la, rn=rn)
