@@ -144,7 +144,9 @@ int marl_q_gather(const float* q, const int* idx, const float* avail, float mask
 int marl_q_masked_max(const float* q, const float* avail, float mask_val, float* out_max, int* out_arg,
                       long rows, int A, void* stream);
 /* Double-Q selection in one pass (q_learner.py:104-117): arg[row] = first-index argmax of q_sel masked with
- * avail (mask_val where avail == 0), out_val[row] = q_val[row, arg] masked the same way; out_arg may be NULL. */
+ * avail (mask_val where avail == 0), out_val[row] = q_val[row, arg] masked the same way; out_arg may be NULL; avail may be NULL
+ * (everything available).  Serves every action count: up to A = 21 a wave stages 64 rows of the three operands through LDS, from
+ * A = 22 on (the tiles of four waves would exceed 64 KiB) one thread scans a row - same comparisons, same results bit for bit. */
 int marl_q_double_select(const float* q_sel, const float* q_val, const float* avail, float mask_val,
                          float* out_val, int* out_arg, long rows, int A, void* stream);
 /* dq = 0; dq[row,idx1[row]] += g1[row/gdiv]; dq[row,idx2[row]] += g2[row/gdiv] (idx2/g2 may be

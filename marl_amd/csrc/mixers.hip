@@ -86,6 +86,23 @@ __global__ __launch_bounds__(256) void q_double_select_kernel(const float* q_sel
   }
 }
 
+// Row-per-thread form of the same selection for action counts whose staged tiles do not fit (4 waves x 3 operands x 64 rows x A
+// floats exceeds 64 KiB from A = 22): same comparisons in the same order, so the same results bit for bit.
+__global__ void q_double_select_rows_kernel(const float* q_sel, const float* q_val, const float* avail, float mask_val,
+                                            float* out_val, int* out_arg, long rows, int A) {
+  for (long r = (long)blockIdx.x * TPB + threadIdx.x; r < rows; r += (long)gridDim.x * TPB) {
+    float best = 0.f;
+    int arg = 0;
+    for (int a = 0; a < A; ++a) {
+      float v = q_sel[r * A + a];
+      if (avail && avail[r * A + a] == 0.f) v = mask_val;
+      if (a == 0 || v > best) { best = v; arg = a; }   // strict >: first index wins ties (torch)
+    }
+    out_val[r] = (avail && avail[r * A + arg] == 0.f) ? mask_val : q_val[r * A + arg];
+    if (out_arg) out_arg[r] = arg;
+  }
+}
+
 // q_masked_max with the staging of q_double_select_kernel: a wave copies 64 rows of q (and avail) into LDS with 16-byte coalesced
 // loads, then one lane per row scans its A values (the thread-per-row kernel above reads 44 - 72 byte rows at a lane stride of a
 // row: 50 us for 614 400 rows x 14 actions where the bytes are worth 12 us).  Same results (strict >: first index wins ties).
@@ -560,7 +577,12 @@ extern "C" int marl_q_double_select(const float* q_sel, const float* q_val, cons
   long nb = (tiles + 3) / 4;
   if (nb > 2048) nb = 2048;
   const size_t lds = (size_t)4 * 3 * ((DS_ROWS * A + 3) & ~3) * sizeof(float);
-  if (lds > 64 * 1024) return (int)hipErrorInvalidValue;
+  if (lds > 64 * 1024) {             // A >= 22: the tiles do not fit, one thread per row (as marl_q_masked_max falls back)
+    hipLaunchKernelGGL(q_double_select_rows_kernel, dim3(nblk(rows)), dim3(TPB), 0, (hipStream_t)stream, q_sel, q_val, avail,
+                       mask_val, out_val, out_arg, rows, A);
+    MARL_CHECK_LAUNCH();
+    return 0;
+  }
   const int vec = ((reinterpret_cast<uintptr_t>(q_sel) | reinterpret_cast<uintptr_t>(q_val) | reinterpret_cast<uintptr_t>(avail)) & 15) == 0;
   hipLaunchKernelGGL(q_double_select_kernel, dim3((unsigned)nb), dim3(256), lds, (hipStream_t)stream, q_sel, q_val, avail,
                      mask_val, out_val, out_arg, rows, A, vec);
