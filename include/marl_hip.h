@@ -598,7 +598,7 @@ int marl_world_head_bwd(const marl_world_weights_t* w, const marl_world_grads_t*
                         const float* den, float dscale, float* dhs, float* ws, size_t ws_bytes, int B, int T, int N, int O,
                         int A, void* stream);
 
-/* ---- MAIC message head (maic_head.hip) ----------------------------------------------------------
+/* ---- MAIC message head (maic_head.hip, maic_head_bwd.hip) ----------------------------------------------------------
  * The parts of MAICAgent (network/MAIC.py:19-47) that its forward evaluates beyond the RNNQNet agent, torch layouts, with
  * rnn_hidden_dim = nn_hidden_size = 64, latent_dim L = 8, attention_dim D = 32 (inference_net only feeds the MI loss):
  *   e0 (64,64), bn (64) weight / bias / running_mean / running_var / num_batches_tracked (int64), e3 (2*N*L, 64)
@@ -631,6 +631,22 @@ int marl_maic_head_fwd(const marl_maic_weights_t* w, const float* h, float* q, c
                        float* var_out, float* lat_out, float* alpha_out, float* msg_out, float* ws, size_t ws_bytes, int bs,
                        int N, int A, int test_mode, int bn_batch, float var_floor, float bn_eps, float bn_momentum,
                        void* stream);
+/* Gradient destinations of the message head's layers (accumulated into).  inference_net has none: it only feeds the MI loss. */
+typedef struct {
+  float *e0_w, *e0_b, *bn_w, *bn_b, *e3_w, *e3_b, *m0_w, *m0_b, *m2_w, *m2_b, *k_w, *k_b, *q_w, *q_b;
+} marl_maic_grads_t;
+/* Bytes of scratch marl_maic_head_bwd needs for bs environments of N agents with A actions (0 for an unsupported shape). */
+size_t marl_maic_bwd_workspace(int bs, int N, int A);
+/* Backward of marl_maic_head_fwd (maic_head_bwd.hip) for a sparse gradient on return_q: row r receives dq_val[r] on action
+ * u_act[r] (an index outside [0, A) reads as no gradient) - the pairs marl_agent_unroll_bwd takes as (dq_idx, dq_val).
+ *   h, eps, test_mode, bn_batch, var_floor, bn_eps: as the forward call had them (eps NULL in test mode).  Intermediates are
+ *   recomputed; in batch-statistics mode so are the statistics, and bn_rm / bn_rv / bn_nbt are NOT moved.
+ *   dh (bs*N, 64) is written: the head's contribution only (the identity path q -> return_q is BPTT's own dq input).
+ *   The gradients of embed_net.{0,1,3}, msg_net.{0,2}, w_key and w_query are ACCUMULATED into g by fixed-order reductions
+ *   (no float atomics: two calls give the same bits).  fp32 throughout; ws: marl_maic_bwd_workspace() bytes. */
+int marl_maic_head_bwd(const marl_maic_weights_t* w, const marl_maic_grads_t* g, const float* h, const float* eps,
+                       const int* u_act, const float* dq_val, float* dh, float* ws, size_t ws_bytes, int bs, int N, int A,
+                       int test_mode, int bn_batch, float var_floor, float bn_eps, void* stream);
 /* eps (E*N, N*8) of a sampled-latent rollout step (replaces the torch generator behind rsample, MAIC.py:68): element (n, c) of
  * environment env0 + e is sqrt(-2 ln(1 - u1)) cos(2 pi u2) with u1, u2 the counter-hash draws 2k, 2k + 1 (k = n*N*8 + c) of
  * stream 8 keyed by (rseed, env, tg = the global step), as marl_select_actions draws its own. */

@@ -65,6 +65,11 @@ class MarlMaicWeights(C.Structure):
                                           "m0_w", "m0_b", "m2_w", "m2_b", "k_w", "k_b", "q_w", "q_b")]
 
 
+class MarlMaicGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("e0_w", "e0_b", "bn_w", "bn_b", "e3_w", "e3_b", "m0_w", "m0_b", "m2_w", "m2_b",
+                                          "k_w", "k_b", "q_w", "q_b")]
+
+
 class MarlAgentGrads(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p),
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
@@ -84,7 +89,7 @@ M3 = C.POINTER(MarlMlp3Weights)
 QT = C.POINTER(MarlQtranWeights)
 RW = C.POINTER(MarlRtwWeights)
 WW, WG = C.POINTER(MarlWorldWeights), C.POINTER(MarlWorldGrads)
-MW = C.POINTER(MarlMaicWeights)
+MW, MG = C.POINTER(MarlMaicWeights), C.POINTER(MarlMaicGrads)
 
 # name -> (restype, argtypes); must list every symbol of include/marl_hip.h
 SIGNATURES = {
@@ -181,6 +186,8 @@ SIGNATURES = {
     "marl_maic_workspace": (SZ, [I, I]),
     "marl_maic_head_fwd": (I, [MW, P, P, P, P, P, P, P, P, P, SZ, I, I, I, I, I, F, F, F, P]),
     "marl_maic_noise": (I, [U, I, U, P, I, I, P]),
+    "marl_maic_bwd_workspace": (SZ, [I, I, I]),
+    "marl_maic_head_bwd": (I, [MW, MG, P, P, P, P, P, P, SZ, I, I, I, I, I, F, F, P]),
     "marl_hip_version": (C.c_char_p, []),
     "marl_experiment_set": (I, [C.c_char_p, I]),
     "marl_experiment_get": (I, [C.c_char_p]),

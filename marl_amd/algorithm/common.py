@@ -171,6 +171,8 @@ class Learner(ResumeMixin):
     _full_len_streak = 0      # consecutive updates whose max_episode_len was the record's full length
     n_stats, den_slot = 2, 1  # the loss tail reads stats[:n_stats]; the optimizer divides by stats[den_slot]
     extra_nets = ()           # attributes of further modules with a <name>_net_params.pkl file of their own
+    launch_ahead = True       # the pass may be launched before max_episode_len is read back, and redone at another length
+    replay_graphs = True      # the pass may be captured into a hipGraph and replayed (args.hip_graph permitting)
 
     def _begin(self, mac, args, name):
         """constructor preamble; the learner then builds mixer / target_mixer / params and calls cuda() and _ready()"""
@@ -193,7 +195,7 @@ class Learner(ResumeMixin):
         self.reducer = GradReducer()
         self.pair = PairedUnroll(x6=x6_mode(args))
         self.loss_readback = LossReadback(args)
-        self.graphs = GraphedUpdate.from_args(args)
+        self.graphs = GraphedUpdate.from_args(args) if self.replay_graphs else None
         self.needs_avail = needs_avail
         self.last_stats = None
         self.sync_replicas()
@@ -224,7 +226,8 @@ class Learner(ResumeMixin):
         early - redoes the pass (forward / backward overwrite their outputs and zero the gradient buffer themselves).
         Returns None when the pass has already been launched."""
         term = (small if small is not None else rec).term
-        if not (term.is_cuda and term.dtype == torch.float32 and term.shape[0] > 0) or self._full_len_streak < 2:
+        if not (term.is_cuda and term.dtype == torch.float32 and term.shape[0] > 0) or self._full_len_streak < 2 \
+                or not self.launch_ahead:
             db = DeviceBatch.from_record_auto(rec, self.args, reducer=self.reducer, index=index, small=small)
             full = db.T == min(rec.T, self.args.episode_limit)
             self._full_len_streak = self._full_len_streak + 1 if full else 0

@@ -16,8 +16,10 @@ def get_common_args(argv=None):
     p.add_argument('--RTW', type=_bool, default=False)
     # not in the reference's parser (its runner never builds SharedMACWithState + QLearnerWithState): the world-model agent
     p.add_argument('--world_model', type=_bool, default=False)
-    # the reference's parser has no switch for its MAIC agent (network/MAIC.py) either: MAICMAC, inference and rollouts only
+    # the reference's parser has no switch for its MAIC agent (network/MAIC.py) either: MAICMAC, inference and rollouts only ...
     p.add_argument('--MAIC', type=_bool, default=False)
+    # ... and with --MAIC_train the learner that trains it on the TD loss (MAICTDLearner; needs --MAIC)
+    p.add_argument('--MAIC_train', type=_bool, default=False)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')

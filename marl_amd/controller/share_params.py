@@ -297,8 +297,9 @@ class RTWMAC(SharedMAC):
 
 class MAICMAC(SharedMAC):
     """SharedMAC over a MAICAgent (reference network/MAIC.py).  The reference ships the agent without a controller, so this
-    class is the project's own, shaped like RTWMAC / SharedMACWithState.  Inference only: every pass is the agent unroll
-    followed by the message head (csrc/maic_head.hip); training belongs to a later change (MAICQLearner.train raises).
+    class is the project's own, shaped like RTWMAC / SharedMACWithState.  Every pass is the agent unroll followed by the
+    message head (csrc/maic_head.hip); ``head_over`` / ``head_backward`` are what MAICTDLearner trains through
+    (MAICQLearner.train still raises).
 
     BatchNorm follows ``self.agent.training``.  ``self.agent.eval()``: running statistics, every environment on its own.
     Training mode (a freshly built agent; the reference never leaves it): the statistics of ALL rows of a head call and
@@ -357,21 +358,54 @@ class MAICMAC(SharedMAC):
             ops.maic_noise(rseed, env.env0, env.global_step(t), eps, E, N)
         self.agent.head(h, q.view(E * N, A), E, bool(evaluate), eps)
 
-    def _maic_q_values(self, batch, T, which, test_mode, eps):
-        q, hs = self._batch_unroll(batch, T, which)
-        B, N, A = q.shape[0], self.n_agents, self.n_actions
+    def head_over(self, hs, q, B, T, test_mode, eps):
+        """q (B,T,N,A) += the gated messages from hs (B,T,N,64), in place.  ``self.agent.eval()``: one head call over all B*T*N
+        rows.  Training mode: batch statistics are per call, so one call per transition index t over the B*N rows of that
+        index (the running statistics move T times).  eps (B,T,N,N*latent_dim) or None."""
+        N, A = self.n_agents, self.n_actions
         NL = N * self.args.latent_dim
-        if eps is not None:
-            eps = to_dev(eps, q.device).view(B, T, N, NL)
         if not self.agent.training:
             self.agent.head(hs.view(B * T * N, -1), q.view(B * T * N, A), B * T, test_mode,
                             None if eps is None else eps.view(B * T * N, NL))
-            return q, hs, {}
-        for t in range(T):       # batch statistics are per call: one call per transition index
+            return
+        for t in range(T):
             qt = q[:, t].contiguous()
             self.agent.head(hs[:, t].contiguous().view(B * N, -1), qt.view(B * N, A), B, test_mode,
                             None if eps is None else eps[:, t].contiguous().view(B * N, NL))
             q[:, t] = qt
+
+    def head_backward(self, hs, u_act, dq_val, B, T, test_mode, eps, dhs, buf):
+        """The backward counterpart of ``head_over``, over the same rows per call: dhs (B,T,N,64) is written with the head's
+        contribution to the gradient on hs for the sparse pairs u_act, dq_val (B,T,N); the head's weight gradients
+        accumulate into the agent's .grad views."""
+        N = self.n_agents
+        NL = N * self.args.latent_dim
+        if not self.agent.training:
+            self.agent.head_backward(hs.view(B * T * N, -1), u_act.reshape(-1), dq_val.reshape(-1), B * T, test_mode,
+                                     None if eps is None else eps.view(B * T * N, NL), dhs.view(B * T * N, -1))
+            return
+        # the rows of one index, made contiguous in scratch buffers (buf: the learner's Scratch) that every index uses again
+        H = hs.shape[-1]
+        g = lambda name, src: buf.get("maic_bwd_" + name, (B, N) + tuple(src.shape[3:]), src.device, src.dtype)
+        u_act, dq_val = u_act.view(B, T, N), dq_val.view(B, T, N)
+        ht, ut, vt, dh = g("h", hs), g("u", u_act), g("v", dq_val), g("dh", dhs)
+        et = None if eps is None else g("eps", eps)
+        for t in range(T):
+            ht.copy_(hs[:, t])
+            ut.copy_(u_act[:, t])
+            vt.copy_(dq_val[:, t])
+            if et is not None:
+                et.copy_(eps[:, t])
+            self.agent.head_backward(ht.view(B * N, H), ut.view(-1), vt.view(-1), B, test_mode,
+                                     None if et is None else et.view(B * N, NL), dh.view(B * N, H))
+            dhs[:, t] = dh
+
+    def _maic_q_values(self, batch, T, which, test_mode, eps):
+        q, hs = self._batch_unroll(batch, T, which)
+        B, N = q.shape[0], self.n_agents
+        if eps is not None:
+            eps = to_dev(eps, q.device).view(B, T, N, N * self.args.latent_dim)
+        self.head_over(hs, q, B, T, test_mode, eps)
         return q, hs, {}
 
     def get_current_q_values(self, batch, max_episode_len, test_mode=False, eps=None):

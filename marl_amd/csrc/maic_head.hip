@@ -1,4 +1,5 @@
-// MAIC message head (reference network/MAIC.py:52-94, MAICAgent.forward after fc2) on gfx950: inference only.
+// MAIC message head (reference network/MAIC.py:52-94, MAICAgent.forward after fc2) on gfx950: the forward.  Its backward is
+// maic_head_bwd.hip.
 //
 // Per environment of N agents (row = b * N + agent, h = the GRU output of the row):
 //   y = embed_net.0 h;  z = LeakyReLU(BatchNorm(y));  p = embed_net.3 z            (2 N L columns: means | log-variances)
@@ -25,27 +26,14 @@
 // float atomics, the same bits on every run), writes scale / shift and updates running_mean / running_var /
 // num_batches_tracked, launch 3 is the head reading y back.
 #include "synth_env.h"
-#include "head_tile.h"
-#include "../../include/marl_hip.h"
+#include "maic_common.h"
 
 namespace {
 
+using namespace maic;
 using head_tile::drow;
 
-constexpr int MC_H = 64;             // rnn_hidden_dim
-constexpr int MC_NH = 64;            // nn_hidden_size
-constexpr int MC_L = 8;              // latent_dim
-constexpr int MC_D = 32;             // attention_dim
-constexpr int MC_NMAX = 16;
-constexpr int MC_AMAX = 32;
-constexpr int MC_LDH = MC_H + 4;
-constexpr int MC_LDL = MC_NMAX * MC_L + 4;
-constexpr int MC_LDK = MC_D + 4;
-constexpr int MC_LDQ = MC_L + 4;     // kq: L products + key . bq
-constexpr int MC_LDA = MC_NMAX + 1;
-constexpr int MC_M0 = MC_H + MC_L;   // row length of msg_net.0
 constexpr unsigned ST_MAIC_EPS = 8;  // hash stream of the sampled latents' noise (synth_env.h streams end at ST_PICK = 7)
-constexpr int MC_RED = 16;           // slices of the statistics merge
 
 struct MaicArgs {
   marl_maic_weights_t w;
@@ -58,16 +46,6 @@ struct MaicArgs {
   int bs, N, A, G, test_mode;
   float var_floor, bn_eps, bn_mom;
 };
-
-__host__ __device__ inline int mc_envs_per_tile(int N) { return N >= 16 ? 1 : 16 / N; }
-
-// every dense product here starts from zero, has K = 64 and a zero-padded X: the unguarded flavour
-__device__ __forceinline__ f32x4 mc_gemm(const float* X, int ldx, int K, const float* __restrict__ W, long ldw, int n0,
-                                         int nvalid) {
-  return head_tile::tile_gemm<false>(f32x4{0, 0, 0, 0}, X, ldx, K, W, ldw, 0, n0, nvalid);
-}
-
-__device__ __forceinline__ float leaky(float t) { return t > 0.0f ? t : 0.01f * t; }
 
 // rows of this workgroup's tile that exist
 __device__ __forceinline__ int tile_rows(const MaicArgs& p, long row0) {
@@ -106,15 +84,6 @@ __global__ __launch_bounds__(64) void maic_embed_stats_kernel(MaicArgs p) {
   }
   p.part[(long)blockIdx.x * 128 + l] = mean;
   p.part[(long)blockIdx.x * 128 + 64 + l] = m2;
-}
-
-// (n, mean, m2) <- merge with (nb, mb, m2b)
-__device__ __forceinline__ void chan_merge(float& n, float& mean, float& m2, float nb, float mb, float m2b) {
-  if (nb == 0.0f) return;
-  const float nt = n + nb, d = mb - mean;
-  mean += d * (nb / nt);
-  m2 += m2b + d * d * (n * nb / nt);
-  n = nt;
 }
 
 // ---- launch 2: merge the nblk partials (slice s takes blocks s, s + 16, ..; then slices 0..15 in order), write the affine map
@@ -232,7 +201,7 @@ __global__ __launch_bounds__(64) void maic_head_kernel(MaicArgs p) {
     float s = sh_kq[r * MC_LDQ + MC_L];
 #pragma unroll
     for (int k = 0; k < MC_L; ++k) s = fmaf(sh_kq[r * MC_LDQ + k], sh_lat[r * MC_LDL + j * MC_L + k], s);
-    s *= 0.17677669529663687f;                                 // 1 / sqrt(attention_dim)
+    s *= MC_QSCALE;
     sh_al[r * MC_LDA + j] = (j == r % N) ? -1e9f : s;          // row0 is a multiple of N: r % N is the agent
   }
   __syncthreads();
@@ -338,14 +307,6 @@ __global__ __launch_bounds__(256) void maic_noise_kernel(unsigned rseed, unsigne
   const unsigned pre = hprefix(rseed, ST_MAIC_EPS, env0 + e, tg);
   const float u1 = u01(hfin(pre, 2u * k)), u2 = u01(hfin(pre, 2u * k + 1u));
   eps[idx] = sqrtf(-2.0f * logf(1.0f - u1)) * cosf(6.283185307179586f * u2);
-}
-
-bool maic_weights_ok(const marl_maic_weights_t* w) {
-  const void* ps[] = {w->e0_w, w->e0_b, w->bn_w, w->bn_b, w->bn_rm, w->bn_rv, w->e3_w, w->e3_b, w->m0_w, w->m0_b,
-                      w->m2_w, w->m2_b, w->k_w, w->k_b, w->q_w, w->q_b};
-  for (const void* q : ps)
-    if (!q) return false;
-  return true;
 }
 
 struct WsLayout {

@@ -1,9 +1,11 @@
-"""MAICAgent mirror (reference network/MAIC.py:10-94): the RNNQNet agent plus the MAIC message head.  Inference only.
+"""MAICAgent mirror (reference network/MAIC.py:10-94): the RNNQNet agent plus the MAIC message head.  ``forward`` is the
+reference's inference forward; ``head_backward`` is the head's backward pass for the TD loss (MAICTDLearner).
 
 The module tree and state_dict keys are the reference's, in its order (embed_net.{0,1,3}, inference_net.{0,1,3}, fc1, rnn,
 fc2, msg_net.{0,2}, w_key, w_query, the BatchNorm buffers included), so a reference-trained state dict loads strictly.
-inference_net is held and saved but never evaluated: it only feeds the MI loss, which belongs to training.  The agent part is
-the HIP unroll kernel (csrc/agent.hip) as in RNNQNet; the head is csrc/maic_head.hip.
+inference_net is held and saved but never evaluated: it only feeds the MI loss, which is not built (neither is the entropy
+loss: ``forward`` refuses ``train_mode`` with a positive weight for either).  The agent part is the HIP unroll kernel
+(csrc/agent.hip) as in RNNQNet; the head is csrc/maic_head.hip, its backward csrc/maic_head_bwd.hip.
 
 BatchNorm follows the module's ``training`` flag as torch does: ``eval()`` normalises with the running statistics; in training
 mode - the state of a freshly built module, and the reference never calls ``.eval()`` - with the statistics of all bs * N rows
@@ -56,6 +58,21 @@ class MAICAgent(RNNQNet):
         ops.maic_head_fwd(self.maic_weights(), h, q, bs, a.n_agents, a.n_actions, test_mode=test_mode, bn_batch=self.training,
                           eps=None if test_mode else eps, var_floor=a.var_floor, bn_eps=bn.eps,
                           bn_momentum=0.1 if bn.momentum is None else bn.momentum, **outs)
+
+    def maic_grads(self):
+        """marl_maic_grads_t over the head parameters' .grad views (the learner's flat gradient buffer); inference_net has no
+        part in it."""
+        return ops.maic_grads({k: v.grad for k, v in self.named_parameters() if not k.startswith("inference_net.")})
+
+    def head_backward(self, h, u_act, dq_val, bs, test_mode, eps, dh):
+        """Backward of ``head`` for the sparse gradient (u_act, dq_val) on the returned q, one pair per row: dh (bs*N, 64) =
+        the head's contribution to the gradient on h (the identity path is BPTT's own), the head's weight gradients
+        accumulate into the .grad views.  Same h, eps and modes as the forward call; the running statistics do not move
+        (csrc/maic_head_bwd.hip)."""
+        a = self.args
+        ops.maic_head_bwd(self.maic_weights(), self.maic_grads(), h, u_act, dq_val, dh, bs, a.n_agents, a.n_actions,
+                          test_mode=test_mode, bn_batch=self.training, eps=None if test_mode else eps, var_floor=a.var_floor,
+                          bn_eps=self.embed_net[1].eps)
 
     def forward(self, inputs, hidden_state, bs, test_mode=False, **kwargs):
         """reference MAIC.py:52-94: (return_q, h, returns) with returns = {}.  ``eps`` (keyword, an extension): the noise of

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
-                   MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, check)
+                   MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, MarlMaicGrads, check)
 
 
 def _p(t):
@@ -811,7 +811,7 @@ def world_head_bwd(w, g, hs, dq_idx, dq_val, obs, obs_bs, obs_t0, den, dscale, d
           "marl_world_head_bwd")
 
 
-# ---- MAIC message head (csrc/maic_head.hip)
+# ---- MAIC message head (csrc/maic_head.hip, csrc/maic_head_bwd.hip)
 MAIC_KEYS = (("e0", "embed_net.0"), ("e3", "embed_net.3"), ("m0", "msg_net.0"), ("m2", "msg_net.2"), ("k", "w_key"),
              ("q", "w_query"))
 MAIC_BN = (("bn_w", "embed_net.1.weight", torch.float32), ("bn_b", "embed_net.1.bias", torch.float32),
@@ -850,6 +850,34 @@ def maic_head_fwd(w, h, q, bs, N, A, test_mode=True, bn_batch=False, eps=None, v
                                  _p(ws), 0 if ws is None else ws.numel() * 4, bs, N, A, 1 if test_mode else 0,
                                  1 if bn_batch else 0, float(var_floor), float(bn_eps), float(bn_momentum), _stream()),
           "marl_maic_head_fwd")
+
+
+def maic_grads(grads):
+    """grads: dict name -> gradient tensor with MAICAgent's parameter keys (the head's layers; inference_net not needed) ->
+    marl_maic_grads_t."""
+    return _fill_struct(MarlMaicGrads, grads, _linear_fields(MAIC_KEYS) + list(MAIC_BN[:2]))
+
+
+def maic_head_bwd(w, g, h, u_act, dq_val, dh, bs, N, A, test_mode=False, bn_batch=False, eps=None, var_floor=0.002, bn_eps=1e-5):
+    """Backward of maic_head_fwd for the sparse gradient (u_act, dq_val) on return_q, one pair per row (csrc/maic_head_bwd.hip):
+    dh (bs*N, 64) = the head's contribution to the gradient on h; the head's weight gradients accumulate into ``g``
+    (marl_maic_grads_t).  ``eps`` and the mode flags as the forward call had them; the running statistics are not moved."""
+    lib = _lib.load()
+    if not lib.marl_maic_supported(N, 1, A, 64, 64, 8, 32):
+        raise ValueError("the gfx950 MAIC head covers N <= 16 and A <= 32 (N %d, A %d)" % (N, A))
+    if not test_mode and eps is None:
+        raise ValueError("sampled latents (test_mode=False) need the eps of the forward call")
+    if bn_batch and bs * N < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got %d row(s)" % (bs * N))
+    for t, cols in ((h, 64), (dh, 64), (u_act, 1), (dq_val, 1)):
+        assert t.is_contiguous() and t.numel() == bs * N * cols
+    if eps is not None:
+        assert eps.is_contiguous() and eps.numel() == bs * N * N * 8
+    ws = WS.get("maic_bwd", lib.marl_maic_bwd_workspace(bs, N, A), h.device)
+    check(lib.marl_maic_head_bwd(C.byref(w), C.byref(g), _p(_f32(h)), _p(_f32(eps)) if eps is not None and not test_mode else None,
+                                 _p(_i32(u_act)), _p(_f32(dq_val)), _p(_f32(dh)), _p(ws), ws.numel() * 4, bs, N, A,
+                                 1 if test_mode else 0, 1 if bn_batch else 0, float(var_floor), float(bn_eps), _stream()),
+          "marl_maic_head_bwd")
 
 
 def maic_noise(rseed, env0, tg, eps, E, N):

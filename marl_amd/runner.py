@@ -24,6 +24,10 @@ MAICQLearner for vdn / qmix / qplex.  Evaluation and rollouts run (the per-step 
 NotImplementedError and touches nothing.  With RTW or world_model it raises ValueError, with qtran_* or overlapped rollouts
 NotImplementedError - all before anything is built.
 
+``args.MAIC_train`` (with MAIC): the learner is MAICTDLearner, which trains the agent on the TD loss through the message
+head's backward pass (the MI and entropy losses are not built); the refusals above hold for it too.  Without MAIC it raises
+ValueError before anything is built.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -43,6 +47,7 @@ from .algorithm.qtran_learner import QTRANLearner
 from .algorithm.rtw_q_learner import RTWQLearner
 from .algorithm.q_learner_state import QLearnerWithState
 from .algorithm.maic_q_learner import MAICQLearner
+from .algorithm.maic_td_learner import MAICTDLearner
 from .utils.logging import Logger
 
 
@@ -68,7 +73,8 @@ _AGENT_SWITCHES = (
             (ValueError, "world_model and RTW are two different agents: choose one"),
             lambda args: not _value_mixer(args), (ValueError, "Mixer {} not recognised."),     # q_learner_state.py:32
             (NotImplementedError, "overlapped rollouts use the whole-rollout kernel, which has no world-model head")),
-    _Switch("MAIC", MAICMAC, lambda mac, logger, args: MAICQLearner(mac, args),
+    _Switch("MAIC", MAICMAC,
+            lambda mac, logger, args: (MAICTDLearner if getattr(args, "MAIC_train", False) else MAICQLearner)(mac, args),
             (ValueError, "MAIC, RTW and world_model are three different agents: choose one"),
             _qtran, (NotImplementedError, "MAIC with a QTRAN learner is not supported"),
             (NotImplementedError, "overlapped rollouts use the whole-rollout kernel, which has no MAIC head")),
@@ -80,6 +86,8 @@ class Runner:
         self.env = env
         if not args.reuse_network:
             raise NotImplementedError("only the shared-parameter controller (reuse_network) is on the hot path")
+        if getattr(args, "MAIC_train", False) and not getattr(args, "MAIC", False):
+            raise ValueError("MAIC_train trains the MAIC agent: it needs MAIC as well")
         mac_cls, make_learner = SharedMAC, lambda mac, logger, args: QLearner(mac, args)
         on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
         for sw in on:
