@@ -647,6 +647,46 @@ size_t marl_maic_bwd_workspace(int bs, int N, int A);
 int marl_maic_head_bwd(const marl_maic_weights_t* w, const marl_maic_grads_t* g, const float* h, const float* eps,
                        const int* u_act, const float* dq_val, float* dh, float* ws, size_t ws_bytes, int bs, int N, int A,
                        int test_mode, int bn_batch, float var_floor, float bn_eps, void* stream);
+/* marl_maic_head_bwd with one more input: dpar_extra (bs*N, 2*N*L) or NULL, a gradient on the post-clamp [mean | var] planes of
+ * embed_net (the MI term's, from marl_maic_aux).  It is added to the head's own d mean / d var before the clamp gate, so one
+ * embed_net backward serves both terms; rows without a TD pair still carry it.  NULL: marl_maic_head_bwd, bit for bit. */
+int marl_maic_head_bwd_ex(const marl_maic_weights_t* w, const marl_maic_grads_t* g, const float* h, const float* eps,
+                          const int* u_act, const float* dq_val, const float* dpar_extra, float* dh, float* ws,
+                          size_t ws_bytes, int bs, int N, int A, int test_mode, int bn_batch, float var_floor, float bn_eps,
+                          void* stream);
+/* ---- MAIC auxiliary losses (maic_aux.hip): the MI and the attention-entropy loss of network/MAIC.py:88-123 ------------
+ * inference_net, torch layouts: i0 (64, 64 + A), ibn (64) weight / bias / running_mean / running_var / num_batches_tracked
+ * (int64, may be NULL), i3 (2*L, 64). */
+typedef struct {
+  const float *i0_w, *i0_b, *ibn_w, *ibn_b;
+  float *ibn_rm, *ibn_rv;
+  long long* ibn_nbt;
+  const float *i3_w, *i3_b;
+} marl_maic_infer_t;
+typedef struct {
+  float *i0_w, *i0_b, *ibn_w, *ibn_b, *i3_w, *i3_b;
+} marl_maic_infer_grads_t;
+size_t marl_maic_aux_workspace(int bs, int N, int A);
+/* Both losses and their gradients in one call over bs environments x N agents (rows as marl_maic_head_fwd):
+ *   h, eps, test_mode, bn_batch, var_floor, bn_eps: as the head's forward call had them; return_q (bs*N, A): its output, read
+ *   for the greedy actions only (lowest index on a tie, no mask).
+ *   mi_out[0]  += mi_weight * mean over the bs*N*N pairs of sum_L KL(g1 || g2)           (MAIC.py:101-118)
+ *   ent_out[0] += entropy_weight * mean over the bs*N rows of -sum_j a' log2 a', a' = max(alpha, 1e-4), alpha the softmax of
+ *                 the UNSCALED, UNMASKED logits w_key(h) . w_query(latent)               (MAIC.py:93-97, 120-123)
+ *   Every gradient is that of mi + ent times (den ? den[0] : 1) * dscale - the pre-scale for an optimizer that divides by den.
+ *   dpar (bs*N, 2*N*L) is written: the MI term's gradient on the post-clamp [mean | var] planes (-> marl_maic_head_bwd_ex);
+ *   dh (bs*N, 64) is written: the part of the MI gradient on h that comes through inference_net's input.
+ *   ACCUMULATED: ig (inference_net: weights, biases, BatchNorm affine) and g->k_w, k_b, q_w, q_b (the entropy term; nothing else
+ *   of g is touched; h and the latent are constants of that term, so it adds nothing to dh).
+ *   bn_batch 1: both BatchNorms on the statistics of this call (inference_net.1 over all bs*N*N pair rows, needs >= 2), and
+ *   with mi_weight > 0 inference_net.1's running statistics move ONCE, as torch moves them (unbiased variance,
+ *   num_batches_tracked += 1); embed_net.1's buffers are never written.  Fixed-order reductions, no float atomics: two calls
+ *   give the same bits.  fp32 throughout; ws: marl_maic_aux_workspace() bytes. */
+int marl_maic_aux(const marl_maic_weights_t* w, const marl_maic_infer_t* iw, const marl_maic_grads_t* g,
+                  const marl_maic_infer_grads_t* ig, const float* h, const float* eps, const float* return_q, float mi_weight,
+                  float entropy_weight, const float* den, float dscale, float* mi_out, float* ent_out, float* dpar, float* dh,
+                  float* ws, size_t ws_bytes, int bs, int N, int A, int test_mode, int bn_batch, float var_floor, float bn_eps,
+                  float bn_momentum, void* stream);
 /* eps (E*N, N*8) of a sampled-latent rollout step (replaces the torch generator behind rsample, MAIC.py:68): element (n, c) of
  * environment env0 + e is sqrt(-2 ln(1 - u1)) cos(2 pi u2) with u1, u2 the counter-hash draws 2k, 2k + 1 (k = n*N*8 + c) of
  * stream 8 keyed by (rseed, env, tg = the global step), as marl_select_actions draws its own. */

@@ -70,6 +70,14 @@ class MarlMaicGrads(C.Structure):
                                           "k_w", "k_b", "q_w", "q_b")]
 
 
+class MarlMaicInfer(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("i0_w", "i0_b", "ibn_w", "ibn_b", "ibn_rm", "ibn_rv", "ibn_nbt", "i3_w", "i3_b")]
+
+
+class MarlMaicInferGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("i0_w", "i0_b", "ibn_w", "ibn_b", "i3_w", "i3_b")]
+
+
 class MarlAgentGrads(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p),
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
@@ -90,6 +98,7 @@ QT = C.POINTER(MarlQtranWeights)
 RW = C.POINTER(MarlRtwWeights)
 WW, WG = C.POINTER(MarlWorldWeights), C.POINTER(MarlWorldGrads)
 MW, MG = C.POINTER(MarlMaicWeights), C.POINTER(MarlMaicGrads)
+MIW, MIG = C.POINTER(MarlMaicInfer), C.POINTER(MarlMaicInferGrads)
 
 # name -> (restype, argtypes); must list every symbol of include/marl_hip.h
 SIGNATURES = {
@@ -188,6 +197,9 @@ SIGNATURES = {
     "marl_maic_noise": (I, [U, I, U, P, I, I, P]),
     "marl_maic_bwd_workspace": (SZ, [I, I, I]),
     "marl_maic_head_bwd": (I, [MW, MG, P, P, P, P, P, P, SZ, I, I, I, I, I, F, F, P]),
+    "marl_maic_head_bwd_ex": (I, [MW, MG, P, P, P, P, P, P, P, SZ, I, I, I, I, I, F, F, P]),
+    "marl_maic_aux_workspace": (SZ, [I, I, I]),
+    "marl_maic_aux": (I, [MW, MIW, MG, MIG, P, P, P, F, F, P, F, P, P, P, P, P, SZ, I, I, I, I, I, F, F, F, P]),
     "marl_hip_version": (C.c_char_p, []),
     "marl_experiment_set": (I, [C.c_char_p, I]),
     "marl_experiment_get": (I, [C.c_char_p]),

@@ -1,6 +1,7 @@
-"""MAICTDLearner: trains a MAICMAC on the TD loss (``--MAIC True --MAIC_train True``).  The reference's
-algorithm/MAIC_q_learner.py is QLearner line for line: its loss has no MI or entropy term, and neither has this one - those two
-losses of network/MAIC.py:88-121 are not built, so inference_net gets no gradient and does not move.
+"""MAICTDLearner: trains a MAICMAC (``--MAIC True --MAIC_train True``).  The reference's algorithm/MAIC_q_learner.py is
+QLearner line for line: its loss has no MI or entropy term although its agent computes them (network/MAIC.py:88-123).  This
+learner trains on the TD loss and, with ``args.mi_loss_weight`` / ``args.entropy_loss_weight`` positive, on those two as well -
+the MI loss is the only thing that gives inference_net a gradient.  The schedule of the two is this project's own.
 
 ``train`` is QLearner's schedule with the message head in it, shaped like QLearnerWithState:
   - the three unrolls keep their hidden states, and csrc/maic_head.hip adds the gated messages to the eval, double-Q
@@ -9,12 +10,21 @@ losses of network/MAIC.py:88-121 are not built, so inference_net gets no gradien
     agent; the reference never leaves it) that is one head call per transition index, and every call moves the running
     statistics of its network; ``agent.eval()`` takes one call over all B*T*N rows;
   - after the TD loss, csrc/maic_head_bwd.hip turns the sparse pairs BPTT receives (u_act, dq) into the gradient on hs and
-    the head's weight gradients, over the same rows per call as the forward; BPTT takes that dhs.
+    the head's weight gradients, over the same rows per call as the forward; BPTT takes that dhs;
+  - with a positive weight, csrc/maic_aux.hip runs in front of each of those backward calls, over the same rows and on the
+    eval network's current pass alone (the double-Q continuation and the target pass carry no term):
+    loss = TD + (1/T) sum_t (mi_t + ent_t), T = max_episode_len, one (mi_t, ent_t) per transition index over its B
+    environments, padded steps included (as the world-model prediction term's).  It runs AFTER the loss kernel because its
+    gradients are pre-scaled on the device by den / T, den = sum(mask) - the optimizer divides the whole gradient by den
+    (FusedOptimizer.step) - and den is that kernel's output; what it needs of the forward (hs, eps, the returned Qs) is kept
+    anyway, the rest is recomputed as the head's backward recomputes it.  The two sums land in slots 2 and 3 of the loss
+    statistics (``last_stats``), the returned loss is s[0] / s[1] + (s[2] + s[3]) / T.  Exact in one process only.
+    With both weights zero not one call differs from the TD-only learner.
 The latents' noise is an optional argument of ``train`` (a dict of three (B,T,N,N*latent_dim) tensors: cur, next_eval,
 next_target); absent, it is drawn from a generator this learner owns, seeded from args.seed.
-Target copies carry the BatchNorm buffers.  The update is never launched before max_episode_len is known and never replayed
-from a hipGraph: a redone or replayed pass would move the running statistics and the generator on its own.
-Multi-rank training is not supported: batch statistics are per rank.
+Target copies carry the BatchNorm buffers (inference_net.1's too).  The update is never launched before max_episode_len is known
+and never replayed from a hipGraph: a redone or replayed pass would move the running statistics and the generator on its own.
+Multi-rank training is not supported: batch statistics are per rank, and so is den.
 """
 from __future__ import annotations
 
@@ -40,6 +50,15 @@ class MAICTDLearner(QLearner):
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(int(getattr(args, "seed", 0)))
         self._eps = None
+        self.aux = getattr(args, "mi_loss_weight", 0) > 0 or getattr(args, "entropy_loss_weight", 0) > 0
+        if self.aux:
+            self.n_stats = 4      # TD numerator, sum(mask), sum_t mi_t, sum_t ent_t
+
+    def _loss_fn(self):
+        if not self.aux:
+            return super()._loss_fn()
+        T = float(self.max_episode_len)
+        return lambda s: s[0] / s[1] + (s[2] + s[3]) / T
 
     def train(self, batch, train_step, eps=None):
         self._eps = eps
@@ -79,7 +98,12 @@ class MAICTDLearner(QLearner):
         # and, for the identity path, into BPTT
         u_act = db.u_act.reshape(-1)
         dhs = self._g("dhs", (B, T, N, H))
-        self.eval_net.head_backward(hs, u_act, dq_val, B, T, False, eps["cur"], dhs, self._buf)
+        if self.aux:          # stats[1] = sum(mask) is ready; the two sums go to stats[2], stats[3] (zeroed with the gradient)
+            st = self._flat.stats
+            self.eval_net.head_backward(hs, u_act, dq_val, B, T, False, eps["cur"], dhs, self._buf, q=q_evals,
+                                        aux=(st[2:3], st[3:4], st[1:2]))
+        else:
+            self.eval_net.head_backward(hs, u_act, dq_val, B, T, False, eps["cur"], dhs, self._buf)
         agent_backward(self.eval_net, db, "cur", saved, hs, None, dhs, self._buf, dq_idx=u_act, dq_val=dq_val)
         self._dbg = dict(q_evals=q_evals, q_targets=q_tgt, q_tot=q_tot, q_tot_target=q_tot_tgt, hs=hs)
 

@@ -20,6 +20,9 @@ def get_common_args(argv=None):
     p.add_argument('--MAIC', type=_bool, default=False)
     # ... and with --MAIC_train the learner that trains it on the TD loss (MAICTDLearner; needs --MAIC)
     p.add_argument('--MAIC_train', type=_bool, default=False)
+    # the weights of the agent's MI and attention-entropy losses (network/MAIC.py:88-123) in MAICTDLearner's loss; 0 = TD only
+    p.add_argument('--mi_loss_weight', type=float, default=0.0)
+    p.add_argument('--entropy_loss_weight', type=float, default=0.0)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')

@@ -374,30 +374,55 @@ class MAICMAC(SharedMAC):
                             None if eps is None else eps[:, t].contiguous().view(B * N, NL))
             q[:, t] = qt
 
-    def head_backward(self, hs, u_act, dq_val, B, T, test_mode, eps, dhs, buf):
+    def head_backward(self, hs, u_act, dq_val, B, T, test_mode, eps, dhs, buf, q=None, aux=None):
         """The backward counterpart of ``head_over``, over the same rows per call: dhs (B,T,N,64) is written with the head's
         contribution to the gradient on hs for the sparse pairs u_act, dq_val (B,T,N); the head's weight gradients
-        accumulate into the agent's .grad views."""
-        N = self.n_agents
+        accumulate into the agent's .grad views.
+        ``aux`` = (mi_out, ent_out, den): the agent's MI and entropy losses as well (MAICAgent.aux_backward), over the same rows
+        per call, with ``q`` (B,T,N,A) the Q values ``head_over`` returned.  The sum over the transition indices of the two
+        losses is added into mi_out / ent_out (eval mode: the one call's losses times T - the same number, every index has B
+        rows), the gradients are those of that sum times den[0] / T, and dhs carries both parts."""
+        N, A = self.n_agents, self.n_actions
         NL = N * self.args.latent_dim
+        H = hs.shape[-1]
         if not self.agent.training:
-            self.agent.head_backward(hs.view(B * T * N, -1), u_act.reshape(-1), dq_val.reshape(-1), B * T, test_mode,
-                                     None if eps is None else eps.view(B * T * N, NL), dhs.view(B * T * N, -1))
+            R = B * T * N
+            e = None if eps is None else eps.view(R, NL)
+            plane = None
+            if aux is not None:
+                plane = buf.get("maic_aux_dpar", (R, 2 * NL), hs.device, hs.dtype)
+                dh_aux = buf.get("maic_aux_dh", (R, H), hs.device, hs.dtype)
+                self.agent.aux_backward(hs.view(R, H), q.view(R, A), B * T, test_mode, e, plane, dh_aux, aux[0], aux[1],
+                                        den=aux[2], dscale=1.0 / T, weight_scale=float(T))
+            self.agent.head_backward(hs.view(R, H), u_act.reshape(-1), dq_val.reshape(-1), B * T, test_mode, e, dhs.view(R, H),
+                                     dpar_extra=plane)
+            if aux is not None:
+                dhs.view(R, H).add_(dh_aux)
             return
         # the rows of one index, made contiguous in scratch buffers (buf: the learner's Scratch) that every index uses again
-        H = hs.shape[-1]
         g = lambda name, src: buf.get("maic_bwd_" + name, (B, N) + tuple(src.shape[3:]), src.device, src.dtype)
         u_act, dq_val = u_act.view(B, T, N), dq_val.view(B, T, N)
         ht, ut, vt, dh = g("h", hs), g("u", u_act), g("v", dq_val), g("dh", dhs)
         et = None if eps is None else g("eps", eps)
+        plane = None
+        if aux is not None:
+            qt, dh_aux = g("q", q), g("dh_aux", dhs)
+            plane = buf.get("maic_aux_dpar", (B * N, 2 * NL), hs.device, hs.dtype)
         for t in range(T):
             ht.copy_(hs[:, t])
             ut.copy_(u_act[:, t])
             vt.copy_(dq_val[:, t])
             if et is not None:
                 et.copy_(eps[:, t])
-            self.agent.head_backward(ht.view(B * N, H), ut.view(-1), vt.view(-1), B, test_mode,
-                                     None if et is None else et.view(B * N, NL), dh.view(B * N, H))
+            e = None if et is None else et.view(B * N, NL)
+            if aux is not None:
+                qt.copy_(q[:, t])
+                self.agent.aux_backward(ht.view(B * N, H), qt.view(B * N, A), B, test_mode, e, plane, dh_aux.view(B * N, H),
+                                        aux[0], aux[1], den=aux[2], dscale=1.0 / T)
+            self.agent.head_backward(ht.view(B * N, H), ut.view(-1), vt.view(-1), B, test_mode, e, dh.view(B * N, H),
+                                     dpar_extra=plane)
+            if aux is not None:
+                dh.add_(dh_aux)
             dhs[:, t] = dh
 
     def _maic_q_values(self, batch, T, which, test_mode, eps):

@@ -47,6 +47,7 @@ struct BwdArgs {
   const float* eps;                  // (R, N L) or null (test mode)
   const int* u_act;                  // (R)
   const float* dq_val;               // (R)
+  const float* extra;                // (R, 2 N L) or null: a further gradient on the post-clamp [mean | var] planes
   float* dh;                         // (R, 64)
   float *spart, *ss, *bnsum;         // statistics partials (mean | M2 per tile), scale | shift | mean | rstd, the two column sums
   float *S, *DU, *z, *dbn, *xh, *dy; // (R, 64) planes
@@ -193,17 +194,21 @@ __global__ __launch_bounds__(64) void maic_bwd_pair_kernel(BwdArgs p) {
     f32x4 lat, sd = f32x4{0, 0, 0, 0};
 #pragma unroll
     for (int r = 0; r < 4; ++r) lat[r] = c < NL ? mu[r] + w.e3_b[c] : 0.0f;
-    if (!p.test_mode) {
+    if (!p.test_mode || p.extra) {
       const f32x4 lv = mc_gemm(sh_z, MC_LDH, MC_NH, w.e3_w + (long)NL * MC_NH, MC_NH, n0, NL);
       if (c < NL) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           if (drow(r) < nv) {
             const float ex = expf(lv[r] + w.e3_b[NL + c]);
-            const float sv = sqrtf(fmaxf(ex, p.var_floor));
-            const float e = p.eps[(row0 + drow(r)) * NL + c];
-            lat[r] = fmaf(sv, e, lat[r]);
-            sd[r] = ex >= p.var_floor ? 0.5f * sv * e : 0.0f;
+            if (!p.test_mode) {
+              const float sv = sqrtf(fmaxf(ex, p.var_floor));
+              const float e = p.eps[(row0 + drow(r)) * NL + c];
+              lat[r] = fmaf(sv, e, lat[r]);
+              sd[r] = ex >= p.var_floor ? 0.5f * sv * e : 0.0f;
+            }
+            // d var -> d lv factor of the extra gradient (0 under the clamp), parked where d lv goes at the end
+            if (p.extra) p.dpar[(row0 + drow(r)) * 2 * NL + NL + c] = ex >= p.var_floor ? ex : 0.0f;
           }
         }
       }
@@ -378,8 +383,14 @@ __global__ __launch_bounds__(64) void maic_bwd_pair_kernel(BwdArgs p) {
   }
   for (int idx = l; idx < 16 * NL; idx += 64) {
     const int r = idx / NL, c = idx % NL;
-    const float dmu = sh_dlat[r * MC_LDL + c];
-    const float dlv = dmu * sh_sd[r * MC_LDL + c];
+    float dmu = sh_dlat[r * MC_LDL + c];
+    float dlv = dmu * sh_sd[r * MC_LDL + c];
+    if (p.extra && r < nv) {               // the extra planes join before the clamp gate: one embed_net backward for both
+      const long g = (row0 + r) * 2 * NL + c;
+      dlv = fmaf(p.extra[g + NL], p.dpar[g + NL], dlv);
+      dmu += p.extra[g];
+      sh_dlat[r * MC_LDL + c] = dmu;
+    }
     sh_sd[r * MC_LDL + c] = dlv;
     if (r < nv) {
       p.dpar[(row0 + r) * 2 * NL + c] = dmu;
@@ -391,7 +402,7 @@ __global__ __launch_bounds__(64) void maic_bwd_pair_kernel(BwdArgs p) {
   for (int n0 = 0; n0 < MC_NH; n0 += 16) {
     const int c = n0 + m;
     f32x4 dz = tile_gemm_t(f32x4{0, 0, 0, 0}, sh_dlat, MC_LDL, NL, w.e3_w, MC_NH, n0, MC_NH);
-    if (!p.test_mode) dz = tile_gemm_t(dz, sh_sd, MC_LDL, NL, w.e3_w + (long)NL * MC_NH, MC_NH, n0, MC_NH);
+    if (!p.test_mode || p.extra) dz = tile_gemm_t(dz, sh_sd, MC_LDL, NL, w.e3_w + (long)NL * MC_NH, MC_NH, n0, MC_NH);
     f32x4 dh = tile_gemm_t(f32x4{0, 0, 0, 0}, sh_DU, MC_LDH, MC_NH, w.m0_w, MC_M0, n0, MC_H);
     dh = tile_gemm_t(dh, sh_dk, MC_LDK, MC_D, w.k_w, MC_H, n0, MC_H);
 #pragma unroll
@@ -535,6 +546,14 @@ extern "C" size_t marl_maic_bwd_workspace(int bs, int N, int A) {
 extern "C" int marl_maic_head_bwd(const marl_maic_weights_t* w, const marl_maic_grads_t* g, const float* h, const float* eps,
                                   const int* u_act, const float* dq_val, float* dh, float* ws, size_t ws_bytes, int bs, int N,
                                   int A, int test_mode, int bn_batch, float var_floor, float bn_eps, void* stream) {
+  return marl_maic_head_bwd_ex(w, g, h, eps, u_act, dq_val, nullptr, dh, ws, ws_bytes, bs, N, A, test_mode, bn_batch, var_floor,
+                               bn_eps, stream);
+}
+
+extern "C" int marl_maic_head_bwd_ex(const marl_maic_weights_t* w, const marl_maic_grads_t* g, const float* h, const float* eps,
+                                     const int* u_act, const float* dq_val, const float* dpar_extra, float* dh, float* ws,
+                                     size_t ws_bytes, int bs, int N, int A, int test_mode, int bn_batch, float var_floor,
+                                     float bn_eps, void* stream) {
   if (!w || !maic_weights_ok(w) || !g || !maic_grads_ok(g) || !h || !u_act || !dq_val || !dh || !ws || bs < 0 ||
       !marl_maic_supported(N, 1, A, MC_H, MC_NH, MC_L, MC_D))
     return (int)hipErrorInvalidValue;
@@ -545,7 +564,7 @@ extern "C" int marl_maic_head_bwd(const marl_maic_weights_t* w, const marl_maic_
   const BwdLayout L = bwd_layout(bs, N, A);
   BwdArgs a{};
   a.w = *w; a.g = *g;
-  a.h = h; a.eps = test_mode ? nullptr : eps; a.u_act = u_act; a.dq_val = dq_val; a.dh = dh;
+  a.h = h; a.eps = test_mode ? nullptr : eps; a.u_act = u_act; a.dq_val = dq_val; a.extra = dpar_extra; a.dh = dh;
   a.spart = ws + L.spart; a.ss = ws + L.ss; a.bnsum = ws + L.bnsum;
   a.S = ws + L.S; a.DU = ws + L.DU; a.z = ws + L.z; a.dbn = ws + L.dbn; a.xh = ws + L.xh; a.dy = ws + L.dy;
   a.dkey = ws + L.dkey; a.dpar = ws + L.dpar; a.dm2 = ws + L.dm2;

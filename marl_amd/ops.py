@@ -11,7 +11,8 @@ import torch
 
 from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
-                   MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, MarlMaicGrads, check)
+                   MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, MarlMaicGrads, MarlMaicInfer,
+                   MarlMaicInferGrads, check)
 
 
 def _p(t):
@@ -858,10 +859,13 @@ def maic_grads(grads):
     return _fill_struct(MarlMaicGrads, grads, _linear_fields(MAIC_KEYS) + list(MAIC_BN[:2]))
 
 
-def maic_head_bwd(w, g, h, u_act, dq_val, dh, bs, N, A, test_mode=False, bn_batch=False, eps=None, var_floor=0.002, bn_eps=1e-5):
+def maic_head_bwd(w, g, h, u_act, dq_val, dh, bs, N, A, test_mode=False, bn_batch=False, eps=None, var_floor=0.002, bn_eps=1e-5,
+                  dpar_extra=None):
     """Backward of maic_head_fwd for the sparse gradient (u_act, dq_val) on return_q, one pair per row (csrc/maic_head_bwd.hip):
     dh (bs*N, 64) = the head's contribution to the gradient on h; the head's weight gradients accumulate into ``g``
-    (marl_maic_grads_t).  ``eps`` and the mode flags as the forward call had them; the running statistics are not moved."""
+    (marl_maic_grads_t).  ``eps`` and the mode flags as the forward call had them; the running statistics are not moved.
+    ``dpar_extra`` (bs*N, 2*N*8): a further gradient on embed_net's post-clamp [mean | var] planes (maic_aux's), carried through
+    the same embed_net backward; rows without a TD pair still receive it."""
     lib = _lib.load()
     if not lib.marl_maic_supported(N, 1, A, 64, 64, 8, 32):
         raise ValueError("the gfx950 MAIC head covers N <= 16 and A <= 32 (N %d, A %d)" % (N, A))
@@ -874,10 +878,62 @@ def maic_head_bwd(w, g, h, u_act, dq_val, dh, bs, N, A, test_mode=False, bn_batc
     if eps is not None:
         assert eps.is_contiguous() and eps.numel() == bs * N * N * 8
     ws = WS.get("maic_bwd", lib.marl_maic_bwd_workspace(bs, N, A), h.device)
-    check(lib.marl_maic_head_bwd(C.byref(w), C.byref(g), _p(_f32(h)), _p(_f32(eps)) if eps is not None and not test_mode else None,
-                                 _p(_i32(u_act)), _p(_f32(dq_val)), _p(_f32(dh)), _p(ws), ws.numel() * 4, bs, N, A,
-                                 1 if test_mode else 0, 1 if bn_batch else 0, float(var_floor), float(bn_eps), _stream()),
-          "marl_maic_head_bwd")
+    e = _p(_f32(eps)) if eps is not None and not test_mode else None
+    tail = (_p(_f32(dh)), _p(ws), ws.numel() * 4, bs, N, A, 1 if test_mode else 0, 1 if bn_batch else 0, float(var_floor),
+            float(bn_eps), _stream())
+    if dpar_extra is None:
+        check(lib.marl_maic_head_bwd(C.byref(w), C.byref(g), _p(_f32(h)), e, _p(_i32(u_act)), _p(_f32(dq_val)), *tail),
+              "marl_maic_head_bwd")
+        return
+    assert dpar_extra.is_contiguous() and dpar_extra.numel() == bs * N * 2 * N * 8
+    check(lib.marl_maic_head_bwd_ex(C.byref(w), C.byref(g), _p(_f32(h)), e, _p(_i32(u_act)), _p(_f32(dq_val)),
+                                    _p(_f32(dpar_extra)), *tail), "marl_maic_head_bwd_ex")
+
+
+# ---- MAIC auxiliary losses (csrc/maic_aux.hip)
+MAIC_INFER_KEYS = (("i0", "inference_net.0"), ("i3", "inference_net.3"))
+MAIC_INFER_BN = (("ibn_w", "inference_net.1.weight", torch.float32), ("ibn_b", "inference_net.1.bias", torch.float32),
+                 ("ibn_rm", "inference_net.1.running_mean", torch.float32), ("ibn_rv", "inference_net.1.running_var", torch.float32),
+                 ("ibn_nbt", "inference_net.1.num_batches_tracked", torch.int64))
+
+
+def maic_infer_weights(tensors):
+    """tensors: dict name -> tensor with MAICAgent's inference_net parameter and buffer keys -> marl_maic_infer_t."""
+    return _fill_struct(MarlMaicInfer, tensors, _linear_fields(MAIC_INFER_KEYS) + list(MAIC_INFER_BN))
+
+
+def maic_infer_grads(grads):
+    """grads: dict name -> gradient tensor with inference_net's parameter keys -> marl_maic_infer_grads_t."""
+    return _fill_struct(MarlMaicInferGrads, grads, _linear_fields(MAIC_INFER_KEYS) + list(MAIC_INFER_BN[:2]))
+
+
+def maic_aux(w, iw, g, ig, h, return_q, bs, N, A, mi_weight, entropy_weight, mi_out, ent_out, dpar, dh, test_mode=False,
+             bn_batch=False, eps=None, den=None, dscale=1.0, var_floor=0.002, bn_eps=1e-5, bn_momentum=0.1):
+    """The MI and the entropy loss of MAICAgent (network/MAIC.py:88-123) with their gradients, one call (csrc/maic_aux.hip).
+    mi_out / ent_out (one-float device views, e.g. slots of the loss statistics) += the two weighted losses; dpar
+    (bs*N, 2*N*8) = the MI gradient on embed_net's post-clamp [mean | var] planes (-> maic_head_bwd's dpar_extra); dh (bs*N, 64) =
+    the MI gradient on h through inference_net's input; inference_net's gradients accumulate into ``ig``, the entropy term's
+    into w_key / w_query of ``g``.  Gradients are scaled by den[0] * dscale (den None: dscale).  ``h``, ``eps`` and the mode flags
+    as the head's forward call had them, ``return_q`` its output.  bn_batch: inference_net.1's running statistics move once
+    (mi_weight > 0); embed_net.1's are never written."""
+    lib = _lib.load()
+    if not lib.marl_maic_supported(N, 1, A, 64, 64, 8, 32):
+        raise ValueError("the gfx950 MAIC head covers N <= 16 and A <= 32 (N %d, A %d)" % (N, A))
+    if not test_mode and eps is None:
+        raise ValueError("sampled latents (test_mode=False) need the eps of the forward call")
+    if bn_batch and bs * N < 2:
+        raise ValueError("Expected more than 1 value per channel when training, got %d row(s)" % (bs * N))
+    for t, cols in ((h, 64), (dh, 64), (return_q, A), (dpar, 2 * N * 8)):
+        assert t.is_contiguous() and t.numel() == bs * N * cols
+    if eps is not None:
+        assert eps.is_contiguous() and eps.numel() == bs * N * N * 8
+    ws = WS.get("maic_aux", lib.marl_maic_aux_workspace(bs, N, A), h.device)
+    check(lib.marl_maic_aux(C.byref(w), C.byref(iw), C.byref(g), C.byref(ig), _p(_f32(h)),
+                            _p(_f32(eps)) if eps is not None and not test_mode else None, _p(_f32(return_q)), float(mi_weight),
+                            float(entropy_weight), _p(_f32(den)) if den is not None else None, float(dscale), _p(_f32(mi_out)),
+                            _p(_f32(ent_out)), _p(_f32(dpar)), _p(_f32(dh)), _p(ws), ws.numel() * 4, bs, N, A,
+                            1 if test_mode else 0, 1 if bn_batch else 0, float(var_floor), float(bn_eps), float(bn_momentum),
+                            _stream()), "marl_maic_aux")
 
 
 def maic_noise(rseed, env0, tg, eps, E, N):

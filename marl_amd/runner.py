@@ -25,8 +25,9 @@ NotImplementedError and touches nothing.  With RTW or world_model it raises Valu
 NotImplementedError - all before anything is built.
 
 ``args.MAIC_train`` (with MAIC): the learner is MAICTDLearner, which trains the agent on the TD loss through the message
-head's backward pass (the MI and entropy losses are not built); the refusals above hold for it too.  Without MAIC it raises
-ValueError before anything is built.
+head's backward pass and, with ``args.mi_loss_weight`` / ``args.entropy_loss_weight`` positive, on the agent's MI and
+attention-entropy losses (csrc/maic_aux.hip); the refusals above hold for it too.  Without MAIC it raises ValueError before
+anything is built, and so does a positive loss weight without MAIC_train.
 
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
@@ -88,6 +89,9 @@ class Runner:
             raise NotImplementedError("only the shared-parameter controller (reuse_network) is on the hot path")
         if getattr(args, "MAIC_train", False) and not getattr(args, "MAIC", False):
             raise ValueError("MAIC_train trains the MAIC agent: it needs MAIC as well")
+        if (getattr(args, "mi_loss_weight", 0) > 0 or getattr(args, "entropy_loss_weight", 0) > 0) \
+                and not getattr(args, "MAIC_train", False):
+            raise ValueError("mi_loss_weight / entropy_loss_weight are terms of MAICTDLearner's loss: they need MAIC_train")
         mac_cls, make_learner = SharedMAC, lambda mac, logger, args: QLearner(mac, args)
         on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
         for sw in on:

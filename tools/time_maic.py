@@ -7,7 +7,8 @@ tools/time_rtw.py with the same arguments is the yardstick next to it.
     python tools/time_maic.py --train [--shape ...] [--envs ...] [--train_T 120]
 times training instead: the head's backward alone (csrc/maic_head_bwd.hip, sampled latents, one call over envs * N rows) and one
 MAICTDLearner update (qmix, BatchNorm in batch-statistics mode: one head call per transition index) beside a plain QLearner update
-of the same shape, HIP events."""
+of the same shape, HIP events; and beside them the auxiliary pass alone (csrc/maic_aux.hip: the MI and entropy losses with their
+gradients, one call over envs * N rows) and the update with both loss weights on (0.001 / 0.01)."""
 import argparse
 import os
 import sys
@@ -87,6 +88,22 @@ def head_bwd_ms(args, E, train):
     return _timed(lambda: mac.agent.head_backward(h, u, v, E, False, eps, dh), 20)
 
 
+def aux_ms(args, E, train):
+    N, A = args.n_agents, args.n_actions
+    dev = torch.device("cuda")
+    mac = MAICMAC(args)
+    mac.cuda()
+    mac.agent.train(train)
+    for p in mac.agent.parameters():
+        p.grad = torch.zeros_like(p)
+    h, dh = torch.randn(E * N, 64, device=dev), torch.empty(E * N, 64, device=dev)
+    eps = torch.randn(E * N, N * args.latent_dim, device=dev)
+    q = torch.randn(E * N, A, device=dev)
+    dpar = torch.empty(E * N, 2 * N * args.latent_dim, device=dev)
+    out = torch.zeros(2, device=dev)
+    return _timed(lambda: mac.agent.aux_backward(h, q, E, False, eps, dpar, dh, out[0:1], out[1:2]), 20)
+
+
 def update_ms(args, E, maic):
     from marl_amd.algorithm.q_learner import QLearner
     from marl_amd.algorithm.maic_td_learner import MAICTDLearner
@@ -112,6 +129,11 @@ def train_main(o):
         print("%-5s envs %5d T %d  head backward alone: eval %.3f ms, batch %.3f ms   update: QLearner %.2f ms, MAICTDLearner %.2f ms "
               "(x%.1f)" % (o.shape, E, o.train_T, head_bwd_ms(args, E, False), head_bwd_ms(args, E, True), plain, maic, maic / plain),
               flush=True)
+        args.mi_loss_weight, args.entropy_loss_weight = 0.001, 0.01
+        both = update_ms(args, E, True)
+        print("%-5s envs %5d T %d  auxiliary pass alone: eval %.3f ms, batch %.3f ms   update with both loss weights on %.2f ms "
+              "(x%.2f of the TD-only update)" % (o.shape, E, o.train_T, aux_ms(args, E, False), aux_ms(args, E, True), both,
+                                                 both / maic), flush=True)
 
 
 def main():
