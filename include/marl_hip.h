@@ -455,6 +455,20 @@ int marl_qtran_loss(const float* jq, const float* jq_tgt, const float* v, const 
                     void* stream);
 size_t marl_loss_workspace(long rows);
 
+/* TD(lambda) returns (td_lambda.hip; utils/rl_utils.py:4-14, build_td_lambda_targets - a function the reference ships and never
+ * calls).  Per episode b over the T steps of the batch, q[t] = q_next_tot[b, t] (the target network's value at the next state of
+ * step t), m = 1 - padded:
+ *   done = sum_t m[t] term[t],  G[T] = q[T-1] (1 - done),
+ *   G[t] = lambda gamma G[t+1] + m[t] (r[t] + (1 - lambda) gamma q[t] (1 - term[t])),  t = T-1 .. 0;   ret[b, t] = G[t].
+ * That is the reference's function called with target_qs[:, t+1] = q[t] and terminated = term * m (quirk Q15: the batches here
+ * carry term = 1 on padded steps).  lambda = 0: m (r + gamma q (1 - term)), the one-step target; lambda = 1: the Monte-Carlo
+ * return, bootstrapped from q[T-1] only when the episode did not terminate inside the window.  A row with m = 0 contributes nothing,
+ * whatever finite values r and q hold there.  All five arrays: contiguous (B, T) fp32; ret may not alias an input; nothing outside
+ * ret[0 : B*T] is written.  One wave per episode, no atomics: two calls give the same bits.  B <= 0 or T <= 0: returns 0, no launch.
+ * A learner hands G to the loss kernels as r with gamma = 0 (their target is then G + 0 q (1 - term) = G). */
+int marl_td_lambda_returns(const float* q_next_tot, const float* r, const float* term, const float* padded,
+                           float gamma, float lambda, float* ret, int B, int T, void* stream);
+
 /* ---- optimizer (optim.hip): clip_grad_norm_ + RMSprop / Adam on ONE flat buffer -------------
  * (q_learner.py:42-47,170-173; torch defaults).  g is the un-normalised gradient; den points to
  * sum(mask) on the device (NULL = 1).  sumsq[0] receives sum g^2 (before scaling). */

@@ -168,6 +168,7 @@ SIGNATURES = {
     "marl_td_loss": (I, [P, P, P, P, P, F, P, P, P, L, P]),
     "marl_qtran_loss": (I, [P, P, P, P, P, P, P, P, P, F, F, F, P, P, P, P, P, P, L, P]),
     "marl_loss_workspace": (SZ, [L]),
+    "marl_td_lambda_returns": (I, [P, P, P, P, F, F, P, I, I, P]),
     "marl_grad_sumsq": (I, [P, L, P, P, P]),
     "marl_sumsq_workspace": (SZ, [L]),
     "marl_rmsprop_step": (I, [P, P, P, L, F, F, F, F, P, P, P]),

@@ -3,6 +3,7 @@ tail, the fused clip+optimizer wrapper, the agent backward pass and data-paralle
 from __future__ import annotations
 
 import copy
+import numbers
 import os
 import warnings
 import weakref
@@ -163,6 +164,16 @@ class LossReadback:
         return LossReadback.Handle(buf, ev, fn)
 
 
+def td_lambda_of(args):
+    """args.td_lambda: None / absent (one-step targets) or a number in [0, 1]; anything else is an error"""
+    lam = getattr(args, "td_lambda", None)
+    if lam is None:
+        return None
+    if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not 0.0 <= lam <= 1.0:
+        raise ValueError("td_lambda must be None or a number in [0, 1], got %r" % (lam,))
+    return float(lam)
+
+
 class Learner(ResumeMixin):
     """The frame of QLearner and QTRANLearner: construction around the learner's own mixers, the batch intake of ``train``,
     the loss tail, the target copies and the model files.  A learner provides ``_forward_backward(db)``, ``cuda()``,
@@ -176,6 +187,8 @@ class Learner(ResumeMixin):
 
     def _begin(self, mac, args, name):
         """constructor preamble; the learner then builds mixer / target_mixer / params and calls cuda() and _ready()"""
+        self.td_lambda = td_lambda_of(args)      # raises before anything is built
+        self._td_dbg = {}
         self.max_episode_len = args.episode_limit
         self.gamma = args.gamma
         self.lr = args.lr
@@ -211,6 +224,21 @@ class Learner(ResumeMixin):
         return self._buf.get(name, shape, self.device, dt)
 
     # ------------------------------------------------------------------ the hot path
+    def _td_inputs(self, db, q_next_tot):
+        """What the loss kernels get as (r, gamma).  args.td_lambda None: the batch's rewards and gamma - their target is the
+        one-step r + gamma q (1 - term), and nothing is launched.  Otherwise the TD(lambda) returns G of q_next_tot (B*T,
+        the target network's value at each step's next state; csrc/td_lambda.hip, reference utils/rl_utils.py:4-14) and
+        gamma = 0: the kernels' target is then G + 0 q (1 - term) = G (q_next_tot must be finite on every row, padded ones
+        included), and their padding mask applies as before.  Episodes are whole on a rank: nothing crosses ranks."""
+        lam = self.td_lambda = td_lambda_of(self.args)
+        if lam is None:
+            self._td_dbg = {}
+            return db.r, self.gamma
+        G = self._g("td_ret", (db.B * db.T,))
+        ops.td_lambda_returns(q_next_tot, db.r, db.term, db.padded, self.gamma, lam, G, db.B, db.T)
+        self._td_dbg = {"td_targets": G}
+        return G, 0.0
+
     def get_max_episode_len(self, batch):
         """reference q_learner.py:49-66 (quirk Q2); returns the batch cut to [:, :T] and T."""
         T = DeviceBatch.first_terminated_len(torch.as_tensor(np.asarray(batch['terminated'])), self.args.episode_limit)
@@ -509,7 +537,7 @@ class GraphedUpdate:
         return GraphedUpdate() if mode else None
 
     SCHEDULE_ARGS = ("gemm_mode", "mixer_dtype", "mixer_wgrad_dtype", "double_q", "no_loss_fold", "lazy_loss", "gamma",
-                     "two_hyper_layers", "last_action", "reuse_network")
+                     "two_hyper_layers", "last_action", "reuse_network", "td_lambda")
 
     @staticmethod
     def _schedule_key(args):

@@ -20,6 +20,7 @@ the MI loss is the only thing that gives inference_net a gradient.  The schedule
     anyway, the rest is recomputed as the head's backward recomputes it.  The two sums land in slots 2 and 3 of the loss
     statistics (``last_stats``), the returned loss is s[0] / s[1] + (s[2] + s[3]) / T.  Exact in one process only.
     With both weights zero not one call differs from the TD-only learner.
+``args.td_lambda`` reaches this learner through QLearner._loss_backward with no lines of its own.
 The latents' noise is an optional argument of ``train`` (a dict of three (B,T,N,N*latent_dim) tensors: cur, next_eval,
 next_target); absent, it is drawn from a generator this learner owns, seeded from args.seed.
 Target copies carry the BatchNorm buffers (inference_net.1's too).  The update is never launched before max_episode_len is known
@@ -105,7 +106,7 @@ class MAICTDLearner(QLearner):
         else:
             self.eval_net.head_backward(hs, u_act, dq_val, B, T, False, eps["cur"], dhs, self._buf)
         agent_backward(self.eval_net, db, "cur", saved, hs, None, dhs, self._buf, dq_idx=u_act, dq_val=dq_val)
-        self._dbg = dict(q_evals=q_evals, q_targets=q_tgt, q_tot=q_tot, q_tot_target=q_tot_tgt, hs=hs)
+        self._dbg = dict(q_evals=q_evals, q_targets=q_tgt, q_tot=q_tot, q_tot_target=q_tot_tgt, hs=hs, **self._td_dbg)
 
     def _update_targets(self):
         super()._update_targets()

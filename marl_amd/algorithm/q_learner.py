@@ -5,7 +5,8 @@ every ``target_update_cycle``), but is an explicit forward/backward schedule of 
 three agent unrolls, mixer forward (+target), TD loss, mixer backward, BPTT, fused clip+optimizer.
 Reference quirks Q1 (double-Q pass continues from the eval net's final hidden state), Q2
 (get_max_episode_len ignores unterminated episodes), Q4/Q5 (mask constant, first-index argmax) and
-Q6 (target sync rule) are reproduced.
+Q6 (target sync rule) are reproduced.  With ``args.td_lambda`` set the TD target is the lambda-return of q_tot_target
+(Learner._td_inputs; quirk Q15) instead of the one-step bootstrap; unset, not one call differs.
 """
 from __future__ import annotations
 
@@ -149,12 +150,13 @@ class QLearner(Learner):
         """TD loss (un-normalised numerator + sum(mask) land in the tail of the gradient buffer, zeroed before) and the
         mixer backward.  Returns dq_chosen, the gradient on the taken actions' Qs."""
         BT = db.B * db.T
+        r, gamma = self._td_inputs(db, q_tot_tgt)        # args.td_lambda set: the lambda-returns as r, and gamma = 0
         if fold:
             # fused QMIX: eval-mixer forward, TD loss and mixer backward are ONE launch (the backward recomputes q_tot anyway)
-            return self.mixer.hip_loss_backward(q_chosen.view(BT, db.N), db.s, BT, q_tot_tgt, db.r, db.term, db.padded, self.gamma,
+            return self.mixer.hip_loss_backward(q_chosen.view(BT, db.N), db.s, BT, q_tot_tgt, r, db.term, db.padded, gamma,
                                                 self._flat.stats[:2], q_tot=q_tot)
         dq_tot = self._g("dq_tot", (BT,))
-        ops.td_loss(q_tot, q_tot_tgt, db.r, db.term, db.padded, self.gamma, dq_tot, self._flat.stats[:2], BT)
+        ops.td_loss(q_tot, q_tot_tgt, r, db.term, db.padded, gamma, dq_tot, self._flat.stats[:2], BT)
         return self.mixer.hip_backward(ctx, dq_tot, BT)
 
     def _forward_backward(self, db):
@@ -167,7 +169,7 @@ class QLearner(Learner):
         # instead of scattering them into a dense (B,T,N,A) tensor
         agent_backward(self.eval_net, db, "cur", saved, None, None, None, self._buf,
                        dq_idx=db.u_act.reshape(-1), dq_val=dq_chosen.reshape(-1).contiguous())
-        self._dbg = dict(q_evals=q_evals, q_targets=q_tgt, q_tot=q_tot, q_tot_target=q_tot_tgt)
+        self._dbg = dict(q_evals=q_evals, q_targets=q_tgt, q_tot=q_tot, q_tot_target=q_tot_tgt, **self._td_dbg)
 
     def get_q_and_q_tot_table(self):
         """Matrix-game diagnostic (reference :211-262): 3x3 q_tot table + per-agent Q rows with

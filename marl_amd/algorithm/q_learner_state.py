@@ -13,6 +13,8 @@
   - the returned loss is TD + pred: s[0] / s[1] + s[2] / K.
 terminate_out never reaches a loss: its gradient is zero and it does not move (RMSprop and Adam leave a parameter with zero
 gradient and zero state unchanged), but it stays in the parameter list, the clip norm and the flat buffer.
+``args.td_lambda`` reaches this learner through QLearner._loss_backward (the lambda-returns of q_tot_target, r included) with no
+lines of its own.
 Multi-rank training is not supported: the prediction term's scale needs the global sum(mask) before the all-reduce.
 """
 from __future__ import annotations
@@ -60,7 +62,7 @@ class QLearnerWithState(QLearner):
         ops.world_head_bwd(w_eval, self.eval_net.agent.world_grads(), hs, u_act, dq_val, on, on_bs, on_t0,
                            self._flat.stats[1:2], 2.0 / (B * T * N * O), dhs, B, T, N, O, A, ep_len=db.ep_len, ep_map=emap)
         agent_backward(self.eval_net, db, "cur", saved, hs, None, dhs, self._buf, dq_idx=u_act, dq_val=dq_val)
-        self._dbg = dict(q_evals=q_evals, q_targets=q_tgt, q_tot=q_tot, q_tot_target=q_tot_tgt, hs=hs)
+        self._dbg = dict(q_evals=q_evals, q_targets=q_tgt, q_tot=q_tot, q_tot_target=q_tot_tgt, hs=hs, **self._td_dbg)
 
     def _loss_fn(self):
         """TD + pred = s[0] / s[1] + s[2] / K (q_learner_state.py:183)"""

@@ -104,8 +104,9 @@ class QTRANLearner(Learner):
 
         self._flat.zero_grad()
         d_jq, d_v, d_so, d_sn = g("d_jq", (BT,)), g("d_v", (BT,)), g("d_so", (BT,)), g("d_sn", (BT,))
-        ops.qtran_loss(joint_q, joint_q_tgt, v, joint_q_hat, q_sum_opt, q_sum_nopt, db.r, db.term, db.padded,
-                       self.gamma, a.lambda_opt, a.lambda_nopt, d_jq, d_v, d_so, d_sn, self._flat.stats, BT)
+        r, gamma = self._td_inputs(db, joint_q_tgt)      # args.td_lambda set: the lambda-returns of joint_q_tgt as r, and gamma = 0
+        ops.qtran_loss(joint_q, joint_q_tgt, v, joint_q_hat, q_sum_opt, q_sum_nopt, r, db.term, db.padded,
+                       gamma, a.lambda_opt, a.lambda_nopt, d_jq, d_v, d_so, d_sn, self._flat.stats, BT)
 
         # backward: heads -> dhs, individual Qs -> dq, then BPTT
         dhs = g("dhs", (B, T, N, H))
@@ -119,7 +120,7 @@ class QTRANLearner(Learner):
         agent_backward(self.eval_net, db, "cur", saved, hs, None, dhs, self._buf, dq_idx=u_act, dq_val=d_sn,
                        dq_idx2=opt_eval, dq_val2=d_so, dq_gdiv=N)
         self._dbg = dict(q_evals=q_evals, hs=hs, joint_q=joint_q, joint_q_targets=joint_q_tgt, v=v,
-                         joint_q_hat=joint_q_hat)
+                         joint_q_hat=joint_q_hat, **self._td_dbg)
 
     def _loss_fn(self):
         lo, ln = self.args.lambda_opt, self.args.lambda_nopt

@@ -23,6 +23,9 @@ def get_common_args(argv=None):
     # the weights of the agent's MI and attention-entropy losses (network/MAIC.py:88-123) in MAICTDLearner's loss; 0 = TD only
     p.add_argument('--mi_loss_weight', type=float, default=0.0)
     p.add_argument('--entropy_loss_weight', type=float, default=0.0)
+    # TD(lambda) returns as the Q learners' targets (the reference ships utils/rl_utils.py:build_td_lambda_targets and never calls
+    # it); absent = None = the one-step target.  get_mixer_args leaves the field alone: a namespace without it means "off"
+    p.add_argument('--td_lambda', type=float, default=None)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')
@@ -122,7 +125,10 @@ def get_centralv_args(args):
 
 
 def get_reinforce_args(args):
-    """reference :181-200"""
+    """reference :181-200.  Its table has no td_lambda: the parser's unset (None) --td_lambda is taken off again, so the namespace
+    has the reference's fields (a value the user gave stays)"""
+    if getattr(args, "td_lambda", 0) is None:
+        del args.td_lambda
     return _assign(args, dict(_ACTOR_CRITIC))
 
 

@@ -385,6 +385,17 @@ def qtran_loss(jq, jq_tgt, v, jq_hat, qs_opt, qs_nopt, r, term, padded, gamma, l
                               _p(d_qsn), _p(out4), _p(ws), rows, _stream()), "marl_qtran_loss")
 
 
+def td_lambda_returns(q_next_tot, r, term, padded, gamma, lam, out, B, T):
+    """TD(lambda) returns of B episodes over T steps (csrc/td_lambda.hip; reference utils/rl_utils.py:4-14 with the terminal
+    flag masked by the padding).  All arrays hold B*T contiguous floats; ``out`` may not alias an input."""
+    lib = _lib.load()
+    for t in (q_next_tot, r, term, padded, out):
+        assert _f32(t).is_contiguous() and t.numel() >= B * T, "td_lambda_returns: contiguous (B, T) float32 arrays"
+    check(lib.marl_td_lambda_returns(_p(q_next_tot), _p(r), _p(term), _p(padded), float(gamma), float(lam), _p(out),
+                                     int(B), int(T), _stream()), "marl_td_lambda_returns")
+    return out
+
+
 def grad_sumsq(g, n, out1):
     lib = _lib.load()
     ws = WS.get("sumsq", lib.marl_sumsq_workspace(n), g.device)

@@ -24,6 +24,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=0, help="untimed updates before the timed ones (first-call allocations)")
     ap.add_argument("--mixer-dtype", default="fp32", choices=["fp32", "bf16"])
     ap.add_argument("--gemm-mode", default="f32", choices=["f32", "bf16x6"])
+    ap.add_argument("--td-lambda", type=float, default=None, help="args.td_lambda: TD(lambda) returns as the targets")
     o = ap.parse_args()
     from marl_amd.controller.share_params import SharedMAC
     from marl_amd.algorithm.q_learner import QLearner
@@ -33,6 +34,8 @@ def main():
     args = bench.make_args(o.alg, o.shape, o.T)
     args.mixer_dtype = o.mixer_dtype
     args.gemm_mode = o.gemm_mode
+    if o.td_lambda is not None:
+        args.td_lambda = o.td_lambda
     torch.manual_seed(0)
     mac = SharedMAC(args)
     learner = QTRANLearner(mac, args) if o.alg.startswith("qtran") else QLearner(mac, args)
