@@ -469,6 +469,34 @@ size_t marl_loss_workspace(long rows);
 int marl_td_lambda_returns(const float* q_next_tot, const float* r, const float* term, const float* padded,
                            float gamma, float lambda, float* ret, int B, int T, void* stream);
 
+/* ---- stochastic policy of the actor-critic learners (policy.hip; central-V) ---------------------
+ * A row is one agent at one step: logits z (A floats, the agent's fc2 output), availability a in {0,1}^A, exploration rate eps:
+ *   p = softmax(z) over all A actions,  n = sum_k a_k,  pt_k = a_k ((1 - eps) p_k + eps / n),  pi_k = pt_k / sum_j pt_j.
+ * A row with n = 0 (a padded step) has no policy: it contributes nothing to any sum, its outputs are exact zeros and its logits are
+ * never looked at.  fp32 throughout; fixed-order sums, no float atomics: two calls give the same bits.
+ *
+ * marl_policy_probs: pi (rows, A) of logits / avail (rows, A); pi may be logits itself, not avail.
+ *
+ * marl_policy_loss_bwd: the actor loss of rows = B*T*N agent steps, row r belonging to (episode, step) r / N.  With m = 1 - padded
+ * and Adv = G - v of that step (constants of the gradient; formed here) and u the taken action:
+ *   logp[r] = log pi_r(u[r])  (0 on a row without a policy, or whose m = 0),
+ *   out2 = { - sum_r m Adv logp[r],  sum_r m } = { numerator of L_actor, N * sum(m) }  (un-normalised, as marl_td_loss leaves them),
+ *   dlogits (rows, A) = the gradient of out2[0] by the logits: - m Adv d log pi(u) / dz, through pt and the renormalisation
+ *   (at eps = 0: - m Adv (delta_uk - pi_k)); the dense dq of marl_agent_unroll_bwd.
+ * G, v, padded: (rows / N); ws: marl_loss_workspace() bytes; dlogits may be logits itself, not avail.
+ *
+ * marl_policy_sample: one action per live agent of a lock-step, the argument shape of marl_select_actions.  With
+ * x = u01(hash(rseed, SAMPLE, env0 + e, tg, n)) the action is the first k in index order with a_k = 1 whose running fp32 sum of
+ * pi over the available actions up to k exceeds x; the last available action when rounding leaves none.  Environments with
+ * alive[e] == 0 get -1. */
+int marl_policy_probs(const float* logits, const float* avail, float eps, float* pi, long rows, int A, void* stream);
+int marl_policy_loss_bwd(const float* logits, const float* avail, const int* u, const float* G, const float* v,
+                         const float* padded, float eps, float* dlogits, float* logp, float* out2, float* ws, long rows,
+                         int N, int A, void* stream);
+int marl_policy_sample(const float* logits, const float* avail, long avail_es, const int* alive, float eps,
+                       unsigned rseed, int env0, const int* tg, int tg0, int* act_out, long act_es,
+                       int E, int N, int A, void* stream);
+
 /* ---- optimizer (optim.hip): clip_grad_norm_ + RMSprop / Adam on ONE flat buffer -------------
  * (q_learner.py:42-47,170-173; torch defaults).  g is the un-normalised gradient; den points to
  * sum(mask) on the device (NULL = 1).  sumsq[0] receives sum g^2 (before scaling). */

@@ -169,6 +169,9 @@ SIGNATURES = {
     "marl_qtran_loss": (I, [P, P, P, P, P, P, P, P, P, F, F, F, P, P, P, P, P, P, L, P]),
     "marl_loss_workspace": (SZ, [L]),
     "marl_td_lambda_returns": (I, [P, P, P, P, F, F, P, I, I, P]),
+    "marl_policy_probs": (I, [P, P, F, P, L, I, P]),
+    "marl_policy_loss_bwd": (I, [P, P, P, P, P, P, F, P, P, P, P, L, I, I, P]),
+    "marl_policy_sample": (I, [P, P, L, P, F, U, I, P, I, P, L, I, I, I, P]),
     "marl_grad_sumsq": (I, [P, L, P, P, P]),
     "marl_sumsq_workspace": (SZ, [L]),
     "marl_rmsprop_step": (I, [P, P, P, L, F, F, F, F, P, P, P]),

@@ -23,6 +23,7 @@ class SharedMAC:
     # the head seam: a subclass whose Q values are "the unroll, then a head kernel that adds a term to q" overrides these two
     # attributes, _step_head (serial choose_action) and rollout_head (batched lock-step)
     head_name = None                  # as error texts name the head; None: the whole-rollout kernels may run
+    stochastic = False                # True: training rollouts sample from the policy over the logits (PolicyMAC)
     choose_action_inputs = "agent"    # what the serial rollout hands choose_action: "agent" the agent's own row of obs /
                                       # last action / availability, "avail_all" every agent's availability, "all" all three whole
 
@@ -245,6 +246,39 @@ class SharedMACWithState(SharedMAC):
     def get_next_q_values(self, batch, max_episode_len):
         """reference :340-375 (inputs o_next, u_onehot[t])"""
         return self._world_q_values(batch, max_episode_len, "next")
+
+
+class PolicyMAC(SharedMAC):
+    """The actor of the actor-critic learners (central-V): SharedMAC over the unchanged RNNQNet, whose fc2 output is read as the
+    logits of a stochastic policy (csrc/policy.hip: the softmax mixed with epsilon of the uniform policy over the available
+    actions).  Training rollouts sample from it - ``stochastic`` sends them down the per-step path with ops.policy_sample in the
+    place of ops.select_actions; evaluation is greedy, and the policy's argmax over the available actions is the masked argmax of
+    the logits, so an evaluation rollout is SharedMAC's at epsilon 0, the whole-rollout kernel included."""
+
+    stochastic = True
+
+    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
+        """One agent, one env: pi of the agent's row, then its argmax (``evaluate``) or one np.random.choice draw from it."""
+        dev = self.device()
+        N, O, A = self.n_agents, self.obs_shape, self.n_actions
+        avail = np.asarray(avail_actions, dtype=np.float32).reshape(A)
+        la = -1
+        if self.args.last_action:
+            nz = np.nonzero(np.asarray(last_action))[0]
+            la = int(nz[0]) if nz.size else -1
+        obs_full = torch.zeros(1, 1, N, O, device=dev)
+        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
+        ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
+        ufed[0, 0, agent_num] = la
+        q, h_out = self._agent_step_one(obs_full, ufed)
+        self.hidden_states[0, agent_num] = h_out[agent_num]
+        pi = torch.empty(1, A, device=dev)
+        ops.policy_probs(q[0, 0, agent_num].contiguous().view(1, A), to_dev(avail, dev).view(1, A),
+                         0.0 if evaluate else epsilon, pi, 1, A)
+        pi = pi[0].cpu().numpy().astype(np.float64)
+        if evaluate:
+            return int(np.argmax(pi))
+        return int(np.random.choice(A, p=pi / pi.sum()))
 
 
 class RTWMAC(SharedMAC):

@@ -2,11 +2,13 @@
 // epilogues (after their hypernet GEMMs) and the TD / QTRAN losses.  HBM-bound elementwise work:
 // coalesced over the row axis, reductions by wave shuffles, deterministic two-stage sums.
 #include "common.h"
+#include "sums.h"
 #include "../../include/marl_hip.h"
 
 namespace {
 
 constexpr int TPB = 256;
+static_assert(TPB == SUMS_TPB, "the loss kernels launch sums.h's workgroup size");
 inline int nblk(long n, int cap = 65535 * 16) {
   long b = (n + TPB - 1) / TPB;
   if (b > cap) b = cap;
@@ -461,39 +463,7 @@ inline int qplex_tile_rows(int N, int K, const void* a, const void* b, const voi
   return 0;
 }
 
-// ---- deterministic two-stage sums ------------------------------------------------------------------
-template <int NV>
-__device__ __forceinline__ void block_partials(float (&v)[NV], float* ws) {
-  __shared__ float sh[NV][TPB / 64];
-#pragma unroll
-  for (int i = 0; i < NV; ++i) {
-    const float s = wave_sum(v[i]);
-    if ((threadIdx.x & 63) == 0) sh[i][threadIdx.x >> 6] = s;
-  }
-  __syncthreads();
-  if (threadIdx.x < NV) {
-    float s = 0.f;
-    for (int w = 0; w < TPB / 64; ++w) s += sh[threadIdx.x][w];
-    ws[(long)blockIdx.x * NV + threadIdx.x] = s;
-  }
-}
-
-__global__ void finish_sums_kernel(const float* ws, int nblocks, int nv, float* out) {
-  __shared__ float sh[TPB];
-  for (int i = 0; i < nv; ++i) {
-    float s = 0.f;
-    for (int b = threadIdx.x; b < nblocks; b += TPB) s += ws[(long)b * nv + i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = TPB / 2; o > 0; o >>= 1) {
-      if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out[i] = sh[0];
-    __syncthreads();
-  }
-}
-
+// ---- deterministic two-stage sums: block_partials / finish_sums_kernel (sums.h; TPB = SUMS_TPB = 256)
 __global__ void td_loss_kernel(const float* q_tot, const float* q_tgt, const float* r, const float* term,
                                const float* padded, float gamma, float* dq_tot, float* ws, long rows) {
   float acc[2] = {0.f, 0.f};

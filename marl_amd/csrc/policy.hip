@@ -1,0 +1,252 @@
+// Stochastic policy head of the actor-critic learners (central-V; include/marl_hip.h has the definition).  A row is one agent at one
+// step: logits z (A, the agent's fc2 output), availability a in {0,1}^A, exploration rate eps:
+//   p = softmax(z),  n = sum a,  pt_k = a_k ((1 - eps) p_k + eps / n),  pi_k = pt_k / sum_j pt_j.
+// The kernels shift by mx = the largest AVAILABLE logit (any shift gives the same p): with e_k = exp(min(z_k - mx, 80)),
+// S = sum e, Sa = sum a e, w_k = (1 - eps) e_k + eps S / n and D = (1 - eps) Sa + eps S the policy is pi_k = a_k w_k / D, where
+// Sa >= 1 keeps D away from 0 and the clamp keeps S finite when an unavailable logit towers over the available ones.
+// Gradient of log pi_u by z_i (through pt and the renormalisation; delta_ui - pi_i at eps = 0):
+//   g_i = (1 - eps) [ e_u (delta_ui - e_i / S) / w_u  -  e_i (a_i - Sa / S) / D ].
+//
+// Lane mapping of the two batch kernels (probs, loss_bwd): rows are A consecutive floats (44 bytes at A = 11), so one lane per row
+// against global memory would spend most of every 64-byte request.  A wave stages 64 rows of logits and availability - one
+// contiguous run of 64 A floats each - into LDS with 16-byte coalesced loads, every lane then walks its own row in LDS, writes the
+// result over the logits tile, and the wave stores that tile back as one contiguous run.  The tiles are private to a wave: no
+// workgroup barrier.  The LDS walk is at a lane stride of A dwords: conflict-free for odd A, two-way for A = 14 or 18.  From
+// A = 29 the tiles of four waves pass 56 KiB and the row-per-lane kernel runs instead (same arithmetic in the same order).
+// The sampler runs once per lock-step over E N rows (25 600 at most in the measured set-ups): one lane per row, like select_kernel.
+#include "synth_env.h"
+#include "sums.h"
+#include "../../include/marl_hip.h"
+
+namespace {
+
+constexpr int TPB = SUMS_TPB;
+constexpr int PT_ROWS = 64;          // rows per wave tile
+constexpr int PT_MAX_BLOCKS = 1024;  // one grid pass covers 1024 x 4 x 64 = 262 144 rows (and the loss workspace holds 1024 rows of partials)
+constexpr float EXP_CLAMP = 80.f;
+
+struct RowPolicy { float mx, S, Sa, D, cw, ew; int n; };     // w_k = cw e_k + ew
+
+// the scalars of one row; z, a: the row's A logits / availability flags (LDS or global)
+__device__ __forceinline__ RowPolicy row_policy(const float* z, const float* a, int A, float eps) {
+  RowPolicy p;
+  p.n = 0; p.mx = 0.f;
+  for (int k = 0; k < A; ++k) {
+    if (a[k] == 0.f) continue;
+    const float v = z[k];
+    if (p.n == 0 || v > p.mx) p.mx = v;
+    ++p.n;
+  }
+  p.S = 0.f; p.Sa = 0.f; p.D = 1.f; p.cw = 0.f; p.ew = 0.f;
+  if (p.n == 0) return p;
+  for (int k = 0; k < A; ++k) {
+    const float e = expf(fminf(z[k] - p.mx, EXP_CLAMP));
+    p.S += e;
+    if (a[k] != 0.f) p.Sa += e;
+  }
+  p.cw = 1.f - eps;
+  p.ew = eps * p.S / (float)p.n;
+  p.D = p.cw * p.Sa + eps * p.S;
+  return p;
+}
+__device__ __forceinline__ float row_e(const RowPolicy& p, float z) { return expf(fminf(z - p.mx, EXP_CLAMP)); }
+
+// pi of one row, written over out (out may be z)
+__device__ __forceinline__ void row_probs(const float* z, const float* a, float* out, int A, float eps) {
+  const RowPolicy p = row_policy(z, a, A, eps);
+  const float inv = 1.f / p.D;
+  for (int k = 0; k < A; ++k) out[k] = (p.n > 0 && a[k] != 0.f) ? (p.cw * row_e(p, z[k]) + p.ew) * inv : 0.f;
+}
+
+// scale * d log pi_u / dz written over out (out may be z); returns log pi_u.  A row without a policy (n = 0, or a taken action
+// that is not available) returns `false`: exact zeros and log pi = 0, whatever z holds
+__device__ __forceinline__ bool row_logp_grad(const float* z, const float* a, float* out, int A, float eps, int u, float scale,
+                                              float& logp) {
+  const RowPolicy p = row_policy(z, a, A, eps);
+  logp = 0.f;
+  if (p.n == 0 || u < 0 || u >= A || a[u] == 0.f) {
+    for (int k = 0; k < A; ++k) out[k] = 0.f;
+    return false;
+  }
+  if (p.n == 1) {                      // the one available action: pi = 1 whatever the logits hold, log pi = 0, no gradient
+    for (int k = 0; k < A; ++k) out[k] = 0.f;
+    return true;
+  }
+  const float eu = row_e(p, z[u]);
+  const float wu = p.cw * eu + p.ew;
+  logp = logf(wu) - logf(p.D);
+  const float invS = 1.f / p.S, Pa = p.Sa * invS;
+  const float c1 = p.cw * eu / wu, c2 = p.cw / p.D;
+  for (int k = 0; k < A; ++k) {
+    const float e = row_e(p, z[k]);
+    const float ak = a[k] != 0.f ? 1.f : 0.f;
+    out[k] = scale * (c1 * ((k == u ? 1.f : 0.f) - e * invS) - c2 * e * (ak - Pa));
+  }
+  return true;
+}
+
+struct PolicyArgs {
+  const float *logits, *avail;       // (rows, A)
+  const int* u;                      // (rows)            loss only
+  const float *G, *v, *padded;       // (rows / N)        loss only
+  float eps;
+  float *out, *logp, *ws;            // (rows, A): pi or dlogits; (rows); partial sums
+  long rows;
+  int N, A, vec;
+};
+
+// one row of the loss: m = 1 - padded, Adv = G - v of the row's (episode, step); out = -m Adv d log pi_u / dz
+__device__ __forceinline__ void loss_row(const PolicyArgs& p, long r, const float* z, const float* a, float* out, float (&acc)[2]) {
+  const long bt = r / p.N;
+  const float m = 1.f - p.padded[bt];
+  float adv = 0.f;
+  if (m != 0.f) adv = p.G[bt] - p.v[bt];                 // a padded step's G and v are never looked at
+  float lp = 0.f;
+  if (m == 0.f) {
+    for (int k = 0; k < p.A; ++k) out[k] = 0.f;          // a padded step: exact zeros, its logits are never looked at
+  } else if (row_logp_grad(z, a, out, p.A, p.eps, p.u[r], -m * adv, lp)) {
+    acc[0] += -m * adv * lp;
+  }
+  p.logp[r] = lp;
+  acc[1] += m;
+}
+
+template <bool LOSS>
+__global__ __launch_bounds__(TPB) void policy_tiled_kernel(PolicyArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float pt_smem[];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int A = p.A;
+  const int TS = (PT_ROWS * A + 3) & ~3;                  // floats per tile (16-byte multiple)
+  float* Sz = pt_smem + (size_t)wave * 2 * TS;
+  float* Sa = Sz + TS;
+  float acc[2] = {0.f, 0.f};
+  const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
+  for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
+    const long r0 = tile * PT_ROWS;
+    const int n = (int)((p.rows - r0 < PT_ROWS ? p.rows - r0 : PT_ROWS) * A);
+    // the tile is one contiguous run of n floats: copied as it lies (r0 A 4 is a multiple of 16; the host checked the bases)
+    const float* gz = p.logits + r0 * A;
+    const float* ga = p.avail + r0 * A;
+    float* go = p.out + r0 * A;
+    const int n4 = p.vec ? n >> 2 : 0;
+    for (int e = lane; e < n4; e += 64) {
+      reinterpret_cast<f32x4*>(Sz)[e] = reinterpret_cast<const f32x4*>(gz)[e];
+      reinterpret_cast<f32x4*>(Sa)[e] = reinterpret_cast<const f32x4*>(ga)[e];
+    }
+    for (int e = 4 * n4 + lane; e < n; e += 64) { Sz[e] = gz[e]; Sa[e] = ga[e]; }
+    __builtin_amdgcn_s_waitcnt(0xC07F);                   // this wave's LDS writes (lgkmcnt(0)); no cross-wave sharing
+    __builtin_amdgcn_wave_barrier();
+    const long r = r0 + lane;
+    if (r < p.rows) {
+      if (LOSS) loss_row(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
+      else row_probs(Sz + lane * A, Sa + lane * A, Sz + lane * A, A, p.eps);
+    }
+    __builtin_amdgcn_s_waitcnt(0xC07F);
+    __builtin_amdgcn_wave_barrier();
+    for (int e = lane; e < n4; e += 64) reinterpret_cast<f32x4*>(go)[e] = reinterpret_cast<const f32x4*>(Sz)[e];
+    for (int e = 4 * n4 + lane; e < n; e += 64) go[e] = Sz[e];
+    __builtin_amdgcn_s_waitcnt(0xC07F);                   // the tile is read out before the next trip overwrites it
+    __builtin_amdgcn_wave_barrier();
+  }
+  if (LOSS) block_partials<2>(acc, p.ws);
+}
+
+// row-per-lane form for action counts whose tiles do not fit: same arithmetic in the same order
+template <bool LOSS>
+__global__ __launch_bounds__(TPB) void policy_rows_kernel(PolicyArgs p) {
+  float acc[2] = {0.f, 0.f};
+  for (long r = (long)blockIdx.x * TPB + threadIdx.x; r < p.rows; r += (long)gridDim.x * TPB) {
+    const float* z = p.logits + r * p.A;
+    const float* a = p.avail + r * p.A;
+    float* out = p.out + r * p.A;
+    if (LOSS) loss_row(p, r, z, a, out, acc);
+    else row_probs(z, a, out, p.A, p.eps);
+  }
+  if (LOSS) block_partials<2>(acc, p.ws);
+}
+
+template <bool LOSS>
+int launch_policy(PolicyArgs p, hipStream_t s, int& nb) {
+  const size_t lds = (size_t)4 * 2 * ((PT_ROWS * p.A + 3) & ~3) * sizeof(float);
+  if (lds <= 56 * 1024) {            // (block_partials keeps a few floats of its own)
+    const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
+    long b = (tiles + 3) / 4;
+    nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
+    p.vec = ((reinterpret_cast<uintptr_t>(p.logits) | reinterpret_cast<uintptr_t>(p.avail) | reinterpret_cast<uintptr_t>(p.out)) & 15) == 0;
+    hipLaunchKernelGGL(policy_tiled_kernel<LOSS>, dim3((unsigned)nb), dim3(TPB), lds, s, p);
+  } else {
+    long b = (p.rows + TPB - 1) / TPB;
+    nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
+    hipLaunchKernelGGL(policy_rows_kernel<LOSS>, dim3((unsigned)nb), dim3(TPB), 0, s, p);
+  }
+  MARL_CHECK_LAUNCH();
+  return 0;
+}
+
+// marl_select_actions' argument shape; the draw is the ST_SAMPLE stream's
+__global__ void policy_sample_kernel(const float* logits, const float* avail, long avail_es, const int* alive, float eps,
+                                     unsigned rseed, int env0, const int* tg, int tg0, int* act_out, long act_es, int E,
+                                     int N, int A) {
+  const long total = (long)E * N;
+  for (long i = (long)blockIdx.x * TPB + threadIdx.x; i < total; i += (long)gridDim.x * TPB) {
+    const int e = (int)(i / N), n = (int)(i - (long)e * N);
+    int* out = act_out + e * act_es + n;
+    if (alive && !alive[e]) { *out = -1; continue; }
+    const float* z = logits + i * A;
+    const float* av = avail + e * avail_es + (long)n * A;
+    const RowPolicy p = row_policy(z, av, A, eps);
+    const unsigned tgl = (unsigned)(tg ? tg[e] : tg0);
+    const float u = u01(hkey(rseed, ST_SAMPLE, (unsigned)(env0 + e), tgl, (unsigned)n));
+    const float inv = 1.f / p.D;
+    int arg = -1, last = 0;          // no action available: cannot happen for a live agent; action 0, as select_kernel
+    float cum = 0.f;
+    for (int k = 0; k < A; ++k) {
+      if (av[k] == 0.f) continue;
+      last = k;
+      cum += (p.cw * row_e(p, z[k]) + p.ew) * inv;
+      if (cum > u) { arg = k; break; }
+    }
+    *out = arg >= 0 ? arg : last;    // rounding left the running sum at or below u: the last available action
+  }
+}
+
+}  // namespace
+
+extern "C" int marl_policy_sample(const float* logits, const float* avail, long avail_es, const int* alive, float eps,
+                                  unsigned rseed, int env0, const int* tg, int tg0, int* act_out, long act_es, int E, int N,
+                                  int A, void* stream) {
+  const long total = (long)E * N;
+  if (total <= 0 || A <= 0) return 0;
+  if (!logits || !avail || !act_out) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(policy_sample_kernel, dim3((unsigned)((total + TPB - 1) / TPB)), dim3(TPB), 0, (hipStream_t)stream, logits,
+                     avail, avail_es, alive, eps, rseed, env0, tg, tg0, act_out, act_es, E, N, A);
+  MARL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int marl_policy_probs(const float* logits, const float* avail, float eps, float* pi, long rows, int A, void* stream) {
+  if (rows <= 0 || A <= 0) return 0;
+  if (!logits || !avail || !pi || pi == avail) return (int)hipErrorInvalidValue;
+  PolicyArgs p = {};
+  p.logits = logits; p.avail = avail; p.eps = eps; p.out = pi; p.rows = rows; p.N = 1; p.A = A;
+  int nb;
+  return launch_policy<false>(p, (hipStream_t)stream, nb);
+}
+
+extern "C" int marl_policy_loss_bwd(const float* logits, const float* avail, const int* u, const float* G, const float* v,
+                                    const float* padded, float eps, float* dlogits, float* logp, float* out2, float* ws,
+                                    long rows, int N, int A, void* stream) {
+  if (rows <= 0 || A <= 0) return 0;
+  if (!logits || !avail || !u || !G || !v || !padded || !dlogits || !logp || !out2 || !ws || N <= 0 || rows % N != 0 ||
+      dlogits == avail)
+    return (int)hipErrorInvalidValue;
+  PolicyArgs p = {};
+  p.logits = logits; p.avail = avail; p.u = u; p.G = G; p.v = v; p.padded = padded; p.eps = eps;
+  p.out = dlogits; p.logp = logp; p.ws = ws; p.rows = rows; p.N = N; p.A = A;
+  int nb;
+  const int rc = launch_policy<true>(p, (hipStream_t)stream, nb);
+  if (rc) return rc;
+  hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, (const float*)ws, nb, 2, out2);
+  MARL_CHECK_LAUNCH();
+  return 0;
+}

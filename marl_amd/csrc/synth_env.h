@@ -7,7 +7,9 @@
 #pragma once
 #include "common.h"
 
-enum { ST_OBS = 0, ST_STATE, ST_AVAIL, ST_REWARD, ST_LEN, ST_WON, ST_EXPLORE, ST_PICK };
+// (ST_SAMPLE: the draws of the stochastic policy, policy.hip.  Its number is also the MAIC latent noise's, maic_head.hip: the two
+// never meet, a policy controller has no head)
+enum { ST_OBS = 0, ST_STATE, ST_AVAIL, ST_REWARD, ST_LEN, ST_WON, ST_EXPLORE, ST_PICK, ST_SAMPLE };
 
 __host__ __device__ inline unsigned mix32(unsigned x) {
   x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;

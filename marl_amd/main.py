@@ -2,6 +2,7 @@
 
     python -m marl_amd.main --alg qmix --map 2s3z --n_envs 1024 --n_steps 500000
     python -m marl_amd.main --env matrix --alg qplex --n_envs 32 --n_steps 20000
+    python -m marl_amd.main --map 2s3z --alg central_v --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --MAIC True --load_model True --evaluate True --evaluate_epoch 1 --n_envs 64
 
 ``--env synthetic`` (default) uses the synthetic SMAC-shaped device env with the dims of ``--map``;
@@ -10,7 +11,7 @@ from __future__ import annotations
 
 import sys
 
-from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args
+from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .runner import Runner
@@ -22,6 +23,11 @@ MAPS = {"2s3z": (5, 80, 120, 11, 120), "3s5z": (8, 128, 216, 14, 150), "MMM2": (
 def build(argv=None):
     args = get_common_args(argv)
     get_mixer_args(args)
+    if args.alg == 'central_v':
+        given = args.td_lambda
+        get_centralv_args(args)
+        if given is not None:           # the table's 0.8 is the default, not an override of --td_lambda
+            args.td_lambda = given
     get_RTW_args(args)
     get_maic_args(args)
     if args.env == 'smac':

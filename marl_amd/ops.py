@@ -396,6 +396,35 @@ def td_lambda_returns(q_next_tot, r, term, padded, gamma, lam, out, B, T):
     return out
 
 
+def policy_probs(logits, avail, eps, pi, rows, A):
+    """pi (rows, A) of the stochastic policy (csrc/policy.hip): softmax of the logits, mixed with eps of the uniform policy over the
+    available actions, renormalised over them; a row without an available action is all zeros"""
+    for t in (logits, avail, pi):
+        assert _f32(t).is_contiguous() and t.numel() >= rows * A
+    check(_lib.load().marl_policy_probs(_p(logits), _p(avail), float(eps), _p(pi), rows, A, _stream()), "marl_policy_probs")
+    return pi
+
+
+def policy_loss_bwd(logits, avail, u, G, v, padded, eps, dlogits, logp, out2, rows, N, A):
+    """The actor loss of rows = B*T*N agent steps: logp (rows), out2 = {- sum m (G - v) logp, N sum m} and dlogits (rows, A), the
+    un-normalised gradient of out2[0] by the logits - the dense dq of agent_unroll_bwd."""
+    lib = _lib.load()
+    for t, n in ((logits, rows * A), (avail, rows * A), (dlogits, rows * A), (logp, rows), (G, rows // N), (v, rows // N),
+                 (padded, rows // N)):
+        assert _f32(t).is_contiguous() and t.numel() >= n
+    assert _i32(u).is_contiguous() and u.numel() >= rows and out2.numel() >= 2
+    ws = WS.get("loss", lib.marl_loss_workspace(rows), logits.device)
+    check(lib.marl_policy_loss_bwd(_p(logits), _p(avail), _p(u), _p(G), _p(v), _p(padded), float(eps), _p(dlogits), _p(logp),
+                                   _p(_f32(out2)), _p(ws), rows, N, A, _stream()), "marl_policy_loss_bwd")
+
+
+def policy_sample(logits, avail, avail_es, alive, eps, rseed, env0, tg, tg0, act_out, act_es, E, N, A):
+    """select_actions' arguments; draws every live agent's action from the stochastic policy"""
+    check(_lib.load().marl_policy_sample(_p(_f32(logits)), _p(_f32(avail)), avail_es, _p(alive), float(eps),
+                                         int(rseed) & 0xFFFFFFFF, env0, _p(tg), tg0, _p(_i32(act_out)), act_es,
+                                         E, N, A, _stream()), "marl_policy_sample")
+
+
 def grad_sumsq(g, n, out1):
     lib = _lib.load()
     ws = WS.get("sumsq", lib.marl_sumsq_workspace(n), g.device)

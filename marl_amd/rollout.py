@@ -9,6 +9,8 @@
   With an RTW controller (RTWMAC) the reflection head (csrc/rtw_head.hip, act mode) runs between the agent step and the
   selection; such rollouts always take this per-step path (the whole-rollout kernels have no head).  The world-model head
   (SharedMACWithState) and the MAIC message head (MAICMAC, csrc/maic_head.hip; test mode = ``evaluate``) run at the same place.
+  With a stochastic controller (PolicyMAC) a TRAINING rollout takes this per-step path too, unfused, and draws its actions with
+  ops.policy_sample (csrc/policy.hip; the ST_SAMPLE stream keyed by (rseed, env, global step, agent)); evaluation is untouched.
   MAIC's sampled latents (training rollouts) take their noise from the counter hash keyed by (rseed, env, global step, agent,
   column) through a Box-Muller transform (ops.maic_noise), so a rollout is a pure function of its seeds.
 """
@@ -157,7 +159,10 @@ class RolloutWorker:
         if a.replay_dir != '' and evaluate:
             env.close()
         mode = getattr(self, "rollout_mode", "whole")      # "whole" | "fused_step" | "unfused" (tests)
-        if mode == "whole" and mac.head_name is None and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
+        # a stochastic controller (PolicyMAC) samples its training actions: the per-step path with ops.policy_sample, unfused
+        sample = mac.stochastic and not evaluate
+        if mode == "whole" and mac.head_name is None and not sample and hasattr(env, "whole_rollout") \
+                and env.supports_whole_rollout():
             # the persistent kernel writes every field of the record, so training rollouts can be
             # played straight into the replay ring (record_sink = the ReplayBuffer; zero-copy store)
             sink = getattr(self, "record_sink", None)
@@ -181,7 +186,8 @@ class RolloutWorker:
         if a.epsilon_anneal_scale == 'episode':
             epsilon = epsilon - self.anneal_epsilon if epsilon > self.min_epsilon else epsilon
         w = mac.agent.weights()
-        fused = hasattr(env, "fused_step") and mode != "unfused"
+        fused = hasattr(env, "fused_step") and mode != "unfused" and not sample
+        select = ops.policy_sample if sample else ops.select_actions
         env.observe(0, rec)
         for t in range(T):
             # agent step = the unroll kernel with T=1 reading slot t of the record in place
@@ -191,8 +197,8 @@ class RolloutWorker:
             if fused:
                 env.fused_step(t, q, epsilon, self.rseed, rec)
             else:
-                ops.select_actions(q, rec.avail[:, t], (T + 1) * N * A, alive, epsilon, self.rseed, env.env0, None,
-                                   env.global_step(t), act, N, E, N, A)
+                select(q, rec.avail[:, t], (T + 1) * N * A, alive, epsilon, self.rseed, env.env0, None,
+                       env.global_step(t), act, N, E, N, A)
                 env.step(t, act, rec, alive)
                 env.observe(t + 1, rec)
             if a.epsilon_anneal_scale == 'step':
@@ -247,6 +253,9 @@ class RolloutWorker:
         if mac.head_name is not None:
             raise RuntimeError("launch_episodes runs the whole-rollout kernel, which has no %s head: use generate_episodes"
                                % mac.head_name)
+        if mac.stochastic:
+            raise RuntimeError("launch_episodes runs the whole-rollout kernel, which does not sample from a stochastic policy: "
+                               "use generate_episodes")
         if not (getattr(env, "batched", False) and hasattr(env, "whole_rollout") and env.supports_whole_rollout()):
             raise RuntimeError("launch_episodes needs a batched env with the whole-rollout kernel")
         dev = require_cuda("RolloutWorker")

@@ -29,6 +29,11 @@ head's backward pass and, with ``args.mi_loss_weight`` / ``args.entropy_loss_wei
 attention-entropy losses (csrc/maic_aux.hip); the refusals above hold for it too.  Without MAIC it raises ValueError before
 anything is built, and so does a positive loss weight without MAIC_train.
 
+``args.alg == 'central_v'``: PolicyMAC and CentralVLearner (algorithm/central_v.py), trained ON-POLICY: the episodes a rollout just
+generated are the batch of the one update that follows it - nothing goes through the replay buffer - and the learner is told the
+exploration rate they were drawn at.  With RTW / world_model / MAIC it raises ValueError, with overlapped rollouts
+NotImplementedError (an on-policy update needs the weights the last one wrote) - before anything is built.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -41,7 +46,7 @@ import numpy as np
 import torch
 
 from .rollout import RolloutWorker
-from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC, MAICMAC
+from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC, MAICMAC, PolicyMAC
 from .common.replaybuffer import ReplayBuffer
 from .algorithm.q_learner import QLearner
 from .algorithm.qtran_learner import QTRANLearner
@@ -49,6 +54,7 @@ from .algorithm.rtw_q_learner import RTWQLearner
 from .algorithm.q_learner_state import QLearnerWithState
 from .algorithm.maic_q_learner import MAICQLearner
 from .algorithm.maic_td_learner import MAICTDLearner
+from .algorithm.central_v import CentralVLearner
 from .utils.logging import Logger
 
 
@@ -94,6 +100,13 @@ class Runner:
             raise ValueError("mi_loss_weight / entropy_loss_weight are terms of MAICTDLearner's loss: they need MAIC_train")
         mac_cls, make_learner = SharedMAC, lambda mac, logger, args: QLearner(mac, args)
         on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
+        self.on_policy = args.alg == 'central_v'
+        if self.on_policy:
+            if on:
+                raise ValueError("central_v trains the plain shared agent as a policy: not with %s" % on[0].name)
+            if getattr(args, "overlap_rollout", False):
+                raise NotImplementedError("central_v is on-policy: a rollout needs the weights the last update wrote")
+            mac_cls = PolicyMAC
         for sw in on:
             for hit, refusal in ((sw is not on[0], sw.combined), (sw.alg_refused(args), sw.alg),
                                  (getattr(args, "overlap_rollout", False), sw.overlap)):
@@ -105,7 +118,7 @@ class Runner:
             get_maic_args(args)
         self.mac = mac_cls(args)
         self.rolloutWorker = RolloutWorker(env, self.mac, args)
-        self.buffer = ReplayBuffer(args)
+        self.buffer = None if self.on_policy else ReplayBuffer(args)
         self.rolloutWorker.record_sink = self.buffer   # batched rollouts write into the replay ring in place
         self.args = args
         self.eval_win_rates = []
@@ -117,7 +130,9 @@ class Runner:
         os.makedirs(self.save_path, exist_ok=True)
         logger.setup_tb(self.save_path + '/tb/other')
         self.logger = logger
-        if _value_mixer(args):
+        if self.on_policy:
+            self.learner = CentralVLearner(self.mac, args)
+        elif _value_mixer(args):
             self.learner = make_learner(self.mac, logger, args)
         elif _qtran(args):
             self.learner = QTRANLearner(self.mac, args)
@@ -187,10 +202,15 @@ class Runner:
             self.logger.log_stat("episode_length", steps, self.time_steps)
             self.logger.log_stat("train_win_rate", sum(win_tags) / n_ep, self.time_steps)
             self.logger.log_stat("train_episode_reward", sum(rewards) / n_ep, self.time_steps)
-            self.buffer.store_episode(episodes)
+            if self.on_policy:                                   # one update on the episodes just generated
+                loss = self.learner.train(episodes, self.train_steps, epsilon=self.rolloutWorker.epsilon)
+                self.losses.append(loss)
+                self.train_steps += 1
+            else:
+                self.buffer.store_episode(episodes)
             if self.overlap:
                 pending, in_flight = self._launch_rollout()      # rollout k+1 flies while update k trains below
-            for _ in range(a.train_steps):
+            for _ in range(0 if self.on_policy else a.train_steps):
                 mini_batch = self.buffer.sample(min(self.buffer.current_size, a.batch_size), exclude=in_flight)
                 loss = self.learner.train(mini_batch, self.train_steps)
                 self.losses.append(loss)

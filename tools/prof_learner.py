@@ -26,7 +26,9 @@ def main():
     ap.add_argument("--gemm-mode", default="f32", choices=["f32", "bf16x6"])
     ap.add_argument("--td-lambda", type=float, default=None, help="args.td_lambda: TD(lambda) returns as the targets")
     o = ap.parse_args()
-    from marl_amd.controller.share_params import SharedMAC
+    from marl_amd.controller.share_params import SharedMAC, PolicyMAC
+    from marl_amd.algorithm.central_v import CentralVLearner
+    from marl_amd.common.arguments import get_centralv_args
     from marl_amd.algorithm.q_learner import QLearner
     from marl_amd.algorithm.qtran_learner import QTRANLearner
     from marl_amd.rollout import RolloutWorker
@@ -37,23 +39,31 @@ def main():
     if o.td_lambda is not None:
         args.td_lambda = o.td_lambda
     torch.manual_seed(0)
-    mac = SharedMAC(args)
-    learner = QTRANLearner(mac, args) if o.alg.startswith("qtran") else QLearner(mac, args)
+    if o.alg == "central_v":
+        get_centralv_args(args)          # (after --td-lambda's slot: the table sets 0.8)
+        if o.td_lambda is not None:
+            args.td_lambda = o.td_lambda
+        mac = PolicyMAC(args)
+        learner = CentralVLearner(mac, args)
+    else:
+        mac = SharedMAC(args)
+        learner = QTRANLearner(mac, args) if o.alg.startswith("qtran") else QLearner(mac, args)
     env = SyntheticSMACEnv(o.envs, args.n_agents, args.obs_shape, args.state_shape, args.n_actions, args.episode_limit,
                            seed=1, fixed_length=True)
     w = RolloutWorker(env, mac, args)
     ep, _, _, _ = w.generate_episodes(o.envs)
     for _ in range(o.rollouts):
         w.generate_episodes(o.envs)
+    train = (lambda ep, i: learner.train(ep, i, epsilon=w.epsilon)) if o.alg == "central_v" else learner.train
     for i in range(o.warmup):
-        learner.train(ep, i)
+        train(ep, i)
     import gc
     gc.collect()
     gc.disable()            # a generation-2 collection costs 35-60 ms here - several updates (as bench.py / timeit do)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(o.updates):
-        learner.train(ep, i)
+        train(ep, i)
     torch.cuda.synchronize()
     print("updates/s %.2f" % (o.updates / (time.perf_counter() - t0)))
 
