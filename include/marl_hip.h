@@ -469,7 +469,7 @@ size_t marl_loss_workspace(long rows);
 int marl_td_lambda_returns(const float* q_next_tot, const float* r, const float* term, const float* padded,
                            float gamma, float lambda, float* ret, int B, int T, void* stream);
 
-/* ---- stochastic policy of the actor-critic learners (policy.hip; central-V) ---------------------
+/* ---- stochastic policy of the policy-gradient learners (policy.hip; central-V, REINFORCE) --------
  * A row is one agent at one step: logits z (A floats, the agent's fc2 output), availability a in {0,1}^A, exploration rate eps:
  *   p = softmax(z) over all A actions,  n = sum_k a_k,  pt_k = a_k ((1 - eps) p_k + eps / n),  pi_k = pt_k / sum_j pt_j.
  * A row with n = 0 (a padded step) has no policy: it contributes nothing to any sum, its outputs are exact zeros and its logits are
@@ -485,6 +485,24 @@ int marl_td_lambda_returns(const float* q_next_tot, const float* r, const float*
  *   (at eps = 0: - m Adv (delta_uk - pi_k)); the dense dq of marl_agent_unroll_bwd.
  * G, v, padded: (rows / N); ws: marl_loss_workspace() bytes; dlogits may be logits itself, not avail.
  *
+ * marl_policy_loss_bwd_ex: the same pass without a baseline and with an entropy bonus beta >= 0 (REINFORCE; central-V with
+ * --policy_entropy_coef).  v may be NULL: Adv = G.  A row "has a policy" when n > 0 and its taken action is available.  With a the
+ * row's availability flags, the entropy of the policy the action was drawn from (eps mixing included, as in log pi) is
+ *   H_r = - sum_{k: a_k = 1} pi_k log pi_k,  a term with pi_k = 0 being 0 (at eps = 0 the fp32 exponent underflows once a logit sits
+ *   about 104 below the largest available one: 0 log 0 is 0, not NaN);  H = 0 and no entropy gradient on a row with n = 1;
+ * a row without a policy, or with m = 0, contributes nothing to any sum, its dlogits are exact zeros, its logits are never looked at.
+ *   L = [ - sum_r m Adv logp[r] - beta sum_r m H_r ] / (N sum m)      (REINFORCE: Adv = G, the discounted Monte-Carlo return -
+ *       marl_td_lambda_returns with lambda = 1 and an all-zero q_next_tot: an episode cut at max_episode_len gets no bootstrap),
+ *   out3 = { - sum m Adv logp - beta sum m H,  sum_r m,  sum_r m H }  (un-normalised),
+ *   ent[r] = H_r (0 where the row has no policy or m = 0); ent may be NULL,
+ *   dlogits = - m Adv d log pi(u) / dz - beta m dH / dz.  With the kernel's e_k = exp(z_k - mx), S = sum e, Sa = sum a e,
+ *   D = (1 - eps) Sa + eps S, c2 = (1 - eps) / D, Pa = Sa / S, L1 = sum_k a_k e_k log pi_k and Hn = sum_k pi_k log pi_k:
+ *     dH/dz_i = - c2 (a_i e_i log pi_i - e_i L1 / S) + c2 e_i (a_i - Pa) Hn    (at eps = 0: - pi_i (log pi_i + H) on available
+ *     actions, exactly 0 on unavailable ones).
+ * The entropy is folded into the same pass over the staged rows: no bytes moved beyond ent.  beta = 0 with v given returns
+ * marl_policy_loss_bwd's dlogits, logp and first two statistics bit for bit.  ws: marl_loss_workspace() bytes (three partials
+ * per workgroup); beta < 0 is an error.
+ *
  * marl_policy_sample: one action per live agent of a lock-step, the argument shape of marl_select_actions.  With
  * x = u01(hash(rseed, SAMPLE, env0 + e, tg, n)) the action is the first k in index order with a_k = 1 whose running fp32 sum of
  * pi over the available actions up to k exceeds x; the last available action when rounding leaves none.  Environments with
@@ -493,6 +511,9 @@ int marl_policy_probs(const float* logits, const float* avail, float eps, float*
 int marl_policy_loss_bwd(const float* logits, const float* avail, const int* u, const float* G, const float* v,
                          const float* padded, float eps, float* dlogits, float* logp, float* out2, float* ws, long rows,
                          int N, int A, void* stream);
+int marl_policy_loss_bwd_ex(const float* logits, const float* avail, const int* u, const float* G, const float* v,
+                            const float* padded, float eps, float beta, float* dlogits, float* logp, float* ent, float* out3,
+                            float* ws, long rows, int N, int A, void* stream);
 int marl_policy_sample(const float* logits, const float* avail, long avail_es, const int* alive, float eps,
                        unsigned rseed, int env0, const int* tg, int tg0, int* act_out, long act_es,
                        int E, int N, int A, void* stream);

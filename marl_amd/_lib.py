@@ -171,6 +171,7 @@ SIGNATURES = {
     "marl_td_lambda_returns": (I, [P, P, P, P, F, F, P, I, I, P]),
     "marl_policy_probs": (I, [P, P, F, P, L, I, P]),
     "marl_policy_loss_bwd": (I, [P, P, P, P, P, P, F, P, P, P, P, L, I, I, P]),
+    "marl_policy_loss_bwd_ex": (I, [P, P, P, P, P, P, F, F, P, P, P, P, P, L, I, I, P]),
     "marl_policy_sample": (I, [P, P, L, P, F, U, I, P, I, P, L, I, I, I, P]),
     "marl_grad_sumsq": (I, [P, L, P, P, P]),
     "marl_sumsq_workspace": (SZ, [L]),

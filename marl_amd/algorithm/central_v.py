@@ -6,7 +6,11 @@ V(s) = Linear(S, critic_dim) - ReLU - Linear(critic_dim, critic_dim) - ReLU - Li
 m = 1 - padded, M = sum m and G the lambda-returns of V_target(s_next) (csrc/td_lambda.hip; a constant of the gradient):
 
     L_critic = sum m (G - V(s))^2 / M          Adv = G - V(s)  (the same forward pass, a constant of the gradient)
-    L_actor  = - sum m Adv log pi(u) / (N M)
+    L_actor  = [ - sum m Adv log pi(u) - beta sum m H ] / (N M)
+
+beta = ``args.policy_entropy_coef`` >= 0 (default 0) weighs the entropy H of the policy each action was drawn from (algorithm/
+reinforce.py has the definition).  With 0 the actor pass is ops.policy_loss_bwd, exactly as before the bonus existed; a positive
+value runs ops.policy_loss_bwd_ex with v and leaves the mean entropy per live agent step in ``self.entropy``.
 
 One update pass: the eval unroll with saved planes, the critic on s, the target critic on s_next, td_lambda_returns, td_loss on
 (V, G) - the ``_td_inputs`` idiom: G as r, gamma = 0 -, the critic backward, policy_loss_bwd, BPTT on its dense gradient.  Two
@@ -24,6 +28,7 @@ import torch.nn as nn
 
 from .. import ops
 from ..hostutil import flatten_module, lin_of, require_cuda
+from .reinforce import entropy_coef_of
 from .common import (LearnerParams, FlatView, FusedOptimizer, Learner, LossReadback, GradReducer, Scratch, agent_backward,
                      td_lambda_of)
 
@@ -51,6 +56,7 @@ class CentralVLearner(Learner):
         if GradReducer().enabled:
             raise NotImplementedError("CentralVLearner trains on one rank: its two gradient buffers have no all-reduce")
         self.td_lambda = td_lambda_of(args)          # raises before anything is built
+        self.beta = entropy_coef_of(args)            # (so does a negative weight)
         if not getattr(mac, "stochastic", False):
             raise ValueError("CentralVLearner needs a stochastic controller (PolicyMAC)")
         self.args = args
@@ -68,11 +74,11 @@ class CentralVLearner(Learner):
         self.critic_optimizer = FusedOptimizer(self._cflat, args.optimizer, args.lr_critic, args.grad_norm_clip)
         self._buf = Scratch()
         self.reducer = GradReducer()
-        self.loss_readback, self.actor_readback = LossReadback(args), LossReadback(args)
+        self.loss_readback, self.actor_readback, self.entropy_readback = LossReadback(args), LossReadback(args), LossReadback(args)
         self.graphs = None
         self.needs_avail = True                      # the policy is over the current step's available actions
         self.last_stats = self.actor_stats = None
-        self.actor_loss = float("nan")
+        self.actor_loss = self.entropy = float("nan")
         self._td_dbg, self._dbg = {}, {}
 
     def sync_replicas(self):
@@ -141,10 +147,15 @@ class CentralVLearner(Learner):
         # 7. - 8. the actor: Adv = G - V is formed inside the loss kernel; its dense gradient on the logits goes to BPTT (the fp32
         # kernel in either gemm mode: the split BPTT takes sparse gradients only)
         dlogits, logp = g("dlogits", (B, T, N, A)), g("logp", (R,))
-        ops.policy_loss_bwd(logits, db.avail, db.u_act.reshape(-1), G, v.view(BT), db.padded, self.epsilon, dlogits, logp,
-                            self._flat.stats[:2], R, N, A)
-        agent_backward(self.eval_net, db, "cur", saved, None, dlogits, None, self._buf)
         self._dbg = dict(logits=logits, v=v.view(BT), v_next=v_next.view(BT), td_targets=G, logp=logp, dlogits=dlogits)
+        if self.beta == 0.0:
+            ops.policy_loss_bwd(logits, db.avail, db.u_act.reshape(-1), G, v.view(BT), db.padded, self.epsilon, dlogits, logp,
+                                self._flat.stats[:2], R, N, A)
+        else:                                        # the entropy bonus, folded into the same pass: stats = {numerator, N M, sum m H}
+            ent = self._dbg["ent"] = g("ent", (R,))
+            ops.policy_loss_bwd_ex(logits, db.avail, db.u_act.reshape(-1), G, v.view(BT), db.padded, self.epsilon, self.beta,
+                                   dlogits, logp, ent, self._flat.stats[:3], R, N, A)
+        agent_backward(self.eval_net, db, "cur", saved, None, dlogits, None, self._buf)
 
     def train(self, batch, train_step, epsilon=0.0):
         """One update on the episodes just generated; ``epsilon``: the exploration rate their actions were drawn at.  Returns the
@@ -160,6 +171,8 @@ class CentralVLearner(Learner):
             self._update_targets()
         self.last_stats, self.actor_stats = cs, st
         self.actor_loss = self.actor_readback.read(st[:2], self._loss_fn())
+        if self.beta != 0.0:
+            self.entropy = self.entropy_readback.read(st[:3], lambda s: s[2] / s[1])
         return self.loss_readback.read(cs[:2], self._loss_fn())
 
     def get_q_and_q_tot_table(self):

@@ -1,4 +1,4 @@
-// Stochastic policy head of the actor-critic learners (central-V; include/marl_hip.h has the definition).  A row is one agent at one
+// Stochastic policy head of the policy-gradient learners (central-V, REINFORCE; include/marl_hip.h has the definition).  A row is one agent at one
 // step: logits z (A, the agent's fc2 output), availability a in {0,1}^A, exploration rate eps:
 //   p = softmax(z),  n = sum a,  pt_k = a_k ((1 - eps) p_k + eps / n),  pi_k = pt_k / sum_j pt_j.
 // The kernels shift by mx = the largest AVAILABLE logit (any shift gives the same p): with e_k = exp(min(z_k - mx, 80)),
@@ -58,11 +58,27 @@ __device__ __forceinline__ void row_probs(const float* z, const float* a, float*
   for (int k = 0; k < A; ++k) out[k] = (p.n > 0 && a[k] != 0.f) ? (p.cw * row_e(p, z[k]) + p.ew) * inv : 0.f;
 }
 
+// { L1, Hn } = { sum a_k e_k log pi_k, sum pi_k log pi_k } of a row with a policy; a term whose pi_k = 0 is 0
+__device__ __forceinline__ float2 row_ent_sums(const RowPolicy& p, const float* z, const float* a, int A) {
+  const float logD = logf(p.D), invD = 1.f / p.D;
+  float L1 = 0.f, Hn = 0.f;
+  for (int k = 0; k < A; ++k) {
+    if (a[k] == 0.f) continue;
+    const float e = row_e(p, z[k]);
+    const float w = p.cw * e + p.ew;
+    if (w > 0.f) {
+      const float lp = logf(w) - logD;
+      L1 += e * lp;
+      Hn += w * invD * lp;
+    }
+  }
+  return make_float2(L1, Hn);
+}
+
 // scale * d log pi_u / dz written over out (out may be z); returns log pi_u.  A row without a policy (n = 0, or a taken action
 // that is not available) returns `false`: exact zeros and log pi = 0, whatever z holds
-__device__ __forceinline__ bool row_logp_grad(const float* z, const float* a, float* out, int A, float eps, int u, float scale,
-                                              float& logp) {
-  const RowPolicy p = row_policy(z, a, A, eps);
+__device__ __forceinline__ bool row_logp_grad_of(const RowPolicy& p, const float* z, const float* a, float* out, int A, int u,
+                                                 float scale, float& logp) {
   logp = 0.f;
   if (p.n == 0 || u < 0 || u >= A || a[u] == 0.f) {
     for (int k = 0; k < A; ++k) out[k] = 0.f;
@@ -84,13 +100,52 @@ __device__ __forceinline__ bool row_logp_grad(const float* z, const float* a, fl
   }
   return true;
 }
+__device__ __forceinline__ bool row_logp_grad(const float* z, const float* a, float* out, int A, float eps, int u, float scale,
+                                              float& logp) {
+  return row_logp_grad_of(row_policy(z, a, A, eps), z, a, out, A, u, scale, logp);
+}
+
+// row_logp_grad with the entropy H = - sum_{a_k = 1} pi_k log pi_k of the row's policy (0 log 0 = 0: w_k underflows to 0 at
+// eps = 0 once z_k sits about 104 below mx) and, for hs != 0, out = scale d log pi_u / dz - hs dH / dz.  With
+// L1 = sum a_k e_k log pi_k and Hn = sum pi_k log pi_k = -H (one walk, before out - which may be z - is written):
+//   dH/dz_i = -c2 (a_i e_i log pi_i - e_i L1 / S) + c2 e_i (a_i - Pa) Hn          (the second walk; -pi_i (log pi_i + H) at eps = 0).
+// hs = 0 takes row_logp_grad's own walk: the same bits.  A row with n = 1 has H = 0 and no gradient
+__device__ __forceinline__ bool row_logp_ent_grad(const float* z, const float* a, float* out, int A, float eps, int u, float scale,
+                                                  float hs, float& logp, float& H) {
+  const RowPolicy p = row_policy(z, a, A, eps);
+  H = 0.f;
+  const bool spread = p.n > 1 && u >= 0 && u < A && a[u] != 0.f;      // a policy over more than one action
+  if (!spread || hs == 0.f) {
+    if (spread) H = -row_ent_sums(p, z, a, A).y;
+    return row_logp_grad_of(p, z, a, out, A, u, scale, logp);
+  }
+  const float2 s = row_ent_sums(p, z, a, A);
+  const float L1 = s.x, Hn = s.y;
+  H = -Hn;
+  const float eu = row_e(p, z[u]);
+  const float wu = p.cw * eu + p.ew;
+  const float logD = logf(p.D);
+  logp = logf(wu) - logD;
+  const float invS = 1.f / p.S, Pa = p.Sa * invS;
+  const float c1 = p.cw * eu / wu, c2 = p.cw / p.D;
+  const float L1S = L1 * invS;
+  for (int k = 0; k < A; ++k) {
+    const float e = row_e(p, z[k]);
+    const float ak = a[k] != 0.f ? 1.f : 0.f;
+    const float w = p.cw * e + p.ew;
+    const float elp = (ak != 0.f && w > 0.f) ? e * (logf(w) - logD) : 0.f;
+    const float dH = c2 * (e * (ak - Pa) * Hn - (elp - e * L1S));
+    out[k] = scale * (c1 * ((k == u ? 1.f : 0.f) - e * invS) - c2 * e * (ak - Pa)) - hs * dH;
+  }
+  return true;
+}
 
 struct PolicyArgs {
   const float *logits, *avail;       // (rows, A)
   const int* u;                      // (rows)            loss only
   const float *G, *v, *padded;       // (rows / N)        loss only
-  float eps;
-  float *out, *logp, *ws;            // (rows, A): pi or dlogits; (rows); partial sums
+  float eps, beta;                   // beta: weight of the entropy bonus (loss_bwd_ex)
+  float *out, *logp, *ent, *ws;      // (rows, A): pi or dlogits; (rows); (rows) or NULL (loss_bwd_ex); partial sums
   long rows;
   int N, A, vec;
 };
@@ -111,7 +166,28 @@ __device__ __forceinline__ void loss_row(const PolicyArgs& p, long r, const floa
   acc[1] += m;
 }
 
-template <bool LOSS>
+// loss_row without a baseline (v NULL: Adv = G) and with the entropy bonus: out = -m Adv d log pi_u / dz - beta m dH / dz,
+// acc = { -m Adv log pi_u - beta m H, m, m H }
+__device__ __forceinline__ void loss_row_ex(const PolicyArgs& p, long r, const float* z, const float* a, float* out, float (&acc)[3]) {
+  const long bt = r / p.N;
+  const float m = 1.f - p.padded[bt];
+  float adv = 0.f;
+  if (m != 0.f) adv = p.v ? p.G[bt] - p.v[bt] : p.G[bt];
+  float lp = 0.f, H = 0.f;
+  if (m == 0.f) {
+    for (int k = 0; k < p.A; ++k) out[k] = 0.f;
+  } else if (row_logp_ent_grad(z, a, out, p.A, p.eps, p.u[r], -m * adv, p.beta * m, lp, H)) {
+    acc[0] += -m * adv * lp;
+    if (p.beta != 0.f) acc[0] -= p.beta * m * H;
+    acc[2] += m * H;
+  }
+  p.logp[r] = lp;
+  if (p.ent) p.ent[r] = H;
+  acc[1] += m;
+}
+
+// EX (with LOSS): loss_row_ex and its three partial sums
+template <bool LOSS, bool EX = false>
 __global__ __launch_bounds__(TPB) void policy_tiled_kernel(PolicyArgs p) {
   extern __shared__ __attribute__((aligned(16))) float pt_smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -119,7 +195,7 @@ __global__ __launch_bounds__(TPB) void policy_tiled_kernel(PolicyArgs p) {
   const int TS = (PT_ROWS * A + 3) & ~3;                  // floats per tile (16-byte multiple)
   float* Sz = pt_smem + (size_t)wave * 2 * TS;
   float* Sa = Sz + TS;
-  float acc[2] = {0.f, 0.f};
+  float acc[EX ? 3 : 2] = {};
   const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
   for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
     const long r0 = tile * PT_ROWS;
@@ -138,7 +214,8 @@ __global__ __launch_bounds__(TPB) void policy_tiled_kernel(PolicyArgs p) {
     __builtin_amdgcn_wave_barrier();
     const long r = r0 + lane;
     if (r < p.rows) {
-      if (LOSS) loss_row(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
+      if constexpr (EX) loss_row_ex(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
+      else if constexpr (LOSS) loss_row(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
       else row_probs(Sz + lane * A, Sa + lane * A, Sz + lane * A, A, p.eps);
     }
     __builtin_amdgcn_s_waitcnt(0xC07F);
@@ -148,24 +225,25 @@ __global__ __launch_bounds__(TPB) void policy_tiled_kernel(PolicyArgs p) {
     __builtin_amdgcn_s_waitcnt(0xC07F);                   // the tile is read out before the next trip overwrites it
     __builtin_amdgcn_wave_barrier();
   }
-  if (LOSS) block_partials<2>(acc, p.ws);
+  if (LOSS) block_partials<EX ? 3 : 2>(acc, p.ws);
 }
 
 // row-per-lane form for action counts whose tiles do not fit: same arithmetic in the same order
-template <bool LOSS>
+template <bool LOSS, bool EX = false>
 __global__ __launch_bounds__(TPB) void policy_rows_kernel(PolicyArgs p) {
-  float acc[2] = {0.f, 0.f};
+  float acc[EX ? 3 : 2] = {};
   for (long r = (long)blockIdx.x * TPB + threadIdx.x; r < p.rows; r += (long)gridDim.x * TPB) {
     const float* z = p.logits + r * p.A;
     const float* a = p.avail + r * p.A;
     float* out = p.out + r * p.A;
-    if (LOSS) loss_row(p, r, z, a, out, acc);
+    if constexpr (EX) loss_row_ex(p, r, z, a, out, acc);
+    else if constexpr (LOSS) loss_row(p, r, z, a, out, acc);
     else row_probs(z, a, out, p.A, p.eps);
   }
-  if (LOSS) block_partials<2>(acc, p.ws);
+  if (LOSS) block_partials<EX ? 3 : 2>(acc, p.ws);
 }
 
-template <bool LOSS>
+template <bool LOSS, bool EX = false>
 int launch_policy(PolicyArgs p, hipStream_t s, int& nb) {
   const size_t lds = (size_t)4 * 2 * ((PT_ROWS * p.A + 3) & ~3) * sizeof(float);
   if (lds <= 56 * 1024) {            // (block_partials keeps a few floats of its own)
@@ -173,11 +251,11 @@ int launch_policy(PolicyArgs p, hipStream_t s, int& nb) {
     long b = (tiles + 3) / 4;
     nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
     p.vec = ((reinterpret_cast<uintptr_t>(p.logits) | reinterpret_cast<uintptr_t>(p.avail) | reinterpret_cast<uintptr_t>(p.out)) & 15) == 0;
-    hipLaunchKernelGGL(policy_tiled_kernel<LOSS>, dim3((unsigned)nb), dim3(TPB), lds, s, p);
+    hipLaunchKernelGGL((policy_tiled_kernel<LOSS, EX>), dim3((unsigned)nb), dim3(TPB), lds, s, p);
   } else {
     long b = (p.rows + TPB - 1) / TPB;
     nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
-    hipLaunchKernelGGL(policy_rows_kernel<LOSS>, dim3((unsigned)nb), dim3(TPB), 0, s, p);
+    hipLaunchKernelGGL((policy_rows_kernel<LOSS, EX>), dim3((unsigned)nb), dim3(TPB), 0, s, p);
   }
   MARL_CHECK_LAUNCH();
   return 0;
@@ -247,6 +325,24 @@ extern "C" int marl_policy_loss_bwd(const float* logits, const float* avail, con
   const int rc = launch_policy<true>(p, (hipStream_t)stream, nb);
   if (rc) return rc;
   hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, (const float*)ws, nb, 2, out2);
+  MARL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int marl_policy_loss_bwd_ex(const float* logits, const float* avail, const int* u, const float* G, const float* v,
+                                       const float* padded, float eps, float beta, float* dlogits, float* logp, float* ent,
+                                       float* out3, float* ws, long rows, int N, int A, void* stream) {
+  if (rows <= 0 || A <= 0) return 0;
+  if (!logits || !avail || !u || !G || !padded || !dlogits || !logp || !out3 || !ws || N <= 0 || rows % N != 0 ||
+      dlogits == avail || !(beta >= 0.f))
+    return (int)hipErrorInvalidValue;
+  PolicyArgs p = {};
+  p.logits = logits; p.avail = avail; p.u = u; p.G = G; p.v = v; p.padded = padded; p.eps = eps; p.beta = beta;
+  p.out = dlogits; p.logp = logp; p.ent = ent; p.ws = ws; p.rows = rows; p.N = N; p.A = A;
+  int nb;
+  const int rc = launch_policy<true, true>(p, (hipStream_t)stream, nb);
+  if (rc) return rc;
+  hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, (const float*)ws, nb, 3, out3);
   MARL_CHECK_LAUNCH();
   return 0;
 }

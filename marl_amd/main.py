@@ -3,6 +3,7 @@
     python -m marl_amd.main --alg qmix --map 2s3z --n_envs 1024 --n_steps 500000
     python -m marl_amd.main --env matrix --alg qplex --n_envs 32 --n_steps 20000
     python -m marl_amd.main --map 2s3z --alg central_v --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --map 2s3z --alg reinforce --policy_entropy_coef 0.01 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --MAIC True --load_model True --evaluate True --evaluate_epoch 1 --n_envs 64
 
 ``--env synthetic`` (default) uses the synthetic SMAC-shaped device env with the dims of ``--map``;
@@ -11,7 +12,8 @@ from __future__ import annotations
 
 import sys
 
-from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args
+from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
+    get_reinforce_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .runner import Runner
@@ -28,6 +30,8 @@ def build(argv=None):
         get_centralv_args(args)
         if given is not None:           # the table's 0.8 is the default, not an override of --td_lambda
             args.td_lambda = given
+    elif args.alg == 'reinforce':
+        get_reinforce_args(args)
     get_RTW_args(args)
     get_maic_args(args)
     if args.env == 'smac':

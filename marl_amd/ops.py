@@ -418,6 +418,20 @@ def policy_loss_bwd(logits, avail, u, G, v, padded, eps, dlogits, logp, out2, ro
                                    _p(_f32(out2)), _p(ws), rows, N, A, _stream()), "marl_policy_loss_bwd")
 
 
+def policy_loss_bwd_ex(logits, avail, u, G, v, padded, eps, beta, dlogits, logp, ent, out3, rows, N, A):
+    """policy_loss_bwd without a baseline (``v`` None: Adv = G) and with the entropy bonus ``beta`` >= 0 of the policy the actions
+    were drawn from: out3 = {- sum m Adv logp - beta sum m H, N sum m, sum m H}, ent (rows) = H or None, and
+    dlogits = - m Adv dlogp/dz - beta m dH/dz.  beta = 0 with v: policy_loss_bwd's dlogits, logp and statistics bit for bit."""
+    lib = _lib.load()
+    for t, n in ((logits, rows * A), (avail, rows * A), (dlogits, rows * A), (logp, rows), (G, rows // N), (padded, rows // N)) + \
+            (() if v is None else ((v, rows // N),)) + (() if ent is None else ((ent, rows),)):
+        assert _f32(t).is_contiguous() and t.numel() >= n
+    assert _i32(u).is_contiguous() and u.numel() >= rows and out3.numel() >= 3
+    ws = WS.get("loss", lib.marl_loss_workspace(rows), logits.device)
+    check(lib.marl_policy_loss_bwd_ex(_p(logits), _p(avail), _p(u), _p(G), _p(v), _p(padded), float(eps), float(beta), _p(dlogits),
+                                      _p(logp), _p(ent), _p(_f32(out3)), _p(ws), rows, N, A, _stream()), "marl_policy_loss_bwd_ex")
+
+
 def policy_sample(logits, avail, avail_es, alive, eps, rseed, env0, tg, tg0, act_out, act_es, E, N, A):
     """select_actions' arguments; draws every live agent's action from the stochastic policy"""
     check(_lib.load().marl_policy_sample(_p(_f32(logits)), _p(_f32(avail)), avail_es, _p(alive), float(eps),

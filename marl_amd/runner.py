@@ -29,7 +29,8 @@ head's backward pass and, with ``args.mi_loss_weight`` / ``args.entropy_loss_wei
 attention-entropy losses (csrc/maic_aux.hip); the refusals above hold for it too.  Without MAIC it raises ValueError before
 anything is built, and so does a positive loss weight without MAIC_train.
 
-``args.alg == 'central_v'``: PolicyMAC and CentralVLearner (algorithm/central_v.py), trained ON-POLICY: the episodes a rollout just
+``args.alg == 'central_v'`` / ``'reinforce'``: PolicyMAC and CentralVLearner (algorithm/central_v.py) or ReinforceLearner
+(algorithm/reinforce.py), trained ON-POLICY: the episodes a rollout just
 generated are the batch of the one update that follows it - nothing goes through the replay buffer - and the learner is told the
 exploration rate they were drawn at.  With RTW / world_model / MAIC it raises ValueError, with overlapped rollouts
 NotImplementedError (an on-policy update needs the weights the last one wrote) - before anything is built.
@@ -55,6 +56,7 @@ from .algorithm.q_learner_state import QLearnerWithState
 from .algorithm.maic_q_learner import MAICQLearner
 from .algorithm.maic_td_learner import MAICTDLearner
 from .algorithm.central_v import CentralVLearner
+from .algorithm.reinforce import ReinforceLearner
 from .utils.logging import Logger
 
 
@@ -88,6 +90,9 @@ _AGENT_SWITCHES = (
 )
 
 
+_ON_POLICY = {'central_v': CentralVLearner, 'reinforce': ReinforceLearner}      # policy-gradient learners over PolicyMAC
+
+
 class Runner:
     def __init__(self, env, logger, args):
         self.env = env
@@ -100,12 +105,12 @@ class Runner:
             raise ValueError("mi_loss_weight / entropy_loss_weight are terms of MAICTDLearner's loss: they need MAIC_train")
         mac_cls, make_learner = SharedMAC, lambda mac, logger, args: QLearner(mac, args)
         on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
-        self.on_policy = args.alg == 'central_v'
+        self.on_policy = args.alg in _ON_POLICY
         if self.on_policy:
             if on:
-                raise ValueError("central_v trains the plain shared agent as a policy: not with %s" % on[0].name)
+                raise ValueError("%s trains the plain shared agent as a policy: not with %s" % (args.alg, on[0].name))
             if getattr(args, "overlap_rollout", False):
-                raise NotImplementedError("central_v is on-policy: a rollout needs the weights the last update wrote")
+                raise NotImplementedError("%s is on-policy: a rollout needs the weights the last update wrote" % args.alg)
             mac_cls = PolicyMAC
         for sw in on:
             for hit, refusal in ((sw is not on[0], sw.combined), (sw.alg_refused(args), sw.alg),
@@ -131,7 +136,7 @@ class Runner:
         logger.setup_tb(self.save_path + '/tb/other')
         self.logger = logger
         if self.on_policy:
-            self.learner = CentralVLearner(self.mac, args)
+            self.learner = _ON_POLICY[args.alg](self.mac, args)
         elif _value_mixer(args):
             self.learner = make_learner(self.mac, logger, args)
         elif _qtran(args):
