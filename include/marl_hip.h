@@ -518,6 +518,55 @@ int marl_policy_sample(const float* logits, const float* avail, long avail_es, c
                        unsigned rseed, int env0, const int* tg, int tg0, int* act_out, long act_es,
                        int E, int N, int A, void* stream);
 
+/* ---- COMA: the counterfactual critic (coma.hip; the reference ships the argument table only - the definitions are this
+ * project's own, from the published algorithm) ----------------------------------------------------------------------------
+ * Rows r = (b T + t) N + i: agent i at step t of episode b; R = B T N; u (R) int32 the taken actions; D = critic_dim.  The critic is
+ * fc1 = Linear(K, D) - ReLU - fc2 = Linear(D, D) - ReLU - fc3 = Linear(D, A) over the per-row input
+ *   x_r = [ s | o_i | one-hot(u_j) for every agent j, agent i's own block zeroed | one-hot(u_j at t-1) for all j (zero at t = 0) |
+ *           one-hot(i) ],   K = S + O + 2 N A + N,
+ * in this column order of fc1.weight (D, K), actions j-major.  x is never materialised: the first layer factors exactly into
+ *   h1_r = relu( W_s s_bt + b  +  W_o o_r  +  sum_{j != i} Wu[j, u_j] + [t > 0] sum_j Wl[j, u_j(t-1)] + Wid[i] ).
+ * An action index outside [0, A) is an all-zero one-hot.  fp32 throughout, fixed-order sums, no float atomics: two calls give the
+ * same bits; every entry point returns 0 without a launch on an empty shape.  D must be a multiple of 4, at most 1024; pre_s, Wt,
+ * h1, dh1, dpre, dsum 16-byte aligned.
+ *
+ * marl_coma_onehot_cols: Wt (C, D) = the K-major copy of columns [col0, col0 + C) of the row-major W (D, ldw): Wt[c][d] =
+ *   W[d][col0 + c].  With col0 = S + O and C = 2 N A + N its rows are Wu (N A), Wl (N A), Wid (N): every gather below reads D
+ *   contiguous floats.
+ * marl_coma_fc1_fwd: pre_s (B T, D) = W_s s + b (marl_linear on the state block, once per step); h1 (R, D) holds W_o o on entry
+ *   (marl_linear on the observation block) and relu of the sum above on return.  The step's sum over all j is formed once and
+ *   agent i subtracts its own column.
+ * marl_coma_fc1_bwd: dh1, h1 (R, D) -> dpre = dh1 (h1 > 0) (R, D; may be dh1), dsum (B T, D) = sum_i dpre in agent order, and the
+ *   gradient of the one-hot columns ADDED into dW[d][col0 + c] (dW row stride lddw):
+ *     action (j, k): sum over the steps with u_j = k of (dsum - dpre_j);  last action (j, k): sum over the steps with t > 0 and
+ *     u_j(t-1) = k of dsum;  id i: sum of dpre_i  -  per slab of steps in step order, then over the slabs in slab order.
+ *   The state block's gradient is marl_linear_wgrad on (dsum, s), the observation block's on (dpre, o), the bias's the column sums
+ *   of dsum.  ws: marl_coma_fc1_bwd_workspace() bytes; 2 A D floats of LDS (at most 64 KiB).
+ * marl_coma_q_taken: out (B, N, T), out[b, i, t] = q[b, t + shift, i, u[b, t + shift, i]] for 0 <= t + shift < T, else 0
+ *   (shift = 1 on the target critic's Q: q_next, zero at the window's last step).
+ * marl_coma_loss_bwd: both losses of one forward pass.  With m = 1 - padded (B T), pi the policy of marl_policy_probs (a row has
+ *   a policy when n > 0 and its taken action is available), G (B, N, T) the lambda-returns (constants of the gradient):
+ *     q_taken[r] = Q_r(u_r),  adv[r] = Q_r(u_r) - sum_k pi_r(k) Q_r(k)  (a constant of the gradient; exactly 0 when n = 1),
+ *     logp[r] = log pi_r(u_r),  ent[r] = H_r  as in marl_policy_loss_bwd_ex,
+ *     dlogits = - m Adv d log pi(u) / dz - beta m dH / dz  (beta = 0: the plain gradient walk),
+ *     dq (R, A) = - 2 m (G - Q_u) at column u, exact zeros elsewhere,
+ *     out_c2 = { sum m (G - Q_u)^2, sum_r m } and out_a3 = { - sum m Adv logp - beta sum m H, sum_r m, sum m H }, un-normalised
+ *     (sum_r m = N sum m, the denominator of both losses).
+ *   A row with m = 0 or without a policy contributes nothing to the numerators, its dlogits and dq are exact zeros, its four
+ *   per-row outputs are 0 and its logits and Q are never looked at.  dlogits may be logits and dq may be q; no other aliasing.
+ *   ws: marl_loss_workspace() bytes (four partials per workgroup); beta < 0 is an error. */
+int marl_coma_onehot_cols(const float* W, long ldw, int col0, float* Wt, int C, int D, void* stream);
+int marl_coma_fc1_fwd(const float* pre_s, const float* Wt, const int* u, float* h1, int B, int T, int N, int A, int D,
+                      void* stream);
+size_t marl_coma_fc1_bwd_workspace(int B, int T, int N, int A, int D);
+int marl_coma_fc1_bwd(const float* dh1, const float* h1, const int* u, float* dpre, float* dsum, float* dW, long lddw,
+                      int col0, float* ws, size_t ws_bytes, int B, int T, int N, int A, int D, void* stream);
+int marl_coma_q_taken(const float* q, const int* u, float* out, int shift, int B, int T, int N, int A, void* stream);
+int marl_coma_loss_bwd(const float* logits, const float* avail, const float* q, const int* u, const float* G,
+                       const float* padded, float eps, float beta, float* dlogits, float* dq, float* logp, float* ent,
+                       float* adv, float* q_taken, float* out_c2, float* out_a3, float* ws, int B, int T, int N, int A,
+                       void* stream);
+
 /* ---- optimizer (optim.hip): clip_grad_norm_ + RMSprop / Adam on ONE flat buffer -------------
  * (q_learner.py:42-47,170-173; torch defaults).  g is the un-normalised gradient; den points to
  * sum(mask) on the device (NULL = 1).  sumsq[0] receives sum g^2 (before scaling). */

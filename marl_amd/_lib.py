@@ -173,6 +173,12 @@ SIGNATURES = {
     "marl_policy_loss_bwd": (I, [P, P, P, P, P, P, F, P, P, P, P, L, I, I, P]),
     "marl_policy_loss_bwd_ex": (I, [P, P, P, P, P, P, F, F, P, P, P, P, P, L, I, I, P]),
     "marl_policy_sample": (I, [P, P, L, P, F, U, I, P, I, P, L, I, I, I, P]),
+    "marl_coma_onehot_cols": (I, [P, L, I, P, I, I, P]),
+    "marl_coma_fc1_fwd": (I, [P, P, P, P, I, I, I, I, I, P]),
+    "marl_coma_fc1_bwd_workspace": (SZ, [I, I, I, I, I]),
+    "marl_coma_fc1_bwd": (I, [P, P, P, P, P, P, L, I, P, SZ, I, I, I, I, I, P]),
+    "marl_coma_q_taken": (I, [P, P, P, I, I, I, I, I, P]),
+    "marl_coma_loss_bwd": (I, [P, P, P, P, P, P, F, F, P, P, P, P, P, P, P, P, P, I, I, I, I, P]),
     "marl_grad_sumsq": (I, [P, L, P, P, P]),
     "marl_sumsq_workspace": (SZ, [L]),
     "marl_rmsprop_step": (I, [P, P, P, L, F, F, F, F, P, P, P]),

@@ -67,7 +67,7 @@ class CentralVLearner(Learner):
         self.epsilon = 0.0
         self.eval_net = mac
         self.eval_net.cuda()
-        self.critic = VCritic(args)
+        self.critic = self._make_critic(args)
         self.target_critic = copy.deepcopy(self.critic)
         self.cuda()
         self.optimizer = FusedOptimizer(self._flat, args.optimizer, args.lr_actor, args.grad_norm_clip)
@@ -80,6 +80,9 @@ class CentralVLearner(Learner):
         self.last_stats = self.actor_stats = None
         self.actor_loss = self.entropy = float("nan")
         self._td_dbg, self._dbg = {}, {}
+
+    def _make_critic(self, args):
+        return VCritic(args)
 
     def sync_replicas(self):
         """one rank: nothing to broadcast"""

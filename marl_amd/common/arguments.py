@@ -26,7 +26,7 @@ def get_common_args(argv=None):
     # TD(lambda) returns as the Q learners' targets (the reference ships utils/rl_utils.py:build_td_lambda_targets and never calls
     # it); absent = None = the one-step target.  get_mixer_args leaves the field alone: a namespace without it means "off"
     p.add_argument('--td_lambda', type=float, default=None)
-    # weight of the entropy bonus on the actor loss of the policy-gradient learners (central_v, reinforce); the reference's tables
+    # weight of the entropy bonus on the actor loss of the policy-gradient learners (central_v, reinforce, coma); the reference's tables
     # carry entropy_coefficient = 0.001 and nothing reads it.  (--entropy_loss_weight is MAIC's attention entropy)
     p.add_argument('--policy_entropy_coef', type=float, default=0.0)
     p.add_argument('--env', type=str, default='smac')

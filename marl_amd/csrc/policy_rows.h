@@ -1,0 +1,131 @@
+// Row helpers of the stochastic policy (policy.hip has the definition and the derivation): the scalars of a row, pi, log pi(u) and
+// the entropy with their gradients by the logits.  Shared by policy.hip and coma.hip; a row's A logits / availability flags may
+// lie in LDS or in global memory.
+#pragma once
+#include "sums.h"
+
+namespace {
+
+constexpr int PT_ROWS = 64;          // rows per wave tile
+constexpr int PT_MAX_BLOCKS = 1024;  // one grid pass covers 1024 x 4 x 64 = 262 144 rows (and the loss workspace holds 1024 rows of partials)
+constexpr float EXP_CLAMP = 80.f;
+
+struct RowPolicy { float mx, S, Sa, D, cw, ew; int n; };     // w_k = cw e_k + ew
+
+// the scalars of one row; z, a: the row's A logits / availability flags (LDS or global)
+__device__ __forceinline__ RowPolicy row_policy(const float* z, const float* a, int A, float eps) {
+  RowPolicy p;
+  p.n = 0; p.mx = 0.f;
+  for (int k = 0; k < A; ++k) {
+    if (a[k] == 0.f) continue;
+    const float v = z[k];
+    if (p.n == 0 || v > p.mx) p.mx = v;
+    ++p.n;
+  }
+  p.S = 0.f; p.Sa = 0.f; p.D = 1.f; p.cw = 0.f; p.ew = 0.f;
+  if (p.n == 0) return p;
+  for (int k = 0; k < A; ++k) {
+    const float e = expf(fminf(z[k] - p.mx, EXP_CLAMP));
+    p.S += e;
+    if (a[k] != 0.f) p.Sa += e;
+  }
+  p.cw = 1.f - eps;
+  p.ew = eps * p.S / (float)p.n;
+  p.D = p.cw * p.Sa + eps * p.S;
+  return p;
+}
+__device__ __forceinline__ float row_e(const RowPolicy& p, float z) { return expf(fminf(z - p.mx, EXP_CLAMP)); }
+
+// pi of one row, written over out (out may be z)
+__device__ __forceinline__ void row_probs(const float* z, const float* a, float* out, int A, float eps) {
+  const RowPolicy p = row_policy(z, a, A, eps);
+  const float inv = 1.f / p.D;
+  for (int k = 0; k < A; ++k) out[k] = (p.n > 0 && a[k] != 0.f) ? (p.cw * row_e(p, z[k]) + p.ew) * inv : 0.f;
+}
+
+// { L1, Hn } = { sum a_k e_k log pi_k, sum pi_k log pi_k } of a row with a policy; a term whose pi_k = 0 is 0
+__device__ __forceinline__ float2 row_ent_sums(const RowPolicy& p, const float* z, const float* a, int A) {
+  const float logD = logf(p.D), invD = 1.f / p.D;
+  float L1 = 0.f, Hn = 0.f;
+  for (int k = 0; k < A; ++k) {
+    if (a[k] == 0.f) continue;
+    const float e = row_e(p, z[k]);
+    const float w = p.cw * e + p.ew;
+    if (w > 0.f) {
+      const float lp = logf(w) - logD;
+      L1 += e * lp;
+      Hn += w * invD * lp;
+    }
+  }
+  return make_float2(L1, Hn);
+}
+
+// scale * d log pi_u / dz written over out (out may be z); returns log pi_u.  A row without a policy (n = 0, or a taken action
+// that is not available) returns `false`: exact zeros and log pi = 0, whatever z holds
+__device__ __forceinline__ bool row_logp_grad_of(const RowPolicy& p, const float* z, const float* a, float* out, int A, int u,
+                                                 float scale, float& logp) {
+  logp = 0.f;
+  if (p.n == 0 || u < 0 || u >= A || a[u] == 0.f) {
+    for (int k = 0; k < A; ++k) out[k] = 0.f;
+    return false;
+  }
+  if (p.n == 1) {                      // the one available action: pi = 1 whatever the logits hold, log pi = 0, no gradient
+    for (int k = 0; k < A; ++k) out[k] = 0.f;
+    return true;
+  }
+  const float eu = row_e(p, z[u]);
+  const float wu = p.cw * eu + p.ew;
+  logp = logf(wu) - logf(p.D);
+  const float invS = 1.f / p.S, Pa = p.Sa * invS;
+  const float c1 = p.cw * eu / wu, c2 = p.cw / p.D;
+  for (int k = 0; k < A; ++k) {
+    const float e = row_e(p, z[k]);
+    const float ak = a[k] != 0.f ? 1.f : 0.f;
+    out[k] = scale * (c1 * ((k == u ? 1.f : 0.f) - e * invS) - c2 * e * (ak - Pa));
+  }
+  return true;
+}
+__device__ __forceinline__ bool row_logp_grad(const float* z, const float* a, float* out, int A, float eps, int u, float scale,
+                                              float& logp) {
+  return row_logp_grad_of(row_policy(z, a, A, eps), z, a, out, A, u, scale, logp);
+}
+
+// row_logp_grad with the entropy H = - sum_{a_k = 1} pi_k log pi_k of the row's policy (0 log 0 = 0: w_k underflows to 0 at
+// eps = 0 once z_k sits about 104 below mx) and, for hs != 0, out = scale d log pi_u / dz - hs dH / dz.  With
+// L1 = sum a_k e_k log pi_k and Hn = sum pi_k log pi_k = -H (one walk, before out - which may be z - is written):
+//   dH/dz_i = -c2 (a_i e_i log pi_i - e_i L1 / S) + c2 e_i (a_i - Pa) Hn          (the second walk; -pi_i (log pi_i + H) at eps = 0).
+// hs = 0 takes row_logp_grad's own walk: the same bits.  A row with n = 1 has H = 0 and no gradient
+__device__ __forceinline__ bool row_logp_ent_grad_of(const RowPolicy& p, const float* z, const float* a, float* out, int A, int u,
+                                                     float scale, float hs, float& logp, float& H) {
+  H = 0.f;
+  const bool spread = p.n > 1 && u >= 0 && u < A && a[u] != 0.f;      // a policy over more than one action
+  if (!spread || hs == 0.f) {
+    if (spread) H = -row_ent_sums(p, z, a, A).y;
+    return row_logp_grad_of(p, z, a, out, A, u, scale, logp);
+  }
+  const float2 s = row_ent_sums(p, z, a, A);
+  const float L1 = s.x, Hn = s.y;
+  H = -Hn;
+  const float eu = row_e(p, z[u]);
+  const float wu = p.cw * eu + p.ew;
+  const float logD = logf(p.D);
+  logp = logf(wu) - logD;
+  const float invS = 1.f / p.S, Pa = p.Sa * invS;
+  const float c1 = p.cw * eu / wu, c2 = p.cw / p.D;
+  const float L1S = L1 * invS;
+  for (int k = 0; k < A; ++k) {
+    const float e = row_e(p, z[k]);
+    const float ak = a[k] != 0.f ? 1.f : 0.f;
+    const float w = p.cw * e + p.ew;
+    const float elp = (ak != 0.f && w > 0.f) ? e * (logf(w) - logD) : 0.f;
+    const float dH = c2 * (e * (ak - Pa) * Hn - (elp - e * L1S));
+    out[k] = scale * (c1 * ((k == u ? 1.f : 0.f) - e * invS) - c2 * e * (ak - Pa)) - hs * dH;
+  }
+  return true;
+}
+__device__ __forceinline__ bool row_logp_ent_grad(const float* z, const float* a, float* out, int A, float eps, int u, float scale,
+                                                  float hs, float& logp, float& H) {
+  return row_logp_ent_grad_of(row_policy(z, a, A, eps), z, a, out, A, u, scale, hs, logp, H);
+}
+
+}  // namespace

@@ -3,6 +3,7 @@
     python -m marl_amd.main --alg qmix --map 2s3z --n_envs 1024 --n_steps 500000
     python -m marl_amd.main --env matrix --alg qplex --n_envs 32 --n_steps 20000
     python -m marl_amd.main --map 2s3z --alg central_v --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --map 2s3z --alg coma --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg reinforce --policy_entropy_coef 0.01 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --MAIC True --load_model True --evaluate True --evaluate_epoch 1 --n_envs 64
 
@@ -13,7 +14,7 @@ from __future__ import annotations
 import sys
 
 from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
-    get_reinforce_args
+    get_reinforce_args, get_coma_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .runner import Runner
@@ -25,9 +26,9 @@ MAPS = {"2s3z": (5, 80, 120, 11, 120), "3s5z": (8, 128, 216, 14, 150), "MMM2": (
 def build(argv=None):
     args = get_common_args(argv)
     get_mixer_args(args)
-    if args.alg == 'central_v':
+    if args.alg in ('central_v', 'coma'):
         given = args.td_lambda
-        get_centralv_args(args)
+        (get_centralv_args if args.alg == 'central_v' else get_coma_args)(args)
         if given is not None:           # the table's 0.8 is the default, not an override of --td_lambda
             args.td_lambda = given
     elif args.alg == 'reinforce':
@@ -52,9 +53,19 @@ def build(argv=None):
     return args, env
 
 
+def make_runner(args, env, logger=None):
+    """the Runner of a built (args, env).  ``--alg coma`` names its learner here: the runner's own table of on-policy learners
+    holds central_v and reinforce, and a Runner built on the bare name 'coma' still refuses it"""
+    learner_cls = None
+    if args.alg == 'coma':
+        from .algorithm.coma import COMALearner
+        learner_cls = COMALearner
+    return Runner(env, logger if logger is not None else Logger(), args, learner_cls=learner_cls)
+
+
 def main(argv=None):
     args, env = build(argv)
-    runner = Runner(env, Logger(), args)
+    runner = make_runner(args, env)
     if not args.evaluate:
         loss = runner.run(0)
         print("final loss", loss)

@@ -439,6 +439,61 @@ def policy_sample(logits, avail, avail_es, alive, eps, rseed, env0, tg, tg0, act
                                          E, N, A, _stream()), "marl_policy_sample")
 
 
+def _dense(t, n):
+    assert _f32(t).is_contiguous() and t.numel() >= n
+    return _p(t)
+
+
+def coma_onehot_cols(W, col0, Wt, C, D):
+    """Wt (C, D) = the K-major copy of columns [col0, col0 + C) of the row-major weight W (D, K) (csrc/coma.hip)"""
+    assert W.dim() == 2 and W.stride(1) == 1 and W.shape[0] == D and col0 + C <= W.shape[1]
+    check(_lib.load().marl_coma_onehot_cols(_p(_f32(W)), W.stride(0), col0, _dense(Wt, C * D), C, D, _stream()),
+          "marl_coma_onehot_cols")
+
+
+def coma_fc1_fwd(pre_s, Wt, u, h1, B, T, N, A, D):
+    """h1 (R, D) holds the observation block's product on entry and relu(h1 + pre_s[step] + the gathered one-hot columns) on return:
+    the COMA critic's first layer without its (R, K) input (include/marl_hip.h)"""
+    R = B * T * N
+    assert _i32(u).is_contiguous() and u.numel() >= R
+    check(_lib.load().marl_coma_fc1_fwd(_dense(pre_s, B * T * D), _dense(Wt, (2 * N * A + N) * D), _p(u), _dense(h1, R * D),
+                                        B, T, N, A, D, _stream()), "marl_coma_fc1_fwd")
+
+
+def coma_fc1_bwd(dh1, h1, u, dpre, dsum, dW, col0, B, T, N, A, D):
+    """dpre = dh1 (h1 > 0), dsum = its per-step agent sum, and the one-hot columns' gradient added into dW[:, col0:col0 + 2NA + N]
+    (dW: the (D, K) gradient view of fc1.weight)"""
+    lib = _lib.load()
+    R = B * T * N
+    assert _i32(u).is_contiguous() and u.numel() >= R
+    assert dW.dim() == 2 and dW.stride(1) == 1 and dW.shape[0] == D and col0 + 2 * N * A + N <= dW.shape[1]
+    ws = WS.get("coma_fc1", lib.marl_coma_fc1_bwd_workspace(B, T, N, A, D), dh1.device)
+    check(lib.marl_coma_fc1_bwd(_dense(dh1, R * D), _dense(h1, R * D), _p(u), _dense(dpre, R * D), _dense(dsum, B * T * D),
+                                _p(_f32(dW)), dW.stride(0), col0, _p(ws), ws.numel() * 4, B, T, N, A, D, _stream()),
+          "marl_coma_fc1_bwd")
+
+
+def coma_q_taken(q, u, out, shift, B, T, N, A):
+    """out (B, N, T): the taken action's Q at step t + shift, 0 past the window"""
+    R = B * T * N
+    assert _i32(u).is_contiguous() and u.numel() >= R
+    check(_lib.load().marl_coma_q_taken(_dense(q, R * A), _p(u), _dense(out, R), int(shift), B, T, N, A, _stream()),
+          "marl_coma_q_taken")
+
+
+def coma_loss_bwd(logits, avail, q, u, G, padded, eps, beta, dlogits, dq, logp, ent, adv, q_taken, out_c2, out_a3, B, T, N, A):
+    """COMA's two losses of one critic pass (include/marl_hip.h): G (B, N, T); out_c2 = {critic numerator, N M},
+    out_a3 = {actor numerator, N M, sum m H}; dlogits / dq (R, A) un-normalised"""
+    lib = _lib.load()
+    R = B * T * N
+    assert _i32(u).is_contiguous() and u.numel() >= R and out_c2.numel() >= 2 and out_a3.numel() >= 3
+    ws = WS.get("loss", lib.marl_loss_workspace(R), logits.device)
+    check(lib.marl_coma_loss_bwd(_dense(logits, R * A), _dense(avail, R * A), _dense(q, R * A), _p(u), _dense(G, R),
+                                 _dense(padded, B * T), float(eps), float(beta), _dense(dlogits, R * A), _dense(dq, R * A),
+                                 _dense(logp, R), _dense(ent, R), _dense(adv, R), _dense(q_taken, R), _p(_f32(out_c2)),
+                                 _p(_f32(out_a3)), _p(ws), B, T, N, A, _stream()), "marl_coma_loss_bwd")
+
+
 def grad_sumsq(g, n, out1):
     lib = _lib.load()
     ws = WS.get("sumsq", lib.marl_sumsq_workspace(n), g.device)

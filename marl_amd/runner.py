@@ -34,6 +34,9 @@ anything is built, and so does a positive loss weight without MAIC_train.
 generated are the batch of the one update that follows it - nothing goes through the replay buffer - and the learner is told the
 exploration rate they were drawn at.  With RTW / world_model / MAIC it raises ValueError, with overlapped rollouts
 NotImplementedError (an on-policy update needs the weights the last one wrote) - before anything is built.
+``learner_cls`` (a constructor argument): a further on-policy learner over PolicyMAC, named by the caller instead of by the runner's
+own table; everything above holds for it.  The launcher passes COMALearner (algorithm/coma.py) for ``--alg coma``
+(``main.make_runner``); a Runner built without it keeps answering 'learner coma cannot find!', as it always has.
 
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
@@ -94,7 +97,7 @@ _ON_POLICY = {'central_v': CentralVLearner, 'reinforce': ReinforceLearner}      
 
 
 class Runner:
-    def __init__(self, env, logger, args):
+    def __init__(self, env, logger, args, learner_cls=None):
         self.env = env
         if not args.reuse_network:
             raise NotImplementedError("only the shared-parameter controller (reuse_network) is on the hot path")
@@ -105,7 +108,7 @@ class Runner:
             raise ValueError("mi_loss_weight / entropy_loss_weight are terms of MAICTDLearner's loss: they need MAIC_train")
         mac_cls, make_learner = SharedMAC, lambda mac, logger, args: QLearner(mac, args)
         on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
-        self.on_policy = args.alg in _ON_POLICY
+        self.on_policy = learner_cls is not None or args.alg in _ON_POLICY
         if self.on_policy:
             if on:
                 raise ValueError("%s trains the plain shared agent as a policy: not with %s" % (args.alg, on[0].name))
@@ -136,7 +139,7 @@ class Runner:
         logger.setup_tb(self.save_path + '/tb/other')
         self.logger = logger
         if self.on_policy:
-            self.learner = _ON_POLICY[args.alg](self.mac, args)
+            self.learner = (learner_cls or _ON_POLICY[args.alg])(self.mac, args)
         elif _value_mixer(args):
             self.learner = make_learner(self.mac, logger, args)
         elif _qtran(args):
