@@ -320,6 +320,39 @@ int marl_agent_unroll_fwd_x6(const marl_agent_weights_t* w, const float* obs, lo
                              int O, int A, int last_action, int reuse_network, int cu_budget, float* gi_out,
                              const float* gi_in, void* stream);
 
+/* ---- which kernel a forward unroll runs (host only: no GPU, no launch) ------------------------------------------------------------
+ * The launch plan of marl_agent_unroll_fwd (x6 = 0) or marl_agent_unroll_fwd_x6 (x6 = 1) for these dimensions, taken from the
+ * same host function the launch itself calls.  `flags` says what the caller would pass: */
+#define MARL_UNROLL_SAVED 1        /* saved != NULL */
+#define MARL_UNROLL_GI_OUT 2       /* gi_out != NULL */
+#define MARL_UNROLL_GI_IN 4        /* gi_in != NULL */
+#define MARL_UNROLL_HS 8           /* hs != NULL */
+#define MARL_UNROLL_OBS_ALIGNED 16 /* obs on a 16-byte boundary */
+#define MARL_UNROLL_H_ALIGNED 32   /* h0 and h_last each NULL or on a 16-byte boundary */
+/* Returns 0 and fills plan[8], or non-zero where the entry point would refuse the call (and for B <= 0 or T <= 0, where it launches
+ * nothing):
+ *   plan[0] kernel family: */
+#define MARL_UNROLL_F32_PIPE 0     /* agent.hip: agent_fwd_pipe_kernel, software-pipelined */
+#define MARL_UNROLL_F32_MULTI 1    /* agent.hip: agent_fwd_kernel, the multi-tile kernel */
+#define MARL_UNROLL_X6 2           /* agent_x6.hip */
+#define MARL_UNROLL_X6_R6 3        /* agent_x6p.hip: the round-6 decomposition */
+/*   plan[1] row tiles (16 rows) per workgroup
+ *   plan[2] workgroups
+ *   plan[3] workgroups that hold plan[1] whole tiles.  fp32 and round-6: tiles / plan[1], the last workgroup holds what is left.
+ *           agent_x6.hip: its n_full argument - the workgroups after the first plan[3] hold ONE tile each (the last round of a
+ *           launch that runs in rounds); with two tiles per workgroup and plan[3] == plan[2] an odd tile count leaves the last
+ *           workgroup without a second tile
+ *   plan[4] action tiles of fc2 (1: A <= 16 columns, 2)
+ *   plan[5] fc1 chunks: 16-column chunks of the input for the fp32 kernels (KC), 32-column chunks for the split kernels (3, 5, 7)
+ *   plan[6] how a step's observations are read: */
+#define MARL_UNROLL_IN_ELEMENT 0   /* float by float (O % 4 != 0 or obs not 16-byte aligned) */
+#define MARL_UNROLL_IN_VECTOR 1    /* 16-byte vectors through the prefetch registers */
+#define MARL_UNROLL_IN_HALF 2      /* ... one column half of the tile at a time (wide observations) */
+#define MARL_UNROLL_IN_W2L 3       /* ... six prefetch registers, fc2 fragments in LDS (saving, wide observations, two action tiles) */
+/*   plan[7] 1 when the launch really reads gi_in (0: it computes every step itself) */
+int marl_agent_unroll_fwd_plan(int x6, int B, int T, int N, int O, int A, int last_action, int reuse_network, int cu_budget,
+                               int flags, int* plan);
+
 /* ---- BPTT of the unroll on the same split arithmetic (agent_bwd_x6.hip) -------------------------------------------------------
  * Opt-in (args.gemm_mode = "bf16x6"): marl_agent_unroll_bwd with every fp32 product - the delta pass and the weight-gradient
  * reductions over rows - as six bf16 MFMA products; bias gradients are exact fp32 sums.  Same argument meaning (no dense dq and no

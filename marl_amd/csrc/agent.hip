@@ -1713,34 +1713,33 @@ extern "C" int marl_agent_unroll_reuse_supported(int B, int T, int N, int O, int
   return 1;
 }
 
-extern "C" int marl_agent_unroll_fwd(const marl_agent_weights_t* w, const float* obs, long obs_bs, int obs_t0,
-                                     const int* ufed, long u_bs, int u_t0, const int* ep_len, const int* ep_map,
-                                     const float* h0, float* q, float* hs, float* h_last, float* saved, int B,
-                                     int T, int N, int O, int A, int last_action, int reuse_network, int cu_budget,
-                                     float* gi_out, const float* gi_in, void* stream) {
-  if (B <= 0 || T <= 0) return 0;
-  if (w->H != H || A > 32 || A < 1 || cu_budget < 0 || cu_budget > 256) return (int)hipErrorInvalidValue;
+// What a forward launch does, decided on the host from the dimensions and from what the caller passes: the ONE place both
+// marl_agent_unroll_fwd and the plan query (marl_agent_unroll_fwd_plan, agent_x6.hip) take it from.
+struct FwdPlan {
+  int RT, KC, AC, vload, half, w2l, pipe, xs;      // xs: the launch reads gi_in
+  long n_wg;
+  size_t lds;
+};
+
+// flags: MARL_UNROLL_* of include/marl_hip.h.  0, or hipErrorInvalidValue where the entry point refuses the call.
+static int fwd_plan(int B, int T, int N, int O, int A, int last_action, int reuse_network, int cu_budget, int flags, FwdPlan* pl) {
+  if (A > 32 || A < 1 || cu_budget < 0 || cu_budget > 256) return (int)hipErrorInvalidValue;
   if (cu_budget == 0) cu_budget = 256;      // CUs this launch may occupy: 128 lets two independent unrolls run side by side
-  FwdArgs a;
-  a.W1 = w->fc1_w; a.b1 = w->fc1_b; a.Wih = w->w_ih; a.Whh = w->w_hh; a.bih = w->b_ih; a.bhh = w->b_hh;
-  a.W2 = w->fc2_w; a.b2 = w->fc2_b;
-  a.obs = obs; a.obs_bs = obs_bs; a.obs_t0 = obs_t0; a.ufed = ufed; a.u_bs = u_bs; a.u_t0 = u_t0; a.ep_len = ep_len; a.ep_map = ep_map; a.h0 = h0; a.q = q; a.hs = hs; a.h_last = h_last; a.saved = saved;
-  a.B = B; a.T = T; a.N = N; a.O = O; a.A = A; a.gi_out = saved ? gi_out : nullptr; a.gi_in = gi_in;
-  a.has_act = last_action ? 1 : 0; a.has_id = reuse_network ? 1 : 0;
-  a.I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
-  a.KC = (a.I + 15) / 16;
-  a.R = (long)B * N;
-  const int KS = a.KC * 16 + MARL_PAD_K;
+  const bool saved = (flags & MARL_UNROLL_SAVED) != 0, gi_in = (flags & MARL_UNROLL_GI_IN) != 0;
+  const int I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
+  const int KC = (I + 15) / 16;
+  const long R = (long)B * N;
+  const int KS = KC * 16 + MARL_PAD_K;
   const size_t per_row = (size_t)(KS + 3 * HS) * 4 + 32 + 8;   // + row tables: 2 long + 4 int, + 2 int reserved (ulds in the kernel's carve)
-  const size_t fixed = (size_t)4 * a.KC * 64 * 16 + 16 + (((size_t)T * 4 + 15) & ~(size_t)15);   // fc1 fragments + step flags of the x-reusing variants (pipelined: 4; else one per step)
-  a.vload = (O % 4 == 0) && ((reinterpret_cast<uintptr_t>(obs) & 15) == 0) && O >= 4;
+  const size_t fixed = (size_t)4 * KC * 64 * 16 + 16 + (((size_t)T * 4 + 15) & ~(size_t)15);   // fc1 fragments + step flags of the x-reusing variants (pipelined: 4; else one per step)
+  int vload = (O % 4 == 0) && (flags & MARL_UNROLL_OBS_ALIGNED) && O >= 4;
   int rt_cap = 8;
   bool half = false, w2l = false;
   const bool xs_off = !marl_switches()->fwd_xs;      // A/B switch for measurements (common.h: MarlSwitches)
-  const bool xs_req = a.vload && gi_in && !saved && T >= 2 && !xs_off;      // the launch reads stored input-side sums
-  if (a.vload && !xs_req) {   // the workgroup keeps one step's obs tile (rows * O/4 float4) in NLDW * 512 registers
+  const bool xs_req = vload && gi_in && !saved && T >= 2 && !xs_off;      // the launch reads stored input-side sums
+  if (vload && !xs_req) {   // the workgroup keeps one step's obs tile (rows * O/4 float4) in NLDW * 512 registers
     int cap2 = (NLDW * FNT) / (16 * (O / 4));
-    const long tiles = (a.R + 15) / 16;
+    const long tiles = (R + 15) / 16;
     const int cus = T > 1 ? cu_budget : 256;
     const int want = (int)((tiles + cus - 1) / cus);                 // row tiles per workgroup that fill the CUs in one round
     // activation-saving unroll, wide observations, two action tiles: six prefetch registers, fc2 fragments in LDS (W2L kernels)
@@ -1756,56 +1755,101 @@ extern "C" int marl_agent_unroll_fwd(const marl_agent_weights_t* w, const float*
     }                                                                // stores across the tile loop and waits vmcnt(0) for
                                                                      // the right half at the end of every gate phase
                                                                      // (measured 2.2 -> 3.2 ms at MMM2 / 1024 envs)
-    if (cap2 < 1) { a.vload = 0; half = false; } else if (cap2 < rt_cap) rt_cap = cap2;
+    if (cap2 < 1) { vload = 0; half = false; } else if (cap2 < rt_cap) rt_cap = cap2;
   }
   // a single step (rollout) is latency-bound: many small workgroups overlap their prologues better than
   // 256 big ones; a long unroll amortises the prologue and wants one workgroup per CU
   if (T == 1 && rt_cap > marl_fwd_rt_single) rt_cap = marl_fwd_rt_single;
   const size_t fixed_k = fixed + (w2l ? (size_t)2 * 4 * 64 * 16 : 0);
-  a.RT = pick_rt(a.R, per_row, fixed_k, rt_cap, T > 1 ? cu_budget : 256);
-  const size_t lds = fixed_k + per_row * a.RT * 16;
+  const int RT = pick_rt(R, per_row, fixed_k, rt_cap, T > 1 ? cu_budget : 256);
+  const size_t lds = fixed_k + per_row * RT * 16;
   if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
-  const long rows = a.RT * 16;
-  dim3 grid((unsigned)((a.R + rows - 1) / rows)), block(FNT);
-  hipStream_t s = (hipStream_t)stream;
+  const long rows = RT * 16;
   // per-step outputs are addressed with 32-bit byte offsets
   if ((double)B * T * N * H * 4.0 >= 4294967296.0) return (int)hipErrorInvalidValue;
-  hipError_t e;
+  pl->RT = RT; pl->KC = KC; pl->AC = A <= 16 ? 1 : 2; pl->vload = vload; pl->half = half; pl->w2l = w2l;
+  pl->n_wg = (R + rows - 1) / rows;
+  pl->pipe = 0; pl->xs = xs_req; pl->lds = lds;
   // few row tiles per workgroup and a long unroll: the software-pipelined variant (one barrier per step)
-  if (a.vload && !w2l && a.RT <= marl_fwd_pipe_max_rt && T >= 4 && (long)a.RT * 16 * (O / 4) <= (long)NLDW * FNT) {
+  if (vload && !w2l && RT <= marl_fwd_pipe_max_rt && T >= 4 && (long)RT * 16 * (O / 4) <= (long)NLDW * FNT) {
     const size_t per_row_p = (size_t)(2 * KS + 4 * HS) * 4 + 32;
-    const size_t lds_p = fixed + per_row_p * a.RT * 16 + 64;
-    if (lds_p <= 160 * 1024) {
-      const void* fp;
-      const bool xs = gi_in && !saved && !xs_off;
-      if (A <= 16) fp = saved ? (const void*)agent_fwd_pipe_kernel<1, true> : xs ? (const void*)agent_fwd_pipe_kernel<1, false, true> : (const void*)agent_fwd_pipe_kernel<1, false>;
-      else fp = saved ? (const void*)agent_fwd_pipe_kernel<2, true> : xs ? (const void*)agent_fwd_pipe_kernel<2, false, true> : (const void*)agent_fwd_pipe_kernel<2, false>;
-      e = hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_p);
-      if (e != hipSuccess) return (int)e;
-      void* kp[] = {(void*)&a};
-      e = hipLaunchKernel(fp, grid, block, kp, lds_p, s);
-      if (e != hipSuccess) return (int)e;
-      MARL_CHECK_LAUNCH();
-      return 0;
-    }
+    const size_t lds_p = fixed + per_row_p * RT * 16 + 64;
+    if (lds_p <= 160 * 1024) { pl->pipe = 1; pl->xs = gi_in && !saved && !xs_off; pl->lds = lds_p; }
+  }
+  return 0;
+}
+
+// the fp32 half of marl_agent_unroll_fwd_plan (agent_x6.hip): fwd_plan() in the public plan[8] layout
+__attribute__((visibility("hidden"))) int marl_agent_fwd_f32_plan(int B, int T, int N, int O, int A, int last_action, int reuse_network,
+                                                                   int cu_budget, int flags, int* plan) {
+  FwdPlan pl;
+  const int e = fwd_plan(B, T, N, O, A, last_action, reuse_network, cu_budget, flags, &pl);
+  if (e) return e;
+  const long tiles = ((long)B * N + 15) / 16;
+  plan[0] = pl.pipe ? MARL_UNROLL_F32_PIPE : MARL_UNROLL_F32_MULTI;
+  plan[1] = pl.RT; plan[2] = (int)pl.n_wg; plan[3] = (int)(tiles / pl.RT); plan[4] = pl.AC; plan[5] = pl.KC;
+  plan[6] = pl.w2l ? MARL_UNROLL_IN_W2L : pl.half && !pl.pipe && !pl.xs ? MARL_UNROLL_IN_HALF : pl.vload ? MARL_UNROLL_IN_VECTOR : MARL_UNROLL_IN_ELEMENT;
+  plan[7] = pl.xs;
+  return 0;
+}
+
+extern "C" int marl_agent_unroll_fwd(const marl_agent_weights_t* w, const float* obs, long obs_bs, int obs_t0,
+                                     const int* ufed, long u_bs, int u_t0, const int* ep_len, const int* ep_map,
+                                     const float* h0, float* q, float* hs, float* h_last, float* saved, int B,
+                                     int T, int N, int O, int A, int last_action, int reuse_network, int cu_budget,
+                                     float* gi_out, const float* gi_in, void* stream) {
+  if (B <= 0 || T <= 0) return 0;
+  if (w->H != H) return (int)hipErrorInvalidValue;
+  FwdPlan pl;
+  const int flags = (saved ? MARL_UNROLL_SAVED : 0) | (gi_out ? MARL_UNROLL_GI_OUT : 0) | (gi_in ? MARL_UNROLL_GI_IN : 0) | (hs ? MARL_UNROLL_HS : 0) |
+                    ((reinterpret_cast<uintptr_t>(obs) & 15) == 0 ? MARL_UNROLL_OBS_ALIGNED : 0) |
+                    (!(reinterpret_cast<uintptr_t>(h0) & 15) && !(reinterpret_cast<uintptr_t>(h_last) & 15) ? MARL_UNROLL_H_ALIGNED : 0);
+  const int pe = fwd_plan(B, T, N, O, A, last_action, reuse_network, cu_budget, flags, &pl);
+  if (pe) return pe;
+  FwdArgs a;
+  a.W1 = w->fc1_w; a.b1 = w->fc1_b; a.Wih = w->w_ih; a.Whh = w->w_hh; a.bih = w->b_ih; a.bhh = w->b_hh;
+  a.W2 = w->fc2_w; a.b2 = w->fc2_b;
+  a.obs = obs; a.obs_bs = obs_bs; a.obs_t0 = obs_t0; a.ufed = ufed; a.u_bs = u_bs; a.u_t0 = u_t0; a.ep_len = ep_len; a.ep_map = ep_map; a.h0 = h0; a.q = q; a.hs = hs; a.h_last = h_last; a.saved = saved;
+  a.B = B; a.T = T; a.N = N; a.O = O; a.A = A; a.gi_out = saved ? gi_out : nullptr; a.gi_in = gi_in;
+  a.has_act = last_action ? 1 : 0; a.has_id = reuse_network ? 1 : 0;
+  a.I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
+  a.KC = pl.KC;
+  a.R = (long)B * N;
+  a.vload = pl.vload;
+  a.RT = pl.RT;
+  dim3 grid((unsigned)pl.n_wg), block(FNT);
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  if (pl.pipe) {
+    const void* fp;
+    const bool xs = pl.xs != 0;
+    if (A <= 16) fp = saved ? (const void*)agent_fwd_pipe_kernel<1, true> : xs ? (const void*)agent_fwd_pipe_kernel<1, false, true> : (const void*)agent_fwd_pipe_kernel<1, false>;
+    else fp = saved ? (const void*)agent_fwd_pipe_kernel<2, true> : xs ? (const void*)agent_fwd_pipe_kernel<2, false, true> : (const void*)agent_fwd_pipe_kernel<2, false>;
+    e = hipFuncSetAttribute(fp, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+    if (e != hipSuccess) return (int)e;
+    void* kp[] = {(void*)&a};
+    e = hipLaunchKernel(fp, grid, block, kp, pl.lds, s);
+    if (e != hipSuccess) return (int)e;
+    MARL_CHECK_LAUNCH();
+    return 0;
   }
   const void* fn;
 #define FWD_PICK(AC_, SV_, VL_) (const void*)agent_fwd_kernel<AC_, SV_, VL_>
-  const bool sv = saved != nullptr, vl = a.vload != 0;
-  if (xs_req) {
+  const bool sv = saved != nullptr, vl = pl.vload != 0;
+  if (pl.xs) {
     fn = A <= 16 ? (const void*)agent_fwd_kernel<1, false, true, NLDW, true> : (const void*)agent_fwd_kernel<2, false, true, NLDW, true>;
-  } else if (w2l) {
+  } else if (pl.w2l) {
     fn = (const void*)agent_fwd_kernel<2, true, true, 6, false, false, true>;
-  } else if (vl && half) {
+  } else if (vl && pl.half) {
     fn = A <= 16 ? (const void*)agent_fwd_kernel<1, false, true, NLDW, false, true> : (const void*)agent_fwd_kernel<2, false, true, NLDW, false, true>;
   } else
   if (A <= 16) fn = sv ? (vl ? FWD_PICK(1, true, true) : FWD_PICK(1, true, false)) : (vl ? FWD_PICK(1, false, true) : FWD_PICK(1, false, false));
   else fn = sv ? (vl ? FWD_PICK(2, true, true) : FWD_PICK(2, true, false)) : (vl ? FWD_PICK(2, false, true) : FWD_PICK(2, false, false));
 #undef FWD_PICK
-  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
   if (e != hipSuccess) return (int)e;
   void* kargs[] = {(void*)&a};
-  e = hipLaunchKernel(fn, grid, block, kargs, lds, s);
+  e = hipLaunchKernel(fn, grid, block, kargs, pl.lds, s);
   if (e != hipSuccess) return (int)e;
   MARL_CHECK_LAUNCH();
   return 0;

@@ -533,26 +533,90 @@ extern "C" int marl_agent_unroll_x6_plain_r6(int B, int T, int N, int O, int A, 
          marl_agent_x6p_tiles(B, T, N, O, A, last_action, reuse_network, cu_budget) ? 1 : 0;
 }
 
+// What a launch of the split unroll does, decided on the host from the dimensions and from what the caller passes: the ONE place
+// both marl_agent_unroll_fwd_x6 and the plan query take it from.
+struct X6Plan {
+  int tpw;                 // > 0: the round-6 decomposition (agent_x6p.hip) at that many row tiles per workgroup
+  int RT, n_full, wide;    // this file's kernel: row tiles per workgroup, workgroups that hold RT of them, 0 / 1 / 2 = three / five / seven fc1 chunks
+  long n_wg;
+  size_t lds;
+};
+
+// flags: MARL_UNROLL_* of include/marl_hip.h.  0, or hipErrorInvalidValue where the entry point refuses the call.
+static int x6_plan(int B, int T, int N, int O, int A, int last_action, int reuse_network, int cu_budget, int flags, X6Plan* pl) {
+  const bool saved = (flags & MARL_UNROLL_SAVED) != 0, gi_in = (flags & MARL_UNROLL_GI_IN) != 0, hs = (flags & MARL_UNROLL_HS) != 0;
+  if (cu_budget < 0 || cu_budget > 256 || !marl_agent_unroll_x6_supported(B, T, N, O, A, last_action, reuse_network))
+    return (int)hipErrorInvalidValue;
+  if (saved && gi_in) return (int)hipErrorInvalidValue;      // a launch stores the input-side sums or reads them
+  if (!(flags & MARL_UNROLL_OBS_ALIGNED)) return (int)hipErrorInvalidValue;      // either kernel reads obs as 16-byte vectors
+  pl->tpw = 0;
+  // a plain unroll of a large batch: the round-6 decomposition (agent_x6p.hip), which reads h0 and writes h_last as 16-byte vectors;
+  // this file's kernel takes the other alignments
+  if (!saved && !gi_in && !hs && (flags & MARL_UNROLL_H_ALIGNED)) {
+    pl->tpw = marl_agent_x6p_tiles(B, T, N, O, A, last_action, reuse_network, cu_budget);
+    if (pl->tpw) {
+      const long tiles = ((long)B * N + 15) / 16;
+      pl->RT = pl->tpw; pl->n_wg = (tiles + pl->tpw - 1) / pl->tpw; pl->n_full = (int)(tiles / pl->tpw); pl->wide = 0; pl->lds = 0;
+      return 0;
+    }
+  }
+  if (cu_budget == 0) cu_budget = 256;
+  const int I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
+  const int KI = (I + 31) / 32 * 32;
+  const long tiles = ((long)B * N + 15) / 16;
+  // two row tiles per workgroup once there are more tiles than CUs this launch may occupy (more than two do not fit LDS: larger
+  // batches run in rounds of workgroups, and when the last round is at most one tile per CU its workgroups hold one tile each)
+  const int wide = KI > 160 ? 2 : KI > 96 ? 1 : 0;      // five / seven fc1 chunks: one row tile per workgroup (LDS), any number of rounds
+  const int rt = tiles > cu_budget && !wide ? 2 : 1;
+  if (rt * 16 * (O / 4) > 3 * 256) return (int)hipErrorInvalidValue;        // (the prefetch registers: three float4 per thread of one team)
+  long n_wg = (tiles + rt - 1) / rt;
+  int n_full = (int)n_wg;
+  if (rt == 2) {
+    const long k = (tiles + 2 * cu_budget - 1) / (2 * cu_budget), rem = tiles - 2L * cu_budget * (k - 1);
+    if (rem <= cu_budget) { n_full = (int)(cu_budget * (k - 1)); n_wg = n_full + rem; }
+  }
+  const int rows = rt * 16, IP = KI + 8;
+  const size_t lds = (size_t)2 * 3 * rows * IP * 2 + (size_t)4 * 3 * rows * HP * 2 + (size_t)2 * rt * 4 * 3 * 1024 + (size_t)rows * (2 * 8 + 4 * 4) +
+                     (((size_t)T * 4 + 15) & ~(size_t)15) + (wide == 2 ? (size_t)4 * 2 * 3 * 1024 : 0);      // (+ the fc1 fragments of the widest instantiation that live in LDS)
+  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  pl->RT = rt; pl->n_full = n_full; pl->wide = wide; pl->n_wg = n_wg; pl->lds = lds;
+  return 0;
+}
+
+int marl_agent_fwd_f32_plan(int B, int T, int N, int O, int A, int last_action, int reuse_network, int cu_budget, int flags, int* plan);   // agent.hip
+
+extern "C" int marl_agent_unroll_fwd_plan(int x6, int B, int T, int N, int O, int A, int last_action, int reuse_network, int cu_budget,
+                                          int flags, int* plan) {
+  if (!plan || B <= 0 || T <= 0) return (int)hipErrorInvalidValue;
+  if (!x6) return marl_agent_fwd_f32_plan(B, T, N, O, A, last_action, reuse_network, cu_budget, flags, plan);
+  X6Plan pl;
+  const int e = x6_plan(B, T, N, O, A, last_action, reuse_network, cu_budget, flags, &pl);
+  if (e) return e;
+  plan[0] = pl.tpw ? MARL_UNROLL_X6_R6 : MARL_UNROLL_X6;
+  plan[1] = pl.RT; plan[2] = (int)pl.n_wg; plan[3] = pl.n_full;
+  plan[4] = pl.wide == 2 ? 2 : 1; plan[5] = 3 + 2 * pl.wide; plan[6] = MARL_UNROLL_IN_VECTOR;
+  plan[7] = !pl.tpw && (flags & MARL_UNROLL_GI_IN) ? 1 : 0;
+  return 0;
+}
+
 extern "C" int marl_agent_unroll_fwd_x6(const marl_agent_weights_t* w, const float* obs, long obs_bs, int obs_t0,
                                         const int* ufed, long u_bs, int u_t0, const int* ep_len, const int* ep_map,
                                         const float* h0, float* q, float* hs, float* h_last, float* saved, int B, int T, int N,
                                         int O, int A, int last_action, int reuse_network, int cu_budget, float* gi_out,
                                         const float* gi_in, void* stream) {
   if (B <= 0 || T <= 0) return 0;
-  if (w->H != H || cu_budget < 0 || cu_budget > 256 || !marl_agent_unroll_x6_supported(B, T, N, O, A, last_action, reuse_network))
-    return (int)hipErrorInvalidValue;
-  if (saved && gi_in) return (int)hipErrorInvalidValue;      // a launch stores the input-side sums or reads them
-  // a plain unroll of a large batch: the round-6 decomposition (agent_x6p.hip), which reads h0 and writes h_last as 16-byte vectors;
-  // this file's kernel takes the other alignments
-  if (!saved && !gi_in && !hs && !(reinterpret_cast<uintptr_t>(h0) & 15) && !(reinterpret_cast<uintptr_t>(h_last) & 15)) {
-    const int tpw = marl_agent_x6p_tiles(B, T, N, O, A, last_action, reuse_network, cu_budget);
-    if (tpw) return marl_agent_x6p_launch(w, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, ep_len, ep_map, h0, q, h_last, B, T, N, O, A, last_action,
-                                          reuse_network, tpw, stream);
-  }
-  if ((reinterpret_cast<uintptr_t>(obs) & 15) || (h0 && (reinterpret_cast<uintptr_t>(h0) & 3)) || (saved && (reinterpret_cast<uintptr_t>(saved) & 15)) ||
+  if (w->H != H) return (int)hipErrorInvalidValue;
+  X6Plan pl;
+  const int flags = (saved ? MARL_UNROLL_SAVED : 0) | (gi_out ? MARL_UNROLL_GI_OUT : 0) | (gi_in ? MARL_UNROLL_GI_IN : 0) | (hs ? MARL_UNROLL_HS : 0) |
+                    ((reinterpret_cast<uintptr_t>(obs) & 15) == 0 ? MARL_UNROLL_OBS_ALIGNED : 0) |
+                    (!(reinterpret_cast<uintptr_t>(h0) & 15) && !(reinterpret_cast<uintptr_t>(h_last) & 15) ? MARL_UNROLL_H_ALIGNED : 0);
+  const int pe = x6_plan(B, T, N, O, A, last_action, reuse_network, cu_budget, flags, &pl);
+  if (pe) return pe;
+  if (pl.tpw) return marl_agent_x6p_launch(w, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, ep_len, ep_map, h0, q, h_last, B, T, N, O, A, last_action,
+                                           reuse_network, pl.tpw, stream);
+  if ((h0 && (reinterpret_cast<uintptr_t>(h0) & 3)) || (saved && (reinterpret_cast<uintptr_t>(saved) & 15)) ||
       (gi_out && (reinterpret_cast<uintptr_t>(gi_out) & 15)) || (gi_in && (reinterpret_cast<uintptr_t>(gi_in) & 15)))
     return (int)hipErrorInvalidValue;
-  if (cu_budget == 0) cu_budget = 256;
   X6Args a;
   a.W1 = w->fc1_w; a.b1 = w->fc1_b; a.Wih = w->w_ih; a.Whh = w->w_hh; a.bih = w->b_ih; a.bhh = w->b_hh; a.W2 = w->fc2_w; a.b2 = w->fc2_b;
   a.obs = obs; a.obs_bs = obs_bs; a.obs_t0 = obs_t0; a.ufed = ufed; a.u_bs = u_bs; a.u_t0 = u_t0; a.ep_len = ep_len; a.ep_map = ep_map;
@@ -562,23 +626,9 @@ extern "C" int marl_agent_unroll_fwd_x6(const marl_agent_weights_t* w, const flo
   a.I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
   a.KI = (a.I + 31) / 32 * 32;
   a.R = (long)B * N;
-  const long tiles = (a.R + 15) / 16;
-  // two row tiles per workgroup once there are more tiles than CUs this launch may occupy (more than two do not fit LDS: larger
-  // batches run in rounds of workgroups, and when the last round is at most one tile per CU its workgroups hold one tile each)
-  const int wide = a.KI > 160 ? 2 : a.KI > 96 ? 1 : 0;      // five / seven fc1 chunks: one row tile per workgroup (LDS), any number of rounds
-  const int rt = tiles > cu_budget && !wide ? 2 : 1;
-  if (rt * 16 * (O / 4) > 3 * 256) return (int)hipErrorInvalidValue;        // (the prefetch registers: three float4 per thread of one team)
-  a.RT = rt;
-  long n_wg = (tiles + rt - 1) / rt;
-  a.n_full = (int)n_wg;
-  if (rt == 2) {
-    const long k = (tiles + 2 * cu_budget - 1) / (2 * cu_budget), rem = tiles - 2L * cu_budget * (k - 1);
-    if (rem <= cu_budget) { a.n_full = (int)(cu_budget * (k - 1)); n_wg = a.n_full + rem; }
-  }
-  const int rows = rt * 16, IP = a.KI + 8;
-  const size_t lds = (size_t)2 * 3 * rows * IP * 2 + (size_t)4 * 3 * rows * HP * 2 + (size_t)2 * rt * 4 * 3 * 1024 + (size_t)rows * (2 * 8 + 4 * 4) +
-                     (((size_t)T * 4 + 15) & ~(size_t)15) + (wide == 2 ? (size_t)4 * 2 * 3 * 1024 : 0);      // (+ the fc1 fragments of the widest instantiation that live in LDS)
-  if (lds > 160 * 1024) return (int)hipErrorInvalidValue;
+  a.RT = pl.RT;
+  a.n_full = pl.n_full;
+  const int wide = pl.wide, rt = pl.RT;
   const void* fn;
 #define X6_PICKF(SAVE_, XS_, GIO_) (wide == 2 ? (const void*)agent_fwd_x6_kernel<1, SAVE_, XS_, GIO_, 7, 2>                         \
                                     : wide == 1 ? (const void*)agent_fwd_x6_kernel<1, SAVE_, XS_, GIO_, 5, 1>                       \
@@ -588,11 +638,11 @@ extern "C" int marl_agent_unroll_fwd_x6(const marl_agent_weights_t* w, const flo
   else if (gi_in) fn = X6_PICKF(false, true, false);
   else fn = X6_PICKF(false, false, false);
 #undef X6_PICKF
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
   if (e != hipSuccess) return (int)e;
-  dim3 grid((unsigned)n_wg), block(XNT);
+  dim3 grid((unsigned)pl.n_wg), block(XNT);
   void* kargs[] = {(void*)&a};
-  e = hipLaunchKernel(fn, grid, block, kargs, lds, (hipStream_t)stream);
+  e = hipLaunchKernel(fn, grid, block, kargs, pl.lds, (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
   MARL_CHECK_LAUNCH();
   return 0;

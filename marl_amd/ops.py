@@ -200,6 +200,23 @@ def agent_unroll_fwd_x6(w, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, h0, q, hs, h_l
           "marl_agent_unroll_fwd_x6")
 
 
+UNROLL_FAMILIES = ("f32-pipe", "f32-multi", "x6", "x6-r6")          # plan[0] of marl_agent_unroll_fwd_plan (include/marl_hip.h)
+UNROLL_INPUT_PATHS = ("element", "vector", "half", "w2l")            # plan[6]
+
+
+def agent_unroll_fwd_plan(x6, B, T, N, O, A, last_action=True, reuse_network=True, cu_budget=0, saved=False, gi_out=False,
+                          gi_in=False, hs=True, obs_aligned=True, h_aligned=True):
+    """The launch plan of agent_unroll_fwd (x6 False) / agent_unroll_fwd_x6 (x6 True), from the host function the launch itself
+    calls - no GPU: (family, row tiles per workgroup, workgroups, workgroups holding that many tiles, action tiles, fc1 chunks,
+    input path, reads gi_in), or None where the entry point refuses the call.  The keywords say what the caller would pass."""
+    flags = (1 if saved else 0) | (2 if gi_out else 0) | (4 if gi_in else 0) | (8 if hs else 0) | (16 if obs_aligned else 0) | (32 if h_aligned else 0)
+    plan = (C.c_int * 8)()
+    if _lib.load().marl_agent_unroll_fwd_plan(1 if x6 else 0, B, T, N, O, A, 1 if last_action else 0, 1 if reuse_network else 0,
+                                              int(cu_budget), flags, plan) != 0:
+        return None
+    return tuple(plan)
+
+
 def saved_shape(T, B, N, planes=6, H=64):
     """Shape of the activation buffer an unroll saves for BPTT (planes = 6) or of its input-side gate sums (planes = 3):
     the kernels use a tile layout [T][16-row tile][plane][column tile][lane][4] (csrc/agent.hip: sv_off), so the row count is

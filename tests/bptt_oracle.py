@@ -172,14 +172,21 @@ def make_dq(c, form):
 
 
 # --------------------------------------------------------------------------------------------------------- the operation
-def _step(p, pre, h):
-    """oracle/nets.agent_step from the fc1 pre-activation on"""
+def gates(p, pre, h):
+    """x, gi, gh, r, z, n of oracle/nets.agent_step from the fc1 pre-activation on (tests/unroll_oracle.py reads the vectors the
+    forward kernels save from here)"""
     x = torch.relu(pre)
     gi = F.linear(x, p["rnn.weight_ih"], p["rnn.bias_ih"])
     gh = F.linear(h, p["rnn.weight_hh"], p["rnn.bias_hh"])
     r = torch.sigmoid(gi[:, :H] + gh[:, :H])
     z = torch.sigmoid(gi[:, H:2 * H] + gh[:, H:2 * H])
     n = torch.tanh(gi[:, 2 * H:] + r * gh[:, 2 * H:])
+    return x, gi, gh, r, z, n
+
+
+def _step(p, pre, h):
+    """oracle/nets.agent_step from the fc1 pre-activation on"""
+    x, gi, gh, r, z, n = gates(p, pre, h)
     h2 = (1.0 - z) * n + z * h
     return nets.lin(p, "fc2", h2), h2
 

@@ -132,6 +132,47 @@ def test_split_kernel_capability_predicates():
     assert lib.marl_agent_bwd_x6_workspace(1024, 5, 11) == 160 * slab                  # 320 tiles: less than one full round of two-tile workgroups
 
 
+def test_forward_unroll_plan_query_at_the_learners_sizes():
+    """marl_agent_unroll_fwd_plan (a host function, no GPU: the planner the launch itself calls) at the sizes the learner runs -
+    (family 0 fp32 pipelined / 1 fp32 multi-tile / 2 split / 3 split round-6, row tiles per workgroup, workgroups, workgroups holding
+    that many tiles, action tiles, fc1 chunks, input path 0 element / 1 vector / 2 half-tile / 3 W2L, reads gi_in)."""
+    from marl_amd import ops
+    q = ops.agent_unroll_fwd_plan
+    save, plain, cont = dict(saved=True, gi_out=True), dict(hs=False), dict(gi_in=True, hs=False)
+    s2 = lambda x6, E, cu, kw: q(x6, E, 120, 5, 80, 11, cu_budget=cu, **kw)
+    # 2s3z, 512 environments = 160 row tiles: the pair schedule (128 CUs) packs two tiles per workgroup, the whole chip one (pipelined)
+    assert s2(0, 512, 128, save) == (1, 2, 80, 80, 1, 6, 1, 0) and s2(0, 512, 128, cont) == (1, 2, 80, 80, 1, 6, 1, 1)
+    assert s2(0, 512, 0, save) == s2(0, 512, 0, plain) == (0, 1, 160, 160, 1, 6, 1, 0) and s2(0, 512, 0, cont) == (0, 1, 160, 160, 1, 6, 1, 1)
+    assert s2(1, 512, 128, save) == (2, 2, 80, 80, 1, 3, 1, 0) and s2(1, 512, 0, save) == s2(1, 512, 0, plain) == (2, 1, 160, 160, 1, 3, 1, 0)
+    assert s2(1, 512, 0, cont) == (2, 1, 160, 160, 1, 3, 1, 1)
+    # 4096 environments = 1280 tiles: fp32 at the six tiles LDS allows (half-tile prefetch when nothing is saved) / five on the whole
+    # chip; the split kernel in rounds - 2 x 256 two-tile + 256 one-tile workgroups - and its plain unroll on round 6 at five tiles
+    assert s2(0, 4096, 128, save) == (1, 6, 214, 213, 1, 6, 1, 0) and s2(0, 4096, 128, plain) == (1, 6, 214, 213, 1, 6, 2, 0)
+    assert s2(0, 4096, 0, save) == (1, 5, 256, 256, 1, 6, 1, 0) and s2(0, 4096, 0, cont) == (1, 5, 256, 256, 1, 6, 1, 1)
+    assert s2(1, 4096, 128, save) == (2, 2, 640, 640, 1, 3, 1, 0) and s2(1, 4096, 0, save) == (2, 2, 768, 512, 1, 3, 1, 0)
+    assert s2(1, 4096, 0, plain) == (3, 5, 256, 256, 1, 3, 1, 0) and s2(1, 4096, 0, cont) == (2, 2, 768, 512, 1, 3, 1, 1)
+    assert s2(1, 4096, 0, dict(hs=True)) == (2, 2, 768, 512, 1, 3, 1, 0)          # (hidden states wanted: not the round-6 kernel)
+    # MMM2 at 1024 environments = 640 tiles: saving on W2L at three tiles alone on the chip, two beside the target unroll
+    mm = lambda x6, cu, kw: q(x6, 1024, 120, 10, 176, 18, cu_budget=cu, **kw)
+    assert mm(0, 0, save) == (1, 3, 214, 213, 2, 13, 3, 0) and mm(0, 128, save) == (1, 2, 320, 320, 2, 13, 1, 0)
+    assert mm(0, 0, plain) == (1, 3, 214, 213, 2, 13, 2, 0) and mm(0, 128, plain) == (1, 4, 160, 160, 2, 13, 2, 0)
+    assert mm(0, 0, cont) == (1, 3, 214, 213, 2, 13, 1, 1)
+    assert mm(1, 0, save) == mm(1, 128, save) == mm(1, 0, plain) == (2, 1, 640, 640, 2, 7, 1, 0) and mm(1, 0, cont) == (2, 1, 640, 640, 2, 7, 1, 1)
+    # the round-6 threshold: more than 512 tiles, whole chip, no hidden states, h0 / h_last 16-byte aligned
+    r6 = lambda rows, **kw: q(1, rows, 4, 1, 48, 11, **dict(dict(hs=False), **kw))
+    assert r6(8192) == (2, 2, 256, 256, 1, 3, 1, 0) and r6(8193) == (3, 3, 171, 171, 1, 3, 1, 0)
+    assert r6(8193, hs=True) == r6(8193, h_aligned=False) == r6(8193, cu_budget=128) == (2, 2, 257, 256, 1, 3, 1, 0)
+    assert bool(lib_r6(8193)) and not lib_r6(8192)
+    # refusals: what either entry point returns hipErrorInvalidValue for
+    assert q(0, 512, 120, 5, 80, 33) is None and q(1, 512, 120, 5, 80, 11, obs_aligned=False) is None and q(1, 512, 3, 5, 80, 11) is None
+    assert q(0, 512, 120, 5, 80, 11, obs_aligned=False) == (1, 1, 160, 160, 1, 6, 0, 0)          # (fp32: element-wise instead)
+
+
+def lib_r6(rows):
+    from marl_amd import ops
+    return ops.agent_unroll_x6_plain_r6(rows, 4, 1, 48, 11)
+
+
 def test_qtran_row_kernel_predicates_and_workspace():
     """Host functions of the QTRAN row-level kernels (no GPU): which state widths / encoder widths they cover, and the slab
     workspace the row-gradient kernel asks for (256 workgroups x [64 x 16 ceil(S/16) | 64 x AEP | 64 x 64 | AEP x AEP | 256])."""
