@@ -837,6 +837,46 @@ int marl_maic_aux(const marl_maic_weights_t* w, const marl_maic_infer_t* iw, con
  * stream 8 keyed by (rseed, env, tg = the global step), as marl_select_actions draws its own. */
 int marl_maic_noise(unsigned rseed, int env0, unsigned tg, float* eps, int E, int N, void* stream);
 
+/* ---- CommNet communication head (commnet.hip) ---------------------------------------------------------------------------
+ * The communicating actor of the +commnet algorithms (the reference ships only their argument table; the definition is this
+ * project's own, taken from the published implementation the table comes from).  CommNetAgent, H = 64, K = args.k rounds:
+ *   encoding = Linear(I, H), f_obs = GRUCell(H, H), f_comm = GRUCell(H, H), decoding = Linear(H, A)   (torch's gate order r, z, n)
+ * Per step t and environment, over the N agent rows (x_t the virtual input [obs | one-hot(u_{t-1}) | agent id]):
+ *   e      = sigmoid(encoding(x_t))
+ *   h_t    = f_obs(e, h_{t-1})                  the ONLY recurrence in time: marl_agent_unroll_fwd over an identity front layer
+ *   g^(0)  = f_comm(0, h_t)                     round 0 runs with a zero input: its input side is b_ih alone (also at K = 1)
+ *   g^(j)  = f_comm(c^(j), g^(j-1)),  c_i^(j) = (sum over l != i of g_l^(j-1)) / N      j = 1 .. K-1: the divisor is N, not N - 1
+ *   logits = decoding(g^(K-1))
+ * Dead agents and finished environments are NOT masked out of the sum.  Nothing couples two environments or two steps.
+ * The head entries below take G = B*T environment-steps ("groups") of N rows each; all rows of a group are in one workgroup, a
+ * workgroup's 16-row tile holds marl_commnet_groups_per_workgroup(N) = 16 / N whole groups.  fp32 MFMA products. */
+typedef struct {
+  const float *w_ih, *w_hh, *b_ih, *b_hh;   /* f_comm: (192,64), (192,64), (192), (192) */
+  const float *dec_w, *dec_b;               /* decoding: (A,64), (A) */
+} marl_commnet_weights_t;
+typedef struct {
+  float *w_ih, *w_hh, *b_ih, *b_hh, *dec_w, *dec_b;
+} marl_commnet_grads_t;
+/* 1 when the head kernels cover the shape: 1 <= N <= 16, 1 <= A <= 32, 1 <= K <= 4.  Outside it both entries return
+ * hipErrorInvalidValue and launch nothing. */
+int marl_commnet_supported(int N, int A, int K);
+int marl_commnet_groups_per_workgroup(int N);
+/* logits (G,N,A) <- hs (G,N,64).  G = 0 launches nothing and returns 0. */
+int marl_commnet_head_fwd(const marl_commnet_weights_t* w, const float* hs, float* logits, long G, int N, int A, int K,
+                          void* stream);
+/* The backward of marl_commnet_head_fwd: dhs (G,N,64) is WRITTEN with the gradient on hs for dlogits (G,N,A); the gradients of
+ * f_comm's four tensors and of decoding's two are ADDED into g.  Every intermediate is recomputed from hs (nothing is kept by the
+ * forward).  Reverse over the rounds: dc_i = dgi_i W_ih, and every other agent l of the group receives (sum_{i != l} dc_i) / N.
+ * Weight gradients: one partial slab per workgroup, added in slab order by a second kernel - no float atomics, two calls give the
+ * same bits.  ws: marl_commnet_bwd_workspace() bytes (at most 256 slabs of 27040 floats). */
+size_t marl_commnet_bwd_workspace(long G, int N, int A, int K);
+int marl_commnet_head_bwd(const marl_commnet_weights_t* w, const marl_commnet_grads_t* g, const float* hs, const float* dlogits,
+                          float* dhs, float* ws, size_t ws_bytes, long G, int N, int A, int K, void* stream);
+/* The encoder's sigmoid, elementwise over n floats: x <- sigmoid(x) in place (on marl_linear's output), and
+ * dxp = de * e * (1 - e) (dxp may be de).  float4 over the 16-byte aligned middle; any 4-byte aligned view gives the same bits. */
+int marl_commnet_sigmoid_fwd(float* x, long n, void* stream);
+int marl_commnet_sigmoid_bwd(const float* de, const float* e, float* dxp, long n, void* stream);
+
 const char* marl_hip_version(void);
 
 /* Experiment switches (A/B measurements, variant tests): one table per process; NO entry point reads the environment.

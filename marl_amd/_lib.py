@@ -78,6 +78,14 @@ class MarlMaicInferGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("i0_w", "i0_b", "ibn_w", "ibn_b", "i3_w", "i3_b")]
 
 
+class MarlCommnetWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "dec_w", "dec_b")]
+
+
+class MarlCommnetGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "dec_w", "dec_b")]
+
+
 class MarlAgentGrads(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p),
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
@@ -99,6 +107,7 @@ RW = C.POINTER(MarlRtwWeights)
 WW, WG = C.POINTER(MarlWorldWeights), C.POINTER(MarlWorldGrads)
 MW, MG = C.POINTER(MarlMaicWeights), C.POINTER(MarlMaicGrads)
 MIW, MIG = C.POINTER(MarlMaicInfer), C.POINTER(MarlMaicInferGrads)
+CW, CG = C.POINTER(MarlCommnetWeights), C.POINTER(MarlCommnetGrads)
 
 # name -> (restype, argtypes); must list every symbol of include/marl_hip.h
 SIGNATURES = {
@@ -212,6 +221,13 @@ SIGNATURES = {
     "marl_maic_head_bwd_ex": (I, [MW, MG, P, P, P, P, P, P, P, SZ, I, I, I, I, I, F, F, P]),
     "marl_maic_aux_workspace": (SZ, [I, I, I]),
     "marl_maic_aux": (I, [MW, MIW, MG, MIG, P, P, P, F, F, P, F, P, P, P, P, P, SZ, I, I, I, I, I, F, F, F, P]),
+    "marl_commnet_supported": (I, [I, I, I]),
+    "marl_commnet_groups_per_workgroup": (I, [I]),
+    "marl_commnet_head_fwd": (I, [CW, P, P, L, I, I, I, P]),
+    "marl_commnet_bwd_workspace": (SZ, [L, I, I, I]),
+    "marl_commnet_head_bwd": (I, [CW, CG, P, P, P, P, SZ, L, I, I, I, P]),
+    "marl_commnet_sigmoid_fwd": (I, [P, L, P]),
+    "marl_commnet_sigmoid_bwd": (I, [P, P, P, L, P]),
     "marl_hip_version": (C.c_char_p, []),
     "marl_experiment_set": (I, [C.c_char_p, I]),
     "marl_experiment_get": (I, [C.c_char_p]),

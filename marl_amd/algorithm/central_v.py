@@ -29,7 +29,7 @@ import torch.nn as nn
 from .. import ops
 from ..hostutil import flatten_module, lin_of, require_cuda
 from .reinforce import entropy_coef_of
-from .common import (LearnerParams, FlatView, FusedOptimizer, Learner, LossReadback, GradReducer, Scratch, agent_backward,
+from .common import (LearnerParams, FlatView, FusedOptimizer, Learner, LossReadback, GradReducer, Scratch, policy_backward, policy_hs,
                      td_lambda_of)
 
 
@@ -134,7 +134,8 @@ class CentralVLearner(Learner):
         # 1. the eval unroll keeps its activations for BPTT (the split kernel in gemm_mode "bf16x6", where QLearner's takes it)
         logits, saved, h_last = g("logits", (B, T, N, A)), g("saved", ops.saved_shape(T, B, N)), g("h_last", (B * N, H))
         oc, oc_bs, oc_t0 = db.o_cur
-        self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, logits, None, h_last, saved, h0=None,
+        hs = policy_hs(self.eval_net, g, (B, T, N, H))
+        self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, logits, hs, h_last, saved, h0=None,
                              ep_len=db.ep_len, ep_map=getattr(db, 'o_map', None))
         # 2. - 4. V(s), V_target(s_next) and its lambda-returns (padded steps carry zero states: finite on every row)
         v, h1, h2 = self._critic_forward(self.critic, db.s, BT, "", True)
@@ -158,7 +159,7 @@ class CentralVLearner(Learner):
             ent = self._dbg["ent"] = g("ent", (R,))
             ops.policy_loss_bwd_ex(logits, db.avail, db.u_act.reshape(-1), G, v.view(BT), db.padded, self.epsilon, self.beta,
                                    dlogits, logp, ent, self._flat.stats[:3], R, N, A)
-        agent_backward(self.eval_net, db, "cur", saved, None, dlogits, None, self._buf)
+        policy_backward(self.eval_net, db, saved, hs, dlogits, self._buf)
 
     def train(self, batch, train_step, epsilon=0.0):
         """One update on the episodes just generated; ``epsilon``: the exploration rate their actions were drawn at.  Returns the

@@ -34,7 +34,7 @@ import torch.nn as nn
 from .. import ops
 from ..hostutil import lin_of
 from .central_v import CentralVLearner
-from .common import agent_backward, td_lambda_of
+from .common import policy_backward, policy_hs, td_lambda_of
 
 
 def critic_input_dim(args):
@@ -112,7 +112,8 @@ class COMALearner(CentralVLearner):
         # 1. the eval unroll keeps its activations for BPTT
         logits, saved, h_last = g("logits", (B, T, N, A)), g("saved", ops.saved_shape(T, B, N)), g("h_last", (B * N, H))
         oc, oc_bs, oc_t0 = db.o_cur
-        self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, logits, None, h_last, saved, h0=None,
+        hs = policy_hs(self.eval_net, g, (B, T, N, H))
+        self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, logits, hs, h_last, saved, h0=None,
                              ep_len=db.ep_len, ep_map=getattr(db, 'o_map', None))
         # 2. - 4. Q, the target critic's Q of the next step's taken action, its lambda-returns per agent (r, term and padded are
         # expanded over the agents on the host side: plumbing)
@@ -136,7 +137,7 @@ class COMALearner(CentralVLearner):
                          ent=ent)
         # 6. - 7. the critic backward, and BPTT on the dense gradient of the logits (the fp32 kernel in either gemm mode)
         self._critic_backward(db, h1, h2, dq)
-        agent_backward(self.eval_net, db, "cur", saved, None, dlogits, None, self._buf)
+        policy_backward(self.eval_net, db, saved, hs, dlogits, self._buf)
 
     def get_q_and_q_tot_table(self):
         raise NotImplementedError("COMA has no joint Q table: its critic is counterfactual, one agent's actions at a time")

@@ -381,6 +381,21 @@ def agent_backward(mac, db, which, saved, hs, dq, dhs, buf, dq_idx=None, dq_val=
     ops.linear_wgrad(dxp.view(M, H), xin, ag.fc1.weight.grad, ag.fc1.bias.grad, M, H, I, bf16=False)   # agent layers stay fp32
 
 
+def policy_backward(mac, db, saved, hs, dlogits, buf):
+    """The actor's backward of the policy learners on the dense gradient of the logits: a controller with a ``backward`` of its own
+    (CommNetMAC: head, recurrence and encoder) runs that; otherwise BPTT of the plain unroll, exactly as before."""
+    if hasattr(mac, "backward"):
+        mac.backward(db, saved, hs, dlogits, buf)
+    else:
+        agent_backward(mac, db, "cur", saved, None, dlogits, None, buf)
+
+
+def policy_hs(mac, g, shape):
+    """what a controller with a ``backward`` of its own keeps between its unroll and that backward, in the learner's scratch buffers
+    (``mac.planes``; passed to the unroll in the place of hs) - None for a controller without one"""
+    return mac.planes(g, shape) if hasattr(mac, "backward") else None
+
+
 class GradReducer:
     """Data-parallel exchange step: ONE all-reduce(sum) of [gradients | loss numerators | sum(mask)]
     over RCCL/xGMI (SURVEY 8e exactness rule: un-normalised numerators are summed, the division by

@@ -17,7 +17,7 @@ import os
 
 from .. import ops
 from ..hostutil import require_cuda
-from .common import LearnerParams, FlatView, FusedOptimizer, Learner, LossReadback, GradReducer, Scratch, agent_backward
+from .common import LearnerParams, FlatView, FusedOptimizer, Learner, LossReadback, GradReducer, Scratch, policy_backward, policy_hs
 
 
 def entropy_coef_of(args):
@@ -76,7 +76,8 @@ class ReinforceLearner(Learner):
         BT, R = B * T, B * T * N
         logits, saved, h_last = g("logits", (B, T, N, A)), g("saved", ops.saved_shape(T, B, N)), g("h_last", (B * N, H))
         oc, oc_bs, oc_t0 = db.o_cur
-        self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, logits, None, h_last, saved, h0=None,
+        hs = policy_hs(self.eval_net, g, (B, T, N, H))
+        self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, logits, hs, h_last, saved, h0=None,
                              ep_len=db.ep_len, ep_map=getattr(db, 'o_map', None))
         # the Monte-Carlo return: lambda = 1 leaves q_next only in the bootstrap of an unterminated episode, and q_next is 0
         G, q0 = g("td_ret", (BT,)), g("q_next0", (BT,))
@@ -86,7 +87,7 @@ class ReinforceLearner(Learner):
         dlogits, logp, ent = g("dlogits", (B, T, N, A)), g("logp", (R,)), g("ent", (R,))
         ops.policy_loss_bwd_ex(logits, db.avail, db.u_act.reshape(-1), G, None, db.padded, self.epsilon, self.beta, dlogits, logp,
                                ent, self._flat.stats[:3], R, N, A)
-        agent_backward(self.eval_net, db, "cur", saved, None, dlogits, None, self._buf)
+        policy_backward(self.eval_net, db, saved, hs, dlogits, self._buf)
         self._dbg = dict(logits=logits, td_targets=G, logp=logp, ent=ent, dlogits=dlogits)
 
     def train(self, batch, train_step, epsilon=0.0):

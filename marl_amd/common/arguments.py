@@ -29,6 +29,8 @@ def get_common_args(argv=None):
     # weight of the entropy bonus on the actor loss of the policy-gradient learners (central_v, reinforce, coma); the reference's tables
     # carry entropy_coefficient = 0.001 and nothing reads it.  (--entropy_loss_weight is MAIC's attention entropy)
     p.add_argument('--policy_entropy_coef', type=float, default=0.0)
+    # communication rounds of the +commnet actors; absent = get_commnet_args' table (2 on map 3m, otherwise 3)
+    p.add_argument('--commnet_k', type=int, default=None)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')

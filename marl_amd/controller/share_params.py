@@ -17,6 +17,7 @@ from ..network.q_network import RNNQNet
 from ..network.rtw import RTWAgent
 from ..network.world_model import Agent as WorldAgent
 from ..network.maic import MAICAgent
+from ..network.commnet import CommNetAgent, FRONT_A
 
 
 class SharedMAC:
@@ -132,6 +133,17 @@ class SharedMAC:
 
     def rollout_head(self, h, q, rec, t, E, evaluate, rseed, env):
         """q (E,1,N,A) += the head's term at lock-step t of a batched rollout (h (E*N,H): the step's GRU output)"""
+
+    def rollout_weights(self):
+        """what a batched rollout looks up once and hands to every ``rollout_step``"""
+        return self.agent.weights()
+
+    def rollout_step(self, w, rec, t, h, q, E):
+        """the agent step of lock-step t of a batched rollout: the unroll kernel with T = 1 reading slot t of the record in place;
+        h (E*N,H) is advanced in place, q (E,1,N,A) written"""
+        N, T, a = self.n_agents, rec.T, self.args
+        ops.agent_unroll_fwd(w, rec.obs, (T + 1) * N, t, rec.u, T * N, t - 1, h, q, None, h, None,
+                             E, 1, N, self.obs_shape, self.n_actions, a.last_action, a.reuse_network)
 
     # ------------------------------------------------------------------ batched primitives
     def unroll_x6(self, B, T, obs=None):
@@ -279,6 +291,145 @@ class PolicyMAC(SharedMAC):
         if evaluate:
             return int(np.argmax(pi))
         return int(np.random.choice(A, p=pi / pi.sum()))
+
+
+def commnet_k_of(args, n_agents=None, n_actions=None):
+    """args.k as the head kernels take it; anything they do not cover is an error.  ``n_agents`` / ``n_actions``: instead of the
+    namespace's (the launcher checks k alone before it knows them)"""
+    k = getattr(args, "k", None)
+    N = args.n_agents if n_agents is None else n_agents
+    A = args.n_actions if n_actions is None else n_actions
+    if isinstance(k, bool) or not isinstance(k, int) or not ops.commnet_supported(N, A, k):
+        raise ValueError("CommNet: k = %r rounds with %d agents and %d actions is outside the head kernels' range "
+                         "(marl_commnet_supported)" % (k, N, A))
+    return k
+
+
+class CommNetPlanes:
+    """What CommNetMAC.backward reads of the unroll it follows, in buffers the caller owns: the hidden states ``hs`` and the encoder's
+    output ``e``, both (B, T, N, H).  Passed to ``unroll`` in the place of ``hs`` and then to ``backward``: an unroll that is not given
+    these planes cannot write them."""
+
+    def __init__(self, hs, e):
+        assert hs.shape == e.shape and hs.is_contiguous() and e.is_contiguous()
+        self.hs, self.e = hs, e
+
+
+class CommNetMAC(PolicyMAC):
+    """PolicyMAC over a CommNetAgent (network/commnet.py; the project's own definition - DESIGN section 9): the logits of an
+    environment-step come from all N agents' hidden states.  Every pass is encoder (ops.linear + the sigmoid kernel) -> the agent
+    unroll over the identity front layer (h_t = f_obs(e_t, h_{t-1}), the fp32 kernels in either gemm_mode) -> the communication head
+    (csrc/commnet.hip).  ``backward`` is what the policy learners call in the place of agent_backward.
+
+    Padded steps: the encoder reads the stored observation rows (no zero padding at t >= ep_len), so logits there are finite and
+    deterministic but are not the float64 restatement's; every loss masks them and the recurrence runs forward only."""
+
+    head_name = "commnet"
+
+    def __init__(self, args):
+        self.k = commnet_k_of(args)          # raises before anything is built
+        PolicyMAC.__init__(self, args)
+        self._cbuf = {}
+
+    def _build_agents(self, input_shape):
+        self.agent = CommNetAgent(input_shape, self.args)
+
+    def _scratch(self, name, shape, dtype=torch.float32, zero=False):
+        key = (name, tuple(shape), dtype)
+        t = self._cbuf.get(key)
+        if t is None or t.device != self.device():
+            t = (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=self.device())
+            self._cbuf[key] = t
+        return t
+
+    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
+        raise NotImplementedError("CommNetMAC.choose_action: communication needs every agent's observation in one call - "
+                                  "use a batched rollout")
+
+    def rollout_weights(self):
+        return None
+
+    def _input(self, obs, remap0, ufed, remapi, ep_map=None):
+        """the virtual input [obs | one-hot(u_{t-1}) | agent id] as agent_backward builds it"""
+        a, N, A, O = self.args, self.n_agents, self.n_actions, self.obs_shape
+        kw = {}
+        if a.last_action:
+            kw.update(idx=ufed.reshape(-1, 1), nhot=1, hot_w=A, remapi=remapi)
+        return ops.src(obs.reshape(-1, O), nid=N if a.reuse_network else 0, remap0=remap0, emap0=ep_map, **kw)
+
+    def _encode(self, x, e, M):
+        """e (M, 64) = sigmoid(encoding(x))"""
+        ag = self.agent
+        ops.linear(x, ag.encoding.weight, ag.encoding.bias, e.view(M, -1), M, self.args.rnn_hidden_dim, self._get_input_shape())
+        ops.commnet_sigmoid_fwd(e)
+
+    def rollout_step(self, w, rec, t, h, q, E):
+        N, T, A, H = self.n_agents, rec.T, self.n_actions, self.args.rnn_hidden_dim
+        if E == 0:
+            return
+        x = self._input(rec.obs, (N, (T + 1) * N, t * N), rec.u, (N, T * N, (t - 1) * N))
+        e = self._scratch("step_e", (E, 1, N, H))
+        self._encode(x, e, E * N)
+        ops.agent_unroll_fwd(self.agent.front_weights(), e, N, 0, None, 0, 0, h, self._scratch("step_q", (E, 1, N, FRONT_A)),
+                             None, h, None, E, 1, N, H, FRONT_A, False, False)
+        ops.commnet_head_fwd(self.agent.head_weights(), h, q, E, N, A, self.k)
+
+    def unroll(self, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, B, T, q, hs=None, h_last=None, saved=None, h0="state",
+               ep_len=None, ep_map=None, cu_budget=0, gi_out=None, gi_in=None):
+        """SharedMAC.unroll's signature; q receives the logits.  ``hs``: None, a (B, T, N, H) tensor, or the CommNetPlanes a later
+        ``backward`` reads (``planes``).  ``ep_len`` is not applied to the encoder (class docstring); gate-sum reuse does not exist here."""
+        if gi_out is not None or gi_in is not None:
+            raise ValueError("CommNetMAC.unroll has no gate-sum reuse")
+        N, A, H = self.n_agents, self.n_actions, self.args.rnn_hidden_dim
+        if B == 0:
+            return
+        if h0 == "state":
+            h0 = None if self.hidden_states is None else self.hidden_states.reshape(B * N, -1).contiguous()
+        x = self._input(obs, (T * N, obs_bs, obs_t0 * N), ufed, (T * N, u_bs, u_t0 * N), ep_map)
+        if isinstance(hs, CommNetPlanes):
+            assert tuple(hs.hs.shape) == (B, T, N, H)
+            e, hs = hs.e, hs.hs
+        else:
+            e = self._scratch("e", (B, T, N, H))
+            if hs is None:
+                hs = self._scratch("hs", (B, T, N, H))
+        self._encode(x, e, B * T * N)
+        ops.agent_unroll_fwd(self.agent.front_weights(), e, T * N, 0, None, 0, 0, h0, self._scratch("q0", (B, T, N, FRONT_A)),
+                             hs, h_last, saved, B, T, N, H, FRONT_A, False, False, cu_budget=cu_budget)
+        ops.commnet_head_fwd(self.agent.head_weights(), hs, q, B * T, N, A, self.k)
+
+    def planes(self, get, shape):
+        """the CommNetPlanes of an unroll of ``shape`` = (B, T, N, H) in buffers from ``get(name, shape)`` (the learner's scratch)"""
+        return CommNetPlanes(get("hs", shape), get("commnet_e", shape))
+
+    def backward(self, db, saved, planes, dlogits, buf):
+        """The backward of the ``unroll`` that wrote ``planes`` (and ``saved``), on the batch's current observations: the head's
+        backward (dhs and the gradients of f_comm and
+        decoding), BPTT through the identity front with dhs as the gradient on the hidden states (f_obs's gradients; its dxp is the
+        gradient on e), the sigmoid's backward and the encoder's weight gradient - accumulated into the .grad views."""
+        B, T, N, A, O = db.B, db.T, db.N, db.A, db.O
+        H = self.args.rnn_hidden_dim
+        M = B * T * N
+        if M == 0:
+            return
+        if not isinstance(planes, CommNetPlanes) or tuple(planes.hs.shape) != (B, T, N, H):
+            raise TypeError("CommNetMAC.backward reads the CommNetPlanes (B, T, N, H) its unroll was given")
+        hs, e = planes.hs, planes.e
+        ag, dev = self.agent, hs.device
+        dhs = buf.get("commnet_dhs", (B, T, N, H), dev)
+        ops.commnet_head_bwd(ag.head_weights(), ag.head_grads(), hs, dlogits, dhs, B * T, N, A, self.k)
+        de = buf.get("dxp", (B, T, N, H), dev)
+        # the BPTT entry wants one form of dq: a sparse pair of zeros; the dummy fc2's gradients go to scratch
+        zi, zv = self._scratch("dq_idx", (M,), torch.int32, zero=True), self._scratch("dq_val", (M,), zero=True)
+        grads = {"rnn.weight_ih": ag.f_obs.weight_ih.grad, "rnn.weight_hh": ag.f_obs.weight_hh.grad,
+                 "rnn.bias_ih": ag.f_obs.bias_ih.grad, "rnn.bias_hh": ag.f_obs.bias_hh.grad,
+                 "fc2.weight": self._scratch("d_dummy_w", (FRONT_A, H)), "fc2.bias": self._scratch("d_dummy_b", (FRONT_A,))}
+        ops.agent_unroll_bwd(ag.front_weights(), None, dhs, saved, None, de, None, grads, B, T, N, FRONT_A, dq_idx=zi, dq_val=zv,
+                             x6=False)
+        ops.commnet_sigmoid_bwd(de, e, de)
+        obs, obs_bs, obs_t0 = db.o_cur
+        x = self._input(obs, (T * N, obs_bs, obs_t0 * N), db.u_fed, (T * N, db.u_bs, -N), getattr(db, "o_map", None))
+        ops.linear_wgrad(de.view(M, H), x, ag.encoding.weight.grad, ag.encoding.bias.grad, M, H, self._get_input_shape(), bf16=False)
 
 
 class RTWMAC(SharedMAC):

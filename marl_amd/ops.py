@@ -12,7 +12,7 @@ import torch
 from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
                    MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, MarlMaicGrads, MarlMaicInfer,
-                   MarlMaicInferGrads, check)
+                   MarlMaicInferGrads, MarlCommnetWeights, MarlCommnetGrads, check)
 
 
 def _p(t):
@@ -509,6 +509,69 @@ def coma_loss_bwd(logits, avail, q, u, G, padded, eps, beta, dlogits, dq, logp, 
                                  _dense(padded, B * T), float(eps), float(beta), _dense(dlogits, R * A), _dense(dq, R * A),
                                  _dense(logp, R), _dense(ent, R), _dense(adv, R), _dense(q_taken, R), _p(_f32(out_c2)),
                                  _p(_f32(out_a3)), _p(ws), B, T, N, A, _stream()), "marl_coma_loss_bwd")
+
+
+# ---- CommNet communication head (csrc/commnet.hip)
+_COMMNET_KEYS = (("w_ih", "f_comm.weight_ih"), ("w_hh", "f_comm.weight_hh"), ("b_ih", "f_comm.bias_ih"), ("b_hh", "f_comm.bias_hh"),
+                 ("dec_w", "decoding.weight"), ("dec_b", "decoding.bias"))
+
+
+def commnet_supported(N, A, K):
+    return bool(_lib.load().marl_commnet_supported(int(N), int(A), int(K)))
+
+
+def commnet_groups_per_workgroup(N):
+    """whole groups (environment-steps) in one 16-row tile of the head kernels"""
+    return int(_lib.load().marl_commnet_groups_per_workgroup(int(N)))
+
+
+def _commnet_struct(cls, tensors):
+    w = cls()
+    for f, k in _COMMNET_KEYS:
+        t = tensors[k]
+        assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda, k
+        setattr(w, f, t.data_ptr())
+    w._keep = tensors
+    return w
+
+
+def commnet_weights(tensors):
+    """tensors: dict name -> tensor with CommNetAgent's keys (f_comm.*, decoding.*)"""
+    return _commnet_struct(MarlCommnetWeights, tensors)
+
+
+def commnet_grads(grads):
+    """grads: dict of the same keys -> gradient tensors (accumulated into)"""
+    return _commnet_struct(MarlCommnetGrads, grads)
+
+
+def commnet_head_fwd(w, hs, logits, G, N, A, K):
+    """logits (G,N,A) <- hs (G,N,64): K rounds of f_comm over each group's N rows, then decoding"""
+    assert hs.is_contiguous() and logits.is_contiguous()
+    check(_lib.load().marl_commnet_head_fwd(C.byref(w), _p(_f32(hs)), _p(_f32(logits)), int(G), int(N), int(A), int(K), _stream()),
+          "marl_commnet_head_fwd")
+
+
+def commnet_head_bwd(w, g, hs, dlogits, dhs, G, N, A, K):
+    """dhs (G,N,64) written; f_comm's and decoding's gradients added into g (fixed-order slab reduction)"""
+    lib = _lib.load()
+    assert hs.is_contiguous() and dlogits.is_contiguous() and dhs.is_contiguous()
+    ws = WS.get("commnet_bwd", lib.marl_commnet_bwd_workspace(int(G), int(N), int(A), int(K)), hs.device)
+    check(lib.marl_commnet_head_bwd(C.byref(w), C.byref(g), _p(_f32(hs)), _p(_f32(dlogits)), _p(_f32(dhs)), _p(ws), ws.numel() * 4,
+                                    int(G), int(N), int(A), int(K), _stream()), "marl_commnet_head_bwd")
+
+
+def commnet_sigmoid_fwd(x):
+    """x <- sigmoid(x) in place (any contiguous float32 view)"""
+    assert x.is_contiguous()
+    check(_lib.load().marl_commnet_sigmoid_fwd(_p(_f32(x)), x.numel(), _stream()), "marl_commnet_sigmoid_fwd")
+
+
+def commnet_sigmoid_bwd(de, e, dxp):
+    """dxp = de * e * (1 - e); dxp may be de"""
+    assert de.is_contiguous() and e.is_contiguous() and dxp.is_contiguous() and de.numel() == e.numel() == dxp.numel()
+    check(_lib.load().marl_commnet_sigmoid_bwd(_p(_f32(de)), _p(_f32(e)), _p(_f32(dxp)), de.numel(), _stream()),
+          "marl_commnet_sigmoid_bwd")
 
 
 def grad_sumsq(g, n, out1):

@@ -185,14 +185,13 @@ class RolloutWorker:
         epsilon = 0 if evaluate else self.epsilon
         if a.epsilon_anneal_scale == 'episode':
             epsilon = epsilon - self.anneal_epsilon if epsilon > self.min_epsilon else epsilon
-        w = mac.agent.weights()
+        w = mac.rollout_weights()
         fused = hasattr(env, "fused_step") and mode != "unfused" and not sample
         select = ops.policy_sample if sample else ops.select_actions
         env.observe(0, rec)
         for t in range(T):
-            # agent step = the unroll kernel with T=1 reading slot t of the record in place
-            ops.agent_unroll_fwd(w, rec.obs, (T + 1) * N, t, rec.u, T * N, t - 1, h, q, None, h, None,
-                                 E, 1, N, O, A, a.last_action, a.reuse_network)
+            # agent step: by default the unroll kernel with T=1 reading slot t of the record in place (SharedMAC.rollout_step)
+            mac.rollout_step(w, rec, t, h, q, E)
             mac.rollout_head(h, q, rec, t, E, evaluate, self.rseed, env)     # q += the controller's head term, if it has one
             if fused:
                 env.fused_step(t, q, epsilon, self.rseed, rec)

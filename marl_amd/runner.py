@@ -37,6 +37,8 @@ NotImplementedError (an on-policy update needs the weights the last one wrote) -
 ``learner_cls`` (a constructor argument): a further on-policy learner over PolicyMAC, named by the caller instead of by the runner's
 own table; everything above holds for it.  The launcher passes COMALearner (algorithm/coma.py) for ``--alg coma``
 (``main.make_runner``); a Runner built without it keeps answering 'learner coma cannot find!', as it always has.
+``mac_cls`` (a constructor argument, with ``learner_cls``): the stochastic controller that learner trains in the place of PolicyMAC - the
+launcher passes CommNetMAC for the three ``+commnet`` algorithms; a Runner built on a bare ``+commnet`` name answers 'cannot find!' too.
 
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
@@ -97,8 +99,9 @@ _ON_POLICY = {'central_v': CentralVLearner, 'reinforce': ReinforceLearner}      
 
 
 class Runner:
-    def __init__(self, env, logger, args, learner_cls=None):
+    def __init__(self, env, logger, args, learner_cls=None, mac_cls=None):
         self.env = env
+        policy_mac_cls = mac_cls if mac_cls is not None else PolicyMAC
         if not args.reuse_network:
             raise NotImplementedError("only the shared-parameter controller (reuse_network) is on the hot path")
         if getattr(args, "MAIC_train", False) and not getattr(args, "MAIC", False):
@@ -114,7 +117,7 @@ class Runner:
                 raise ValueError("%s trains the plain shared agent as a policy: not with %s" % (args.alg, on[0].name))
             if getattr(args, "overlap_rollout", False):
                 raise NotImplementedError("%s is on-policy: a rollout needs the weights the last update wrote" % args.alg)
-            mac_cls = PolicyMAC
+            mac_cls = policy_mac_cls
         for sw in on:
             for hit, refusal in ((sw is not on[0], sw.combined), (sw.alg_refused(args), sw.alg),
                                  (getattr(args, "overlap_rollout", False), sw.overlap)):
