@@ -17,20 +17,16 @@ One update pass: the eval unroll with saved planes, the critic on s, the target 
 flat buffers, two optimizers of ``args.optimizer``'s kind (lr_actor over the agent, lr_critic over the critic), each with its own
 clip and its own denominator (N M and M); the target critic follows every ``target_update_cycle`` updates; there is no target
 actor.  ``args.td_lambda`` None means 0, the one-step target.  No hipGraph replay, no launch ahead of max_episode_len, one rank.
+Construction, storage, the tail of an update, checkpoints and resume state are PolicyLearner's (algorithm/policy_learner.py).
 """
 from __future__ import annotations
-
-import copy
-import os
 
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..hostutil import flatten_module, lin_of, require_cuda
-from .reinforce import entropy_coef_of
-from .common import (LearnerParams, FlatView, FusedOptimizer, Learner, LossReadback, GradReducer, Scratch, policy_backward, policy_hs,
-                     td_lambda_of)
+from ..hostutil import lin_of
+from .policy_learner import PolicyLearner
 
 
 class VCritic(nn.Module):
@@ -46,63 +42,12 @@ class VCritic(nn.Module):
         return self.fc3(torch.relu(self.fc2(torch.relu(self.fc1(s)))))
 
 
-class CentralVLearner(Learner):
-    launch_ahead = False
-    replay_graphs = False
+class CentralVLearner(PolicyLearner):
     extra_nets = ("critic",)
-    mixer = target_mixer = None
-
-    def __init__(self, mac, args):
-        if GradReducer().enabled:
-            raise NotImplementedError("CentralVLearner trains on one rank: its two gradient buffers have no all-reduce")
-        self.td_lambda = td_lambda_of(args)          # raises before anything is built
-        self.beta = entropy_coef_of(args)            # (so does a negative weight)
-        if not getattr(mac, "stochastic", False):
-            raise ValueError("CentralVLearner needs a stochastic controller (PolicyMAC)")
-        self.args = args
-        self.max_episode_len = args.episode_limit
-        self.gamma = args.gamma
-        self.model_dir = args.model_dir + '/' + args.alg + '/' + args.map
-        self.device = require_cuda("CentralVLearner")
-        self.epsilon = 0.0
-        self.eval_net = mac
-        self.eval_net.cuda()
-        self.critic = self._make_critic(args)
-        self.target_critic = copy.deepcopy(self.critic)
-        self.cuda()
-        self.optimizer = FusedOptimizer(self._flat, args.optimizer, args.lr_actor, args.grad_norm_clip)
-        self.critic_optimizer = FusedOptimizer(self._cflat, args.optimizer, args.lr_critic, args.grad_norm_clip)
-        self._buf = Scratch()
-        self.reducer = GradReducer()
-        self.loss_readback, self.actor_readback, self.entropy_readback = LossReadback(args), LossReadback(args), LossReadback(args)
-        self.graphs = None
-        self.needs_avail = True                      # the policy is over the current step's available actions
-        self.last_stats = self.actor_stats = None
-        self.actor_loss = self.entropy = float("nan")
-        self._td_dbg, self._dbg = {}, {}
+    _no_q_table = "central-V has no Q table: its critic is a state value"
 
     def _make_critic(self, args):
         return VCritic(args)
-
-    def sync_replicas(self):
-        """one rank: nothing to broadcast"""
-
-    # ------------------------------------------------------------------ storage
-    def cuda(self):
-        dev = self.device
-        self.eval_net.agent.to(dev)
-        self.critic.to(dev)
-        self.target_critic.to(dev)
-        self.params = list(self.eval_net.parameters())
-        self._flat = LearnerParams(self.params, dev)                              # the actor's buffer: stats = {L_actor numerator, N M}
-        self.eval_net.agent._flat = FlatView(self._flat.flat, self.eval_net.agent.parameters(), 0)
-        self.eval_net._dev = dev
-        self._cflat = LearnerParams(list(self.critic.parameters()), dev)          # the critic's: stats = {L_critic numerator, M}
-        self.critic._flat = FlatView(self._cflat.flat, self.critic.parameters(), 0)
-        flatten_module(self.target_critic, dev)
-
-    def _update_targets(self):
-        self.target_critic._flat.flat.copy_(self._cflat.flat)
 
     # ------------------------------------------------------------------ the hot path
     def _critic_forward(self, net, s, BT, tag, keep):
@@ -126,17 +71,12 @@ class CentralVLearner(Learner):
         l1.wgrad(dh1, ops.src(s), BT, Yact=h1)
 
     def _forward_backward(self, db):
-        a, g = self.args, self._g
-        B, T, N, A, H = db.B, db.T, db.N, db.A, a.rnn_hidden_dim
+        g = self._g
+        B, T, N, A = db.B, db.T, db.N, db.A
         BT, R = B * T, B * T * N
-        lam = self.td_lambda = td_lambda_of(a)
-        lam = 0.0 if lam is None else lam
-        # 1. the eval unroll keeps its activations for BPTT (the split kernel in gemm_mode "bf16x6", where QLearner's takes it)
-        logits, saved, h_last = g("logits", (B, T, N, A)), g("saved", ops.saved_shape(T, B, N)), g("h_last", (B * N, H))
-        oc, oc_bs, oc_t0 = db.o_cur
-        hs = policy_hs(self.eval_net, g, (B, T, N, H))
-        self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, logits, hs, h_last, saved, h0=None,
-                             ep_len=db.ep_len, ep_map=getattr(db, 'o_map', None))
+        lam = self._lambda()
+        # 1. the eval unroll keeps its activations for BPTT
+        logits, saved, hs = self._actor_unroll(db)
         # 2. - 4. V(s), V_target(s_next) and its lambda-returns (padded steps carry zero states: finite on every row)
         v, h1, h2 = self._critic_forward(self.critic, db.s, BT, "", True)
         v_next = self._critic_forward(self.target_critic, db.s_next, BT, "t", False)
@@ -148,8 +88,7 @@ class CentralVLearner(Learner):
         dv = g("c_dv", (BT, 1))
         ops.td_loss(v.view(BT), v_next.view(BT), G, db.term, db.padded, 0.0, dv.view(BT), self._cflat.stats[:2], BT)
         self._critic_backward(db.s, h1, h2, dv, BT)
-        # 7. - 8. the actor: Adv = G - V is formed inside the loss kernel; its dense gradient on the logits goes to BPTT (the fp32
-        # kernel in either gemm mode: the split BPTT takes sparse gradients only)
+        # 7. - 8. the actor: Adv = G - V is formed inside the loss kernel; its dense gradient on the logits goes to BPTT
         dlogits, logp = g("dlogits", (B, T, N, A)), g("logp", (R,))
         self._dbg = dict(logits=logits, v=v.view(BT), v_next=v_next.view(BT), td_targets=G, logp=logp, dlogits=dlogits)
         if self.beta == 0.0:
@@ -159,57 +98,4 @@ class CentralVLearner(Learner):
             ent = self._dbg["ent"] = g("ent", (R,))
             ops.policy_loss_bwd_ex(logits, db.avail, db.u_act.reshape(-1), G, v.view(BT), db.padded, self.epsilon, self.beta,
                                    dlogits, logp, ent, self._flat.stats[:3], R, N, A)
-        policy_backward(self.eval_net, db, saved, hs, dlogits, self._buf)
-
-    def train(self, batch, train_step, epsilon=0.0):
-        """One update on the episodes just generated; ``epsilon``: the exploration rate their actions were drawn at.  Returns the
-        critic loss; the actor loss is left in ``self.actor_loss`` (both through LossReadback)."""
-        self.epsilon = float(epsilon)
-        return Learner.train(self, batch, train_step)
-
-    def _finish_update(self, train_step):
-        cs, st = self._cflat.stats, self._flat.stats
-        self.critic_optimizer.step(den=cs[1:2])
-        self.optimizer.step(den=st[1:2])
-        if train_step > 0 and train_step % self.args.target_update_cycle == 0:
-            self._update_targets()
-        self.last_stats, self.actor_stats = cs, st
-        self.actor_loss = self.actor_readback.read(st[:2], self._loss_fn())
-        if self.beta != 0.0:
-            self.entropy = self.entropy_readback.read(st[:3], lambda s: s[2] / s[1])
-        return self.loss_readback.read(cs[:2], self._loss_fn())
-
-    def get_q_and_q_tot_table(self):
-        raise NotImplementedError("central-V has no Q table: its critic is a state value")
-
-    # ------------------------------------------------------------------ checkpoints
-    def save_models(self, train_step):
-        num = str(train_step // self.args.save_cycle)
-        os.makedirs(self.model_dir, exist_ok=True)
-        self.eval_net.save_models(self.model_dir + '/' + num + '_rnn_net_params.pkl')
-        torch.save({k: v.detach().cpu() for k, v in self.critic.state_dict().items()},
-                   self.model_dir + '/' + num + '_critic_net_params.pkl')
-
-    def load_models(self):
-        path_rnn, path_critic = self.model_dir + '/rnn_net_params.pkl', self.model_dir + '/critic_net_params.pkl'
-        if not os.path.exists(path_rnn):
-            raise Exception("No model!")
-        self.eval_net.load_models(path_rnn)
-        self.critic.load_state_dict(torch.load(path_critic, map_location='cpu'))
-        print('Successfully load the model: {} and {}'.format(path_rnn, path_critic))
-
-    def resume_state(self):
-        cpu = lambda t: t.detach().cpu().clone()
-        return {"alg": self.args.alg, "n_params": int(self._flat.n), "n_critic": int(self._cflat.n),
-                "params": cpu(self._flat.flat), "critic": cpu(self._cflat.flat),
-                "target_critic": cpu(self.target_critic._flat.flat), "optimizer": self.optimizer.state_dict(),
-                "critic_optimizer": self.critic_optimizer.state_dict()}
-
-    def load_resume_state(self, sd):
-        if sd["alg"] != self.args.alg or sd["n_params"] != int(self._flat.n) or sd.get("n_critic") != int(self._cflat.n):
-            raise ValueError("resume state of a different learner (%s, %d parameters)" % (sd["alg"], sd["n_params"]))
-        self._flat.flat.copy_(sd["params"])
-        self._cflat.flat.copy_(sd["critic"])
-        self.target_critic._flat.flat.copy_(sd["target_critic"])
-        self.optimizer.load_state_dict(sd["optimizer"])
-        self.critic_optimizer.load_state_dict(sd["critic_optimizer"])
+        self._actor_backward(db, saved, hs, dlogits)

@@ -24,7 +24,8 @@ gets no bootstrap (REINFORCE's convention here).  beta = ``args.policy_entropy_c
 One update pass: the eval unroll with saved planes (the split kernel in gemm_mode "bf16x6"; the critic and the BPTT are fp32), the
 critic, the target critic, coma_q_taken, td_lambda_returns, coma_loss_bwd (both losses, dlogits and dQ from one pass), the critic
 backward, BPTT.  Storage, the two optimizers (lr_actor, lr_critic; both denominators N M), the target sync, checkpoints and resume
-state are CentralVLearner's.  ``args.td_lambda`` None means 0.  No target actor, one rank, no hipGraph replay.
+state are PolicyLearner's (algorithm/policy_learner.py), as CentralVLearner's.  ``args.td_lambda`` None means 0.  No target actor,
+one rank, no hipGraph replay.
 """
 from __future__ import annotations
 
@@ -34,7 +35,6 @@ import torch.nn as nn
 from .. import ops
 from ..hostutil import lin_of
 from .central_v import CentralVLearner
-from .common import policy_backward, policy_hs, td_lambda_of
 
 
 def critic_input_dim(args):
@@ -56,6 +56,8 @@ class QCritic(nn.Module):
 
 
 class COMALearner(CentralVLearner):
+    _no_q_table = "COMA has no joint Q table: its critic is counterfactual, one agent's actions at a time"
+
     def _make_critic(self, args):
         return QCritic(args)
 
@@ -104,17 +106,12 @@ class COMALearner(CentralVLearner):
         ops.linear_wgrad(dh1, self._obs_rows(db), gw[:, S:S + O], None, R, D, O, lddw=K)
 
     def _forward_backward(self, db):
-        a, g = self.args, self._g
-        B, T, N, A, H = db.B, db.T, db.N, db.A, a.rnn_hidden_dim
-        BT, R = B * T, B * T * N
-        lam = self.td_lambda = td_lambda_of(a)
-        lam = 0.0 if lam is None else lam
+        g = self._g
+        B, T, N, A = db.B, db.T, db.N, db.A
+        R = B * T * N
+        lam = self._lambda()
         # 1. the eval unroll keeps its activations for BPTT
-        logits, saved, h_last = g("logits", (B, T, N, A)), g("saved", ops.saved_shape(T, B, N)), g("h_last", (B * N, H))
-        oc, oc_bs, oc_t0 = db.o_cur
-        hs = policy_hs(self.eval_net, g, (B, T, N, H))
-        self.eval_net.unroll(oc, oc_bs, oc_t0, db.u_fed, db.u_bs, -1, B, T, logits, hs, h_last, saved, h0=None,
-                             ep_len=db.ep_len, ep_map=getattr(db, 'o_map', None))
+        logits, saved, hs = self._actor_unroll(db)
         # 2. - 4. Q, the target critic's Q of the next step's taken action, its lambda-returns per agent (r, term and padded are
         # expanded over the agents on the host side: plumbing)
         u = db.u_act.reshape(-1)
@@ -137,7 +134,4 @@ class COMALearner(CentralVLearner):
                          ent=ent)
         # 6. - 7. the critic backward, and BPTT on the dense gradient of the logits (the fp32 kernel in either gemm mode)
         self._critic_backward(db, h1, h2, dq)
-        policy_backward(self.eval_net, db, saved, hs, dlogits, self._buf)
-
-    def get_q_and_q_tot_table(self):
-        raise NotImplementedError("COMA has no joint Q table: its critic is counterfactual, one agent's actions at a time")
+        self._actor_backward(db, saved, hs, dlogits)

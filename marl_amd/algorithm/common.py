@@ -1,5 +1,7 @@
-"""Shared machinery of the two learners: flat parameter/gradient storage with a statistics
-tail, the fused clip+optimizer wrapper, the agent backward pass and data-parallel reduction."""
+"""Shared machinery of the learners: flat parameter/gradient storage with a statistics tail, the fused clip+optimizer wrapper,
+resume state, the loss readback, ``Learner`` - the frame every learner is built on (the Q-learning family directly, the
+policy-gradient family through algorithm/policy_learner.py) -, the agent backward pass and the policy learners' seam to a
+controller's own backward, data-parallel reduction, the paired unrolls and the hipGraph replay of an update."""
 from __future__ import annotations
 
 import copy
@@ -12,7 +14,7 @@ import numpy as np
 import torch
 
 from .. import ops, experiments
-from ..hostutil import FlatParams, DeviceBatch, AsyncInt, require_cuda
+from ..hostutil import FlatParams, DeviceBatch, AsyncInt, Scratch, require_cuda
 from ..network.mixer import x6_mode
 from ..rollout import EpisodeBatch
 
@@ -175,10 +177,12 @@ def td_lambda_of(args):
 
 
 class Learner(ResumeMixin):
-    """The frame of QLearner and QTRANLearner: construction around the learner's own mixers, the batch intake of ``train``,
-    the loss tail, the target copies and the model files.  A learner provides ``_forward_backward(db)``, ``cuda()``,
-    ``sync_replicas()`` and the three items of the loss tail: how many statistics slots it reads, which of them is the
-    denominator, and ``_loss_fn()``."""
+    """The frame of every learner: the batch intake of ``train``, the scratch buffers, the model files and (ResumeMixin) the resume
+    state; for the Q-learning family (QLearner and its subclasses, QTRANLearner) also the construction around the learner's own
+    mixers (``_begin`` / ``_ready``), the loss tail and the target copies.  Such a learner provides ``_forward_backward(db)``,
+    ``cuda()``, ``sync_replicas()`` and the three items of the loss tail: how many statistics slots it reads, which of them is the
+    denominator, and ``_loss_fn()``.  PolicyLearner (algorithm/policy_learner.py) has a constructor and a tail of its own: no
+    target actor, no mixer (``mixer`` None: no mixer file), two optimizers where there is a critic."""
     _full_len_streak = 0      # consecutive updates whose max_episode_len was the record's full length
     n_stats, den_slot = 2, 1  # the loss tail reads stats[:n_stats]; the optimizer divides by stats[den_slot]
     extra_nets = ()           # attributes of further modules with a <name>_net_params.pkl file of their own
@@ -312,39 +316,28 @@ class Learner(ResumeMixin):
         return self.loss_readback.read(stats[:self.n_stats], self._loss_fn())
 
     # ------------------------------------------------------------------ checkpoints (reference q_learner.py:193-209)
+    def _file_nets(self):
+        """the modules beside the agent with a <name>_net_params.pkl file of their own (a learner without a mixer has no mixer file)"""
+        return (("mixer",) if self.mixer is not None else ()) + self.extra_nets
+
     def save_models(self, train_step):
         num = str(train_step // self.args.save_cycle)
         if not os.path.exists(self.model_dir):
             os.makedirs(self.model_dir)
         self.eval_net.save_models(self.model_dir + '/' + num + '_rnn_net_params.pkl')
-        for name in ("mixer",) + self.extra_nets:
+        for name in self._file_nets():
             torch.save({k: v.detach().cpu() for k, v in getattr(self, name).state_dict().items()},
                        self.model_dir + '/' + num + '_' + name + '_net_params.pkl')
 
     def load_models(self):
-        if os.path.exists(self.model_dir + '/rnn_net_params.pkl'):
-            path_rnn = self.model_dir + '/rnn_net_params.pkl'
-            path_mix = self.model_dir + '/mixer_net_params.pkl'
-            self.eval_net.load_models(path_rnn)
-            for name in ("mixer",) + self.extra_nets:
-                getattr(self, name).load_state_dict(torch.load(self.model_dir + '/' + name + '_net_params.pkl', map_location='cpu'))
-            self.sync_replicas()
-            print('Successfully load the model: {} and {}'.format(path_rnn, path_mix))
-        else:
+        paths = [self.model_dir + '/' + name + '_net_params.pkl' for name in ("rnn",) + self._file_nets()]
+        if not os.path.exists(paths[0]):
             raise Exception("No model!")
-
-
-class Scratch:
-    def __init__(self):
-        self.d = {}
-
-    def get(self, name, shape, device, dtype=torch.float32):
-        key = (name, tuple(shape), dtype)
-        t = self.d.get(key)
-        if t is None or t.device != device:
-            t = torch.empty(*shape, dtype=dtype, device=device)
-            self.d[key] = t
-        return t
+        self.eval_net.load_models(paths[0])
+        for name, path in zip(self._file_nets(), paths[1:]):
+            getattr(self, name).load_state_dict(torch.load(path, map_location='cpu'))
+        self.sync_replicas()
+        print('Successfully load the model: ' + ' and '.join(paths))
 
 
 def agent_backward(mac, db, which, saved, hs, dq, dhs, buf, dq_idx=None, dq_val=None, dq_idx2=None, dq_val2=None, dq_gdiv=1):
@@ -370,13 +363,10 @@ def agent_backward(mac, db, which, saved, hs, dq, dhs, buf, dq_idx=None, dq_val=
                          dq_idx2=dq_idx2, dq_val2=dq_val2, dq_gdiv=dq_gdiv, x6=x6)
     obs, obs_bs, obs_t0 = db.o_cur if which == "cur" else db.o_next
     remap0 = None if (obs_bs == T * N and obs_t0 == 0) else (T * N, obs_bs, obs_t0 * N)
-    kw = {}
-    if args.last_action:
-        kw.update(idx=db.u_fed.reshape(-1, 1), nhot=1, hot_w=A, remapi=(T * N, db.u_bs, (-1 if which == "cur" else 0) * N))
     emap = getattr(db, 'o_map', None)
     if emap is not None and remap0 is None:
         remap0 = (T * N, obs_bs, obs_t0 * N)
-    xin = ops.src(obs.reshape(-1, O), nid=N if args.reuse_network else 0, remap0=remap0, emap0=emap, **kw)
+    xin = ops.agent_input_src(args, N, A, O, obs, remap0, db.u_fed, (T * N, db.u_bs, (-1 if which == "cur" else 0) * N), emap)
     I = O + (A if args.last_action else 0) + (N if args.reuse_network else 0)
     ops.linear_wgrad(dxp.view(M, H), xin, ag.fc1.weight.grad, ag.fc1.bias.grad, M, H, I, bf16=False)   # agent layers stay fp32
 

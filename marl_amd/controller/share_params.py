@@ -11,7 +11,7 @@ import numpy as np
 import torch
 
 from .. import ops
-from ..hostutil import require_cuda, to_dev, onehot_to_index, flatten_module
+from ..hostutil import Scratch, require_cuda, to_dev, onehot_to_index, flatten_module
 from ..network.mixer import x6_mode
 from ..network.q_network import RNNQNet
 from ..network.rtw import RTWAgent
@@ -91,24 +91,29 @@ class SharedMAC:
     def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
         """One agent, one env (reference :37-72), same numpy RNG draw order: one uniform per call, one choice only when
         exploring.  ``avail_actions``: the agent's row, or every agent's (choose_action_inputs = "avail_all")."""
-        dev = self.device()
-        N, O = self.n_agents, self.obs_shape
         avail = np.asarray(avail_actions, dtype=np.float32)
         if self.choose_action_inputs == "avail_all":
-            avail = avail.reshape(N, self.n_actions)
-        la = -1
-        if self.args.last_action:
-            nz = np.nonzero(np.asarray(last_action))[0]
-            la = int(nz[0]) if nz.size else -1
-        # run row `agent_num` of a 1-episode batch: pad the agent axis so the id block matches
-        obs_full = torch.zeros(1, 1, N, O, device=dev)
-        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
-        ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
-        ufed[0, 0, agent_num] = la
+            avail = avail.reshape(self.n_agents, self.n_actions)
+        obs_full, ufed = self._one_agent_inputs(obs, last_action, agent_num)
         q, h_out = self._agent_step_one(obs_full, ufed)
         self._step_head(h_out, q, obs_full, avail, evaluate)
         self.hidden_states[0, agent_num] = h_out[agent_num]
         return self._draw(q[0, 0, agent_num].cpu(), avail if avail.ndim == 1 else avail[agent_num], epsilon)
+
+    def _one_agent_inputs(self, obs, last_action, agent_num):
+        """(obs_full (1,1,N,O), ufed (1,1,N)) that run row ``agent_num`` of a 1-episode batch: the agent axis is padded so the id
+        block matches; the last-action index is -1 where there is none"""
+        dev = self.device()
+        N, O = self.n_agents, self.obs_shape
+        la = -1
+        if self.args.last_action:
+            nz = np.nonzero(np.asarray(last_action))[0]
+            la = int(nz[0]) if nz.size else -1
+        obs_full = torch.zeros(1, 1, N, O, device=dev)
+        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
+        ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
+        ufed[0, 0, agent_num] = la
+        return obs_full, ufed
 
     def _agent_step_one(self, obs_full, ufed):
         """the T = 1 unroll of one environment from self.hidden_states: (q (1,1,N,A), h_out (N,H))"""
@@ -271,17 +276,9 @@ class PolicyMAC(SharedMAC):
 
     def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
         """One agent, one env: pi of the agent's row, then its argmax (``evaluate``) or one np.random.choice draw from it."""
-        dev = self.device()
-        N, O, A = self.n_agents, self.obs_shape, self.n_actions
+        dev, A = self.device(), self.n_actions
         avail = np.asarray(avail_actions, dtype=np.float32).reshape(A)
-        la = -1
-        if self.args.last_action:
-            nz = np.nonzero(np.asarray(last_action))[0]
-            la = int(nz[0]) if nz.size else -1
-        obs_full = torch.zeros(1, 1, N, O, device=dev)
-        obs_full[0, 0, agent_num] = to_dev(np.asarray(obs, dtype=np.float32).reshape(O), dev)
-        ufed = torch.full((1, 1, N), -1, dtype=torch.int32, device=dev)
-        ufed[0, 0, agent_num] = la
+        obs_full, ufed = self._one_agent_inputs(obs, last_action, agent_num)
         q, h_out = self._agent_step_one(obs_full, ufed)
         self.hidden_states[0, agent_num] = h_out[agent_num]
         pi = torch.empty(1, A, device=dev)
@@ -329,18 +326,13 @@ class CommNetMAC(PolicyMAC):
     def __init__(self, args):
         self.k = commnet_k_of(args)          # raises before anything is built
         PolicyMAC.__init__(self, args)
-        self._cbuf = {}
+        self._cbuf = Scratch()
 
     def _build_agents(self, input_shape):
         self.agent = CommNetAgent(input_shape, self.args)
 
     def _scratch(self, name, shape, dtype=torch.float32, zero=False):
-        key = (name, tuple(shape), dtype)
-        t = self._cbuf.get(key)
-        if t is None or t.device != self.device():
-            t = (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=self.device())
-            self._cbuf[key] = t
-        return t
+        return self._cbuf.get(name, shape, self.device(), dtype, zero)
 
     def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
         raise NotImplementedError("CommNetMAC.choose_action: communication needs every agent's observation in one call - "
@@ -351,11 +343,7 @@ class CommNetMAC(PolicyMAC):
 
     def _input(self, obs, remap0, ufed, remapi, ep_map=None):
         """the virtual input [obs | one-hot(u_{t-1}) | agent id] as agent_backward builds it"""
-        a, N, A, O = self.args, self.n_agents, self.n_actions, self.obs_shape
-        kw = {}
-        if a.last_action:
-            kw.update(idx=ufed.reshape(-1, 1), nhot=1, hot_w=A, remapi=remapi)
-        return ops.src(obs.reshape(-1, O), nid=N if a.reuse_network else 0, remap0=remap0, emap0=ep_map, **kw)
+        return ops.agent_input_src(self.args, self.n_agents, self.n_actions, self.obs_shape, obs, remap0, ufed, remapi, ep_map)
 
     def _encode(self, x, e, M):
         """e (M, 64) = sigmoid(encoding(x))"""

@@ -47,6 +47,22 @@ class FlatParams:
         self.grad.zero_()
 
 
+class Scratch:
+    """named device buffers that live as long as their owner, one per (name, shape, dtype)"""
+
+    def __init__(self):
+        self.d = {}
+
+    def get(self, name, shape, device, dtype=torch.float32, zero=False):
+        """``zero``: filled with zeros when it is allocated (and never again)"""
+        key = (name, tuple(shape), dtype)
+        t = self.d.get(key)
+        if t is None or t.device != device:
+            t = (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=device)
+            self.d[key] = t
+        return t
+
+
 def flatten_module(module: nn.Module, device, with_grad=False):
     fp = FlatParams(list(module.parameters()), device, with_grad=with_grad)
     module._flat = fp

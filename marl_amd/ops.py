@@ -103,6 +103,15 @@ def src(x0=None, x1=None, idx=None, nhot=0, hot_w=0, nid=0, gate=None, remap0=No
     return s
 
 
+def agent_input_src(args, N, A, O, obs, remap0, ufed, remapi, emap):
+    """the agent's virtual input rows [obs | one-hot(u_{t-1}) | agent id] (args.last_action / args.reuse_network permitting) as a
+    row source: obs read through (remap0, emap), the fed action indices ufed through remapi"""
+    kw = {}
+    if args.last_action:
+        kw.update(idx=ufed.reshape(-1, 1), nhot=1, hot_w=A, remapi=remapi)
+    return src(obs.reshape(-1, O), nid=N if args.reuse_network else 0, remap0=remap0, emap0=emap, **kw)
+
+
 def src_width(s):
     return s.k0 + s.k1 + s.nhot * s.hot_w + s.nid
 
@@ -514,6 +523,7 @@ def coma_loss_bwd(logits, avail, q, u, G, padded, eps, beta, dlogits, dq, logp, 
 # ---- CommNet communication head (csrc/commnet.hip)
 _COMMNET_KEYS = (("w_ih", "f_comm.weight_ih"), ("w_hh", "f_comm.weight_hh"), ("b_ih", "f_comm.bias_ih"), ("b_hh", "f_comm.bias_hh"),
                  ("dec_w", "decoding.weight"), ("dec_b", "decoding.bias"))
+_COMMNET_FIELDS = [(field, name, torch.float32) for field, name in _COMMNET_KEYS]
 
 
 def commnet_supported(N, A, K):
@@ -525,24 +535,14 @@ def commnet_groups_per_workgroup(N):
     return int(_lib.load().marl_commnet_groups_per_workgroup(int(N)))
 
 
-def _commnet_struct(cls, tensors):
-    w = cls()
-    for f, k in _COMMNET_KEYS:
-        t = tensors[k]
-        assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda, k
-        setattr(w, f, t.data_ptr())
-    w._keep = tensors
-    return w
-
-
 def commnet_weights(tensors):
     """tensors: dict name -> tensor with CommNetAgent's keys (f_comm.*, decoding.*)"""
-    return _commnet_struct(MarlCommnetWeights, tensors)
+    return _fill_struct(MarlCommnetWeights, tensors, _COMMNET_FIELDS)
 
 
 def commnet_grads(grads):
     """grads: dict of the same keys -> gradient tensors (accumulated into)"""
-    return _commnet_struct(MarlCommnetGrads, grads)
+    return _fill_struct(MarlCommnetGrads, grads, _COMMNET_FIELDS)
 
 
 def commnet_head_fwd(w, hs, logits, G, N, A, K):

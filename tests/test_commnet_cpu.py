@@ -132,11 +132,11 @@ def test_refusals_before_anything_is_built(fake_env, tmp_path):
 
 
 def test_multi_rank_is_refused(monkeypatch):
-    from marl_amd.algorithm import reinforce
+    from marl_amd.algorithm import reinforce, policy_learner
     from marl_amd.controller.share_params import CommNetMAC
     args, _, _ = cn.learner_case("reinforce", "2s3z")
     mac = CommNetMAC(args)
-    monkeypatch.setattr(reinforce, "GradReducer", type("R", (), {"enabled": True}))
+    monkeypatch.setattr(policy_learner, "GradReducer", type("R", (), {"enabled": True}))
     with pytest.raises(NotImplementedError):
         reinforce.ReinforceLearner(mac, args)
     assert not hasattr(mac.agent, "_flat")

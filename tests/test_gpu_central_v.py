@@ -124,7 +124,7 @@ def test_td_lambda_none_is_zero_bit_for_bit():
 
 
 def test_refusals(monkeypatch):
-    from marl_amd.algorithm import central_v
+    from marl_amd.algorithm import central_v, policy_learner
     from marl_amd.controller.share_params import PolicyMAC, SharedMAC
     args, _, _ = po.learner_case("2s3z")
 
@@ -132,7 +132,7 @@ def test_refusals(monkeypatch):
         enabled = True
     mac = PolicyMAC(args)
     with monkeypatch.context() as m:
-        m.setattr(central_v, "GradReducer", Reducer)
+        m.setattr(policy_learner, "GradReducer", Reducer)    # the constructor is PolicyLearner's
         with pytest.raises(NotImplementedError):
             central_v.CentralVLearner(mac, args)
     assert not hasattr(mac.agent, "_flat")                # nothing was built

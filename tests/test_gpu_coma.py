@@ -285,7 +285,7 @@ def test_entropy_bonus_vs_oracle():
 
 
 def test_refusals(monkeypatch):
-    from marl_amd.algorithm import central_v, coma
+    from marl_amd.algorithm import coma, policy_learner
     from marl_amd.controller.share_params import PolicyMAC, SharedMAC
     args, _, _ = co.learner_case("2s3z")
 
@@ -293,7 +293,7 @@ def test_refusals(monkeypatch):
         enabled = True
     mac = PolicyMAC(args)
     with monkeypatch.context() as m:
-        m.setattr(central_v, "GradReducer", Reducer)       # COMALearner's constructor is CentralVLearner's
+        m.setattr(policy_learner, "GradReducer", Reducer)   # COMALearner's constructor is PolicyLearner's
         with pytest.raises(NotImplementedError):
             coma.COMALearner(mac, args)
     assert not hasattr(mac.agent, "_flat")                # nothing was built

@@ -101,10 +101,8 @@ def test_two_updates_vs_oracle(run, monkeypatch):
 def test_plain_path_is_unchanged(alg, monkeypatch):
     """PolicyMAC: one update gives, bit for bit, the parameters a copy of the learner gives with the new dispatch bypassed -
     agent_backward called directly, no hs plane asked for"""
-    import importlib
-    from marl_amd.algorithm import common
+    from marl_amd.algorithm import common, policy_learner as mod         # the one module that calls the two seam functions
     build = {"reinforce": tr.build_product, "central_v": cv.build_product, "coma": tc.build_product}[alg]
-    mod = importlib.import_module("marl_amd.algorithm." + alg)
     out = []
     for bypass in (False, True):
         with monkeypatch.context() as m:

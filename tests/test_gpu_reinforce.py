@@ -112,7 +112,7 @@ def test_central_v_without_the_bonus_launches_no_ex(monkeypatch):
 
 
 def test_refusals(monkeypatch):
-    from marl_amd.algorithm import reinforce, central_v
+    from marl_amd.algorithm import reinforce, central_v, policy_learner
     from marl_amd.controller.share_params import PolicyMAC, SharedMAC
     args, _, _ = pg.learner_case("2s3z")
 
@@ -120,7 +120,7 @@ def test_refusals(monkeypatch):
         enabled = True
     mac = PolicyMAC(args)
     with monkeypatch.context() as m:
-        m.setattr(reinforce, "GradReducer", Reducer)
+        m.setattr(policy_learner, "GradReducer", Reducer)    # the constructor is PolicyLearner's
         with pytest.raises(NotImplementedError):
             reinforce.ReinforceLearner(mac, args)
     assert not hasattr(mac.agent, "_flat")                # nothing was built

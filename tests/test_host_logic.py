@@ -41,6 +41,18 @@ def test_first_terminated_len_matches_reference_rule():
     assert onehot_to_index(oh).tolist() == [1, -1, 2]
 
 
+def test_scratch_is_one_class_and_zero_fills_at_allocation_only():
+    from marl_amd import hostutil
+    from marl_amd.algorithm import common
+    assert common.Scratch is hostutil.Scratch                                  # importable from its old place
+    buf, cpu = hostutil.Scratch(), torch.device("cpu")
+    z = buf.get("z", (3, 2), cpu, torch.int32, zero=True)
+    assert z.dtype == torch.int32 and z.shape == (3, 2) and not z.any()
+    z.fill_(7)
+    assert buf.get("z", (3, 2), cpu, torch.int32, zero=True) is z and (z == 7).all()     # not filled again
+    assert buf.get("z", (3, 2), cpu) is not z and buf.get("z", (2, 3), cpu, torch.int32) is not z   # one per (name, shape, dtype)
+
+
 DROPIN_TOP = ("rollout", "runner", "controller", "algorithm", "common", "network", "env", "utils", "smac")
 
 
