@@ -877,6 +877,61 @@ int marl_commnet_head_bwd(const marl_commnet_weights_t* w, const marl_commnet_gr
 int marl_commnet_sigmoid_fwd(float* x, long n, void* stream);
 int marl_commnet_sigmoid_bwd(const float* de, const float* e, float* dxp, long n, void* stream);
 
+/* ---- G2ANet attention head (g2anet.hip) ---------------------------------------------------------------------------------
+ * The second communicating actor of the policy learners (+g2anet; the reference ships only the argument table get_g2anet_args:
+ * attention_dim = 32, hard = True; the definition is this project's own, taken from the published implementation the table comes
+ * from).  G2ANetAgent, H = 64, D = attention_dim = 32, 22 tensors under the published state-dict names:
+ *   encoding = Linear(I, 64), h = GRUCell(64, 64), hard_bi_GRU = GRU(128, 64, bidirectional), hard_encoding = Linear(128, 2),
+ *   q, k = Linear(64, 32, bias=False), v = Linear(64, 32), decoding = Linear(96, A)                  (torch's gate order r, z, n)
+ * Per step t and environment, over the N agent rows (x_t the virtual input [obs | one-hot(u_{t-1}) | agent id]):
+ *   h_t = h(relu(encoding(x_t)), h_{t-1})       the ONLY recurrence in time: marl_agent_unroll_fwd with fc1 = encoding, rnn = h
+ *   hard (args.hard): the partners of agent i are j_1 < .. < j_{N-1}, all j != i; x_{i,p} = [h_i | h_{j_p}];
+ *     f_{i,p} = GRU_fwd(x_{i,p}, f_{i,p-1}), f_{i,0} = 0;  b_{i,p} = GRU_rev(x_{i,p}, b_{i,p+1}), b_{i,N} = 0;
+ *     y_{i,p} = hard_encoding([f_{i,p} | b_{i,p}]);  w_{i,p} = softmax((y + gumbel) / tau)[1] = sigmoid((y_1 - y_0 + l_{i,p}) / tau),
+ *     l = g_1 - g_0 one Logistic(0, 1) draw per pair (the published gumbel_softmax(tau = 0.01, hard=False), column 1: a soft weight
+ *     that is almost always 0 or 1; the gradient goes through the sigmoid, dy_1 = - dy_0 = dw w (1 - w) / tau).  hard off: w = 1,
+ *     and the hard layers receive no gradient.
+ *   soft: q_i = q(h_i), k_j = k(h_j), v_j = relu(v(h_j)); a_{i,.} = softmax over p of q_i . k_{j_p} / sqrt(32);
+ *     x_i = sum_p a_{i,p} w_{i,p} v_{j_p}      (no renormalisation after w)
+ *   logits_i = decoding([h_i | x_i])
+ * Kept as published: noise in every pass (training and evaluation), tau = 0.01, dead agents and finished environments are not
+ * masked out of the partners, N = 1 has no partner and is refused.  The (N-1) x 128 input of the bidirectional GRU is never built:
+ * W_ih [h_i | h_j] = W_ih[:, :64] h_i + W_ih[:, 64:] h_j, so per direction P_i (with b_ih) and Q_j are computed once per row.
+ * The entries take G = B*T environment-steps ("groups") of N rows each, marl_g2anet_groups_per_workgroup(N) = 16 / N whole groups
+ * in a workgroup's 16-row tile.  fp32 MFMA products. */
+typedef struct {
+  const float *gf_w_ih, *gf_w_hh, *gf_b_ih, *gf_b_hh;   /* hard_bi_GRU *_l0: (192,128), (192,64), (192), (192) */
+  const float *gr_w_ih, *gr_w_hh, *gr_b_ih, *gr_b_hh;   /* hard_bi_GRU *_l0_reverse */
+  const float *he_w, *he_b;                             /* hard_encoding: (2,128), (2) */
+  const float *q_w, *k_w, *v_w, *v_b;                   /* (32,64) each, (32) */
+  const float *dec_w, *dec_b;                           /* decoding: (A,96), (A) */
+} marl_g2anet_weights_t;
+typedef struct {
+  float *gf_w_ih, *gf_w_hh, *gf_b_ih, *gf_b_hh, *gr_w_ih, *gr_w_hh, *gr_b_ih, *gr_b_hh, *he_w, *he_b, *q_w, *k_w, *v_w, *v_b, *dec_w,
+      *dec_b;
+} marl_g2anet_grads_t;
+/* 1 when the head kernels cover the shape: 2 <= N <= 10, 1 <= A <= 32, hard 0 or 1.  Outside it every entry returns
+ * hipErrorInvalidValue and launches nothing. */
+int marl_g2anet_supported(int N, int A, int hard);
+int marl_g2anet_groups_per_workgroup(int N);
+/* logits (G,N,A) <- hs (G,N,64) and noise (G,N,N-1) (NULL: l = 0; not read with hard off).  G = 0 launches nothing, returns 0. */
+int marl_g2anet_head_fwd(const marl_g2anet_weights_t* w, const float* hs, const float* noise, float* logits, long G, int N, int A,
+                         int hard, float tau, void* stream);
+/* The backward of marl_g2anet_head_fwd on the same hs / noise / hard / tau: dhs (G,N,64) is WRITTEN with the gradient on hs for
+ * dlogits (G,N,A); the gradients of the head's sixteen tensors are ADDED into g (hard off: the ten hard tensors are not touched).
+ * Every intermediate is recomputed (nothing is kept by the forward): the forward kernel leaves the plane w (G,N,N-1) in ws, a soft
+ * kernel (decoding, attention, q / k / v) replaces it by d(y_1 - y_0), one hard kernel per direction walks its chain in reverse.
+ * Weight gradients: one partial slab per workgroup and kernel, added in slab order by reduce kernels - no float atomics, two
+ * calls give the same bits.  ws: marl_g2anet_bwd_workspace() bytes (the plane and at most 256 slabs of 37504 floats). */
+size_t marl_g2anet_bwd_workspace(long G, int N, int A, int hard);
+int marl_g2anet_head_bwd(const marl_g2anet_weights_t* w, const marl_g2anet_grads_t* g, const float* hs, const float* noise,
+                         const float* dlogits, float* dhs, float* ws, size_t ws_bytes, long G, int N, int A, int hard, float tau,
+                         void* stream);
+/* noise (E,T,N,N-1) of the hard attention: element (e, t, i, p) = ln(u) - ln(1 - u), u = (k + 0.5) / 2^24 with k the upper 24 bits of
+ * the counter hash of stream ST_GUMBEL keyed by (seed, env0 + e, tg0 + t, i (N-1) + p): finite, |l| <= 17.4.  A rollout step is
+ * T = 1 with tg0 = the global step, so one call over T steps from an episode's first global step gives the per-step draws. */
+int marl_g2anet_noise(unsigned seed, int env0, unsigned tg0, float* noise, int E, int T, int N, void* stream);
+
 const char* marl_hip_version(void);
 
 /* Experiment switches (A/B measurements, variant tests): one table per process; NO entry point reads the environment.

@@ -86,6 +86,18 @@ class MarlCommnetGrads(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("w_ih", "w_hh", "b_ih", "b_hh", "dec_w", "dec_b")]
 
 
+_G2ANET_FIELDS = ("gf_w_ih", "gf_w_hh", "gf_b_ih", "gf_b_hh", "gr_w_ih", "gr_w_hh", "gr_b_ih", "gr_b_hh", "he_w", "he_b", "q_w", "k_w", "v_w",
+                  "v_b", "dec_w", "dec_b")
+
+
+class MarlG2anetWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _G2ANET_FIELDS]
+
+
+class MarlG2anetGrads(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in _G2ANET_FIELDS]
+
+
 class MarlAgentGrads(C.Structure):
     _fields_ = [("w_ih", C.c_void_p), ("w_hh", C.c_void_p), ("b_ih", C.c_void_p), ("b_hh", C.c_void_p),
                 ("fc2_w", C.c_void_p), ("fc2_b", C.c_void_p)]
@@ -108,6 +120,7 @@ WW, WG = C.POINTER(MarlWorldWeights), C.POINTER(MarlWorldGrads)
 MW, MG = C.POINTER(MarlMaicWeights), C.POINTER(MarlMaicGrads)
 MIW, MIG = C.POINTER(MarlMaicInfer), C.POINTER(MarlMaicInferGrads)
 CW, CG = C.POINTER(MarlCommnetWeights), C.POINTER(MarlCommnetGrads)
+GW, GG = C.POINTER(MarlG2anetWeights), C.POINTER(MarlG2anetGrads)
 
 # name -> (restype, argtypes); must list every symbol of include/marl_hip.h
 SIGNATURES = {
@@ -228,6 +241,12 @@ SIGNATURES = {
     "marl_commnet_head_bwd": (I, [CW, CG, P, P, P, P, SZ, L, I, I, I, P]),
     "marl_commnet_sigmoid_fwd": (I, [P, L, P]),
     "marl_commnet_sigmoid_bwd": (I, [P, P, P, L, P]),
+    "marl_g2anet_supported": (I, [I, I, I]),
+    "marl_g2anet_groups_per_workgroup": (I, [I]),
+    "marl_g2anet_head_fwd": (I, [GW, P, P, P, L, I, I, I, F, P]),
+    "marl_g2anet_bwd_workspace": (SZ, [L, I, I, I]),
+    "marl_g2anet_head_bwd": (I, [GW, GG, P, P, P, P, P, SZ, L, I, I, I, F, P]),
+    "marl_g2anet_noise": (I, [U, I, U, P, I, I, I, P]),
     "marl_hip_version": (C.c_char_p, []),
     "marl_experiment_set": (I, [C.c_char_p, I]),
     "marl_experiment_get": (I, [C.c_char_p]),

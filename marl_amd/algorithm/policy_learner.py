@@ -116,6 +116,8 @@ class PolicyLearner(Learner):
         critic loss and leaves the actor loss in ``self.actor_loss``; without a critic, returns the actor loss.  The mean entropy
         per live agent step is left in ``self.entropy`` where it was computed (all through LossReadback)."""
         self.epsilon = float(epsilon)
+        if hasattr(self.eval_net, "set_train_step"):     # a controller that draws noise of its own in the update keys it by the step
+            self.eval_net.set_train_step(train_step)
         return Learner.train(self, batch, train_step)
 
     def _finish_update(self, train_step):

@@ -31,6 +31,9 @@ def get_common_args(argv=None):
     p.add_argument('--policy_entropy_coef', type=float, default=0.0)
     # communication rounds of the +commnet actors; absent = get_commnet_args' table (2 on map 3m, otherwise 3)
     p.add_argument('--commnet_k', type=int, default=None)
+    # the +g2anet actors: hard attention on / off and its temperature; absent = get_g2anet_args' True and the published 0.01
+    p.add_argument('--g2anet_hard', type=_bool, default=None)
+    p.add_argument('--g2anet_tau', type=float, default=None)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')

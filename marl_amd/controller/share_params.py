@@ -18,6 +18,7 @@ from ..network.rtw import RTWAgent
 from ..network.world_model import Agent as WorldAgent
 from ..network.maic import MAICAgent
 from ..network.commnet import CommNetAgent, FRONT_A
+from ..network.g2anet import G2ANetAgent, tau_of
 
 
 class SharedMAC:
@@ -418,6 +419,152 @@ class CommNetMAC(PolicyMAC):
         obs, obs_bs, obs_t0 = db.o_cur
         x = self._input(obs, (T * N, obs_bs, obs_t0 * N), db.u_fed, (T * N, db.u_bs, -N), getattr(db, "o_map", None))
         ops.linear_wgrad(de.view(M, H), x, ag.encoding.weight.grad, ag.encoding.bias.grad, M, H, self._get_input_shape(), bf16=False)
+
+
+def g2anet_shape_of(args, n_agents=None, n_actions=None):
+    """(hard, tau) of a +g2anet namespace as the head kernels take them; a shape they do not cover is an error.  ``n_agents`` /
+    ``n_actions``: instead of the namespace's"""
+    N = args.n_agents if n_agents is None else n_agents
+    A = args.n_actions if n_actions is None else n_actions
+    hard = bool(getattr(args, "hard", True))
+    tau = tau_of(args)
+    if not ops.g2anet_supported(N, A, hard):
+        raise ValueError("G2ANet: %d agents and %d actions are outside the head kernels' range (marl_g2anet_supported)" % (N, A))
+    return hard, tau
+
+
+G2ANET_UPDATE_SALT = 0x5BD1E995      # the learner's update noise is keyed by args.seed ^ this: never the rollout's (seed, env, step)
+
+
+class G2ANetPlanes:
+    """What G2ANetMAC.backward reads of the unroll it follows, in buffers the caller owns: the hidden states ``hs`` (B, T, N, H) and
+    the hard attention's noise ``noise`` (B, T, N, N-1) the unroll's head ran on.  Passed to ``unroll`` in the place of ``hs`` and then
+    to ``backward``: an unroll that is not given these planes cannot write them."""
+
+    def __init__(self, hs, noise):
+        assert hs.is_contiguous() and noise.is_contiguous() and tuple(noise.shape) == tuple(hs.shape[:3]) + (hs.shape[2] - 1,)
+        self.hs, self.noise = hs, noise
+
+
+class G2ANetMAC(PolicyMAC):
+    """PolicyMAC over a G2ANetAgent (network/g2anet.py; the project's own definition - DESIGN section 9): the logits of an
+    environment-step come from all N agents' hidden states through the hard and the soft attention.  Every pass is the agent unroll
+    with fc1 = encoding, rnn = h and a zero fc2 (the fp32 kernels in either gemm_mode) -> the attention head (csrc/g2anet.hip).
+    ``backward`` is what the policy learners call in the place of agent_backward.
+
+    Noise (as published: drawn in every pass, evaluation included): a rollout step's is keyed by (seed, environment, global step),
+    an update's by (args.seed ^ G2ANET_UPDATE_SALT, episode index in the batch, train_step * episode_limit + t) - fresh every update,
+    the same after a resume, never the rollout's.  ``set_train_step`` tells the controller the update it is in."""
+
+    head_name = "g2anet"
+
+    def __init__(self, args):
+        self.hard, self.tau = g2anet_shape_of(args)      # raises before anything is built
+        PolicyMAC.__init__(self, args)
+        self._gbuf = Scratch()
+        self.train_step = 0
+
+    def _build_agents(self, input_shape):
+        self.agent = G2ANetAgent(input_shape, self.args)
+
+    def _scratch(self, name, shape, dtype=torch.float32, zero=False):
+        return self._gbuf.get(name, shape, self.device(), dtype, zero)
+
+    def set_train_step(self, train_step):
+        self.train_step = int(train_step)
+
+    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
+        raise NotImplementedError("G2ANetMAC.choose_action: attention needs every agent's observation in one call - "
+                                  "use a batched rollout")
+
+    def rollout_weights(self):
+        return None
+
+    def update_noise(self, noise, B, T):
+        """noise (B, T, N, N-1) <- the draws of the update ``self.train_step`` (not read with hard off: left alone)"""
+        if self.hard and B * T > 0:
+            ops.g2anet_noise(getattr(self.args, "seed", 0) ^ G2ANET_UPDATE_SALT, 0, self.train_step * self.args.episode_limit, noise,
+                             B, T, self.n_agents)
+
+    def rollout_step(self, w, rec, t, h, q, E):
+        """h_t of lock-step t (the T = 1 unroll reading slot t of the record in place); q is written by ``rollout_head``"""
+        N, T, A, a = self.n_agents, rec.T, self.n_actions, self.args
+        if E == 0:
+            return
+        ops.agent_unroll_fwd(self.agent.front_weights(), rec.obs, (T + 1) * N, t, rec.u, T * N, t - 1, h, self._scratch("step_q", (E, 1, N, A)),
+                             None, h, None, E, 1, N, self.obs_shape, A, a.last_action, a.reuse_network)
+
+    def rollout_head(self, h, q, rec, t, E, evaluate, rseed, env):
+        """q (E,1,N,A) is WRITTEN with the head's logits on h; the step's noise is the counter hash of (rseed, environment, global
+        step), exploring or evaluating"""
+        N, A = self.n_agents, self.n_actions
+        if E == 0:
+            return
+        noise = None
+        if self.hard:
+            noise = self._scratch("step_noise", (E, 1, N, N - 1))
+            ops.g2anet_noise(rseed, env.env0, env.global_step(t), noise, E, 1, N)
+        ops.g2anet_head_fwd(self.agent.head_weights(), h, noise, q, E, N, A, self.hard, self.tau)
+
+    def unroll(self, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, B, T, q, hs=None, h_last=None, saved=None, h0="state",
+               ep_len=None, ep_map=None, cu_budget=0, gi_out=None, gi_in=None):
+        """SharedMAC.unroll's signature; q receives the logits.  ``hs``: None, a (B, T, N, H) tensor, or the G2ANetPlanes a later
+        ``backward`` reads (``planes``; its noise is what the head runs on).  Without planes the update's noise is drawn into the
+        controller's own scratch.  Gate-sum reuse does not exist here."""
+        if gi_out is not None or gi_in is not None:
+            raise ValueError("G2ANetMAC.unroll has no gate-sum reuse")
+        N, A, H, a = self.n_agents, self.n_actions, self.args.rnn_hidden_dim, self.args
+        if B == 0:
+            return
+        if h0 == "state":
+            h0 = None if self.hidden_states is None else self.hidden_states.reshape(B * N, -1).contiguous()
+        if isinstance(hs, G2ANetPlanes):
+            assert tuple(hs.hs.shape) == (B, T, N, H)
+            noise, hs = hs.noise, hs.hs
+        else:
+            noise = self._scratch("noise", (B, T, N, N - 1))
+            self.update_noise(noise, B, T)
+            if hs is None:
+                hs = self._scratch("hs", (B, T, N, H))
+        ops.agent_unroll_fwd(self.agent.front_weights(), obs, obs_bs, obs_t0, ufed, u_bs, u_t0, h0, self._scratch("q0", (B, T, N, A)),
+                             hs, h_last, saved, B, T, N, self.obs_shape, A, a.last_action, a.reuse_network, ep_len=ep_len,
+                             ep_map=ep_map, cu_budget=cu_budget)
+        ops.g2anet_head_fwd(self.agent.head_weights(), hs, noise if self.hard else None, q, B * T, N, A, self.hard, self.tau)
+
+    def planes(self, get, shape):
+        """the G2ANetPlanes of an unroll of ``shape`` = (B, T, N, H) in buffers from ``get(name, shape)`` (the learner's scratch), the
+        noise of the update ``self.train_step`` drawn into them"""
+        B, T, N = shape[:3]
+        planes = G2ANetPlanes(get("hs", shape), get("g2anet_noise", (B, T, N, N - 1)))
+        self.update_noise(planes.noise, B, T)
+        return planes
+
+    def backward(self, db, saved, planes, dlogits, buf):
+        """The backward of the ``unroll`` that wrote ``planes`` (and ``saved``), on the batch's current observations: the head's
+        backward on the same noise (dhs and the sixteen head gradients), BPTT with dhs as the gradient on the hidden states (h's
+        gradients; a pair of zeros for dq, the zero fc2's gradients go to scratch) and the encoder's weight gradient over the
+        virtual input - accumulated into the .grad views."""
+        B, T, N, A, O = db.B, db.T, db.N, db.A, db.O
+        H = self.args.rnn_hidden_dim
+        M = B * T * N
+        if M == 0:
+            return
+        if not isinstance(planes, G2ANetPlanes) or tuple(planes.hs.shape) != (B, T, N, H):
+            raise TypeError("G2ANetMAC.backward reads the G2ANetPlanes (B, T, N, H) its unroll was given")
+        hs, noise = planes.hs, planes.noise
+        ag, dev, args = self.agent, hs.device, self.args
+        dhs = buf.get("g2anet_dhs", (B, T, N, H), dev)
+        ops.g2anet_head_bwd(ag.head_weights(), ag.head_grads(), hs, noise if self.hard else None, dlogits, dhs, B * T, N, A, self.hard,
+                            self.tau)
+        dxp = buf.get("dxp", (B, T, N, H), dev)
+        zi, zv = self._scratch("dq_idx", (M,), torch.int32, zero=True), self._scratch("dq_val", (M,), zero=True)
+        grads = {"rnn.weight_ih": ag.h.weight_ih.grad, "rnn.weight_hh": ag.h.weight_hh.grad,
+                 "rnn.bias_ih": ag.h.bias_ih.grad, "rnn.bias_hh": ag.h.bias_hh.grad,
+                 "fc2.weight": self._scratch("d_dummy_w", (A, H)), "fc2.bias": self._scratch("d_dummy_b", (A,))}
+        ops.agent_unroll_bwd(ag.front_weights(), None, dhs, saved, None, dxp, None, grads, B, T, N, A, dq_idx=zi, dq_val=zv, x6=False)
+        obs, obs_bs, obs_t0 = db.o_cur
+        x = ops.agent_input_src(args, N, A, O, obs, (T * N, obs_bs, obs_t0 * N), db.u_fed, (T * N, db.u_bs, -N), getattr(db, "o_map", None))
+        ops.linear_wgrad(dxp.view(M, H), x, ag.encoding.weight.grad, ag.encoding.bias.grad, M, H, self._get_input_shape(), bf16=False)
 
 
 class RTWMAC(SharedMAC):

@@ -8,8 +8,8 @@
 #include "common.h"
 
 // (ST_SAMPLE: the draws of the stochastic policy, policy.hip.  Its number is also the MAIC latent noise's, maic_head.hip: the two
-// never meet, a policy controller has no head)
-enum { ST_OBS = 0, ST_STATE, ST_AVAIL, ST_REWARD, ST_LEN, ST_WON, ST_EXPLORE, ST_PICK, ST_SAMPLE };
+// never meet, a policy controller has no head.  ST_GUMBEL: the logistic noise of G2ANet's hard attention, g2anet.hip)
+enum { ST_OBS = 0, ST_STATE, ST_AVAIL, ST_REWARD, ST_LEN, ST_WON, ST_EXPLORE, ST_PICK, ST_SAMPLE, ST_GUMBEL };
 
 __host__ __device__ inline unsigned mix32(unsigned x) {
   x ^= x >> 16; x *= 0x7FEB352Du; x ^= x >> 15; x *= 0x846CA68Bu; x ^= x >> 16;

@@ -8,6 +8,9 @@
     python -m marl_amd.main --map 2s3z --alg reinforce+commnet --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg central_v+commnet --commnet_k 2 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg coma+commnet --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --map 2s3z --alg reinforce+g2anet --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --map 2s3z --alg central_v+g2anet --g2anet_hard False --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --map 2s3z --alg coma+g2anet --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --MAIC True --load_model True --evaluate True --evaluate_epoch 1 --n_envs 64
 
 ``--env synthetic`` (default) uses the synthetic SMAC-shaped device env with the dims of ``--map``;
@@ -17,7 +20,7 @@ from __future__ import annotations
 import sys
 
 from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
-    get_reinforce_args, get_coma_args, get_commnet_args
+    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .runner import Runner
@@ -27,29 +30,38 @@ MAPS = {"2s3z": (5, 80, 120, 11, 120), "3s5z": (8, 128, 216, 14, 150), "MMM2": (
 
 
 COMMNET = '+commnet'
+G2ANET = '+g2anet'
 _POLICY_ALGS = ('central_v', 'coma', 'reinforce')
+_ACTORS = {COMMNET: ('commnet', 'CommNet'), G2ANET: ('g2anet', 'G2ANet')}
+
+
+def actor_base(alg):
+    """'coma+commnet' -> ('coma', 'commnet'), 'reinforce+g2anet' -> ('reinforce', 'g2anet'); (alg, None) for a name without such a
+    suffix.  The communicating actors belong to the policy-gradient learners: any other base is an error."""
+    for suffix, (actor, title) in _ACTORS.items():
+        if alg.endswith(suffix):
+            base = alg[:-len(suffix)]
+            if base not in _POLICY_ALGS:
+                raise ValueError("%s: the %s actor is trained by central_v, coma or reinforce, not by %r" % (alg, title, base))
+            return base, actor
+    return alg, None
 
 
 def commnet_base(alg):
     """'coma+commnet' -> 'coma'; None for a name without the suffix.  The communicating actor belongs to the policy-gradient
     learners: any other base is an error."""
-    if not alg.endswith(COMMNET):
-        return None
-    base = alg[:-len(COMMNET)]
-    if base not in _POLICY_ALGS:
-        raise ValueError("%s: the CommNet actor is trained by central_v, coma or reinforce, not by %r" % (alg, base))
-    return base
+    base, actor = actor_base(alg) if alg.endswith(COMMNET) else (None, None)
+    return base if actor == 'commnet' else None
 
 
 def build(argv=None):
     args = get_common_args(argv)
     get_mixer_args(args)
-    commnet = commnet_base(args.alg)             # raises on a Q-learning algorithm with +commnet
-    if commnet is not None:
+    base, actor = actor_base(args.alg)           # raises on a Q-learning algorithm with +commnet / +g2anet
+    if actor is not None:
         on = [sw for sw in ('RTW', 'world_model', 'MAIC') if getattr(args, sw, False)]
         if on:
-            raise ValueError("%s trains the CommNet actor as a policy: not with %s" % (args.alg, on[0]))
-    base = commnet if commnet is not None else args.alg
+            raise ValueError("%s trains the %s actor as a policy: not with %s" % (args.alg, _ACTORS['+' + actor][1], on[0]))
     if base in ('central_v', 'coma'):
         given = args.td_lambda
         (get_centralv_args if base == 'central_v' else get_coma_args)(args)
@@ -57,12 +69,21 @@ def build(argv=None):
             args.td_lambda = given
     elif base == 'reinforce':
         get_reinforce_args(args)
-    if commnet is not None:
+    if actor == 'commnet':
         get_commnet_args(args)          # k = 2 on map 3m, otherwise 3
         if getattr(args, "commnet_k", None) is not None:
             args.k = args.commnet_k
         from .controller.share_params import commnet_k_of
         commnet_k_of(args, n_agents=2, n_actions=1)     # the range of k depends on nothing else: refused before the environment is made
+    elif actor == 'g2anet':
+        get_g2anet_args(args)           # attention_dim = 32, hard = True
+        if getattr(args, "g2anet_hard", None) is not None:
+            args.hard = bool(args.g2anet_hard)
+        from .controller.share_params import g2anet_shape_of
+        if args.env in ('smac', 'synthetic'):           # the map's counts are known here: refused before the environment is made
+            g2anet_shape_of(args, n_agents=MAPS[args.map][0], n_actions=MAPS[args.map][3])
+        else:
+            g2anet_shape_of(args, n_agents=2, n_actions=1)      # (a bad --g2anet_tau all the same)
     get_RTW_args(args)
     get_maic_args(args)
     if args.env == 'smac':
@@ -80,27 +101,32 @@ def build(argv=None):
     args.state_shape, args.obs_shape, args.episode_limit = info["state_shape"], info["obs_shape"], info["episode_limit"]
     args.batch_size = max(args.batch_size, args.n_envs)
     args.buffer_size = max(2 * args.n_envs, min(args.buffer_size, 8 * args.n_envs))
-    if commnet is not None:
+    if actor == 'commnet':
         commnet_k_of(args)              # ... and the environment's agent and action counts with it, before a controller is built
+    elif actor == 'g2anet':
+        g2anet_shape_of(args)
     return args, env
 
 
 def make_runner(args, env, logger=None):
     """the Runner of a built (args, env).  ``--alg coma`` names its learner here: the runner's own table of on-policy learners
     holds central_v and reinforce, and a Runner built on the bare name 'coma' still refuses it.  The three ``+commnet`` algorithms get
-    their learner class and CommNetMAC (``mac_cls``) the same way."""
+    their learner class and CommNetMAC (``mac_cls``) the same way, the three ``+g2anet`` ones theirs and G2ANetMAC."""
     learner_cls = mac_cls = None
-    commnet = commnet_base(args.alg)
-    if args.alg == 'coma' or commnet == 'coma':
+    base, actor = actor_base(args.alg)
+    if base == 'coma':
         from .algorithm.coma import COMALearner
         learner_cls = COMALearner
-    elif commnet is not None:           # the +commnet names are the launcher's: the runner's own table does not hold them
+    elif actor is not None:             # the +commnet / +g2anet names are the launcher's: the runner's own table does not hold them
         from .algorithm.central_v import CentralVLearner
         from .algorithm.reinforce import ReinforceLearner
-        learner_cls = CentralVLearner if commnet == 'central_v' else ReinforceLearner
-    if commnet is not None:
+        learner_cls = CentralVLearner if base == 'central_v' else ReinforceLearner
+    if actor == 'commnet':
         from .controller.share_params import CommNetMAC
         mac_cls = CommNetMAC
+    elif actor == 'g2anet':
+        from .controller.share_params import G2ANetMAC
+        mac_cls = G2ANetMAC
     return Runner(env, logger if logger is not None else Logger(), args, learner_cls=learner_cls, mac_cls=mac_cls)
 
 

@@ -12,7 +12,8 @@ import torch
 from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
                    MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, MarlMaicGrads, MarlMaicInfer,
-                   MarlMaicInferGrads, MarlCommnetWeights, MarlCommnetGrads, check)
+                   MarlMaicInferGrads, MarlCommnetWeights, MarlCommnetGrads, MarlG2anetWeights, MarlG2anetGrads,
+                   check)
 
 
 def _p(t):
@@ -572,6 +573,61 @@ def commnet_sigmoid_bwd(de, e, dxp):
     assert de.is_contiguous() and e.is_contiguous() and dxp.is_contiguous() and de.numel() == e.numel() == dxp.numel()
     check(_lib.load().marl_commnet_sigmoid_bwd(_p(_f32(de)), _p(_f32(e)), _p(_f32(dxp)), de.numel(), _stream()),
           "marl_commnet_sigmoid_bwd")
+
+
+# ---- G2ANet attention head (csrc/g2anet.hip)
+_G2ANET_KEYS = (("gf_w_ih", "hard_bi_GRU.weight_ih_l0"), ("gf_w_hh", "hard_bi_GRU.weight_hh_l0"), ("gf_b_ih", "hard_bi_GRU.bias_ih_l0"),
+                ("gf_b_hh", "hard_bi_GRU.bias_hh_l0"), ("gr_w_ih", "hard_bi_GRU.weight_ih_l0_reverse"),
+                ("gr_w_hh", "hard_bi_GRU.weight_hh_l0_reverse"), ("gr_b_ih", "hard_bi_GRU.bias_ih_l0_reverse"),
+                ("gr_b_hh", "hard_bi_GRU.bias_hh_l0_reverse"), ("he_w", "hard_encoding.weight"), ("he_b", "hard_encoding.bias"),
+                ("q_w", "q.weight"), ("k_w", "k.weight"), ("v_w", "v.weight"), ("v_b", "v.bias"), ("dec_w", "decoding.weight"),
+                ("dec_b", "decoding.bias"))
+_G2ANET_FIELDS = [(field, name, torch.float32) for field, name in _G2ANET_KEYS]
+G2ANET_HEAD_PARAMS = tuple(name for _, name in _G2ANET_KEYS)
+
+
+def g2anet_supported(N, A, hard=True):
+    return bool(_lib.load().marl_g2anet_supported(int(N), int(A), 1 if hard else 0))
+
+
+def g2anet_groups_per_workgroup(N):
+    """whole groups (environment-steps) in one 16-row tile of the head kernels"""
+    return int(_lib.load().marl_g2anet_groups_per_workgroup(int(N)))
+
+
+def g2anet_weights(tensors):
+    """tensors: dict name -> tensor with G2ANetAgent's head keys (G2ANET_HEAD_PARAMS)"""
+    return _fill_struct(MarlG2anetWeights, tensors, _G2ANET_FIELDS)
+
+
+def g2anet_grads(grads):
+    """grads: dict of the same keys -> gradient tensors (accumulated into)"""
+    return _fill_struct(MarlG2anetGrads, grads, _G2ANET_FIELDS)
+
+
+def g2anet_head_fwd(w, hs, noise, logits, G, N, A, hard, tau):
+    """logits (G,N,A) <- hs (G,N,64), noise (G,N,N-1) or None (l = 0): hard attention, soft attention, decoding"""
+    assert hs.is_contiguous() and logits.is_contiguous() and (noise is None or (_f32(noise).is_contiguous() and noise.numel() >= G * N * (N - 1)))
+    check(_lib.load().marl_g2anet_head_fwd(C.byref(w), _p(_f32(hs)), _p(noise), _p(_f32(logits)), int(G), int(N), int(A),
+                                           1 if hard else 0, float(tau), _stream()), "marl_g2anet_head_fwd")
+
+
+def g2anet_head_bwd(w, g, hs, noise, dlogits, dhs, G, N, A, hard, tau):
+    """dhs (G,N,64) written; the head's sixteen gradients added into g (fixed-order slab reductions)"""
+    lib = _lib.load()
+    assert hs.is_contiguous() and dlogits.is_contiguous() and dhs.is_contiguous()
+    assert noise is None or (_f32(noise).is_contiguous() and noise.numel() >= G * N * (N - 1))
+    ws = WS.get("g2anet_bwd", lib.marl_g2anet_bwd_workspace(int(G), int(N), int(A), 1 if hard else 0), hs.device)
+    check(lib.marl_g2anet_head_bwd(C.byref(w), C.byref(g), _p(_f32(hs)), _p(noise), _p(_f32(dlogits)), _p(_f32(dhs)), _p(ws),
+                                   ws.numel() * 4, int(G), int(N), int(A), 1 if hard else 0, float(tau), _stream()),
+          "marl_g2anet_head_bwd")
+
+
+def g2anet_noise(seed, env0, tg0, noise, E, T, N):
+    """noise (E,T,N,N-1) <- the logistic draws of (seed, env0 + e, tg0 + t)"""
+    assert _f32(noise).is_contiguous() and noise.numel() >= E * T * N * (N - 1)
+    check(_lib.load().marl_g2anet_noise(int(seed) & 0xFFFFFFFF, int(env0), int(tg0) & 0xFFFFFFFF, _p(noise), int(E), int(T), int(N),
+                                        _stream()), "marl_g2anet_noise")
 
 
 def grad_sumsq(g, n, out1):
