@@ -373,7 +373,7 @@ def agent_backward(mac, db, which, saved, hs, dq, dhs, buf, dq_idx=None, dq_val=
 
 def policy_backward(mac, db, saved, hs, dlogits, buf):
     """The actor's backward of the policy learners on the dense gradient of the logits: a controller with a ``backward`` of its own
-    (CommNetMAC: head, recurrence and encoder) runs that; otherwise BPTT of the plain unroll, exactly as before."""
+    (GroupHeadMAC, so CommNetMAC and G2ANetMAC: head, recurrence and encoder) runs that; otherwise BPTT of the plain unroll, exactly as before."""
     if hasattr(mac, "backward"):
         mac.backward(db, saved, hs, dlogits, buf)
     else:

@@ -291,6 +291,97 @@ class PolicyMAC(SharedMAC):
         return int(np.random.choice(A, p=pi / pi.sum()))
 
 
+class GroupHeadMAC(PolicyMAC):
+    """PolicyMAC whose logits of an environment-step come from all N agents' hidden states: every pass is a front (what feeds the
+    recurrence, and the agent unroll over it - the fp32 kernels in either gemm_mode) followed by a group head.  ``unroll`` and
+    ``backward`` (what the policy learners call in the place of agent_backward) are written here once; an actor supplies
+      ``planes_cls`` / ``extra``     the planes its backward reads: hs and one more, under that attribute and scratch name
+      ``_extra_plane(get, name, B, T)``   that plane (B, T, N, .) from ``get``, filled if an unroll only reads it
+      ``_front_forward(src, B, T, extra, h0, hs, h_last, saved, **kw)``   the recurrence's input and ops.agent_unroll_fwd
+      ``_head_forward(hs, extra, q, G)`` / ``_head_backward(hs, extra, dlogits, dhs, G)``   the head over G = B T groups
+      ``front_cell`` / ``front_rows``   the GRUCell that holds the recurrence's gradients, the rows of the dummy fc2 (None: n_actions)
+      ``_after_bptt(dxp, extra)``    between BPTT and the encoder's weight gradient (nothing by default)."""
+
+    planes_cls = extra = couples = front_cell = front_rows = None
+
+    def __init__(self, args):
+        PolicyMAC.__init__(self, args)
+        self._buf = Scratch()
+
+    def _scratch(self, name, shape, dtype=torch.float32, zero=False):
+        return self._buf.get(name, shape, self.device(), dtype, zero)
+
+    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
+        raise NotImplementedError("%s.choose_action: %s needs every agent's observation in one call - use a batched rollout"
+                                  % (type(self).__name__, self.couples))
+
+    def rollout_weights(self):
+        return None
+
+    def _input(self, obs, remap0, ufed, remapi, ep_map=None):
+        """the virtual input [obs | one-hot(u_{t-1}) | agent id] as agent_backward builds it"""
+        return ops.agent_input_src(self.args, self.n_agents, self.n_actions, self.obs_shape, obs, remap0, ufed, remapi, ep_map)
+
+    def _after_bptt(self, dxp, extra):
+        pass
+
+    def unroll(self, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, B, T, q, hs=None, h_last=None, saved=None, h0="state",
+               ep_len=None, ep_map=None, cu_budget=0, gi_out=None, gi_in=None):
+        """SharedMAC.unroll's signature; q receives the logits.  ``hs``: None, a (B, T, N, H) tensor, or the ``planes_cls`` a later
+        ``backward`` reads (``planes``).  Without planes the extra plane is the controller's own scratch (and the learner's planes
+        stay untouched).  Gate-sum reuse does not exist here."""
+        if gi_out is not None or gi_in is not None:
+            raise ValueError("%s.unroll has no gate-sum reuse" % type(self).__name__)
+        N, H = self.n_agents, self.args.rnn_hidden_dim
+        if B == 0:
+            return
+        if h0 == "state":
+            h0 = None if self.hidden_states is None else self.hidden_states.reshape(B * N, -1).contiguous()
+        if isinstance(hs, self.planes_cls):
+            assert tuple(hs.hs.shape) == (B, T, N, H)
+            extra, hs = getattr(hs, self.extra), hs.hs
+        else:
+            extra = self._extra_plane(self._scratch, self.extra, B, T)
+            if hs is None:
+                hs = self._scratch("hs", (B, T, N, H))
+        self._front_forward((obs, obs_bs, obs_t0, ufed, u_bs, u_t0), B, T, extra, h0, hs, h_last, saved, ep_len=ep_len, ep_map=ep_map,
+                            cu_budget=cu_budget)
+        self._head_forward(hs, extra, q, B * T)
+
+    def planes(self, get, shape):
+        """the ``planes_cls`` of an unroll of ``shape`` = (B, T, N, H) in buffers from ``get(name, shape)`` (the learner's scratch)"""
+        return self.planes_cls(get("hs", shape), self._extra_plane(get, "%s_%s" % (self.head_name, self.extra), shape[0], shape[1]))
+
+    def backward(self, db, saved, planes, dlogits, buf):
+        """The backward of the ``unroll`` that wrote ``planes`` (and ``saved``), on the batch's current observations: the head's
+        backward (dhs and the head's gradients), BPTT through the front with dhs as the gradient on the hidden states (the
+        gradients of ``front_cell`` and dxp; a pair of zeros for dq, the dummy fc2's gradients go to scratch), ``_after_bptt``
+        and the encoder's weight gradient over the virtual input - accumulated into the .grad views."""
+        B, T, N = db.B, db.T, db.N
+        H = self.args.rnn_hidden_dim
+        M = B * T * N
+        if M == 0:
+            return
+        if not isinstance(planes, self.planes_cls) or tuple(planes.hs.shape) != (B, T, N, H):
+            raise TypeError("%s.backward reads the %s (B, T, N, H) its unroll was given" % (type(self).__name__, self.planes_cls.__name__))
+        hs, extra = planes.hs, getattr(planes, self.extra)
+        ag, dev = self.agent, hs.device
+        dhs = buf.get(self.head_name + "_dhs", (B, T, N, H), dev)
+        self._head_backward(hs, extra, dlogits, dhs, B * T)
+        dxp = buf.get("dxp", (B, T, N, H), dev)
+        # the BPTT entry wants one form of dq: a sparse pair of zeros; the dummy fc2's gradients go to scratch
+        zi, zv = self._scratch("dq_idx", (M,), torch.int32, zero=True), self._scratch("dq_val", (M,), zero=True)
+        cell, rows = getattr(ag, self.front_cell), self.front_rows or self.n_actions
+        grads = {"rnn.weight_ih": cell.weight_ih.grad, "rnn.weight_hh": cell.weight_hh.grad,
+                 "rnn.bias_ih": cell.bias_ih.grad, "rnn.bias_hh": cell.bias_hh.grad,
+                 "fc2.weight": self._scratch("d_dummy_w", (rows, H)), "fc2.bias": self._scratch("d_dummy_b", (rows,))}
+        ops.agent_unroll_bwd(ag.front_weights(), None, dhs, saved, None, dxp, None, grads, B, T, N, rows, dq_idx=zi, dq_val=zv, x6=False)
+        self._after_bptt(dxp, extra)
+        obs, obs_bs, obs_t0 = db.o_cur
+        x = self._input(obs, (T * N, obs_bs, obs_t0 * N), db.u_fed, (T * N, db.u_bs, -N), getattr(db, "o_map", None))
+        ops.linear_wgrad(dxp.view(M, H), x, ag.encoding.weight.grad, ag.encoding.bias.grad, M, H, self._get_input_shape(), bf16=False)
+
+
 def commnet_k_of(args, n_agents=None, n_actions=None):
     """args.k as the head kernels take it; anything they do not cover is an error.  ``n_agents`` / ``n_actions``: instead of the
     namespace's (the launcher checks k alone before it knows them)"""
@@ -313,38 +404,25 @@ class CommNetPlanes:
         self.hs, self.e = hs, e
 
 
-class CommNetMAC(PolicyMAC):
-    """PolicyMAC over a CommNetAgent (network/commnet.py; the project's own definition - DESIGN section 9): the logits of an
-    environment-step come from all N agents' hidden states.  Every pass is encoder (ops.linear + the sigmoid kernel) -> the agent
-    unroll over the identity front layer (h_t = f_obs(e_t, h_{t-1}), the fp32 kernels in either gemm_mode) -> the communication head
-    (csrc/commnet.hip).  ``backward`` is what the policy learners call in the place of agent_backward.
+class CommNetMAC(GroupHeadMAC):
+    """GroupHeadMAC over a CommNetAgent (network/commnet.py; the project's own definition - DESIGN section 9).  The front is the
+    encoder (ops.linear + the sigmoid kernel, into the plane ``e``) and the agent unroll over the identity front layer (h_t =
+    f_obs(e_t, h_{t-1})), so BPTT's dxp is the gradient on e and the sigmoid's backward follows it; the head is the communication head
+    (csrc/commnet.hip).
 
     Padded steps: the encoder reads the stored observation rows (no zero padding at t >= ep_len), so logits there are finite and
     deterministic but are not the float64 restatement's; every loss masks them and the recurrence runs forward only."""
 
     head_name = "commnet"
+    planes_cls, extra, couples = CommNetPlanes, "e", "communication"
+    front_cell, front_rows = "f_obs", FRONT_A
 
     def __init__(self, args):
         self.k = commnet_k_of(args)          # raises before anything is built
-        PolicyMAC.__init__(self, args)
-        self._cbuf = Scratch()
+        GroupHeadMAC.__init__(self, args)
 
     def _build_agents(self, input_shape):
         self.agent = CommNetAgent(input_shape, self.args)
-
-    def _scratch(self, name, shape, dtype=torch.float32, zero=False):
-        return self._cbuf.get(name, shape, self.device(), dtype, zero)
-
-    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
-        raise NotImplementedError("CommNetMAC.choose_action: communication needs every agent's observation in one call - "
-                                  "use a batched rollout")
-
-    def rollout_weights(self):
-        return None
-
-    def _input(self, obs, remap0, ufed, remapi, ep_map=None):
-        """the virtual input [obs | one-hot(u_{t-1}) | agent id] as agent_backward builds it"""
-        return ops.agent_input_src(self.args, self.n_agents, self.n_actions, self.obs_shape, obs, remap0, ufed, remapi, ep_map)
 
     def _encode(self, x, e, M):
         """e (M, 64) = sigmoid(encoding(x))"""
@@ -363,62 +441,27 @@ class CommNetMAC(PolicyMAC):
                              None, h, None, E, 1, N, H, FRONT_A, False, False)
         ops.commnet_head_fwd(self.agent.head_weights(), h, q, E, N, A, self.k)
 
-    def unroll(self, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, B, T, q, hs=None, h_last=None, saved=None, h0="state",
-               ep_len=None, ep_map=None, cu_budget=0, gi_out=None, gi_in=None):
-        """SharedMAC.unroll's signature; q receives the logits.  ``hs``: None, a (B, T, N, H) tensor, or the CommNetPlanes a later
-        ``backward`` reads (``planes``).  ``ep_len`` is not applied to the encoder (class docstring); gate-sum reuse does not exist here."""
-        if gi_out is not None or gi_in is not None:
-            raise ValueError("CommNetMAC.unroll has no gate-sum reuse")
-        N, A, H = self.n_agents, self.n_actions, self.args.rnn_hidden_dim
-        if B == 0:
-            return
-        if h0 == "state":
-            h0 = None if self.hidden_states is None else self.hidden_states.reshape(B * N, -1).contiguous()
-        x = self._input(obs, (T * N, obs_bs, obs_t0 * N), ufed, (T * N, u_bs, u_t0 * N), ep_map)
-        if isinstance(hs, CommNetPlanes):
-            assert tuple(hs.hs.shape) == (B, T, N, H)
-            e, hs = hs.e, hs.hs
-        else:
-            e = self._scratch("e", (B, T, N, H))
-            if hs is None:
-                hs = self._scratch("hs", (B, T, N, H))
-        self._encode(x, e, B * T * N)
+    def _extra_plane(self, get, name, B, T):
+        return get(name, (B, T, self.n_agents, self.args.rnn_hidden_dim))
+
+    def _front_forward(self, src, B, T, e, h0, hs, h_last, saved, ep_len=None, ep_map=None, cu_budget=0):
+        """``ep_len`` is not applied to the encoder (class docstring)"""
+        obs, obs_bs, obs_t0, ufed, u_bs, u_t0 = src
+        N, H = self.n_agents, self.args.rnn_hidden_dim
+        self._encode(self._input(obs, (T * N, obs_bs, obs_t0 * N), ufed, (T * N, u_bs, u_t0 * N), ep_map), e, B * T * N)
         ops.agent_unroll_fwd(self.agent.front_weights(), e, T * N, 0, None, 0, 0, h0, self._scratch("q0", (B, T, N, FRONT_A)),
                              hs, h_last, saved, B, T, N, H, FRONT_A, False, False, cu_budget=cu_budget)
-        ops.commnet_head_fwd(self.agent.head_weights(), hs, q, B * T, N, A, self.k)
 
-    def planes(self, get, shape):
-        """the CommNetPlanes of an unroll of ``shape`` = (B, T, N, H) in buffers from ``get(name, shape)`` (the learner's scratch)"""
-        return CommNetPlanes(get("hs", shape), get("commnet_e", shape))
+    def _head_forward(self, hs, e, q, G):
+        ops.commnet_head_fwd(self.agent.head_weights(), hs, q, G, self.n_agents, self.n_actions, self.k)
 
-    def backward(self, db, saved, planes, dlogits, buf):
-        """The backward of the ``unroll`` that wrote ``planes`` (and ``saved``), on the batch's current observations: the head's
-        backward (dhs and the gradients of f_comm and
-        decoding), BPTT through the identity front with dhs as the gradient on the hidden states (f_obs's gradients; its dxp is the
-        gradient on e), the sigmoid's backward and the encoder's weight gradient - accumulated into the .grad views."""
-        B, T, N, A, O = db.B, db.T, db.N, db.A, db.O
-        H = self.args.rnn_hidden_dim
-        M = B * T * N
-        if M == 0:
-            return
-        if not isinstance(planes, CommNetPlanes) or tuple(planes.hs.shape) != (B, T, N, H):
-            raise TypeError("CommNetMAC.backward reads the CommNetPlanes (B, T, N, H) its unroll was given")
-        hs, e = planes.hs, planes.e
-        ag, dev = self.agent, hs.device
-        dhs = buf.get("commnet_dhs", (B, T, N, H), dev)
-        ops.commnet_head_bwd(ag.head_weights(), ag.head_grads(), hs, dlogits, dhs, B * T, N, A, self.k)
-        de = buf.get("dxp", (B, T, N, H), dev)
-        # the BPTT entry wants one form of dq: a sparse pair of zeros; the dummy fc2's gradients go to scratch
-        zi, zv = self._scratch("dq_idx", (M,), torch.int32, zero=True), self._scratch("dq_val", (M,), zero=True)
-        grads = {"rnn.weight_ih": ag.f_obs.weight_ih.grad, "rnn.weight_hh": ag.f_obs.weight_hh.grad,
-                 "rnn.bias_ih": ag.f_obs.bias_ih.grad, "rnn.bias_hh": ag.f_obs.bias_hh.grad,
-                 "fc2.weight": self._scratch("d_dummy_w", (FRONT_A, H)), "fc2.bias": self._scratch("d_dummy_b", (FRONT_A,))}
-        ops.agent_unroll_bwd(ag.front_weights(), None, dhs, saved, None, de, None, grads, B, T, N, FRONT_A, dq_idx=zi, dq_val=zv,
-                             x6=False)
+    def _head_backward(self, hs, e, dlogits, dhs, G):
+        """dhs and the gradients of f_comm and decoding"""
+        ag = self.agent
+        ops.commnet_head_bwd(ag.head_weights(), ag.head_grads(), hs, dlogits, dhs, G, self.n_agents, self.n_actions, self.k)
+
+    def _after_bptt(self, de, e):
         ops.commnet_sigmoid_bwd(de, e, de)
-        obs, obs_bs, obs_t0 = db.o_cur
-        x = self._input(obs, (T * N, obs_bs, obs_t0 * N), db.u_fed, (T * N, db.u_bs, -N), getattr(db, "o_map", None))
-        ops.linear_wgrad(de.view(M, H), x, ag.encoding.weight.grad, ag.encoding.bias.grad, M, H, self._get_input_shape(), bf16=False)
 
 
 def g2anet_shape_of(args, n_agents=None, n_actions=None):
@@ -446,39 +489,29 @@ class G2ANetPlanes:
         self.hs, self.noise = hs, noise
 
 
-class G2ANetMAC(PolicyMAC):
-    """PolicyMAC over a G2ANetAgent (network/g2anet.py; the project's own definition - DESIGN section 9): the logits of an
-    environment-step come from all N agents' hidden states through the hard and the soft attention.  Every pass is the agent unroll
-    with fc1 = encoding, rnn = h and a zero fc2 (the fp32 kernels in either gemm_mode) -> the attention head (csrc/g2anet.hip).
-    ``backward`` is what the policy learners call in the place of agent_backward.
+class G2ANetMAC(GroupHeadMAC):
+    """GroupHeadMAC over a G2ANetAgent (network/g2anet.py; the project's own definition - DESIGN section 9).  The front is the agent
+    unroll over the observation with fc1 = encoding, rnn = h and a zero fc2; the head is the hard and the soft attention
+    (csrc/g2anet.hip), run on the plane ``noise`` (B, T, N, N-1) that an unroll only reads.
 
     Noise (as published: drawn in every pass, evaluation included): a rollout step's is keyed by (seed, environment, global step),
     an update's by (args.seed ^ G2ANET_UPDATE_SALT, episode index in the batch, train_step * episode_limit + t) - fresh every update,
     the same after a resume, never the rollout's.  ``set_train_step`` tells the controller the update it is in."""
 
     head_name = "g2anet"
+    planes_cls, extra, couples = G2ANetPlanes, "noise", "attention"
+    front_cell = "h"                 # front_rows: n_actions
 
     def __init__(self, args):
         self.hard, self.tau = g2anet_shape_of(args)      # raises before anything is built
-        PolicyMAC.__init__(self, args)
-        self._gbuf = Scratch()
+        GroupHeadMAC.__init__(self, args)
         self.train_step = 0
 
     def _build_agents(self, input_shape):
         self.agent = G2ANetAgent(input_shape, self.args)
 
-    def _scratch(self, name, shape, dtype=torch.float32, zero=False):
-        return self._gbuf.get(name, shape, self.device(), dtype, zero)
-
     def set_train_step(self, train_step):
         self.train_step = int(train_step)
-
-    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
-        raise NotImplementedError("G2ANetMAC.choose_action: attention needs every agent's observation in one call - "
-                                  "use a batched rollout")
-
-    def rollout_weights(self):
-        return None
 
     def update_noise(self, noise, B, T):
         """noise (B, T, N, N-1) <- the draws of the update ``self.train_step`` (not read with hard off: left alone)"""
@@ -506,65 +539,28 @@ class G2ANetMAC(PolicyMAC):
             ops.g2anet_noise(rseed, env.env0, env.global_step(t), noise, E, 1, N)
         ops.g2anet_head_fwd(self.agent.head_weights(), h, noise, q, E, N, A, self.hard, self.tau)
 
-    def unroll(self, obs, obs_bs, obs_t0, ufed, u_bs, u_t0, B, T, q, hs=None, h_last=None, saved=None, h0="state",
-               ep_len=None, ep_map=None, cu_budget=0, gi_out=None, gi_in=None):
-        """SharedMAC.unroll's signature; q receives the logits.  ``hs``: None, a (B, T, N, H) tensor, or the G2ANetPlanes a later
-        ``backward`` reads (``planes``; its noise is what the head runs on).  Without planes the update's noise is drawn into the
-        controller's own scratch.  Gate-sum reuse does not exist here."""
-        if gi_out is not None or gi_in is not None:
-            raise ValueError("G2ANetMAC.unroll has no gate-sum reuse")
-        N, A, H, a = self.n_agents, self.n_actions, self.args.rnn_hidden_dim, self.args
-        if B == 0:
-            return
-        if h0 == "state":
-            h0 = None if self.hidden_states is None else self.hidden_states.reshape(B * N, -1).contiguous()
-        if isinstance(hs, G2ANetPlanes):
-            assert tuple(hs.hs.shape) == (B, T, N, H)
-            noise, hs = hs.noise, hs.hs
-        else:
-            noise = self._scratch("noise", (B, T, N, N - 1))
-            self.update_noise(noise, B, T)
-            if hs is None:
-                hs = self._scratch("hs", (B, T, N, H))
-        ops.agent_unroll_fwd(self.agent.front_weights(), obs, obs_bs, obs_t0, ufed, u_bs, u_t0, h0, self._scratch("q0", (B, T, N, A)),
+    def _extra_plane(self, get, name, B, T):
+        """the noise of the update ``self.train_step``, drawn into the plane"""
+        N = self.n_agents
+        noise = get(name, (B, T, N, N - 1))
+        self.update_noise(noise, B, T)
+        return noise
+
+    def _front_forward(self, src, B, T, noise, h0, hs, h_last, saved, ep_len=None, ep_map=None, cu_budget=0):
+        N, A, a = self.n_agents, self.n_actions, self.args
+        ops.agent_unroll_fwd(self.agent.front_weights(), *src, h0, self._scratch("q0", (B, T, N, A)),
                              hs, h_last, saved, B, T, N, self.obs_shape, A, a.last_action, a.reuse_network, ep_len=ep_len,
                              ep_map=ep_map, cu_budget=cu_budget)
-        ops.g2anet_head_fwd(self.agent.head_weights(), hs, noise if self.hard else None, q, B * T, N, A, self.hard, self.tau)
 
-    def planes(self, get, shape):
-        """the G2ANetPlanes of an unroll of ``shape`` = (B, T, N, H) in buffers from ``get(name, shape)`` (the learner's scratch), the
-        noise of the update ``self.train_step`` drawn into them"""
-        B, T, N = shape[:3]
-        planes = G2ANetPlanes(get("hs", shape), get("g2anet_noise", (B, T, N, N - 1)))
-        self.update_noise(planes.noise, B, T)
-        return planes
+    def _head_forward(self, hs, noise, q, G):
+        ops.g2anet_head_fwd(self.agent.head_weights(), hs, noise if self.hard else None, q, G, self.n_agents, self.n_actions,
+                            self.hard, self.tau)
 
-    def backward(self, db, saved, planes, dlogits, buf):
-        """The backward of the ``unroll`` that wrote ``planes`` (and ``saved``), on the batch's current observations: the head's
-        backward on the same noise (dhs and the sixteen head gradients), BPTT with dhs as the gradient on the hidden states (h's
-        gradients; a pair of zeros for dq, the zero fc2's gradients go to scratch) and the encoder's weight gradient over the
-        virtual input - accumulated into the .grad views."""
-        B, T, N, A, O = db.B, db.T, db.N, db.A, db.O
-        H = self.args.rnn_hidden_dim
-        M = B * T * N
-        if M == 0:
-            return
-        if not isinstance(planes, G2ANetPlanes) or tuple(planes.hs.shape) != (B, T, N, H):
-            raise TypeError("G2ANetMAC.backward reads the G2ANetPlanes (B, T, N, H) its unroll was given")
-        hs, noise = planes.hs, planes.noise
-        ag, dev, args = self.agent, hs.device, self.args
-        dhs = buf.get("g2anet_dhs", (B, T, N, H), dev)
-        ops.g2anet_head_bwd(ag.head_weights(), ag.head_grads(), hs, noise if self.hard else None, dlogits, dhs, B * T, N, A, self.hard,
-                            self.tau)
-        dxp = buf.get("dxp", (B, T, N, H), dev)
-        zi, zv = self._scratch("dq_idx", (M,), torch.int32, zero=True), self._scratch("dq_val", (M,), zero=True)
-        grads = {"rnn.weight_ih": ag.h.weight_ih.grad, "rnn.weight_hh": ag.h.weight_hh.grad,
-                 "rnn.bias_ih": ag.h.bias_ih.grad, "rnn.bias_hh": ag.h.bias_hh.grad,
-                 "fc2.weight": self._scratch("d_dummy_w", (A, H)), "fc2.bias": self._scratch("d_dummy_b", (A,))}
-        ops.agent_unroll_bwd(ag.front_weights(), None, dhs, saved, None, dxp, None, grads, B, T, N, A, dq_idx=zi, dq_val=zv, x6=False)
-        obs, obs_bs, obs_t0 = db.o_cur
-        x = ops.agent_input_src(args, N, A, O, obs, (T * N, obs_bs, obs_t0 * N), db.u_fed, (T * N, db.u_bs, -N), getattr(db, "o_map", None))
-        ops.linear_wgrad(dxp.view(M, H), x, ag.encoding.weight.grad, ag.encoding.bias.grad, M, H, self._get_input_shape(), bf16=False)
+    def _head_backward(self, hs, noise, dlogits, dhs, G):
+        """on the unroll's noise: dhs and the sixteen head gradients"""
+        ag = self.agent
+        ops.g2anet_head_bwd(ag.head_weights(), ag.head_grads(), hs, noise if self.hard else None, dlogits, dhs, G, self.n_agents,
+                            self.n_actions, self.hard, self.tau)
 
 
 class RTWMAC(SharedMAC):

@@ -28,13 +28,12 @@
 // No implicit contraction in this file: a row's value must not depend on where in a tile it sits, and the compiler may fuse the four
 // unrolled instances of a lane's pointwise code differently; the fused operations below are written out.
 #pragma clang fp contract(off)
+#include "group_tile.h"    // the whole-group tile, the W_hh fragments, the GRU point and its backward (H, LD, G3, LDG)
 
 namespace {
 
-constexpr int CN_H = 64;
-constexpr int CN_LD = CN_H + 4;            // row pitch of the 16 x 64 planes: 4 rows apart = 16 banks apart
-constexpr int CN_G3 = 3 * CN_H;
-constexpr int CN_LDG = CN_G3 + 4;          // row pitch of the 16 x 192 gate-gradient planes
+using namespace group_tile;
+
 constexpr int CN_NMAX = 16;
 constexpr int CN_AMAX = 32;
 constexpr int CN_LDA = CN_AMAX + 4;
@@ -42,8 +41,8 @@ constexpr int CN_KMAX = 4;
 constexpr int CN_FWD_WG = 512;             // workgroups of the forward (persistent over the tiles)
 constexpr int CN_BWD_WG = 256;             // workgroups = slabs of the backward
 // one slab: dW_ih | dW_hh | dW_dec (32 rows) | db_ih | db_hh | db_dec
-constexpr int CN_S_IH = 0, CN_S_HH = CN_G3 * CN_H, CN_S_DEC = 2 * CN_G3 * CN_H, CN_S_BIH = CN_S_DEC + CN_AMAX * CN_H;
-constexpr int CN_S_BHH = CN_S_BIH + CN_G3, CN_S_BDEC = CN_S_BHH + CN_G3, CN_SLAB = CN_S_BDEC + CN_AMAX;
+constexpr int CN_S_IH = 0, CN_S_HH = G3 * H, CN_S_DEC = 2 * G3 * H, CN_S_BIH = CN_S_DEC + CN_AMAX * H;
+constexpr int CN_S_BHH = CN_S_BIH + G3, CN_S_BDEC = CN_S_BHH + G3, CN_SLAB = CN_S_BDEC + CN_AMAX;
 
 struct CommArgs {
   marl_commnet_weights_t w;
@@ -57,16 +56,16 @@ struct CommArgs {
   float invN;
 };
 
-// forward-form B fragments of f_comm for column col = 16 w + m: fragment [gate][chunk][i] = W[gate * 64 + col][16 chunk + 4 q + i]
-struct CnW {
-  f32x4 ih[3][4], hh[3][4];
-  float bi[3], bh[3];
+// forward-form B fragments of f_comm for column col = 16 w + m: the W_hh half (group_tile.h) and W_ih in the same form
+struct CnW : HH {
+  f32x4 ih[3][4];
+  float bi[3];
 };
 
 __device__ __forceinline__ void cn_load_w(CnW& W, const marl_commnet_weights_t& w, int col, int q) {
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
-    const long row = (long)(g * CN_H + col) * CN_H;
+    const long row = (long)(g * H + col) * H;
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -74,27 +73,8 @@ __device__ __forceinline__ void cn_load_w(CnW& W, const marl_commnet_weights_t& 
         W.ih[g][c][i] = w.w_ih[row + 16 * c + 4 * q + i];
         W.hh[g][c][i] = w.w_hh[row + 16 * c + 4 * q + i];
       }
-    W.bi[g] = w.b_ih[g * CN_H + col];
-    W.bh[g] = w.b_hh[g * CN_H + col];
-  }
-}
-
-__device__ __forceinline__ f32x4 lds4(const float* X, int ld, int row, int k) {
-  return *reinterpret_cast<const f32x4*>(X + row * ld + k);
-}
-
-// the tile's rows of a (G N, width) array: row r of tile t is global row t gpw N + r, valid while it belongs to a whole group < G
-__device__ __forceinline__ bool cn_row_ok(const CommArgs& p, long tile, int r) {
-  return r < p.gpw * p.N && tile * p.gpw + r / p.N < p.G;
-}
-
-// dst[16][CN_LD] <- rows of src (rows of 64 floats), zeros on the rows that are not valid
-__device__ __forceinline__ void cn_load_tile(const CommArgs& p, long tile, const float* src, float* dst) {
-  const long row0 = tile * p.gpw * p.N;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int idx = threadIdx.x + 256 * k, r = idx >> 6, c = idx & 63;
-    dst[r * CN_LD + c] = cn_row_ok(p, tile, r) ? src[(row0 + r) * CN_H + c] : 0.0f;
+    W.bi[g] = w.b_ih[g * H + col];
+    W.bh[g] = w.b_hh[g * H + col];
   }
 }
 
@@ -103,60 +83,49 @@ __device__ __forceinline__ float cn_others(const float* X, int N, float invN, in
   const int r0 = r / N * N;
   float s = 0.0f;
   for (int l = 0; l < N; ++l)
-    if (r0 + l < 16) s += X[(r0 + l) * CN_LD + c];
-  return (s - X[r * CN_LD + c]) * invN;
+    if (r0 + l < 16) s += X[(r0 + l) * LD + c];
+  return (s - X[r * LD + c]) * invN;
 }
 
-// C[16][CN_LD] <- the communication input of every row of X
+// C[16][LD] <- the communication input of every row of X
 __device__ __forceinline__ void cn_comm(const float* X, float* C, int N, float invN) {
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const int idx = threadIdx.x + 256 * k, r = idx >> 6, c = idx & 63;
-    C[r * CN_LD + c] = cn_others(X, N, invN, r, c);
+    C[r * LD + c] = cn_others(X, N, invN, r, c);
   }
 }
 
-// torch's GRUCell point: r, z = sigmoid, n = tanh(in + r hn), h = (1 - z) n + z hp = n + z (hp - n); every fused operation explicit
-__device__ __forceinline__ void cn_gru_point(float ar, float az, float ain, float ahn, float hp, float& r, float& z, float& n, float& h) {
-  r = __builtin_amdgcn_rcpf(1.0f + __expf(-ar));
-  z = __builtin_amdgcn_rcpf(1.0f + __expf(-az));
-  const float e = __expf(2.0f * __builtin_fmaf(r, ahn, ain));
-  n = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-  h = __builtin_fmaf(z, hp - n, n);
-}
-
 // One f_comm cell for this lane's four elements (rows 4 q + r, column col): input C (has_in false: the zero input of round 0), hidden Gp.
-// Returns the gates as torch's GRUCell names them; hn is the hidden side of the candidate, bias included.
-struct CnCell { float r[4], z[4], n[4], hn[4], hp[4], h[4]; };
-
-__device__ __forceinline__ void cn_cell(const CnW& W, bool has_in, const float* C, const float* Gp, int m, int q, int col, CnCell& o) {
+// The GRU point runs on the hardware exponential.
+__device__ __forceinline__ void cn_cell(const CnW& W, bool has_in, const float* C, const float* Gp, int m, int q, int col, Cell& o) {
   f32x4 ai[3], ah[3];
 #pragma unroll
   for (int g = 0; g < 3; ++g) ai[g] = ah[g] = f32x4{0, 0, 0, 0};
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const f32x4 x = lds4(Gp, CN_LD, m, 16 * c + 4 * q);
+    const f32x4 x = lds4(Gp, LD, m, 16 * c + 4 * q);
     mfma16x4_il3(x, W.hh[0][c], ah[0], x, W.hh[1][c], ah[1], x, W.hh[2][c], ah[2]);
   }
   if (has_in) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const f32x4 x = lds4(C, CN_LD, m, 16 * c + 4 * q);
+      const f32x4 x = lds4(C, LD, m, 16 * c + 4 * q);
       mfma16x4_il3(x, W.ih[0][c], ai[0], x, W.ih[1][c], ai[1], x, W.ih[2][c], ai[2]);
     }
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
-    o.hp[r] = Gp[(4 * q + r) * CN_LD + col];
+    o.hp[r] = Gp[(4 * q + r) * LD + col];
     o.hn[r] = ah[2][r] + W.bh[2];
-    cn_gru_point((ai[0][r] + W.bi[0]) + (ah[0][r] + W.bh[0]), (ai[1][r] + W.bi[1]) + (ah[1][r] + W.bh[1]), ai[2][r] + W.bi[2], o.hn[r],
+    gru_point<true>((ai[0][r] + W.bi[0]) + (ah[0][r] + W.bh[0]), (ai[1][r] + W.bi[1]) + (ah[1][r] + W.bh[1]), ai[2][r] + W.bi[2], o.hn[r],
                  o.hp[r], o.r[r], o.z[r], o.n[r], o.h[r]);
   }
 }
 
 __global__ __launch_bounds__(256) void commnet_fwd_kernel(CommArgs p) {
-  __shared__ __attribute__((aligned(16))) float sh_g[2][16 * CN_LD];
-  __shared__ __attribute__((aligned(16))) float sh_c[16 * CN_LD];
+  __shared__ __attribute__((aligned(16))) float sh_g[2][16 * LD];
+  __shared__ __attribute__((aligned(16))) float sh_c[16 * LD];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63, m = l & 15, q = l >> 4, col = 16 * w + m;
   CnW W;
   cn_load_w(W, p.w, col, q);
@@ -167,11 +136,11 @@ __global__ __launch_bounds__(256) void commnet_fwd_kernel(CommArgs p) {
 #pragma unroll
   for (int c = 0; c < 4; ++c)
 #pragma unroll
-    for (int i = 0; i < 4; ++i) dec[c][i] = (w < 2 && act < p.A) ? p.w.dec_w[(long)act * CN_H + 16 * c + 4 * q + i] : 0.0f;
+    for (int i = 0; i < 4; ++i) dec[c][i] = (w < 2 && act < p.A) ? p.w.dec_w[(long)act * H + 16 * c + 4 * q + i] : 0.0f;
   const float dec_b = (w < 2 && act < p.A) ? p.w.dec_b[act] : 0.0f;
 
   for (long tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
-    cn_load_tile(p, tile, p.hs, sh_g[0]);
+    load_tile(p.gpw * p.N, p.gpw, p.N, p.G, tile, p.hs, sh_g[0]);
     __syncthreads();
     int cur = 0;
     for (int j = 0; j < p.K; ++j) {
@@ -179,53 +148,45 @@ __global__ __launch_bounds__(256) void commnet_fwd_kernel(CommArgs p) {
         cn_comm(sh_g[cur], sh_c, p.N, p.invN);
         __syncthreads();
       }
-      CnCell o;
+      Cell o;
       cn_cell(W, j > 0, sh_c, sh_g[cur], m, q, col, o);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sh_g[cur ^ 1][(4 * q + r) * CN_LD + col] = o.h[r];
+      for (int r = 0; r < 4; ++r) sh_g[cur ^ 1][(4 * q + r) * LD + col] = o.h[r];
       __syncthreads();
       cur ^= 1;
     }
     if (dec_wave) {
       f32x4 acc = f32x4{0, 0, 0, 0};
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc = mfma16x4(lds4(sh_g[cur], CN_LD, m, 16 * c + 4 * q), dec[c], acc);
+      for (int c = 0; c < 4; ++c) acc = mfma16x4(lds4(sh_g[cur], LD, m, 16 * c + 4 * q), dec[c], acc);
       if (act < p.A) {
         const long row0 = tile * p.gpw * p.N;
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (cn_row_ok(p, tile, 4 * q + r)) p.logits[(row0 + 4 * q + r) * p.A + act] = acc[r] + dec_b;
+          if (row_ok(p.gpw * p.N, p.gpw, p.N, p.G, tile, 4 * q + r)) p.logits[(row0 + 4 * q + r) * p.A + act] = acc[r] + dec_b;
       }
     }
     __syncthreads();
   }
 }
 
-// transposed B fragment of a (192, 64) weight, read through L2: [i] = W[16 chunk + 4 q + i][col] - the B operand of dgi W_ih, dgh W_hh
-__device__ __forceinline__ f32x4 cn_wt(const float* __restrict__ W, int c, int q, int col) {
-  f32x4 b;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) b[i] = __ldg(W + (16 * c + 4 * q + i) * CN_H + col);
-  return b;
-}
-
 __global__ __launch_bounds__(256) void commnet_bwd_kernel(CommArgs p) {
-  __shared__ __attribute__((aligned(16))) float sh_gs[CN_KMAX + 1][16 * CN_LD];    // g^(-1) = h, g^(0) .. g^(K-1)
-  __shared__ __attribute__((aligned(16))) float sh_c[16 * CN_LD], sh_dg[16 * CN_LD], sh_dc[16 * CN_LD];
-  __shared__ __attribute__((aligned(16))) float sh_dgi[16 * CN_LDG], sh_dgh[16 * CN_LDG];
+  __shared__ __attribute__((aligned(16))) float sh_gs[CN_KMAX + 1][16 * LD];    // g^(-1) = h, g^(0) .. g^(K-1)
+  __shared__ __attribute__((aligned(16))) float sh_c[16 * LD], sh_dg[16 * LD], sh_dc[16 * LD];
+  __shared__ __attribute__((aligned(16))) float sh_dgi[16 * LDG], sh_dgh[16 * LDG];
   __shared__ __attribute__((aligned(16))) float sh_dl[16 * CN_LDA];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, m = l & 15, q = l >> 4, col = 16 * w + m;
   const int A = p.A, K = p.K;
   CnW W;
   cn_load_w(W, p.w, col, q);
-  // transposed fragment of the decoding weight: [chunk][i] = W_dec[16 chunk + 4 q + i][col] (f_comm's: cn_wt, through L2)
+  // transposed fragment of the decoding weight: [chunk][i] = W_dec[16 chunk + 4 q + i][col] (f_comm's: group_tile's wt, through L2)
   f32x4 tdec[2];
 #pragma unroll
   for (int c = 0; c < 2; ++c)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int a = 16 * c + 4 * q + i;
-      tdec[c][i] = a < A ? p.w.dec_w[(long)a * CN_H + col] : 0.0f;
+      tdec[c][i] = a < A ? p.w.dec_w[(long)a * H + col] : 0.0f;
     }
   // this workgroup's partial weight gradients: tile t of a matrix = gate rows 16 t + 4 q + r, column col
   f32x4 gih[12], ghh[12], gdec[2];
@@ -236,10 +197,10 @@ __global__ __launch_bounds__(256) void commnet_bwd_kernel(CommArgs p) {
 
   for (long tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
     const long row0 = tile * p.gpw * p.N;
-    cn_load_tile(p, tile, p.hs, sh_gs[0]);
+    load_tile(p.gpw * p.N, p.gpw, p.N, p.G, tile, p.hs, sh_gs[0]);
     for (int idx = tid; idx < 16 * CN_AMAX; idx += 256) {
       const int r = idx >> 5, a = idx & 31;
-      sh_dl[r * CN_LDA + a] = (a < A && cn_row_ok(p, tile, r)) ? p.dlogits[(row0 + r) * A + a] : 0.0f;
+      sh_dl[r * CN_LDA + a] = (a < A && row_ok(p.gpw * p.N, p.gpw, p.N, p.G, tile, r)) ? p.dlogits[(row0 + r) * A + a] : 0.0f;
     }
     __syncthreads();
     // ---- the forward planes
@@ -248,10 +209,10 @@ __global__ __launch_bounds__(256) void commnet_bwd_kernel(CommArgs p) {
         cn_comm(sh_gs[j], sh_c, p.N, p.invN);
         __syncthreads();
       }
-      CnCell o;
+      Cell o;
       cn_cell(W, j > 0, sh_c, sh_gs[j], m, q, col, o);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sh_gs[j + 1][(4 * q + r) * CN_LD + col] = o.h[r];
+      for (int r = 0; r < 4; ++r) sh_gs[j + 1][(4 * q + r) * LD + col] = o.h[r];
       __syncthreads();
     }
     // ---- decoding: dg^(K-1) = dlogits W_dec, dW_dec += dlogits^T g^(K-1), db_dec += column sums
@@ -260,10 +221,10 @@ __global__ __launch_bounds__(256) void commnet_bwd_kernel(CommArgs p) {
 #pragma unroll
       for (int c = 0; c < 2; ++c) acc = mfma16x4(lds4(sh_dl, CN_LDA, m, 16 * c + 4 * q), tdec[c], acc);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sh_dg[(4 * q + r) * CN_LD + col] = acc[r];
+      for (int r = 0; r < 4; ++r) sh_dg[(4 * q + r) * LD + col] = acc[r];
       f32x4 b;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) b[i] = sh_gs[K][(4 * q + i) * CN_LD + col];
+      for (int i = 0; i < 4; ++i) b[i] = sh_gs[K][(4 * q + i) * LD + col];
 #pragma unroll
       for (int t = 0; t < 2; ++t) {
         f32x4 a;
@@ -282,23 +243,20 @@ __global__ __launch_bounds__(256) void commnet_bwd_kernel(CommArgs p) {
         cn_comm(gp, sh_c, p.N, p.invN);
         __syncthreads();
       }
-      CnCell o;
+      Cell o;
       cn_cell(W, j > 0, sh_c, gp, m, q, col, o);
       float direct[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 4 * q + r;
-        const float dh = sh_dg[row * CN_LD + col];
-        const float dn = dh * (1.0f - o.z[r]) * (1.0f - o.n[r] * o.n[r]);
-        const float dz = dh * (o.hp[r] - o.n[r]) * o.z[r] * (1.0f - o.z[r]);
-        const float dr = dn * o.hn[r] * o.r[r] * (1.0f - o.r[r]);
-        direct[r] = dh * o.z[r];
-        sh_dgi[row * CN_LDG + col] = dr;
-        sh_dgi[row * CN_LDG + CN_H + col] = dz;
-        sh_dgi[row * CN_LDG + 2 * CN_H + col] = dn;
-        sh_dgh[row * CN_LDG + col] = dr;
-        sh_dgh[row * CN_LDG + CN_H + col] = dz;
-        sh_dgh[row * CN_LDG + 2 * CN_H + col] = dn * o.r[r];
+        const GateGrad g = gru_point_bwd(o, r, sh_dg[row * LD + col]);
+        direct[r] = g.direct;
+        sh_dgi[row * LDG + col] = g.dr;
+        sh_dgi[row * LDG + H + col] = g.dz;
+        sh_dgi[row * LDG + 2 * H + col] = g.dn;
+        sh_dgh[row * LDG + col] = g.dr;
+        sh_dgh[row * LDG + H + col] = g.dz;
+        sh_dgh[row * LDG + 2 * H + col] = g.dn * o.r[r];
       }
       __syncthreads();
       // weight gradients over the tile's 16 rows (k = row): A = dgi^T / dgh^T, B = c / g^(j-1)
@@ -306,49 +264,49 @@ __global__ __launch_bounds__(256) void commnet_bwd_kernel(CommArgs p) {
         f32x4 bc, bg;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-          bc[i] = j > 0 ? sh_c[(4 * q + i) * CN_LD + col] : 0.0f;
-          bg[i] = gp[(4 * q + i) * CN_LD + col];
+          bc[i] = j > 0 ? sh_c[(4 * q + i) * LD + col] : 0.0f;
+          bg[i] = gp[(4 * q + i) * LD + col];
         }
 #pragma unroll
         for (int t = 0; t < 12; ++t) {
           f32x4 ai, ah;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            ai[i] = sh_dgi[(4 * q + i) * CN_LDG + 16 * t + m];
-            ah[i] = sh_dgh[(4 * q + i) * CN_LDG + 16 * t + m];
+            ai[i] = sh_dgi[(4 * q + i) * LDG + 16 * t + m];
+            ah[i] = sh_dgh[(4 * q + i) * LDG + 16 * t + m];
           }
           mfma16x4_il2(ai, bc, gih[t], ah, bg, ghh[t]);
         }
-        if (tid < CN_G3)
+        if (tid < G3)
           for (int r = 0; r < 16; ++r) {
-            gbih += sh_dgi[r * CN_LDG + tid];
-            gbhh += sh_dgh[r * CN_LDG + tid];
+            gbih += sh_dgi[r * LDG + tid];
+            gbhh += sh_dgh[r * LDG + tid];
           }
       }
       // dgh W_hh (and dc = dgi W_ih when the round has an input)
       f32x4 ahh = f32x4{0, 0, 0, 0}, aih = f32x4{0, 0, 0, 0};
 #pragma unroll
-      for (int c = 0; c < 12; ++c) ahh = mfma16x4(lds4(sh_dgh, CN_LDG, m, 16 * c + 4 * q), cn_wt(p.w.w_hh, c, q, col), ahh);
+      for (int c = 0; c < 12; ++c) ahh = mfma16x4(lds4(sh_dgh, LDG, m, 16 * c + 4 * q), wt(p.w.w_hh, H, c, q, col), ahh);
       if (j > 0) {
 #pragma unroll
-        for (int c = 0; c < 12; ++c) aih = mfma16x4(lds4(sh_dgi, CN_LDG, m, 16 * c + 4 * q), cn_wt(p.w.w_ih, c, q, col), aih);
+        for (int c = 0; c < 12; ++c) aih = mfma16x4(lds4(sh_dgi, LDG, m, 16 * c + 4 * q), wt(p.w.w_ih, H, c, q, col), aih);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          sh_dg[(4 * q + r) * CN_LD + col] = direct[r] + ahh[r];
-          sh_dc[(4 * q + r) * CN_LD + col] = aih[r];
+          sh_dg[(4 * q + r) * LD + col] = direct[r] + ahh[r];
+          sh_dc[(4 * q + r) * LD + col] = aih[r];
         }
         __syncthreads();
         // every other agent of the group receives dc / N
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const int idx = tid + 256 * k, r = idx >> 6, c = idx & 63;
-          sh_dg[r * CN_LD + c] += cn_others(sh_dc, p.N, p.invN, r, c);
+          sh_dg[r * LD + c] += cn_others(sh_dc, p.N, p.invN, r, c);
         }
         __syncthreads();
       } else {
 #pragma unroll
         for (int r = 0; r < 4; ++r)
-          if (cn_row_ok(p, tile, 4 * q + r)) p.dhs[(row0 + 4 * q + r) * CN_H + col] = direct[r] + ahh[r];
+          if (row_ok(p.gpw * p.N, p.gpw, p.N, p.G, tile, 4 * q + r)) p.dhs[(row0 + 4 * q + r) * H + col] = direct[r] + ahh[r];
         __syncthreads();
       }
     }
@@ -359,14 +317,14 @@ __global__ __launch_bounds__(256) void commnet_bwd_kernel(CommArgs p) {
   for (int t = 0; t < 12; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      s[CN_S_IH + (16 * t + 4 * q + r) * CN_H + col] = gih[t][r];
-      s[CN_S_HH + (16 * t + 4 * q + r) * CN_H + col] = ghh[t][r];
+      s[CN_S_IH + (16 * t + 4 * q + r) * H + col] = gih[t][r];
+      s[CN_S_HH + (16 * t + 4 * q + r) * H + col] = ghh[t][r];
     }
 #pragma unroll
   for (int t = 0; t < 2; ++t)
 #pragma unroll
-    for (int r = 0; r < 4; ++r) s[CN_S_DEC + (16 * t + 4 * q + r) * CN_H + col] = gdec[t][r];
-  if (tid < CN_G3) {
+    for (int r = 0; r < 4; ++r) s[CN_S_DEC + (16 * t + 4 * q + r) * H + col] = gdec[t][r];
+  if (tid < G3) {
     s[CN_S_BIH + tid] = gbih;
     s[CN_S_BHH + tid] = gbhh;
   }
@@ -380,7 +338,7 @@ __global__ __launch_bounds__(256) void commnet_slab_reduce_kernel(const float* _
   float* dst;
   if (e < CN_S_HH) dst = g.w_ih + e;
   else if (e < CN_S_DEC) dst = g.w_hh + (e - CN_S_HH);
-  else if (e < CN_S_BIH) dst = (e - CN_S_DEC) < A * CN_H ? g.dec_w + (e - CN_S_DEC) : nullptr;
+  else if (e < CN_S_BIH) dst = (e - CN_S_DEC) < A * H ? g.dec_w + (e - CN_S_DEC) : nullptr;
   else if (e < CN_S_BHH) dst = g.b_ih + (e - CN_S_BIH);
   else if (e < CN_S_BDEC) dst = g.b_hh + (e - CN_S_BHH);
   else dst = (e - CN_S_BDEC) < A ? g.dec_b + (e - CN_S_BDEC) : nullptr;
@@ -440,17 +398,12 @@ bool cn_grads_ok(const marl_commnet_grads_t* g) {
   return g && g->w_ih && g->w_hh && g->b_ih && g->b_hh && g->dec_w && g->dec_b;
 }
 
-long cn_tiles(long G, int N) {
-  const int gpw = 16 / N;
-  return (G + gpw - 1) / gpw;
-}
-
 CommArgs cn_args(const marl_commnet_weights_t* w, long G, int N, int A, int K) {
   CommArgs a{};
   a.w = *w;
   a.G = G; a.N = N; a.A = A; a.K = K;
   a.gpw = 16 / N;
-  a.tiles = cn_tiles(G, N);
+  a.tiles = tiles(G, N);
   a.invN = 1.0f / (float)N;
   return a;
 }
@@ -478,7 +431,7 @@ extern "C" int marl_commnet_head_fwd(const marl_commnet_weights_t* w, const floa
 
 extern "C" size_t marl_commnet_bwd_workspace(long G, int N, int A, int K) {
   if (G <= 0 || !marl_commnet_supported(N, A, K)) return 0;
-  const long tiles = cn_tiles(G, N);
+  const long tiles = group_tile::tiles(G, N);
   return (size_t)(tiles < CN_BWD_WG ? tiles : CN_BWD_WG) * CN_SLAB * sizeof(float);
 }
 

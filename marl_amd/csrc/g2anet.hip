@@ -27,26 +27,25 @@
 
 // No implicit contraction in this file (as commnet.hip): a row's value must not depend on where in a tile it sits.
 #pragma clang fp contract(off)
+#include "group_tile.h"    // the whole-group tile, the W_hh fragments, the GRU point and its backward (H, LD, G3, LDG: P, Q, dQ)
 
 namespace {
 
-constexpr int GA_H = 64;
+using namespace group_tile;
+
 constexpr int GA_D = 32;                   // attention_dim
-constexpr int GA_LD = GA_H + 4;            // row pitch of the 16 x 64 planes: 4 rows apart = 16 banks apart
-constexpr int GA_G3 = 3 * GA_H;
-constexpr int GA_LDG = GA_G3 + 4;          // 16 x 192 planes (P, Q, dQ)
-constexpr int GA_LDG4 = 4 * GA_H + 4;      // the gate-gradient plane: dr | dz | dn | dn r
+constexpr int GA_LDG4 = 4 * H + 4;      // the gate-gradient plane: dr | dz | dn | dn r
 constexpr int GA_LDQ = 3 * GA_D + 4;       // q | k | v
 constexpr int GA_LDD = GA_D + 4;           // x, dx, dlogits
 constexpr int GA_NMIN = 2, GA_NMAX = 10, GA_PMAX = GA_NMAX - 1, GA_AMAX = 32;
 constexpr int GA_FWD_WG = 512;             // workgroups of the forward (persistent over the tiles)
 constexpr int GA_BWD_WG = 256;             // workgroups = slabs of a backward kernel
 // the soft kernel's slab: dW_dec[:, :64] (32 rows) | dW_dec[:, 64:] | dW_q | dW_k | dW_v | db_dec | db_v | sum of ds
-constexpr int GA_S2_DH = 0, GA_S2_DX = GA_AMAX * GA_H, GA_S2_Q = GA_S2_DX + GA_AMAX * GA_D, GA_S2_BD = GA_S2_Q + 3 * GA_D * GA_H;
+constexpr int GA_S2_DH = 0, GA_S2_DX = GA_AMAX * H, GA_S2_Q = GA_S2_DX + GA_AMAX * GA_D, GA_S2_BD = GA_S2_Q + 3 * GA_D * H;
 constexpr int GA_S2_BV = GA_S2_BD + GA_AMAX, GA_S2_HE = GA_S2_BV + GA_D, GA_SLAB2 = GA_S2_HE + 1;
 // a hard kernel's slab: dW_ih (192, 128) | dW_hh (192, 64) | db_ih | db_hh | four row-quarter partials of sum ds state (4 x 64)
-constexpr int GA_S3_IH = 0, GA_S3_HH = GA_G3 * 2 * GA_H, GA_S3_BIH = GA_S3_HH + GA_G3 * GA_H, GA_S3_BHH = GA_S3_BIH + GA_G3;
-constexpr int GA_S3_HE = GA_S3_BHH + GA_G3, GA_SLAB3 = GA_S3_HE + 4 * GA_H;
+constexpr int GA_S3_IH = 0, GA_S3_HH = G3 * 2 * H, GA_S3_BIH = GA_S3_HH + G3 * H, GA_S3_BHH = GA_S3_BIH + G3;
+constexpr int GA_S3_HE = GA_S3_BHH + G3, GA_SLAB3 = GA_S3_HE + 4 * H;
 constexpr int GA_SLAB = GA_SLAB3 > GA_SLAB2 ? GA_SLAB3 : GA_SLAB2;
 
 struct GaArgs {
@@ -69,42 +68,6 @@ __device__ __forceinline__ const float* ga_w_hh(const marl_g2anet_weights_t& w, 
 __device__ __forceinline__ const float* ga_b_ih(const marl_g2anet_weights_t& w, int d) { return d ? w.gr_b_ih : w.gf_b_ih; }
 __device__ __forceinline__ const float* ga_b_hh(const marl_g2anet_weights_t& w, int d) { return d ? w.gr_b_hh : w.gf_b_hh; }
 
-// forward-form B fragments of one direction's W_hh for column col = 16 w + m: [gate][chunk][i] = W[gate * 64 + col][16 chunk + 4 q + i]
-struct GaHH {
-  f32x4 hh[3][4];
-  float bh[3];
-};
-
-__device__ __forceinline__ void ga_load_hh(GaHH& W, const float* __restrict__ w_hh, const float* __restrict__ b_hh, int col, int q) {
-#pragma unroll
-  for (int g = 0; g < 3; ++g) {
-    const long row = (long)(g * GA_H + col) * GA_H;
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) W.hh[g][c][i] = w_hh[row + 16 * c + 4 * q + i];
-    W.bh[g] = b_hh[g * GA_H + col];
-  }
-}
-
-__device__ __forceinline__ f32x4 ga_lds4(const float* X, int ld, int row, int k) {
-  return *reinterpret_cast<const f32x4*>(X + row * ld + k);
-}
-
-// row r of tile t is global row t gpw N + r, valid while it belongs to a whole group < G
-__device__ __forceinline__ bool ga_row_ok(const GaArgs& p, long tile, int r) {
-  return r < p.nrows && tile * p.gpw + r / p.N < p.G;
-}
-
-__device__ __forceinline__ void ga_load_tile(const GaArgs& p, long tile, const float* src, float* dst) {
-  const long row0 = tile * p.nrows;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int idx = threadIdx.x + 256 * k, r = idx >> 6, c = idx & 63;
-    dst[r * GA_LD + c] = ga_row_ok(p, tile, r) ? src[(row0 + r) * GA_H + c] : 0.0f;
-  }
-}
-
 // the tile row of partner p of tile row `row` (a row outside the tile's whole groups: itself - its values are never written)
 __device__ __forceinline__ int ga_partner(int row, int p, int N, int nrows) {
   if (row >= nrows) return row;
@@ -115,68 +78,57 @@ __device__ __forceinline__ int ga_partner(int row, int p, int N, int nrows) {
 // the position at which row `i` (agent ai) meets partner agent aj of its group
 __device__ __forceinline__ int ga_pos(int ai, int aj) { return aj < ai ? aj : aj - 1; }
 
-// P[16][GA_LDG] = h W_ih[:, :64]^T + b_ih and Q = h W_ih[:, 64:]^T of one direction (W_ih (192, 128), fragments through L2)
+// P[16][LDG] = h W_ih[:, :64]^T + b_ih and Q = h W_ih[:, 64:]^T of one direction (W_ih (192, 128), fragments through L2)
 __device__ __forceinline__ void ga_pq(const float* __restrict__ w_ih, const float* __restrict__ b_ih, const float* sh_h, float* P, float* Q,
                                       int m, int q, int col) {
 #pragma unroll
   for (int g = 0; g < 3; ++g) {
     f32x4 ap = f32x4{0, 0, 0, 0}, aq = f32x4{0, 0, 0, 0};
-    const float* wr = w_ih + (long)(g * GA_H + col) * (2 * GA_H);
+    const float* wr = w_ih + (long)(g * H + col) * (2 * H);
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const f32x4 x = ga_lds4(sh_h, GA_LD, m, 16 * c + 4 * q);
+      const f32x4 x = lds4(sh_h, LD, m, 16 * c + 4 * q);
       f32x4 bp, bq;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         bp[i] = __ldg(wr + 16 * c + 4 * q + i);
-        bq[i] = __ldg(wr + GA_H + 16 * c + 4 * q + i);
+        bq[i] = __ldg(wr + H + 16 * c + 4 * q + i);
       }
       mfma16x4_il2(x, bp, ap, x, bq, aq);
     }
-    const float b = b_ih[g * GA_H + col];
+    const float b = b_ih[g * H + col];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      P[(4 * q + r) * GA_LDG + g * GA_H + col] = ap[r] + b;
-      Q[(4 * q + r) * GA_LDG + g * GA_H + col] = aq[r];
+      P[(4 * q + r) * LDG + g * H + col] = ap[r] + b;
+      Q[(4 * q + r) * LDG + g * H + col] = aq[r];
     }
   }
 }
 
-// torch's GRU point: r, z = sigmoid, n = tanh(in + r hn), h = n + z (hp - n); every fused operation explicit.  expf, not the
-// hardware exponential behind __expf: the states' error reaches w multiplied by 1 / tau = 100, and with __expf a case with two pairs
-// inside the sigmoid's transition missed the float64 bound on hard_encoding.bias (3.8e-5 against 3.3e-5)
-__device__ __forceinline__ void ga_gru_point(float ar, float az, float ain, float ahn, float hp, float& r, float& z, float& n, float& h) {
-  r = __builtin_amdgcn_rcpf(1.0f + expf(-ar));
-  z = __builtin_amdgcn_rcpf(1.0f + expf(-az));
-  const float e = expf(2.0f * __builtin_fmaf(r, ahn, ain));
-  n = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-  h = __builtin_fmaf(z, hp - n, n);
-}
-
 // One chain step at position p for this lane's four elements (rows 4 q + r, column col): input side P_row + Q_partner, hidden `prev`
-// (has_prev false: the zero state, no product).  hn is the hidden side of the candidate, bias included.
-struct GaCell { float r[4], z[4], n[4], hn[4], hp[4], h[4]; };
-
-__device__ __forceinline__ void ga_cell(const GaHH& W, const float* P, const float* Q, const float* prev, bool has_prev, int p, int N,
-                                        int nrows, int m, int q, int col, GaCell& o) {
+// (has_prev false: the zero state, no product).  The GRU point runs on expf, not the hardware exponential behind __expf: the states'
+// error reaches w multiplied by 1 / tau = 100, and with __expf a case with two pairs inside the sigmoid's transition missed the
+// float64 bound on hard_encoding.bias (3.8e-5 against 3.3e-5)
+__device__ __forceinline__ void ga_cell(const HH& W, const float* P, const float* Q, const float* prev, bool has_prev, int p, int N,
+                                        int nrows, int m, int q, int col, Cell& o) {
   f32x4 ah[3];
 #pragma unroll
   for (int g = 0; g < 3; ++g) ah[g] = f32x4{0, 0, 0, 0};
   if (has_prev) {
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
-      const f32x4 x = ga_lds4(prev, GA_LD, m, 16 * c + 4 * q);
+      const f32x4 x = lds4(prev, LD, m, 16 * c + 4 * q);
       mfma16x4_il3(x, W.hh[0][c], ah[0], x, W.hh[1][c], ah[1], x, W.hh[2][c], ah[2]);
     }
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int row = 4 * q + r, jr = ga_partner(row, p, N, nrows);
-    const float* Pr = P + row * GA_LDG + col;
-    const float* Qr = Q + jr * GA_LDG + col;
-    o.hp[r] = has_prev ? prev[row * GA_LD + col] : 0.0f;
+    const float* Pr = P + row * LDG + col;
+    const float* Qr = Q + jr * LDG + col;
+    o.hp[r] = has_prev ? prev[row * LD + col] : 0.0f;
     o.hn[r] = ah[2][r] + W.bh[2];
-    ga_gru_point((Pr[0] + Qr[0]) + (ah[0][r] + W.bh[0]), (Pr[GA_H] + Qr[GA_H]) + (ah[1][r] + W.bh[1]), Pr[2 * GA_H] + Qr[2 * GA_H],
+    gru_point<false>((Pr[0] + Qr[0]) + (ah[0][r] + W.bh[0]), (Pr[H] + Qr[H]) + (ah[1][r] + W.bh[1]), Pr[2 * H] + Qr[2 * H],
                  o.hn[r], o.hp[r], o.r[r], o.z[r], o.n[r], o.h[r]);
   }
 }
@@ -198,7 +150,7 @@ __device__ __forceinline__ void ga_load_qkv(GaQKV& W, const marl_g2anet_weights_
   for (int s = 0; s < 2; ++s) {
     const int tt = wv + 4 * s;
     const float* M = tt < 2 ? w.q_w : tt < 4 ? w.k_w : w.v_w;
-    const long row = (long)(16 * (tt & 1) + m) * GA_H;
+    const long row = (long)(16 * (tt & 1) + m) * H;
 #pragma unroll
     for (int c = 0; c < 4; ++c)
 #pragma unroll
@@ -214,7 +166,7 @@ __device__ __forceinline__ void ga_qkv(const GaQKV& W, const float* sh_h, float*
     if (tt < 6) {
       f32x4 acc = f32x4{0, 0, 0, 0};
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc = mfma16x4(ga_lds4(sh_h, GA_LD, m, 16 * c + 4 * q), W.f[s][c], acc);
+      for (int c = 0; c < 4; ++c) acc = mfma16x4(lds4(sh_h, LD, m, 16 * c + 4 * q), W.f[s][c], acc);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const float v = acc[r] + W.b[s];
@@ -242,26 +194,26 @@ __device__ __forceinline__ float ga_softmax_at(const float* e, int np, int pp) {
 }
 
 __global__ __launch_bounds__(256) void g2anet_fwd_kernel(GaArgs p) {
-  __shared__ __attribute__((aligned(16))) float sh_h[16 * GA_LD];
-  __shared__ __attribute__((aligned(16))) float sh_pq[4][16 * GA_LDG];        // P, Q forward; P, Q reverse
-  __shared__ __attribute__((aligned(16))) float sh_st[2][2][16 * GA_LD];      // [direction][buffer]
+  __shared__ __attribute__((aligned(16))) float sh_h[16 * LD];
+  __shared__ __attribute__((aligned(16))) float sh_pq[4][16 * LDG];        // P, Q forward; P, Q reverse
+  __shared__ __attribute__((aligned(16))) float sh_st[2][2][16 * LD];      // [direction][buffer]
   __shared__ __attribute__((aligned(16))) float sh_qkv[16 * GA_LDQ];
   __shared__ __attribute__((aligned(16))) float sh_x[16 * GA_LDD];
   __shared__ float sh_s[2][16 * GA_PMAX], sh_e[16 * GA_PMAX], sh_cf[16 * GA_PMAX];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, m = l & 15, q = l >> 4, col = 16 * w + m;
   const int N = p.N, A = p.A, np = N - 1;
   const bool soft = p.logits != nullptr;
-  GaHH Wf, Wb;
+  HH Wf, Wb;
   float dvf[4], dvb[4], dbias = 0.0f;
   if (p.hard) {
-    ga_load_hh(Wf, p.w.gf_w_hh, p.w.gf_b_hh, col, q);
-    ga_load_hh(Wb, p.w.gr_w_hh, p.w.gr_b_hh, col, q);
+    load_hh(Wf, p.w.gf_w_hh, p.w.gf_b_hh, col, q);
+    load_hh(Wb, p.w.gr_w_hh, p.w.gr_b_hh, col, q);
     // hard_encoding's row difference over this thread's four columns of the dot pass (row tid >> 4, columns 4 (tid & 15) ..)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int c = 4 * (tid & 15) + i;
-      dvf[i] = p.w.he_w[2 * GA_H + c] - p.w.he_w[c];
-      dvb[i] = p.w.he_w[3 * GA_H + c] - p.w.he_w[GA_H + c];
+      dvf[i] = p.w.he_w[2 * H + c] - p.w.he_w[c];
+      dvb[i] = p.w.he_w[3 * H + c] - p.w.he_w[H + c];
     }
     dbias = p.w.he_b[1] - p.w.he_b[0];
   }
@@ -275,13 +227,13 @@ __global__ __launch_bounds__(256) void g2anet_fwd_kernel(GaArgs p) {
 #pragma unroll
     for (int c = 0; c < 6; ++c)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) dec[c][i] = (w < 2 && act < A) ? p.w.dec_w[(long)act * (GA_H + GA_D) + 16 * c + 4 * q + i] : 0.0f;
+      for (int i = 0; i < 4; ++i) dec[c][i] = (w < 2 && act < A) ? p.w.dec_w[(long)act * (H + GA_D) + 16 * c + 4 * q + i] : 0.0f;
     dec_b = (w < 2 && act < A) ? p.w.dec_b[act] : 0.0f;
   }
 
   for (long tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
     const long row0 = tile * p.nrows;
-    ga_load_tile(p, tile, p.hs, sh_h);
+    load_tile(p.nrows, p.gpw, p.N, p.G, tile, p.hs, sh_h);
     __syncthreads();
     if (p.hard) {
       ga_pq(p.w.gf_w_ih, p.w.gf_b_ih, sh_h, sh_pq[0], sh_pq[1], m, q, col);
@@ -293,13 +245,13 @@ __global__ __launch_bounds__(256) void g2anet_fwd_kernel(GaArgs p) {
       int cur = 0;
       for (int s = 0; s < np; ++s) {
         const int pf = s, pb = np - 1 - s;
-        GaCell o;
+        Cell o;
         ga_cell(Wf, sh_pq[0], sh_pq[1], sh_st[0][cur], s > 0, pf, N, p.nrows, m, q, col, o);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sh_st[0][cur ^ 1][(4 * q + r) * GA_LD + col] = o.h[r];
+        for (int r = 0; r < 4; ++r) sh_st[0][cur ^ 1][(4 * q + r) * LD + col] = o.h[r];
         ga_cell(Wb, sh_pq[2], sh_pq[3], sh_st[1][cur], s > 0, pb, N, p.nrows, m, q, col, o);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) sh_st[1][cur ^ 1][(4 * q + r) * GA_LD + col] = o.h[r];
+        for (int r = 0; r < 4; ++r) sh_st[1][cur ^ 1][(4 * q + r) * LD + col] = o.h[r];
         __syncthreads();
         cur ^= 1;
         {
@@ -307,8 +259,8 @@ __global__ __launch_bounds__(256) void g2anet_fwd_kernel(GaArgs p) {
           float sf = 0.0f, sb = 0.0f;
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            sf += dvf[i] * sh_st[0][cur][row * GA_LD + c0 + i];
-            sb += dvb[i] * sh_st[1][cur][row * GA_LD + c0 + i];
+            sf += dvf[i] * sh_st[0][cur][row * LD + c0 + i];
+            sb += dvb[i] * sh_st[1][cur][row * LD + c0 + i];
           }
           sf = ga_row16_sum(sf);
           sb = ga_row16_sum(sb);
@@ -323,7 +275,7 @@ __global__ __launch_bounds__(256) void g2anet_fwd_kernel(GaArgs p) {
     // w of every pair (and its score)
     if (tid < 16 * np) {
       const int row = tid / np, pp = tid - row * np;
-      const bool ok = ga_row_ok(p, tile, row);
+      const bool ok = row_ok(p.nrows, p.gpw, p.N, p.G, tile, row);
       float wv = 1.0f;
       if (p.hard) {
         const float ln = (p.noise && ok) ? p.noise[(row0 + row) * np + pp] : 0.0f;
@@ -353,13 +305,13 @@ __global__ __launch_bounds__(256) void g2anet_fwd_kernel(GaArgs p) {
       if (dec_wave) {
         f32x4 acc = f32x4{0, 0, 0, 0};
 #pragma unroll
-        for (int c = 0; c < 4; ++c) acc = mfma16x4(ga_lds4(sh_h, GA_LD, m, 16 * c + 4 * q), dec[c], acc);
+        for (int c = 0; c < 4; ++c) acc = mfma16x4(lds4(sh_h, LD, m, 16 * c + 4 * q), dec[c], acc);
 #pragma unroll
-        for (int c = 0; c < 2; ++c) acc = mfma16x4(ga_lds4(sh_x, GA_LDD, m, 16 * c + 4 * q), dec[4 + c], acc);
+        for (int c = 0; c < 2; ++c) acc = mfma16x4(lds4(sh_x, GA_LDD, m, 16 * c + 4 * q), dec[4 + c], acc);
         if (act < A) {
 #pragma unroll
           for (int r = 0; r < 4; ++r)
-            if (ga_row_ok(p, tile, 4 * q + r)) p.logits[(row0 + 4 * q + r) * A + act] = acc[r] + dec_b;
+            if (row_ok(p.nrows, p.gpw, p.N, p.G, tile, 4 * q + r)) p.logits[(row0 + 4 * q + r) * A + act] = acc[r] + dec_b;
         }
       }
     }
@@ -369,13 +321,13 @@ __global__ __launch_bounds__(256) void g2anet_fwd_kernel(GaArgs p) {
 
 // ---- the soft kernel: decoding, attention and q / k / v in reverse.  dhs is WRITTEN; with hard on, the plane's w becomes ds.
 __global__ __launch_bounds__(256) void g2anet_soft_bwd_kernel(GaArgs p) {
-  __shared__ __attribute__((aligned(16))) float sh_h[16 * GA_LD];
+  __shared__ __attribute__((aligned(16))) float sh_h[16 * LD];
   __shared__ __attribute__((aligned(16))) float sh_qkv[16 * GA_LDQ], sh_dqkv[16 * GA_LDQ];
   __shared__ __attribute__((aligned(16))) float sh_x[16 * GA_LDD], sh_dx[16 * GA_LDD], sh_dl[16 * GA_LDD];
   __shared__ float sh_w[16 * GA_PMAX], sh_e[16 * GA_PMAX], sh_t[16 * GA_PMAX], sh_cf[16 * GA_PMAX], sh_de[16 * GA_PMAX];
   __shared__ float sh_red[256];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, m = l & 15, q = l >> 4, col = 16 * w + m;
-  const int N = p.N, A = p.A, np = N - 1, LW = GA_H + GA_D;
+  const int N = p.N, A = p.A, np = N - 1, LW = H + GA_D;
   GaQKV Wq;
   ga_load_qkv(Wq, p.w, w, m, q);
   // transposed fragments: decoding's h block and x block ([chunk][i] = W_dec[16 chunk + 4 q + i][col or 64 + 16 w + m]), and
@@ -387,13 +339,13 @@ __global__ __launch_bounds__(256) void g2anet_soft_bwd_kernel(GaArgs p) {
     for (int i = 0; i < 4; ++i) {
       const int a = 16 * c + 4 * q + i;
       tdh[c][i] = a < A ? p.w.dec_w[(long)a * LW + col] : 0.0f;
-      tdx[c][i] = (a < A && w < 2) ? p.w.dec_w[(long)a * LW + GA_H + 16 * w + m] : 0.0f;
+      tdx[c][i] = (a < A && w < 2) ? p.w.dec_w[(long)a * LW + H + 16 * w + m] : 0.0f;
     }
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
     const float* M = c < 2 ? p.w.q_w : c < 4 ? p.w.k_w : p.w.v_w;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) tqkv[c][i] = M[(long)(16 * (c & 1) + 4 * q + i) * GA_H + col];
+    for (int i = 0; i < 4; ++i) tqkv[c][i] = M[(long)(16 * (c & 1) + 4 * q + i) * H + col];
   }
   // partial weight gradients: rows 16 t + 4 q + r of a matrix, column col (the x block of decoding: column 16 w + m, waves 0 and 1)
   f32x4 gdh[2], gdx[2], gqkv[3][2];
@@ -407,25 +359,25 @@ __global__ __launch_bounds__(256) void g2anet_soft_bwd_kernel(GaArgs p) {
 
   for (long tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
     const long row0 = tile * p.nrows;
-    ga_load_tile(p, tile, p.hs, sh_h);
+    load_tile(p.nrows, p.gpw, p.N, p.G, tile, p.hs, sh_h);
     for (int idx = tid; idx < 16 * GA_AMAX; idx += 256) {
       const int r = idx >> 5, a = idx & 31;
-      sh_dl[r * GA_LDD + a] = (a < A && ga_row_ok(p, tile, r)) ? p.dlogits[(row0 + r) * A + a] : 0.0f;
+      sh_dl[r * GA_LDD + a] = (a < A && row_ok(p.nrows, p.gpw, p.N, p.G, tile, r)) ? p.dlogits[(row0 + r) * A + a] : 0.0f;
     }
     if (tid < 16 * np) {
       const int row = tid / np, pp = tid - row * np;
-      sh_w[row * GA_PMAX + pp] = !p.hard ? 1.0f : ga_row_ok(p, tile, row) ? p.wplane[(row0 + row) * np + pp] : 0.0f;
+      sh_w[row * GA_PMAX + pp] = !p.hard ? 1.0f : row_ok(p.nrows, p.gpw, p.N, p.G, tile, row) ? p.wplane[(row0 + row) * np + pp] : 0.0f;
     }
     __syncthreads();
     ga_qkv(Wq, sh_h, sh_qkv, w, m, q);
     // dx = dlogits W_dec[:, 64:] (waves 0, 1) and the direct part of dh = dlogits W_dec[:, :64]
     f32x4 dh = f32x4{0, 0, 0, 0};
 #pragma unroll
-    for (int c = 0; c < 2; ++c) dh = mfma16x4(ga_lds4(sh_dl, GA_LDD, m, 16 * c + 4 * q), tdh[c], dh);
+    for (int c = 0; c < 2; ++c) dh = mfma16x4(lds4(sh_dl, GA_LDD, m, 16 * c + 4 * q), tdh[c], dh);
     if (w < 2) {
       f32x4 acc = f32x4{0, 0, 0, 0};
 #pragma unroll
-      for (int c = 0; c < 2; ++c) acc = mfma16x4(ga_lds4(sh_dl, GA_LDD, m, 16 * c + 4 * q), tdx[c], acc);
+      for (int c = 0; c < 2; ++c) acc = mfma16x4(lds4(sh_dl, GA_LDD, m, 16 * c + 4 * q), tdx[c], acc);
 #pragma unroll
       for (int r = 0; r < 4; ++r) sh_dx[(4 * q + r) * GA_LDD + 16 * w + m] = acc[r];
     }
@@ -452,7 +404,7 @@ __global__ __launch_bounds__(256) void g2anet_soft_bwd_kernel(GaArgs p) {
       const float a = __expf(e[pp] - mx) / sum, wv = ww[pp];
       sh_cf[row * GA_PMAX + pp] = a * wv;
       sh_de[row * GA_PMAX + pp] = a * (wv * tt[pp] - dot) * 0.17677669529663687f;
-      if (p.hard && ga_row_ok(p, tile, row)) {
+      if (p.hard && row_ok(p.nrows, p.gpw, p.N, p.G, tile, row)) {
         const float ds = ((a * tt[pp]) * (wv * (1.0f - wv))) / p.tau;
         p.wplane[(row0 + row) * np + pp] = ds;
         ghe += ds;
@@ -489,7 +441,7 @@ __global__ __launch_bounds__(256) void g2anet_soft_bwd_kernel(GaArgs p) {
       f32x4 bh, bx;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        bh[i] = sh_h[(4 * q + i) * GA_LD + col];
+        bh[i] = sh_h[(4 * q + i) * LD + col];
         bx[i] = w < 2 ? sh_x[(4 * q + i) * GA_LDD + 16 * w + m] : 0.0f;
       }
 #pragma unroll
@@ -513,10 +465,10 @@ __global__ __launch_bounds__(256) void g2anet_soft_bwd_kernel(GaArgs p) {
           gbv += sh_dqkv[r * GA_LDQ + 2 * GA_D + tid];
         }
 #pragma unroll
-      for (int c = 0; c < 6; ++c) dh = mfma16x4(ga_lds4(sh_dqkv, GA_LDQ, m, 16 * c + 4 * q), tqkv[c], dh);
+      for (int c = 0; c < 6; ++c) dh = mfma16x4(lds4(sh_dqkv, GA_LDQ, m, 16 * c + 4 * q), tqkv[c], dh);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (ga_row_ok(p, tile, 4 * q + r)) p.dhs[(row0 + 4 * q + r) * GA_H + col] = dh[r];
+        if (row_ok(p.nrows, p.gpw, p.N, p.G, tile, 4 * q + r)) p.dhs[(row0 + 4 * q + r) * H + col] = dh[r];
     }
     __syncthreads();
   }
@@ -527,10 +479,10 @@ __global__ __launch_bounds__(256) void g2anet_soft_bwd_kernel(GaArgs p) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 16 * t + 4 * q + r;
-      s[GA_S2_DH + row * GA_H + col] = gdh[t][r];
+      s[GA_S2_DH + row * H + col] = gdh[t][r];
       if (w < 2) s[GA_S2_DX + row * GA_D + 16 * w + m] = gdx[t][r];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) s[GA_S2_Q + (k * GA_D + row) * GA_H + col] = gqkv[k][t][r];
+      for (int k = 0; k < 3; ++k) s[GA_S2_Q + (k * GA_D + row) * H + col] = gqkv[k][t][r];
     }
   if (tid < GA_AMAX) {
     s[GA_S2_BD + tid] = gbd;
@@ -549,15 +501,15 @@ __global__ __launch_bounds__(256) void g2anet_soft_reduce_kernel(const float* __
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= GA_SLAB2) return;
   const float v = slab_sum(slabs + e, GA_SLAB2, 0, 1, n);
-  const int LW = GA_H + GA_D;
+  const int LW = H + GA_D;
   if (e < GA_S2_DX) {
-    const int a = e / GA_H, c = e % GA_H;
+    const int a = e / H, c = e % H;
     if (a < A) g.dec_w[a * LW + c] += v;
   } else if (e < GA_S2_Q) {
     const int a = (e - GA_S2_DX) / GA_D, c = (e - GA_S2_DX) % GA_D;
-    if (a < A) g.dec_w[a * LW + GA_H + c] += v;
+    if (a < A) g.dec_w[a * LW + H + c] += v;
   } else if (e < GA_S2_BD) {
-    const int k = (e - GA_S2_Q) / (GA_D * GA_H), i = (e - GA_S2_Q) % (GA_D * GA_H);
+    const int k = (e - GA_S2_Q) / (GA_D * H), i = (e - GA_S2_Q) % (GA_D * H);
     float* dst = k == 0 ? g.q_w : k == 1 ? g.k_w : g.v_w;
     dst[i] += v;
   } else if (e < GA_S2_BV) {
@@ -570,51 +522,43 @@ __global__ __launch_bounds__(256) void g2anet_soft_reduce_kernel(const float* __
   }
 }
 
-// transposed B fragment of a row-major weight with row pitch ld, read through L2: [i] = W[16 chunk + 4 q + i][col]
-__device__ __forceinline__ f32x4 ga_wt(const float* __restrict__ W, int ld, int c, int q, int col) {
-  f32x4 b;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) b[i] = __ldg(W + (long)(16 * c + 4 * q + i) * ld + col);
-  return b;
-}
-
 // ---- the hard kernel of direction p.dir: chain step s sits at position s (forward) or N - 2 - s (reverse)
 __global__ __launch_bounds__(256) void g2anet_hard_bwd_kernel(GaArgs p) {
-  __shared__ __attribute__((aligned(16))) float sh_h[16 * GA_LD];
-  __shared__ __attribute__((aligned(16))) float sh_P[16 * GA_LDG], sh_Q[16 * GA_LDG], sh_dQ[16 * GA_LDG];
-  __shared__ __attribute__((aligned(16))) float sh_st[GA_PMAX][16 * GA_LD];
+  __shared__ __attribute__((aligned(16))) float sh_h[16 * LD];
+  __shared__ __attribute__((aligned(16))) float sh_P[16 * LDG], sh_Q[16 * LDG], sh_dQ[16 * LDG];
+  __shared__ __attribute__((aligned(16))) float sh_st[GA_PMAX][16 * LD];
   __shared__ __attribute__((aligned(16))) float sh_dg[16 * GA_LDG4];          // dr | dz | dn | dn r; at the tile's end dP in the first three
   __shared__ float sh_ds[16 * GA_PMAX];
   const int tid = threadIdx.x, w = tid >> 6, l = tid & 63, m = l & 15, q = l >> 4, col = 16 * w + m;
   const int N = p.N, np = N - 1, d = p.dir;
   const float* w_ih = ga_w_ih(p.w, d);
   const float* w_hh = ga_w_hh(p.w, d);
-  GaHH W;
-  ga_load_hh(W, w_hh, ga_b_hh(p.w, d), col, q);
-  const float dv = p.w.he_w[2 * GA_H + d * GA_H + col] - p.w.he_w[d * GA_H + col];
+  HH W;
+  load_hh(W, w_hh, ga_b_hh(p.w, d), col, q);
+  const float dv = p.w.he_w[2 * H + d * H + col] - p.w.he_w[d * H + col];
   f32x4 gihp[12], gihq[12], ghh[12];
 #pragma unroll
   for (int t = 0; t < 12; ++t) gihp[t] = gihq[t] = ghh[t] = f32x4{0, 0, 0, 0};
   float gbih = 0.0f, gbhh = 0.0f, ghe = 0.0f;   // tid < 192: gate row tid; every thread: state column tid & 63 over rows 4 (tid >> 6) ..
-  const int hhcol = tid < 2 * GA_H ? tid : tid + GA_H;      // gate row tid of the hidden side in the gate-gradient plane
+  const int hhcol = tid < 2 * H ? tid : tid + H;      // gate row tid of the hidden side in the gate-gradient plane
 
   for (long tile = blockIdx.x; tile < p.tiles; tile += gridDim.x) {
     const long row0 = tile * p.nrows;
-    ga_load_tile(p, tile, p.hs, sh_h);
+    load_tile(p.nrows, p.gpw, p.N, p.G, tile, p.hs, sh_h);
     if (tid < 16 * np) {
       const int row = tid / np, pp = tid - row * np;
-      sh_ds[row * GA_PMAX + pp] = ga_row_ok(p, tile, row) ? p.wplane[(row0 + row) * np + pp] : 0.0f;
+      sh_ds[row * GA_PMAX + pp] = row_ok(p.nrows, p.gpw, p.N, p.G, tile, row) ? p.wplane[(row0 + row) * np + pp] : 0.0f;
     }
-    for (int idx = tid; idx < 16 * GA_LDG; idx += 256) sh_dQ[idx] = 0.0f;
+    for (int idx = tid; idx < 16 * LDG; idx += 256) sh_dQ[idx] = 0.0f;
     __syncthreads();
     ga_pq(w_ih, ga_b_ih(p.w, d), sh_h, sh_P, sh_Q, m, q, col);
     __syncthreads();
     // ---- the chain's states
     for (int s = 0; s < np; ++s) {
-      GaCell o;
+      Cell o;
       ga_cell(W, sh_P, sh_Q, sh_st[s > 0 ? s - 1 : 0], s > 0, d ? np - 1 - s : s, N, p.nrows, m, q, col, o);
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sh_st[s][(4 * q + r) * GA_LD + col] = o.h[r];
+      for (int r = 0; r < 4; ++r) sh_st[s][(4 * q + r) * LD + col] = o.h[r];
       __syncthreads();
     }
     // ---- hard_encoding's half of this direction: sum of ds state
@@ -623,7 +567,7 @@ __global__ __launch_bounds__(256) void g2anet_hard_bwd_kernel(GaArgs p) {
       for (int s = 0; s < np; ++s) {
         const int pp = d ? np - 1 - s : s;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) ghe += sh_ds[(r4 + r) * GA_PMAX + pp] * sh_st[s][(r4 + r) * GA_LD + c];
+        for (int r = 0; r < 4; ++r) ghe += sh_ds[(r4 + r) * GA_PMAX + pp] * sh_st[s][(r4 + r) * LD + c];
       }
     }
     // ---- the chain in reverse
@@ -635,40 +579,37 @@ __global__ __launch_bounds__(256) void g2anet_hard_bwd_kernel(GaArgs p) {
     for (int s = np - 1; s >= 0; --s) {
       const int pp = d ? np - 1 - s : s;
       const float* prev = sh_st[s > 0 ? s - 1 : 0];
-      GaCell o;
+      Cell o;
       ga_cell(W, sh_P, sh_Q, prev, s > 0, pp, N, p.nrows, m, q, col, o);
       float direct[4];
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int row = 4 * q + r;
-        const float dh = D[r] + sh_ds[row * GA_PMAX + pp] * dv;
-        const float dn = dh * (1.0f - o.z[r]) * (1.0f - o.n[r] * o.n[r]);
-        const float dz = dh * (o.hp[r] - o.n[r]) * o.z[r] * (1.0f - o.z[r]);
-        const float dr = dn * o.hn[r] * o.r[r] * (1.0f - o.r[r]);
-        direct[r] = dh * o.z[r];
-        sh_dg[row * GA_LDG4 + col] = dr;
-        sh_dg[row * GA_LDG4 + GA_H + col] = dz;
-        sh_dg[row * GA_LDG4 + 2 * GA_H + col] = dn;
-        sh_dg[row * GA_LDG4 + 3 * GA_H + col] = dn * o.r[r];
-        dP[0][r] += dr;
-        dP[1][r] += dz;
-        dP[2][r] += dn;
+        const GateGrad g = gru_point_bwd(o, r, D[r] + sh_ds[row * GA_PMAX + pp] * dv);
+        direct[r] = g.direct;
+        sh_dg[row * GA_LDG4 + col] = g.dr;
+        sh_dg[row * GA_LDG4 + H + col] = g.dz;
+        sh_dg[row * GA_LDG4 + 2 * H + col] = g.dn;
+        sh_dg[row * GA_LDG4 + 3 * H + col] = g.dn * o.r[r];
+        dP[0][r] += g.dr;
+        dP[1][r] += g.dz;
+        dP[2][r] += g.dn;
       }
       __syncthreads();
-      if (tid < GA_G3)
+      if (tid < G3)
         for (int r = 0; r < 16; ++r) gbhh += sh_dg[r * GA_LDG4 + hhcol];
       // dQ: at position pp agent pp of a group is the partner of the agents behind it, agent pp + 1 of those up to pp
-      for (int idx = tid; idx < 16 * GA_G3; idx += 256) {
-        const int row = idx / GA_G3, gc = idx - row * GA_G3;
+      for (int idx = tid; idx < 16 * G3; idx += 256) {
+        const int row = idx / G3, gc = idx - row * G3;
         if (row < p.nrows) {
           const int a = row % N, r0 = row - a;
           float sum = 0.0f;
           if (a == pp) {
             for (int ai = pp + 1; ai < N; ++ai) sum += sh_dg[(r0 + ai) * GA_LDG4 + gc];
-            sh_dQ[row * GA_LDG + gc] += sum;
+            sh_dQ[row * LDG + gc] += sum;
           } else if (a == pp + 1) {
             for (int ai = 0; ai <= pp; ++ai) sum += sh_dg[(r0 + ai) * GA_LDG4 + gc];
-            sh_dQ[row * GA_LDG + gc] += sum;
+            sh_dQ[row * LDG + gc] += sum;
           }
         }
       }
@@ -676,18 +617,18 @@ __global__ __launch_bounds__(256) void g2anet_hard_bwd_kernel(GaArgs p) {
         // dW_hh += dgh^T state (k = the tile's rows), and the gradient on the previous state = dgh W_hh + dh z
         f32x4 bg;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) bg[i] = prev[(4 * q + i) * GA_LD + col];
+        for (int i = 0; i < 4; ++i) bg[i] = prev[(4 * q + i) * LD + col];
 #pragma unroll
         for (int t = 0; t < 12; ++t) {
           f32x4 a;
 #pragma unroll
-          for (int i = 0; i < 4; ++i) a[i] = sh_dg[(4 * q + i) * GA_LDG4 + 16 * t + m + (t < 8 ? 0 : GA_H)];
+          for (int i = 0; i < 4; ++i) a[i] = sh_dg[(4 * q + i) * GA_LDG4 + 16 * t + m + (t < 8 ? 0 : H)];
           ghh[t] = mfma16x4(a, bg, ghh[t]);
         }
         f32x4 ahh = f32x4{0, 0, 0, 0};
 #pragma unroll
         for (int c = 0; c < 12; ++c)
-          ahh = mfma16x4(ga_lds4(sh_dg, GA_LDG4, m, 16 * c + 4 * q + (c < 8 ? 0 : GA_H)), ga_wt(w_hh, GA_H, c, q, col), ahh);
+          ahh = mfma16x4(lds4(sh_dg, GA_LDG4, m, 16 * c + 4 * q + (c < 8 ? 0 : H)), wt(w_hh, H, c, q, col), ahh);
 #pragma unroll
         for (int r = 0; r < 4; ++r) D[r] = direct[r] + ahh[r];
       }
@@ -697,32 +638,32 @@ __global__ __launch_bounds__(256) void g2anet_hard_bwd_kernel(GaArgs p) {
 #pragma unroll
     for (int g = 0; g < 3; ++g)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) sh_dg[(4 * q + r) * GA_LDG4 + g * GA_H + col] = dP[g][r];
+      for (int r = 0; r < 4; ++r) sh_dg[(4 * q + r) * GA_LDG4 + g * H + col] = dP[g][r];
     __syncthreads();
     {
       f32x4 bh;
 #pragma unroll
-      for (int i = 0; i < 4; ++i) bh[i] = sh_h[(4 * q + i) * GA_LD + col];
+      for (int i = 0; i < 4; ++i) bh[i] = sh_h[(4 * q + i) * LD + col];
 #pragma unroll
       for (int t = 0; t < 12; ++t) {
         f32x4 ap, aq;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           ap[i] = sh_dg[(4 * q + i) * GA_LDG4 + 16 * t + m];
-          aq[i] = sh_dQ[(4 * q + i) * GA_LDG + 16 * t + m];
+          aq[i] = sh_dQ[(4 * q + i) * LDG + 16 * t + m];
         }
         mfma16x4_il2(ap, bh, gihp[t], aq, bh, gihq[t]);
       }
-      if (tid < GA_G3)
+      if (tid < G3)
         for (int r = 0; r < 16; ++r) gbih += sh_dg[r * GA_LDG4 + tid];
       f32x4 ap = f32x4{0, 0, 0, 0}, aq = f32x4{0, 0, 0, 0};
 #pragma unroll
       for (int c = 0; c < 12; ++c)
-        mfma16x4_il2(ga_lds4(sh_dg, GA_LDG4, m, 16 * c + 4 * q), ga_wt(w_ih, 2 * GA_H, c, q, col), ap,
-                     ga_lds4(sh_dQ, GA_LDG, m, 16 * c + 4 * q), ga_wt(w_ih + GA_H, 2 * GA_H, c, q, col), aq);
+        mfma16x4_il2(lds4(sh_dg, GA_LDG4, m, 16 * c + 4 * q), wt(w_ih, 2 * H, c, q, col), ap,
+                     lds4(sh_dQ, LDG, m, 16 * c + 4 * q), wt(w_ih + H, 2 * H, c, q, col), aq);
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        if (ga_row_ok(p, tile, 4 * q + r)) p.dhs[(row0 + 4 * q + r) * GA_H + col] += ap[r] + aq[r];
+        if (row_ok(p.nrows, p.gpw, p.N, p.G, tile, 4 * q + r)) p.dhs[(row0 + 4 * q + r) * H + col] += ap[r] + aq[r];
     }
     __syncthreads();
   }
@@ -733,11 +674,11 @@ __global__ __launch_bounds__(256) void g2anet_hard_bwd_kernel(GaArgs p) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int row = 16 * t + 4 * q + r;
-      s[GA_S3_IH + row * (2 * GA_H) + col] = gihp[t][r];
-      s[GA_S3_IH + row * (2 * GA_H) + GA_H + col] = gihq[t][r];
-      s[GA_S3_HH + row * GA_H + col] = ghh[t][r];
+      s[GA_S3_IH + row * (2 * H) + col] = gihp[t][r];
+      s[GA_S3_IH + row * (2 * H) + H + col] = gihq[t][r];
+      s[GA_S3_HH + row * H + col] = ghh[t][r];
     }
-  if (tid < GA_G3) {
+  if (tid < G3) {
     s[GA_S3_BIH + tid] = gbih;
     s[GA_S3_BHH + tid] = gbhh;
   }
@@ -746,14 +687,14 @@ __global__ __launch_bounds__(256) void g2anet_hard_bwd_kernel(GaArgs p) {
 
 __global__ __launch_bounds__(256) void g2anet_hard_reduce_kernel(const float* __restrict__ slabs, int n, marl_g2anet_grads_t g, int dir) {
   const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= GA_S3_HE + GA_H) return;
+  if (e >= GA_S3_HE + H) return;
   if (e >= GA_S3_HE) {
     // hard_encoding.weight (2, 128): row 1 receives the sum, row 0 its negative (dy_1 = - dy_0)
     const int c = e - GA_S3_HE;
     float v = 0.0f;
-    for (int k = 0; k < 4; ++k) v = slab_acc(v, slabs + GA_S3_HE + k * GA_H + c, GA_SLAB3, 0, 1, n);
-    g.he_w[2 * GA_H + dir * GA_H + c] += v;
-    g.he_w[dir * GA_H + c] -= v;
+    for (int k = 0; k < 4; ++k) v = slab_acc(v, slabs + GA_S3_HE + k * H + c, GA_SLAB3, 0, 1, n);
+    g.he_w[2 * H + dir * H + c] += v;
+    g.he_w[dir * H + c] -= v;
     return;
   }
   float* dst;
@@ -786,11 +727,6 @@ bool ga_grads_ok(const marl_g2anet_grads_t* g) {
          g->he_b && g->q_w && g->k_w && g->v_w && g->v_b && g->dec_w && g->dec_b;
 }
 
-long ga_tiles(long G, int N) {
-  const int gpw = 16 / N;
-  return (G + gpw - 1) / gpw;
-}
-
 // floats of the plane w / ds in front of the slabs, rounded up to 64
 long ga_plane_floats(long G, int N) { return (G * N * (N - 1) + 63) / 64 * 64; }
 
@@ -800,7 +736,7 @@ GaArgs ga_args(const marl_g2anet_weights_t* w, long G, int N, int A, int hard, f
   a.G = G; a.N = N; a.A = A; a.hard = hard ? 1 : 0; a.tau = tau;
   a.gpw = 16 / N;
   a.nrows = a.gpw * N;
-  a.tiles = ga_tiles(G, N);
+  a.tiles = tiles(G, N);
   return a;
 }
 
@@ -827,7 +763,7 @@ extern "C" int marl_g2anet_head_fwd(const marl_g2anet_weights_t* w, const float*
 
 extern "C" size_t marl_g2anet_bwd_workspace(long G, int N, int A, int hard) {
   if (G <= 0 || !marl_g2anet_supported(N, A, hard)) return 0;
-  const long tiles = ga_tiles(G, N);
+  const long tiles = group_tile::tiles(G, N);
   return (size_t)(ga_plane_floats(G, N) + (tiles < GA_BWD_WG ? tiles : GA_BWD_WG) * (long)GA_SLAB) * sizeof(float);
 }
 
@@ -858,7 +794,7 @@ extern "C" int marl_g2anet_head_bwd(const marl_g2anet_weights_t* w, const marl_g
     a.dir = d;
     hipLaunchKernelGGL(g2anet_hard_bwd_kernel, dim3((unsigned)grid), dim3(256), 0, s, a);
     MARL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(g2anet_hard_reduce_kernel, dim3((GA_S3_HE + GA_H + 255) / 256), dim3(256), 0, s, (const float*)a.slabs, grid, *g, d);
+    hipLaunchKernelGGL(g2anet_hard_reduce_kernel, dim3((GA_S3_HE + H + 255) / 256), dim3(256), 0, s, (const float*)a.slabs, grid, *g, d);
     MARL_CHECK_LAUNCH();
   }
   return 0;

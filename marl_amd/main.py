@@ -18,6 +18,7 @@
 from __future__ import annotations
 
 import sys
+from collections import namedtuple
 
 from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
     get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args
@@ -32,18 +33,40 @@ MAPS = {"2s3z": (5, 80, 120, 11, 120), "3s5z": (8, 128, 216, 14, 150), "MMM2": (
 COMMNET = '+commnet'
 G2ANET = '+g2anet'
 _POLICY_ALGS = ('central_v', 'coma', 'reinforce')
-_ACTORS = {COMMNET: ('commnet', 'CommNet'), G2ANET: ('g2anet', 'G2ANet')}
 
 
-def actor_base(alg):
+def _map_counts(args):
+    """(agents, actions) of --map, known before the environment is made; (2, 1) where no map says them"""
+    return (MAPS[args.map][0], MAPS[args.map][3]) if args.env in ('smac', 'synthetic') else (2, 1)
+
+
+# What the launcher does for an actor suffix.  table: the argument table (commnet: k = 2 on map 3m, otherwise 3; g2anet: attention_dim =
+# 32, hard = True); switch: the command-line override (argparse has typed it) of the table's ``sets``; check: the shape check of
+# controller.share_params (a name: imported when it runs) and early: the (agents, actions) it is handed before the environment is
+# made - CommNet's range of k depends on nothing else, G2ANet's is the map's counts (a bad --g2anet_tau is refused all the same);
+# mac: the controller class, by name as well
+_Actor = namedtuple('_Actor', 'name title table switch sets check early mac')
+_ACTORS = {COMMNET: _Actor(name='commnet', title='CommNet', table=get_commnet_args, switch='commnet_k', sets='k',
+                           check='commnet_k_of', early=lambda args: (2, 1), mac='CommNetMAC'),
+           G2ANET: _Actor(name='g2anet', title='G2ANet', table=get_g2anet_args, switch='g2anet_hard', sets='hard',
+                          check='g2anet_shape_of', early=_map_counts, mac='G2ANetMAC')}
+
+
+def _share(name):
+    from .controller import share_params
+    return getattr(share_params, name)
+
+
+def actor_base(alg, entry=False):
     """'coma+commnet' -> ('coma', 'commnet'), 'reinforce+g2anet' -> ('reinforce', 'g2anet'); (alg, None) for a name without such a
-    suffix.  The communicating actors belong to the policy-gradient learners: any other base is an error."""
-    for suffix, (actor, title) in _ACTORS.items():
+    suffix.  The communicating actors belong to the policy-gradient learners: any other base is an error.  ``entry``: the _ACTORS
+    entry in the place of the actor's name"""
+    for suffix, a in _ACTORS.items():
         if alg.endswith(suffix):
             base = alg[:-len(suffix)]
             if base not in _POLICY_ALGS:
-                raise ValueError("%s: the %s actor is trained by central_v, coma or reinforce, not by %r" % (alg, title, base))
-            return base, actor
+                raise ValueError("%s: the %s actor is trained by central_v, coma or reinforce, not by %r" % (alg, a.title, base))
+            return base, (a if entry else a.name)
     return alg, None
 
 
@@ -57,11 +80,11 @@ def commnet_base(alg):
 def build(argv=None):
     args = get_common_args(argv)
     get_mixer_args(args)
-    base, actor = actor_base(args.alg)           # raises on a Q-learning algorithm with +commnet / +g2anet
+    base, actor = actor_base(args.alg, entry=True)           # raises on a Q-learning algorithm with an actor suffix
     if actor is not None:
         on = [sw for sw in ('RTW', 'world_model', 'MAIC') if getattr(args, sw, False)]
         if on:
-            raise ValueError("%s trains the %s actor as a policy: not with %s" % (args.alg, _ACTORS['+' + actor][1], on[0]))
+            raise ValueError("%s trains the %s actor as a policy: not with %s" % (args.alg, actor.title, on[0]))
     if base in ('central_v', 'coma'):
         given = args.td_lambda
         (get_centralv_args if base == 'central_v' else get_coma_args)(args)
@@ -69,21 +92,12 @@ def build(argv=None):
             args.td_lambda = given
     elif base == 'reinforce':
         get_reinforce_args(args)
-    if actor == 'commnet':
-        get_commnet_args(args)          # k = 2 on map 3m, otherwise 3
-        if getattr(args, "commnet_k", None) is not None:
-            args.k = args.commnet_k
-        from .controller.share_params import commnet_k_of
-        commnet_k_of(args, n_agents=2, n_actions=1)     # the range of k depends on nothing else: refused before the environment is made
-    elif actor == 'g2anet':
-        get_g2anet_args(args)           # attention_dim = 32, hard = True
-        if getattr(args, "g2anet_hard", None) is not None:
-            args.hard = bool(args.g2anet_hard)
-        from .controller.share_params import g2anet_shape_of
-        if args.env in ('smac', 'synthetic'):           # the map's counts are known here: refused before the environment is made
-            g2anet_shape_of(args, n_agents=MAPS[args.map][0], n_actions=MAPS[args.map][3])
-        else:
-            g2anet_shape_of(args, n_agents=2, n_actions=1)      # (a bad --g2anet_tau all the same)
+    if actor is not None:
+        actor.table(args)
+        if getattr(args, actor.switch, None) is not None:
+            setattr(args, actor.sets, getattr(args, actor.switch))
+        n, a = actor.early(args)
+        _share(actor.check)(args, n_agents=n, n_actions=a)      # refused before the environment is made
     get_RTW_args(args)
     get_maic_args(args)
     if args.env == 'smac':
@@ -101,32 +115,26 @@ def build(argv=None):
     args.state_shape, args.obs_shape, args.episode_limit = info["state_shape"], info["obs_shape"], info["episode_limit"]
     args.batch_size = max(args.batch_size, args.n_envs)
     args.buffer_size = max(2 * args.n_envs, min(args.buffer_size, 8 * args.n_envs))
-    if actor == 'commnet':
-        commnet_k_of(args)              # ... and the environment's agent and action counts with it, before a controller is built
-    elif actor == 'g2anet':
-        g2anet_shape_of(args)
+    if actor is not None:
+        _share(actor.check)(args)       # ... and the environment's agent and action counts with it, before a controller is built
     return args, env
 
 
 def make_runner(args, env, logger=None):
     """the Runner of a built (args, env).  ``--alg coma`` names its learner here: the runner's own table of on-policy learners
-    holds central_v and reinforce, and a Runner built on the bare name 'coma' still refuses it.  The three ``+commnet`` algorithms get
-    their learner class and CommNetMAC (``mac_cls``) the same way, the three ``+g2anet`` ones theirs and G2ANetMAC."""
+    holds central_v and reinforce, and a Runner built on the bare name 'coma' still refuses it.  The algorithms with an actor suffix
+    get their learner class and their actor's controller (``mac_cls``, the _ACTORS entry's) the same way."""
     learner_cls = mac_cls = None
-    base, actor = actor_base(args.alg)
+    base, actor = actor_base(args.alg, entry=True)
     if base == 'coma':
         from .algorithm.coma import COMALearner
         learner_cls = COMALearner
-    elif actor is not None:             # the +commnet / +g2anet names are the launcher's: the runner's own table does not hold them
+    elif actor is not None:             # the names with an actor suffix are the launcher's: the runner's own table does not hold them
         from .algorithm.central_v import CentralVLearner
         from .algorithm.reinforce import ReinforceLearner
         learner_cls = CentralVLearner if base == 'central_v' else ReinforceLearner
-    if actor == 'commnet':
-        from .controller.share_params import CommNetMAC
-        mac_cls = CommNetMAC
-    elif actor == 'g2anet':
-        from .controller.share_params import G2ANetMAC
-        mac_cls = G2ANetMAC
+    if actor is not None:
+        mac_cls = _share(actor.mac)
     return Runner(env, logger if logger is not None else Logger(), args, learner_cls=learner_cls, mac_cls=mac_cls)
 
 

@@ -38,8 +38,8 @@ NotImplementedError (an on-policy update needs the weights the last one wrote) -
 own table; everything above holds for it.  The launcher passes COMALearner (algorithm/coma.py) for ``--alg coma``
 (``main.make_runner``); a Runner built without it keeps answering 'learner coma cannot find!', as it always has.
 ``mac_cls`` (a constructor argument, with ``learner_cls``): the stochastic controller that learner trains in the place of PolicyMAC - the
-launcher passes CommNetMAC for the three ``+commnet`` algorithms and G2ANetMAC for the three ``+g2anet`` ones; a Runner built on a bare
-``+commnet`` / ``+g2anet`` name answers 'cannot find!' too.
+launcher passes the GroupHeadMAC subclass of its actor table (CommNetMAC for the three ``+commnet`` algorithms, G2ANetMAC for the three
+``+g2anet`` ones); a Runner built on a bare ``+commnet`` / ``+g2anet`` name answers 'cannot find!' too.
 
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""

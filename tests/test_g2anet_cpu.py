@@ -130,6 +130,38 @@ def test_build_applies_the_tables(fake_env):
     assert main.actor_base("reinforce+g2anet") == ("reinforce", "g2anet") and main.actor_base("qmix") == ("qmix", None)
 
 
+def test_every_suffix_goes_through_its_table_entry(fake_env, monkeypatch):
+    """for every suffix of the launcher's table: build() applies that actor's argument table and its command-line override, and
+    make_runner hands the Runner that actor's controller class"""
+    from marl_amd import main
+    from marl_amd.controller import share_params as sp
+    want = {"+commnet": ("k", "--commnet_k", "2", 2, sp.CommNetMAC), "+g2anet": ("hard", "--g2anet_hard", "False", False, sp.G2ANetMAC)}
+    assert set(main._ACTORS) == set(want)
+    handed = []
+    monkeypatch.setattr(main, "Runner", lambda env, logger, args, learner_cls=None, mac_cls=None: handed.append(mac_cls))
+    for suffix, (name, switch, given, value, cls) in want.items():
+        table = getattr(main.build(["--alg", "reinforce" + suffix, "--map", "2s3z"])[0], name)
+        args, env = main.build(["--alg", "reinforce" + suffix, "--map", "2s3z", switch, given])
+        assert table is not None and getattr(args, name) == value != table
+        main.make_runner(args, env, object())
+        assert handed[-1] is cls
+
+
+def test_backward_refuses_the_other_actors_planes():
+    from types import SimpleNamespace
+    from marl_amd.controller.share_params import CommNetMAC, G2ANetMAC, CommNetPlanes, G2ANetPlanes
+    args = go.learner_case("reinforce", "2s3z")[0]
+    args.k = 3
+    N = args.n_agents
+    db = SimpleNamespace(B=1, T=2, N=N, A=args.n_actions, O=args.obs_shape)
+    hs = torch.zeros(1, 2, N, H)
+    planes = {CommNetMAC: CommNetPlanes(hs, torch.zeros_like(hs)), G2ANetMAC: G2ANetPlanes(hs, torch.zeros(1, 2, N, N - 1))}
+    for cls, other in ((CommNetMAC, G2ANetMAC), (G2ANetMAC, CommNetMAC)):
+        for bad in (planes[other], hs):
+            with pytest.raises(TypeError, match="%s.backward reads the %s " % (cls.__name__, type(planes[cls]).__name__)):
+                cls(args).backward(db, None, bad, None, None)
+
+
 def test_refusals_before_anything_is_built(fake_env, tmp_path):
     from marl_amd import main
     from marl_amd.controller.share_params import G2ANetMAC

@@ -37,31 +37,62 @@ def events(calls, rounds, reps):
     return {k: (statistics.median(x), min(x), max(x)) for k, x in us.items()}
 
 
-def one_shape(shape, o):
-    from marl_amd import ops
-    from marl_amd.controller.share_params import PolicyMAC, CommNetMAC
+def make(actor, shape, o):
+    """(args, controller, learner, rollout worker) of reinforce on ``shape``; ``actor``: 'commnet' (k = o.k), 'g2anet' or None for the
+    plain PolicyMAC - fixed-length episodes, f32 mode, eager launches"""
+    from marl_amd.controller import share_params as sp
     from marl_amd.algorithm.reinforce import ReinforceLearner
-    from marl_amd.common.arguments import get_reinforce_args
+    from marl_amd.common.arguments import get_reinforce_args, get_g2anet_args
     from marl_amd.rollout import RolloutWorker
     from marl_amd.env.synthetic_smac import SyntheticSMACEnv
+    args = bench.make_args("reinforce", shape, o.T)
+    args.gemm_mode, args.hip_graph = "f32", False
+    get_reinforce_args(args)
+    if actor == "commnet":
+        args.alg, args.k = "reinforce+commnet", o.k
+    elif actor == "g2anet":
+        get_g2anet_args(args)
+        args.alg = "reinforce+g2anet"
+    torch.manual_seed(0)
+    mac = {"commnet": sp.CommNetMAC, "g2anet": sp.G2ANetMAC, None: sp.PolicyMAC}[actor](args)
+    learner = ReinforceLearner(mac, args)
+    env = SyntheticSMACEnv(o.envs, args.n_agents, args.obs_shape, args.state_shape, args.n_actions, args.episode_limit,
+                           seed=1, fixed_length=True)
+    w = RolloutWorker(env, mac, args)
+    w.rollout_mode = "unfused"
+    return args, mac, learner, w
+
+
+def time_updates(shape, alg, o, learner, worker, plain_learner, plain_worker):
+    """the update of ``alg`` beside the reinforce update built from the same tree, alternating: host clock around a device synchronise"""
+    ep_a, ep_p = worker.generate_episodes(o.envs)[0], plain_worker.generate_episodes(o.envs)[0]
+    steps = {alg: lambda i: learner.train(ep_a, i, epsilon=worker.epsilon),
+             "reinforce": lambda i: plain_learner.train(ep_p, i, epsilon=plain_worker.epsilon)}
+    for f in steps.values():
+        for i in range(3):
+            f(i)
+    gc.collect()
+    gc.disable()
+    ms = {k: [] for k in steps}
+    for _ in range(o.rounds):
+        for k, f in steps.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for i in range(o.updates):
+                f(i)
+            torch.cuda.synchronize()
+            ms[k].append((time.perf_counter() - t0) * 1e3 / o.updates)
+    gc.enable()
+    for k, x in ms.items():
+        print("%-5s %-18s update  envs %d  median %.2f ms (min %.2f - max %.2f, %d rounds of %d)"
+              % (shape, k, o.envs, statistics.median(x), min(x), max(x), o.rounds, o.updates))
+    print("%-5s %s / reinforce  %.3f" % (shape, alg, statistics.median(ms[alg]) / statistics.median(ms["reinforce"])))
+
+
+def one_shape(shape, o):
+    from marl_amd import ops
     dev = torch.device("cuda")
-
-    def make(commnet):
-        args = bench.make_args("reinforce", shape, o.T)
-        args.gemm_mode, args.hip_graph = "f32", False
-        get_reinforce_args(args)
-        if commnet:
-            args.alg, args.k = "reinforce+commnet", o.k
-        torch.manual_seed(0)
-        mac = (CommNetMAC if commnet else PolicyMAC)(args)
-        learner = ReinforceLearner(mac, args)
-        env = SyntheticSMACEnv(o.envs, args.n_agents, args.obs_shape, args.state_shape, args.n_actions, args.episode_limit,
-                               seed=1, fixed_length=True)
-        w = RolloutWorker(env, mac, args)
-        w.rollout_mode = "unfused"
-        return args, mac, learner, w
-
-    (ca, cmac, cl, cw), (pa, pmac, pl, pw) = make(True), make(False)
+    (ca, cmac, cl, cw), (pa, pmac, pl, pw) = make("commnet", shape, o), make(None, shape, o)
     B, T, N, A, O, H = o.envs, ca.episode_limit, ca.n_agents, ca.n_actions, ca.obs_shape, 64
     G, R = B * T, B * T * N
     # 1. the head alone
@@ -106,27 +137,7 @@ def one_shape(shape, o):
     print("%-5s identity front / plain  %.3f" % (shape, rec["identity front"][0] / rec["plain unroll"][0]))
     del e, obs, saved, hsp, dxp, dhs4, dq, hs, dl, logits, dhs
     # 3. the updates
-    ep_c, ep_p = cw.generate_episodes(o.envs)[0], pw.generate_episodes(o.envs)[0]
-    steps = {"reinforce+commnet": lambda i: cl.train(ep_c, i, epsilon=cw.epsilon), "reinforce": lambda i: pl.train(ep_p, i, epsilon=pw.epsilon)}
-    for f in steps.values():
-        for i in range(3):
-            f(i)
-    gc.collect()
-    gc.disable()
-    ms = {k: [] for k in steps}
-    for _ in range(o.rounds):
-        for k, f in steps.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for i in range(o.updates):
-                f(i)
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3 / o.updates)
-    gc.enable()
-    for k, x in ms.items():
-        print("%-5s %-18s update  envs %d  median %.2f ms (min %.2f - max %.2f, %d rounds of %d)"
-              % (shape, k, o.envs, statistics.median(x), min(x), max(x), o.rounds, o.updates))
-    print("%-5s reinforce+commnet / reinforce  %.3f" % (shape, statistics.median(ms["reinforce+commnet"]) / statistics.median(ms["reinforce"])))
+    time_updates(shape, "reinforce+commnet", o, cl, cw, pl, pw)
 
 
 def main():

@@ -7,44 +7,16 @@
 Defaults: 2s3z and MMM2, T = 120, 4096 episodes, seven rounds."""
 import argparse
 import gc
-import os
-import statistics
-import sys
-import time
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import bench  # noqa: E402
-from time_commnet import events  # noqa: E402
+from time_commnet import events, make, time_updates      # (puts the repository root on sys.path)
 
 
 def one_shape(shape, o):
     from marl_amd import ops
-    from marl_amd.controller.share_params import PolicyMAC, G2ANetMAC
-    from marl_amd.algorithm.reinforce import ReinforceLearner
-    from marl_amd.common.arguments import get_reinforce_args, get_g2anet_args
-    from marl_amd.rollout import RolloutWorker
-    from marl_amd.env.synthetic_smac import SyntheticSMACEnv
     dev = torch.device("cuda")
-
-    def make(g2anet):
-        args = bench.make_args("reinforce", shape, o.T)
-        args.gemm_mode, args.hip_graph = "f32", False
-        get_reinforce_args(args)
-        if g2anet:
-            get_g2anet_args(args)
-            args.alg = "reinforce+g2anet"
-        torch.manual_seed(0)
-        mac = (G2ANetMAC if g2anet else PolicyMAC)(args)
-        learner = ReinforceLearner(mac, args)
-        env = SyntheticSMACEnv(o.envs, args.n_agents, args.obs_shape, args.state_shape, args.n_actions, args.episode_limit,
-                               seed=1, fixed_length=True)
-        w = RolloutWorker(env, mac, args)
-        w.rollout_mode = "unfused"
-        return args, mac, learner, w
-
-    (ga, gmac, gl, gw), (pa, pmac, pl, pw) = make(True), make(False)
+    (ga, gmac, gl, gw), (pa, pmac, pl, pw) = make("g2anet", shape, o), make(None, shape, o)
     B, T, N, A, H = o.envs, ga.episode_limit, ga.n_agents, ga.n_actions, 64
     G, R = B * T, B * T * N
     # 1. the head alone
@@ -69,27 +41,7 @@ def one_shape(shape, o):
     if o.head_only:
         return
     # 2. the updates
-    ep_g, ep_p = gw.generate_episodes(o.envs)[0], pw.generate_episodes(o.envs)[0]
-    steps = {"reinforce+g2anet": lambda i: gl.train(ep_g, i, epsilon=gw.epsilon), "reinforce": lambda i: pl.train(ep_p, i, epsilon=pw.epsilon)}
-    for f in steps.values():
-        for i in range(3):
-            f(i)
-    gc.collect()
-    gc.disable()
-    ms = {k: [] for k in steps}
-    for _ in range(o.rounds):
-        for k, f in steps.items():
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            for i in range(o.updates):
-                f(i)
-            torch.cuda.synchronize()
-            ms[k].append((time.perf_counter() - t0) * 1e3 / o.updates)
-    gc.enable()
-    for k, x in ms.items():
-        print("%-5s %-18s update  envs %d  median %.2f ms (min %.2f - max %.2f, %d rounds of %d)"
-              % (shape, k, o.envs, statistics.median(x), min(x), max(x), o.rounds, o.updates))
-    print("%-5s reinforce+g2anet / reinforce  %.3f" % (shape, statistics.median(ms["reinforce+g2anet"]) / statistics.median(ms["reinforce"])))
+    time_updates(shape, "reinforce+g2anet", o, gl, gw, pl, pw)
 
 
 def main():
