@@ -70,6 +70,28 @@ int marl_linear_wgrad(const float* dY, long lddy, const float* Yact, long ldya, 
                       const marl_group_t* grp, float* ws, size_t ws_bytes, void* stream);
 size_t marl_linear_wgrad_workspace(int M, int N, int K, int groups);
 int marl_wgrad_slabs(int M);
+/* Launch plans of the two functions above, from the host code the launches themselves decide with.  Host only: no GPU, no device
+ * memory touched - only sizes, strides, group strides and the alignment of the pointer VALUES are read (any integer of the right
+ * alignment stands for a pointer).  Return 0, or the hipError_t the entry point itself returns for these arguments (then plan is
+ * undefined); sizes <= 0 launch nothing and give an all-zero plan (family -1).  Both honour marl_experiment_set.
+ * marl_linear_plan, plan[9]:
+ *   [0] operand path of the whole 16-column chunks of dense segment 0: 0 element-wise (k0 < 16 or no segment 0), 1 16-byte
+ *       vectors, 2 dwords (a row stride, base or group stride of x.p0 - or of the gate x.m0 - off the 16-byte grid)
+ *   [1] column tiles per workgroup: 5 for 64 < N <= 80 in fp32, else 4     [2] gate (x.m0 != NULL)     [3] W read k-major
+ *   [4] bf16 operands     [5] W read in 16-byte vectors by those chunks in every group (row-major, ldw % 4 == 0, base and group
+ *       stride aligned)     [6..8] grid x (128-row blocks), y (column blocks), z (groups)
+ * marl_linear_wgrad_plan, plan[8] (ws_bytes as passed to marl_linear_wgrad: it decides the tall kernel's slab count):
+ *   [0] family: 0 generic 64 x 64-block kernel, 1 one-pass full-width kernel, 2 direct kernel, 3 direct kernel in column passes,
+ *       4 LDS-staged tall kernel, 5 thin one-column kernel
+ *   [1], [2] instantiation: direct <KP, NTP> (column passes: 1 and the NTP of the last, plain pass <0, NTP>; every pass before it
+ *       is <1, 0>); tall <KTT, NX>; full-width: gate, 0; generic: bf16, 0; thin: 0, 0
+ *   [3] passes (kernel + slab-reduce pairs)     [4] slabs of each pass as launched (= grid x, = what the reduce adds up)
+ *   [5] gvec, [6] xvec: dY (and Yact) / x.p0 may be read in 16-byte vectors
+ *   [7] column passes: the columns the permuted passes cover (64 or 128); else 0 */
+int marl_linear_plan(const marl_src_t* x, const float* W, long ldw, int w_kmajor, const float* bias, long ldy,
+                     int M, int N, int K, int act, const marl_group_t* grp, int* plan);
+int marl_linear_wgrad_plan(const float* dY, long lddy, const float* Yact, long ldya, const marl_src_t* x, int M, int N, int K,
+                           int flags, const marl_group_t* grp, size_t ws_bytes, int* plan);
 
 /* ---- agent (agent.hip) ----------------------------------------------------------------------
  * T-step unroll of RNNQNet over B*N rows in ONE launch.  Replaces SharedMAC.get_current_q_values /

@@ -128,6 +128,8 @@ SIGNATURES = {
     "marl_linear_wgrad": (I, [P, L, P, L, SRC, P, L, P, I, I, I, I, GRP, P, SZ, P]),
     "marl_linear_wgrad_workspace": (SZ, [I, I, I, I]),
     "marl_wgrad_slabs": (I, [I]),
+    "marl_linear_plan": (I, [SRC, P, L, I, P, L, I, I, I, I, GRP, P]),
+    "marl_linear_wgrad_plan": (I, [P, L, P, L, SRC, I, I, I, I, GRP, SZ, P]),
     "marl_agent_unroll_fwd": (I, [AW, P, L, I, P, L, I, P, P, P, P, P, P, P, I, I, I, I, I, I, I, I, P, P, P]),
     "marl_agent_unroll_reuse_supported": (I, [I, I, I, I, I, I]),
     "marl_agent_unroll_x6_supported": (I, [I, I, I, I, I, I, I]),

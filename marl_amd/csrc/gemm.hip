@@ -747,14 +747,21 @@ inline int launch_wgrad_direct(const WgradArgs& a, hipStream_t s) {
   return 0;
 }
 
-// returns -1 when the shape is not covered (caller uses the LDS-staged kernel)
-inline int try_wgrad_direct(const WgradArgs& a, hipStream_t s) {
-  if (a.N != 64 || a.groups != 1 || a.Yact || !a.gvec || a.M < 4096 || a.x.k1 || a.x.m0 || a.x.k0 < 0 || !a.x.p0) return -1;
+// which instantiation covers the shape (false: none - the caller uses the LDS-staged kernel); host arithmetic only
+inline bool plan_wgrad_direct(const WgradArgs& a, int& KP, int& NTP) {
+  if (a.N != 64 || a.groups != 1 || a.Yact || !a.gvec || a.M < 4096 || a.x.k1 || a.x.m0 || a.x.k0 < 0 || !a.x.p0) return false;
   const bool perm = a.xvec && a.x.k0 >= 64;
-  const int KP = perm ? 1 : 0;
+  KP = perm ? 1 : 0;
   const int rest = a.K - 64 * KP;
-  const int NTP = (rest + 15) / 16;
-  if (NTP > (KP ? 4 : 5) || KP + NTP == 0) return -1;
+  NTP = (rest + 15) / 16;
+  if (NTP > (KP ? 4 : 5) || KP + NTP == 0) return false;
+  return true;
+}
+
+// returns -1 when the shape is not covered
+inline int try_wgrad_direct(const WgradArgs& a, hipStream_t s) {
+  int KP, NTP;
+  if (!plan_wgrad_direct(a, KP, NTP)) return -1;
 #define WD_CASE(kp, nt) if (KP == kp && NTP == nt) return launch_wgrad_direct<kp, nt>(a, s);
   WD_CASE(1, 0) WD_CASE(1, 1) WD_CASE(1, 2) WD_CASE(1, 3) WD_CASE(1, 4)
   WD_CASE(0, 1) WD_CASE(0, 2) WD_CASE(0, 3) WD_CASE(0, 4) WD_CASE(0, 5)
@@ -1003,31 +1010,40 @@ __global__ __launch_bounds__(512, NX >= 7 ? 2 : 4) void wgrad_tall_kernel(WgradA
 }
 
 inline int tall_xp(int K) { const int w = (K + 15) / 16 * 16; return (w % 32 == 16) ? w : w + 16; }
-// returns -1 when the shape is not covered
-inline int try_wgrad_tall(WgradArgs& a, size_t ws_bytes, hipStream_t s) {
-  if (!marl_switches()->wgrad_tall) return -1;      // A/B switch for measurements (common.h: MarlSwitches)
-  if (a.N != 64 || a.groups != 1 || a.Yact || !a.gvec || !a.xvec || a.M < 4096 || a.x.k1 || a.x.m0 || !a.x.p0) return -1;
-  if (a.x.nhot > 1 || a.x.k0 < 16 || a.x.k0 > 224) return -1;
-  if ((a.x.k0 & 3) && (a.x.nhot || a.x.nid || (a.x.ld0 & 3))) return -1;      // ragged dense width: plain dense rows padded to 16 bytes only
+struct TallPlan { int KTT, NX, XP, slabs; size_t lds; };
+// whether the tall kernel takes the shape, and as which instantiation with how many slabs; host arithmetic only
+inline bool plan_wgrad_tall(const WgradArgs& a, size_t ws_bytes, TallPlan& t) {
+  if (!marl_switches()->wgrad_tall) return false;      // A/B switch for measurements (common.h: MarlSwitches)
+  if (a.N != 64 || a.groups != 1 || a.Yact || !a.gvec || !a.xvec || a.M < 4096 || a.x.k1 || a.x.m0 || !a.x.p0) return false;
+  if (a.x.nhot > 1 || a.x.k0 < 16 || a.x.k0 > 224) return false;
+  if ((a.x.k0 & 3) && (a.x.nhot || a.x.nid || (a.x.ld0 & 3))) return false;      // ragged dense width: plain dense rows padded to 16 bytes only
   const int KT = (a.K + 15) / 16;
-  if (KT > 14) return -1;
-  const int XP = tall_xp(a.K);
-  const size_t lds = (size_t)2 * TCH * (TGP + XP) * sizeof(float) + 8 * TCH * (sizeof(long) + 2 * sizeof(int));
+  if (KT > 14) return false;
+  t.XP = tall_xp(a.K);
+  t.lds = (size_t)2 * TCH * (TGP + t.XP) * sizeof(float) + 8 * TCH * (sizeof(long) + 2 * sizeof(int));
   // (dense widths of 196 .. 224 columns - the 216 state columns of 3s5z under the first layer of QTRAN's heads - need seven
   // float4 per producer thread and 84 KB of LDS: one workgroup per CU instead of two, still 2.5x the generic kernel's rate)
   const bool wide = a.x.k0 > 192;
-  if (lds > (wide ? 160 : 80) * 1024) return -1;
+  if (t.lds > (wide ? 160 : 80) * 1024) return false;
   // two slabs per CU when the caller's workspace holds them (marl_linear_wgrad_workspace sizes it so for N == 64)
-  int slabs = a.slabs;
-  if (slabs == 256 && ws_bytes >= (size_t)512 * 64 * (a.K + 1) * sizeof(float)) slabs = 512;
-  a.slabs = slabs;
-  const void* fn = KT <= 6 ? (const void*)wgrad_tall_kernel<6, 3> : KT <= 10 ? (const void*)wgrad_tall_kernel<10, 5>
-                   : wide ? (const void*)wgrad_tall_kernel<14, 7> : (const void*)wgrad_tall_kernel<14, 6>;
-  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  t.slabs = a.slabs;
+  if (t.slabs == 256 && ws_bytes >= (size_t)512 * 64 * (a.K + 1) * sizeof(float)) t.slabs = 512;
+  if (KT <= 6) { t.KTT = 6; t.NX = 3; }
+  else if (KT <= 10) { t.KTT = 10; t.NX = 5; }
+  else { t.KTT = 14; t.NX = wide ? 7 : 6; }
+  return true;
+}
+
+// launches what plan_wgrad_tall() decided (a.slabs becomes the plan's slab count)
+inline int launch_wgrad_tall(WgradArgs& a, const TallPlan& t, hipStream_t s) {
+  a.slabs = t.slabs;
+  const void* fn = t.KTT == 6 ? (const void*)wgrad_tall_kernel<6, 3> : t.KTT == 10 ? (const void*)wgrad_tall_kernel<10, 5>
+                   : t.NX == 7 ? (const void*)wgrad_tall_kernel<14, 7> : (const void*)wgrad_tall_kernel<14, 6>;
+  hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)t.lds);
   if (e != hipSuccess) return (int)e;
-  int xp = XP;
+  int xp = t.XP;
   void* kargs[] = {(void*)&a, (void*)&xp};
-  e = hipLaunchKernel(fn, dim3(slabs), dim3(512), kargs, lds, s);
+  e = hipLaunchKernel(fn, dim3(t.slabs), dim3(512), kargs, t.lds, s);
   if (e != hipSuccess) return (int)e;
   return 0;
 }
@@ -1078,13 +1094,12 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(WgradArgs a) {
   }
 }
 
-// returns -1 when the shape is not covered
-inline int try_wgrad_thin(WgradArgs& a, hipStream_t s) {
-  if (a.N != 1 || a.groups != 1 || a.Yact || !a.xvec || a.M < 4096 || a.K > 252 || (a.x.ld0 & 3)) return -1;
-  if (!a.x.p0 || a.x.k0 != a.K || a.x.k1 || a.x.nhot || a.x.nid || a.x.m0 || a.x.rpe0 || a.x.emap0) return -1;
-  if (a.x.ld0 < (a.K + 3) / 4 * 4) return -1;                // the last 16-byte load of a row stays inside its pitch
-  hipLaunchKernelGGL(wgrad_thin_kernel, dim3(a.slabs), dim3(256), 0, s, a);
-  return 0;
+// whether the one-column kernel takes the shape; host arithmetic only
+inline bool plan_wgrad_thin(const WgradArgs& a) {
+  if (a.N != 1 || a.groups != 1 || a.Yact || !a.xvec || a.M < 4096 || a.K > 252 || (a.x.ld0 & 3)) return false;
+  if (!a.x.p0 || a.x.k0 != a.K || a.x.k1 || a.x.nhot || a.x.nid || a.x.m0 || a.x.rpe0 || a.x.emap0) return false;
+  if (a.x.ld0 < (a.K + 3) / 4 * 4) return false;                // the last 16-byte load of a row stays inside its pitch
+  return true;
 }
 
 struct WredArgs {
@@ -1150,6 +1165,117 @@ inline ConcatSrc to_src(const marl_src_t* s) {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
+// ---- launch plans.  marl_linear / marl_linear_wgrad decide by calling these and launch from the result; marl_linear_plan /
+// marl_linear_wgrad_plan hand the same result to the caller.  Host arithmetic on sizes, strides and pointer VALUES only.
+struct LinPlan { int amode, nc, gate, kmajor, bf, wvec; dim3 grid; };
+
+inline LinArgs linear_args(const marl_src_t* x, const float* W, long ldw, const float* bias, float* Y, long ldy, int M, int N, int K,
+                           int act, float beta, const marl_group_t* grp) {
+  LinArgs a;
+  a.x = to_src(x);
+  a.W = W; a.ldw = ldw; a.bias = bias; a.Y = Y; a.ldy = ldy; a.M = M; a.N = N; a.K = K;
+  a.act = act; a.beta = beta;
+  a.groups = grp ? grp->groups : 1;
+  a.gs_x0 = grp ? grp->gs_x0 : 0; a.gs_x1 = grp ? grp->gs_x1 : 0; a.gs_w = grp ? grp->gs_w : 0;
+  a.gs_b = grp ? grp->gs_b : 0; a.gs_y = grp ? grp->gs_y : 0; a.gs_m0 = grp ? grp->gs_m0 : 0;
+  return a;
+}
+
+inline LinPlan plan_linear(const LinArgs& a, int w_kmajor, int act) {
+  LinPlan p;
+  // fast-path mode of the chunks inside dense segment 0: 1 = 16-byte loads, 2 = dword loads, 0 = none
+  p.amode = 0;
+  p.gate = a.x.m0 != nullptr;
+  if (a.x.p0 && a.x.k0 >= 16) {
+    bool al = (a.x.ld0 % 4 == 0) && aligned16(a.x.p0) && (a.gs_x0 % 4 == 0);
+    if (p.gate) al = al && (a.x.ldm0 % 4 == 0) && aligned16(a.x.m0) && (a.gs_m0 % 4 == 0);
+    p.amode = al ? 1 : 2;
+  }
+  p.bf = (act & 0x100) != 0;        // bf16 operands, fp32 accumulate (mixer GEMMs, opt-in)
+  p.nc = (!p.bf && a.N > 64 && a.N <= 80) ? 5 : 4;
+  p.kmajor = w_kmajor != 0;
+  // what linear_kernel's own `wvec` test gives in EVERY group (it tests W + g * gs_w per workgroup; only the fast chunks use it)
+  p.wvec = !p.kmajor && (a.ldw % 4 == 0) && aligned16(a.W) && (a.groups == 1 || a.gs_w % 4 == 0);
+  p.grid = dim3((a.M + 127) / 128, (a.N + 16 * p.nc - 1) / (16 * p.nc), a.groups);
+  return p;
+}
+
+enum { WG_GENERIC = 0, WG_FULL = 1, WG_DIRECT = 2, WG_PASSES = 3, WG_TALL = 4, WG_THIN = 5 };
+// i0, i1: the instantiation - direct KP, NTP (column passes: 1, NTP of the last, plain pass; the others are <1, 0>); tall KTT, NX;
+// full-width gate, 0; generic bf16, 0.  slabs: of each pass, as launched.  c_rest: columns the permuted passes cover.
+struct WgradPlan { int family, i0, i1, passes, slabs, c_rest; TallPlan tall; };
+
+inline WgradArgs wgrad_args(const float* G, long ldg, const float* Yact, long ldya, const marl_src_t* x, int M, int N, int K,
+                            const marl_group_t* grp, float* ws) {
+  WgradArgs a;
+  a.G = G; a.ldg = ldg; a.Yact = Yact; a.ldya = ldya; a.x = to_src(x);
+  a.ws = ws; a.M = M; a.N = N; a.K = K; a.slabs = marl_wgrad_slabs(M);
+  a.nyb = (N + 63) / 64; a.groups = grp ? grp->groups : 1;
+  a.gs_g = grp ? grp->gs_y : 0; a.gs_ya = grp ? grp->gs_m0 : 0;
+  a.gs_x0 = grp ? grp->gs_x0 : 0; a.gs_x1 = grp ? grp->gs_x1 : 0;
+  a.gvec = (ldg % 4 == 0) && aligned16(G) && (a.gs_g % 4 == 0) &&
+           (!Yact || ((ldya % 4 == 0) && aligned16(Yact) && (a.gs_ya % 4 == 0)));
+  a.xvec = a.x.p0 && !a.x.m0 && (a.x.ld0 % 4 == 0) && aligned16(a.x.p0) && (a.gs_x0 % 4 == 0);
+  return a;
+}
+
+// the sub-problem of column pass [c0, c0 + width) of a column-pass plan (c_rest: what the permuted passes cover)
+inline WgradArgs wgrad_pass_args(const WgradArgs& a, int c0, int c_rest) {
+  WgradArgs b = a;
+  const bool perm = c0 < c_rest;
+  b.x.p0 = a.x.p0 + c0;
+  b.x.k0 = perm ? 64 : a.x.k0 - c0;
+  if (perm) { b.x.idx = nullptr; b.x.nhot = 0; b.x.hot_w = 0; b.x.nid = 0; }
+  b.K = perm ? 64 : a.K - c0;
+  return b;
+}
+
+// 0, or hipErrorInvalidValue where marl_linear_wgrad refuses the call
+inline int plan_wgrad(const WgradArgs& a, bool bf, size_t ws_bytes, WgradPlan& p) {
+  const int K = a.K, N = a.N, M = a.M;
+  p.family = WG_GENERIC; p.i0 = bf ? 1 : 0; p.i1 = 0; p.passes = 1; p.slabs = a.slabs; p.c_rest = 0;
+  // 64-output layers over many rows (fc1 of the agent): LDS-staged tall kernel
+  if (!bf && plan_wgrad_tall(a, ws_bytes, p.tall)) {
+    p.family = WG_TALL; p.i0 = p.tall.KTT; p.i1 = p.tall.NX; p.slabs = p.tall.slabs;
+    return 0;
+  }
+  // Wide inputs of a 64-output layer (fc1 of the agent on 3s5z / MMM2: 150 / 204 columns - more accumulator tiles than
+  // one pass of the direct kernel holds): column passes [0,64), [64,128) as permuted blocks and the rest as plain
+  // tiles, each a direct launch over its own sub-source with its own slabs; G is re-read per pass (3 x 315 MB at
+  // MMM2 / 1024 envs) but nothing is staged through LDS (the LDS-staged kernel took 1.35 ms there).
+  if (!bf && N == 64 && a.groups == 1 && !a.Yact && a.gvec && a.xvec && M >= 4096 && !a.x.k1 && !a.x.m0 && a.x.k0 >= 64 &&
+      K - 64 > 64) {
+    const int c_rest = a.x.k0 >= 128 ? 128 : 64;
+    if ((K - c_rest + 15) / 16 <= 5) {
+      p.family = WG_PASSES; p.c_rest = c_rest; p.passes = 0;
+      for (int c0 = 0; c0 < K; ++p.passes) {
+        const WgradArgs b = wgrad_pass_args(a, c0, c_rest);
+        if (!plan_wgrad_direct(b, p.i0, p.i1)) return (int)hipErrorInvalidValue;
+        c0 += b.K;
+      }
+      p.i0 = 1;                                 // (i0, i1 otherwise hold the last, plain pass: <0, NTP>)
+      return 0;
+    }
+  }
+  if (plan_wgrad_thin(a)) { p.family = WG_THIN; p.i0 = 0; return 0; }      // fp32 either way: one output column is not matrix work
+  if (!bf && plan_wgrad_direct(a, p.i0, p.i1)) { p.family = WG_DIRECT; return 0; }
+  p.i0 = bf ? 1 : 0; p.i1 = 0;
+  bool one_base = a.x.p0 && !a.x.m0 && !a.x.nid && a.x.k0 < 16384 && a.x.k1 < 16384 && a.x.nhot < 16384 && a.x.hot_w < 0xfff0;
+  for (int c4 = 0; one_base && c4 < K; c4 += 4) {       // segment of the first and the last real column of each item
+    auto seg = [&](int k) { return k < a.x.k0 ? 0 : (k - a.x.k0 < a.x.k1 ? 1 : 2); };
+    const int kl = c4 + 3 < K ? c4 + 3 : K - 1;
+    if (seg(c4) != seg(kl)) one_base = false;
+  }
+  if (!bf && a.groups == 1 && N <= WF && K + 1 <= WF && a.gvec && a.ldg >= (N + 3) / 4 * 4 &&
+      (!a.Yact || a.ldya >= (N + 3) / 4 * 4) && M >= 2048 && one_base) {
+    // narrow layer: one pass over G and X
+    const long chunks = ((long)M + WCH - 1) / WCH;
+    p.family = WG_FULL; p.i0 = a.Yact ? 1 : 0;
+    p.slabs = (int)(2L * a.slabs < chunks ? 2L * a.slabs : (chunks < 1 ? 1 : chunks));
+  }
+  return 0;
+}
+
 }  // namespace
 
 ST_DEFINE_SETTER(marl_debug_stamps_wgrad)
@@ -1158,25 +1284,12 @@ extern "C" int marl_linear(const marl_src_t* x, const float* W, long ldw, int w_
                            float* Y, long ldy, int M, int N, int K, int act, float beta,
                            const marl_group_t* grp, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
-  LinArgs a;
-  a.x = to_src(x);
+  LinArgs a = linear_args(x, W, ldw, bias, Y, ldy, M, N, K, act, beta, grp);
   if (concat_width(a.x) != K) return (int)hipErrorInvalidValue;
-  a.W = W; a.ldw = ldw; a.bias = bias; a.Y = Y; a.ldy = ldy; a.M = M; a.N = N; a.K = K;
-  a.act = act; a.beta = beta;
-  a.groups = grp ? grp->groups : 1;
-  a.gs_x0 = grp ? grp->gs_x0 : 0; a.gs_x1 = grp ? grp->gs_x1 : 0; a.gs_w = grp ? grp->gs_w : 0;
-  a.gs_b = grp ? grp->gs_b : 0; a.gs_y = grp ? grp->gs_y : 0; a.gs_m0 = grp ? grp->gs_m0 : 0;
-  // fast-path mode of the chunks inside dense segment 0: 1 = 16-byte loads, 2 = dword loads, 0 = none
-  int amode = 0;
-  const bool gate = a.x.m0 != nullptr;
-  if (a.x.p0 && a.x.k0 >= 16) {
-    bool al = (a.x.ld0 % 4 == 0) && aligned16(a.x.p0) && (a.gs_x0 % 4 == 0);
-    if (gate) al = al && (a.x.ldm0 % 4 == 0) && aligned16(a.x.m0) && (a.gs_m0 % 4 == 0);
-    amode = al ? 1 : 2;
-  }
-  const bool bf = (act & 0x100) != 0;        // bf16 operands, fp32 accumulate (mixer GEMMs, opt-in)
-  const int nc = (!bf && N > 64 && N <= 80) ? 5 : 4;
-  dim3 grid((M + 127) / 128, (N + 16 * nc - 1) / (16 * nc), a.groups), block(256);
+  const LinPlan p = plan_linear(a, w_kmajor, act);
+  const int amode = p.amode, nc = p.nc;
+  const bool gate = p.gate, bf = p.bf;
+  const dim3 grid = p.grid, block(256);
   hipStream_t s = (hipStream_t)stream;
   a.act = act & 0xff;
 #define LIN_GT(AM, KM, BFV, NCV) do { if (gate) hipLaunchKernelGGL((linear_kernel<AM, KM, BFV, true, NCV>), grid, block, 0, s, a); \
@@ -1207,104 +1320,99 @@ extern "C" int marl_wgrad_slabs(int M) {
   return (int)s;
 }
 
+extern "C" int marl_linear_plan(const marl_src_t* x, const float* W, long ldw, int w_kmajor, const float* bias, long ldy,
+                                int M, int N, int K, int act, const marl_group_t* grp, int* plan) {
+  for (int i = 0; i < 9; ++i) plan[i] = 0;
+  if (M <= 0 || N <= 0 || K <= 0) return 0;      // marl_linear launches nothing
+  const LinArgs a = linear_args(x, W, ldw, bias, nullptr, ldy, M, N, K, act, 0.f, grp);
+  if (concat_width(a.x) != K) return (int)hipErrorInvalidValue;
+  const LinPlan p = plan_linear(a, w_kmajor, act);
+  plan[0] = p.amode; plan[1] = p.nc; plan[2] = p.gate; plan[3] = p.kmajor; plan[4] = p.bf; plan[5] = p.wvec;
+  plan[6] = (int)p.grid.x; plan[7] = (int)p.grid.y; plan[8] = (int)p.grid.z;
+  return 0;
+}
+
+extern "C" int marl_linear_wgrad_plan(const float* dY, long lddy, const float* Yact, long ldya, const marl_src_t* x, int M, int N,
+                                      int K, int flags, const marl_group_t* grp, size_t ws_bytes, int* plan) {
+  for (int i = 0; i < 8; ++i) plan[i] = 0;
+  plan[0] = -1;
+  if (M <= 0 || N <= 0 || K <= 0) return 0;      // marl_linear_wgrad launches nothing
+  if (ws_bytes < marl_linear_wgrad_workspace(M, N, K, grp ? grp->groups : 1)) return (int)hipErrorInvalidValue;
+  const WgradArgs a = wgrad_args(dY, lddy, Yact, ldya, x, M, N, K, grp, nullptr);
+  if (concat_width(a.x) != K) return (int)hipErrorInvalidValue;
+  WgradPlan p;
+  const int rc = plan_wgrad(a, (flags & 1) != 0, ws_bytes, p);
+  if (rc != 0) return rc;
+  plan[0] = p.family; plan[1] = p.i0; plan[2] = p.i1; plan[3] = p.passes; plan[4] = p.slabs; plan[5] = a.gvec; plan[6] = a.xvec;
+  plan[7] = p.c_rest;
+  return 0;
+}
+
+static void launch_wgrad_reduce(const float* ws, float* dW, long lddw, float* db, int N, int K, int slabs, int groups, long gs_dw,
+                                long gs_db, hipStream_t s) {
+  WredArgs r;
+  r.ws = ws; r.dW = dW; r.lddw = lddw; r.db = db; r.N = N; r.K = K; r.slabs = slabs; r.groups = groups; r.gs_dw = gs_dw; r.gs_db = gs_db;
+  const long total = (long)N * (K + 1) * groups;
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64 * RSG), 0, s, r);
+}
+
 extern "C" int marl_linear_wgrad(const float* G, long ldg, const float* Yact, long ldya, const marl_src_t* x,
                                  float* dW, long lddw, float* db, int M, int N, int K, int flags,
                                  const marl_group_t* grp, float* ws, size_t ws_bytes, void* stream) {
   if (M <= 0 || N <= 0 || K <= 0) return 0;
   const int groups = grp ? grp->groups : 1;
   if (ws_bytes < marl_linear_wgrad_workspace(M, N, K, groups)) return (int)hipErrorInvalidValue;
-  WgradArgs a;
-  a.G = G; a.ldg = ldg; a.Yact = Yact; a.ldya = ldya; a.x = to_src(x);
+  WgradArgs a = wgrad_args(G, ldg, Yact, ldya, x, M, N, K, grp, ws);
   if (concat_width(a.x) != K) return (int)hipErrorInvalidValue;
-  a.ws = ws; a.M = M; a.N = N; a.K = K; a.slabs = marl_wgrad_slabs(M);
-  a.nyb = (N + 63) / 64; a.groups = groups;
-  a.gs_g = grp ? grp->gs_y : 0; a.gs_ya = grp ? grp->gs_m0 : 0;
-  a.gs_x0 = grp ? grp->gs_x0 : 0; a.gs_x1 = grp ? grp->gs_x1 : 0;
-  a.gvec = (ldg % 4 == 0) && aligned16(G) && (a.gs_g % 4 == 0) &&
-           (!Yact || ((ldya % 4 == 0) && aligned16(Yact) && (a.gs_ya % 4 == 0)));
-  a.xvec = a.x.p0 && !a.x.m0 && (a.x.ld0 % 4 == 0) && aligned16(a.x.p0) && (a.gs_x0 % 4 == 0);
   hipStream_t s = (hipStream_t)stream;
   const bool bf = (flags & 1) != 0;           // bf16 operands, fp32 accumulate (mixer GEMMs, opt-in)
-  if (!bf) {                                  // 64-output layers over many rows (fc1 of the agent): LDS-staged tall kernel
-    const int slabs0 = a.slabs;
-    const int rc = try_wgrad_tall(a, ws_bytes, s);
-    if (rc > 0) return rc;
-    if (rc == 0) {
+  WgradPlan p;
+  const int prc = plan_wgrad(a, bf, ws_bytes, p);
+  if (prc != 0) return prc;
+  if (p.family == WG_TALL) {
+    const int rc = launch_wgrad_tall(a, p.tall, s);
+    if (rc != 0) return rc;
+    MARL_CHECK_LAUNCH();
+    launch_wgrad_reduce(ws, dW, lddw, db, N, K, a.slabs, 1, 0, 0, s);
+    MARL_CHECK_LAUNCH();
+    return 0;
+  }
+  if (p.family == WG_PASSES) {
+    // each pass a direct launch over its own sub-source with its own slabs; only the first carries the bias gradient
+    size_t ws_off = 0;
+    int c0 = 0;
+    for (int pass = 0; c0 < K; ++pass) {
+      WgradArgs b = wgrad_pass_args(a, c0, p.c_rest);
+      const int kw = b.K;
+      b.ws = ws + ws_off;
+      if (try_wgrad_direct(b, s) != 0) return (int)hipErrorInvalidValue;
       MARL_CHECK_LAUNCH();
-      WredArgs r;
-      r.ws = ws; r.dW = dW; r.lddw = lddw; r.db = db; r.N = N; r.K = K; r.slabs = a.slabs; r.groups = 1; r.gs_dw = 0; r.gs_db = 0;
-      const long total = (long)N * (K + 1);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64 * RSG), 0, s, r);
+      launch_wgrad_reduce(b.ws, dW + c0, lddw, pass == 0 ? db : nullptr, N, kw, a.slabs, 1, 0, 0, s);
       MARL_CHECK_LAUNCH();
-      return 0;
+      ws_off += (size_t)a.slabs * N * (kw + 1);
+      c0 += kw;
     }
-    a.slabs = slabs0;
+    return 0;
   }
-  // Wide inputs of a 64-output layer (fc1 of the agent on 3s5z / MMM2: 150 / 204 columns - more accumulator tiles than
-  // one pass of the direct kernel holds): column passes [0,64), [64,128) as permuted blocks and the rest as plain
-  // tiles, each a direct launch over its own sub-source with its own slabs; G is re-read per pass (3 x 315 MB at
-  // MMM2 / 1024 envs) but nothing is staged through LDS (the LDS-staged kernel took 1.35 ms there).
-  if (!bf && a.N == 64 && groups == 1 && !Yact && a.gvec && a.xvec && a.M >= 4096 && !a.x.k1 && !a.x.m0 && a.x.k0 >= 64 &&
-      K - 64 > 64) {
-    const int c_rest = a.x.k0 >= 128 ? 128 : 64;
-    if ((K - c_rest + 15) / 16 <= 5) {
-      size_t ws_off = 0;
-      int c0 = 0;
-      for (int pass = 0; c0 < K; ++pass) {
-        WgradArgs b = a;
-        const bool perm = c0 < c_rest;
-        const int kw = perm ? 64 : K - c0;
-        b.x.p0 = a.x.p0 + c0;
-        b.x.k0 = perm ? 64 : a.x.k0 - c0;
-        if (perm) { b.x.idx = nullptr; b.x.nhot = 0; b.x.hot_w = 0; b.x.nid = 0; }
-        b.K = kw;
-        b.ws = ws + ws_off;
-        if (try_wgrad_direct(b, s) != 0) return (int)hipErrorInvalidValue;
-        MARL_CHECK_LAUNCH();
-        WredArgs r;
-        r.ws = b.ws; r.dW = dW + c0; r.lddw = lddw; r.db = pass == 0 ? db : nullptr; r.N = N; r.K = kw; r.slabs = a.slabs;
-        r.groups = 1; r.gs_dw = 0; r.gs_db = 0;
-        const long total = (long)N * (kw + 1);
-        hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64 * RSG), 0, s, r);
-        MARL_CHECK_LAUNCH();
-        ws_off += (size_t)a.slabs * N * (kw + 1);
-        c0 += kw;
-      }
-      return 0;
-    }
-  }
-  int done = try_wgrad_thin(a, s);            // fp32 either way: one output column is not matrix work
-  if (done != 0) done = bf ? -1 : try_wgrad_direct(a, s);
-  bool one_base = a.x.p0 && !a.x.m0 && !a.x.nid && a.x.k0 < 16384 && a.x.k1 < 16384 && a.x.nhot < 16384 && a.x.hot_w < 0xfff0;
-  for (int c4 = 0; one_base && c4 < K; c4 += 4) {       // segment of the first and the last real column of each item
-    auto seg = [&](int k) { return k < a.x.k0 ? 0 : (k - a.x.k0 < a.x.k1 ? 1 : 2); };
-    const int kl = c4 + 3 < K ? c4 + 3 : K - 1;
-    if (seg(c4) != seg(kl)) one_base = false;
-  }
-  if (done != 0 && !bf && groups == 1 && N <= WF && K + 1 <= WF && a.gvec && ldg >= (N + 3) / 4 * 4 &&
-      (!Yact || ldya >= (N + 3) / 4 * 4) && M >= 2048 && one_base) {
-    // narrow layer: one pass over G and X
+  a.slabs = p.slabs;
+  if (p.family == WG_THIN) {
+    hipLaunchKernelGGL(wgrad_thin_kernel, dim3(a.slabs), dim3(256), 0, s, a);
+  } else if (p.family == WG_DIRECT) {
+    if (try_wgrad_direct(a, s) != 0) return (int)hipErrorInvalidValue;
+  } else if (p.family == WG_FULL) {
     const size_t lds = (size_t)2 * WCH * WFS * sizeof(float) + (size_t)2 * WCH * 4 * sizeof(long) + (size_t)5 * 256 * 16;
-    const long chunks = ((long)M + WCH - 1) / WCH;
-    a.slabs = (int)(2L * a.slabs < chunks ? 2L * a.slabs : (chunks < 1 ? 1 : chunks));
     const void* fn = Yact ? (const void*)wgrad_full_kernel<true> : (const void*)wgrad_full_kernel<false>;
     hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      // 67.5 KB > the 64 KB default
     if (e != hipSuccess) return (int)e;
     if (Yact) hipLaunchKernelGGL(wgrad_full_kernel<true>, dim3(a.slabs), dim3(256), lds, s, a);
     else hipLaunchKernelGGL(wgrad_full_kernel<false>, dim3(a.slabs), dim3(256), lds, s, a);
-    done = 0;
-  }
-  if (done != 0) {
+  } else {
     dim3 grid(a.slabs, a.nyb * groups, (K + 1 + 63) / 64), block(256);
     if (bf) hipLaunchKernelGGL(wgrad_kernel<true>, grid, block, 0, s, a);
     else hipLaunchKernelGGL(wgrad_kernel<false>, grid, block, 0, s, a);
   }
   MARL_CHECK_LAUNCH();
-  WredArgs r;
-  r.ws = ws; r.dW = dW; r.lddw = lddw; r.db = db; r.N = N; r.K = K; r.slabs = a.slabs; r.groups = groups;
-  r.gs_dw = grp ? grp->gs_w : 0; r.gs_db = grp ? grp->gs_b : 0;
-  long total = (long)N * (K + 1) * groups;
-  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)((total + 63) / 64)), dim3(64 * RSG), 0, s, r);
+  launch_wgrad_reduce(ws, dW, lddw, db, N, K, a.slabs, groups, grp ? grp->gs_w : 0, grp ? grp->gs_b : 0, s);
   MARL_CHECK_LAUNCH();
   return 0;
 }

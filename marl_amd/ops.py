@@ -5,6 +5,7 @@ below is a hand-written HIP kernel from marl_amd/csrc.
 """
 from __future__ import annotations
 
+import collections
 import ctypes as C
 
 import torch
@@ -151,6 +152,49 @@ def linear_wgrad(dY, x, dW, db, M, N, K, Yact=None, grp=None, lddw=None, bf16=Fa
                                 C.byref(x), _p(_f32(dW)), lddw, _p(db), M, N, K, flags,
                                 C.byref(grp) if grp is not None else None, _p(ws), ws.numel() * 4, _stream()),
           "marl_linear_wgrad")
+
+
+LINEAR_PATHS = ("element", "vector", "dword")                                     # plan[0] of marl_linear_plan (include/marl_hip.h)
+WGRAD_FAMILIES = ("generic", "full", "direct", "passes", "tall", "thin")          # plan[0] of marl_linear_wgrad_plan
+LinearPlan = collections.namedtuple("LinearPlan", "path tiles gate kmajor bf16 wvec grid")
+WgradPlan = collections.namedtuple("WgradPlan", "family inst passes slabs gvec xvec c_rest")
+
+
+def _pv(t):
+    """a pointer argument of a plan query: a tensor, an integer standing for a pointer (only its alignment is read) or None"""
+    if t is None:
+        return None
+    return C.c_void_p(int(t) if isinstance(t, int) else t.data_ptr())
+
+
+def linear_plan(x, W, ldw, ldy, M, N, K, act=0, w_kmajor=False, grp=None, bf16=False, bias=None):
+    """The launch plan of linear() for these arguments, from the host function the launch itself decides with - no GPU:
+    LinearPlan(path in LINEAR_PATHS, column tiles, gate, kmajor, bf16, wvec, grid), or None where marl_linear refuses the call.
+    x: a MarlSrc; W / bias: tensors or integers standing for pointers."""
+    plan = (C.c_int * 9)()
+    if _lib.load().marl_linear_plan(C.byref(x), _pv(W), ldw, 1 if w_kmajor else 0, _pv(bias), ldy, M, N, K, act | (0x100 if bf16 else 0),
+                                    C.byref(grp) if grp is not None else None, plan) != 0:
+        return None
+    p = tuple(plan)
+    return LinearPlan(LINEAR_PATHS[p[0]], p[1], bool(p[2]), bool(p[3]), bool(p[4]), bool(p[5]), p[6:9])
+
+
+def linear_wgrad_plan(dY, lddy, x, M, N, K, Yact=None, ldya=0, grp=None, bf16=False, ws_bytes=None):
+    """The launch plan of linear_wgrad(): WgradPlan(family in WGRAD_FAMILIES, (instantiation), passes, slabs per pass, gvec, xvec,
+    c_rest), or None where marl_linear_wgrad refuses the call.  ws_bytes None: what linear_wgrad() would pass now - the shared
+    grow-only buffer, grown to this call's need."""
+    lib = _lib.load()
+    if ws_bytes is None:
+        ws_bytes = lib.marl_linear_wgrad_workspace(M, N, K, grp.groups if grp is not None else 1)
+        have = WS.bufs.get("wgrad")
+        if have is not None:
+            ws_bytes = max((ws_bytes + 3) // 4 * 4, have.numel() * 4)
+    plan = (C.c_int * 8)()
+    if lib.marl_linear_wgrad_plan(_pv(dY), lddy, _pv(Yact), ldya, C.byref(x), M, N, K, 1 if bf16 else 0,
+                                  C.byref(grp) if grp is not None else None, ws_bytes, plan) != 0:
+        return None
+    p = tuple(plan)
+    return WgradPlan(WGRAD_FAMILIES[p[0]], (p[1], p[2]), p[3], p[4], bool(p[5]), bool(p[6]), p[7])
 
 
 def agent_weights(params):

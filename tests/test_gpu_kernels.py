@@ -76,8 +76,9 @@ def test_linear_bf16_operands(dev, M, N, K):
 
 def test_linear_and_wgrad_random_shapes(dev):
     """Seeded sweep over odd sizes and virtual-concat compositions (aligned / unaligned dense segment 0, second
-    dense segment, one-hot blocks, agent id, relu gate, k-major weights): every dispatch branch of the GEMM kernels
-    (16-byte / dword / element operand paths, partial tiles) against torch."""
+    dense segment, one-hot blocks, agent id, relu gate, k-major weights): the 16-byte / dword / element operand paths and partial
+    tiles of the forward kernel against torch.  Every weight gradient here runs the generic 64 x 64-block kernel (M < 2048; asserted
+    with the library's plan query) - the other weight-gradient kernels are held to float64 in tests/test_gpu_dense.py."""
     from marl_amd import ops
     rng = np.random.RandomState(1234)
     g = torch.Generator().manual_seed(99)
@@ -122,7 +123,11 @@ def test_linear_and_wgrad_random_shapes(dev):
         gate = torch.randn(M, N, generator=g) if rng.rand() < 0.5 else None
         Gm = dY * (gate > 0) if gate is not None else dY
         dW, db = torch.zeros(N, K, device=dev), torch.zeros(N, device=dev)
-        ops.linear_wgrad(cu(dY, dev), src, dW, db, M, N, K, Yact=cu(gate, dev) if gate is not None else None)
+        dYd, gd = cu(dY, dev), cu(gate, dev) if gate is not None else None
+        assert ops.linear_wgrad_plan(dYd, N, src, M, N, K, Yact=gd, ldya=N).family == "generic", "the plan moved"
+        assert ops.linear_plan(src, cu(W, dev), K, N, M, N, K, act=act).path == (
+            "element" if K0 < 16 else "vector" if (K0 + pad) % 4 == 0 and off == 0 else "dword"), "the plan moved"
+        ops.linear_wgrad(dYd, src, dW, db, M, N, K, Yact=gd)
         sc = max(1.0, M ** 0.5)
         close(dW / sc, (Gm.t() @ X) / sc, 3e-4, 3e-4, msg="wgrad case %d" % case)
         close(db / sc, Gm.sum(0) / sc, 3e-4, 3e-4, msg="bgrad case %d" % case)
@@ -184,7 +189,8 @@ def test_linear_concat_and_groups(dev):
                                             (4097, 80, 79, 0, False), (2100, 33, 20, 5, True), (9000, 1, 64, 0, False)])
 def test_wgrad_full_width(dev, M, N, K0, HW, gate):
     """Narrow layers (N <= 80, K + 1 <= 80; QTRAN's 78-wide encoders, 64-wide heads) take the one-pass full-width
-    weight-gradient kernel when dY rows are 16-byte aligned (row stride padded to 4 floats): dW, db vs torch."""
+    weight-gradient kernel when dY rows are 16-byte aligned (row stride padded to 4 floats) - but for the one-output case, which the
+    thin one-column kernel takes first; the plan query says which ran: dW, db vs torch."""
     from marl_amd import ops
     g = torch.Generator().manual_seed(M + N + K0)
     K = K0 + HW
@@ -202,6 +208,8 @@ def test_wgrad_full_width(dev, M, N, K0, HW, gate):
     pad = lambda t: cu(torch.cat([t, torch.zeros(t.shape[0], ld(t.shape[1]) - t.shape[1])], 1), dev)[:, :t.shape[1]]
     xs = ops.src(pad(X0), idx=cu(idx, dev, torch.int32) if HW else None, nhot=1 if HW else 0, hot_w=HW)
     dW, db = torch.full((N, K), 0.5, device=dev), torch.full((N,), 0.25, device=dev)
+    plan = ops.linear_wgrad_plan(pad(dY), ld(N), xs, M, N, K, Yact=pad(Ya) if gate else None, ldya=ld(N) if gate else 0)
+    assert (plan.family, plan.inst) == (("thin", (0, 0)) if N == 1 else ("full", (int(gate), 0))), "the plan moved"
     ops.linear_wgrad(pad(dY), xs, dW, db, M, N, K, Yact=pad(Ya) if gate else None)
     Gm = dY * (Ya > 0) if gate else dY
     close(dW - 0.5, Gm.t() @ Xfull, 2e-3, 1e-3)
@@ -218,6 +226,7 @@ def test_wgrad_one_output_column(dev, M, K):
     ld = (K + 3) // 4 * 4
     Xd = cu(torch.cat([X, torch.full((M, ld - K), float("nan"))], 1), dev)[:, :K] if ld != K else cu(X, dev)
     dW, db = torch.full((1, K), 0.5, device=dev), torch.full((1,), 0.25, device=dev)
+    assert ops.linear_wgrad_plan(cu(dY, dev), 1, ops.src(Xd), M, 1, K).family == "thin", "the plan moved"
     for rep in range(2):
         ops.linear_wgrad(cu(dY, dev), ops.src(Xd), dW, db, M, 1, K)
     ref = (dY.double().t() @ X.double()).float()
@@ -452,8 +461,10 @@ def test_mlp3_x6_split(dev, rows, S, NH, HW, N3, G, remap):
 
 @pytest.mark.parametrize("B,O", [(6, 24), (30, 24), (20, 80), (17, 116), (21, 64), (19, 52), (18, 128), (17, 176), (17, 148)])
 def test_wgrad_large_rows_and_remap(dev, B, O):
-    """B >= 17 (M >= 4096 rows, 64 outputs) takes the direct no-LDS kernel (O >= 128: in column passes), B = 6 the
-    LDS-staged one."""
+    """B >= 17 (M >= 4096 rows, 64 outputs, K = O + 12 <= 224 columns) takes the LDS-staged tall kernel - <6, 3> up to 96 columns,
+    <10, 5> up to 160, <14, 6> beyond - and B = 6 (1500 rows) the generic 64 x 64-block kernel; asserted with the library's plan
+    query.  (The direct kernel and its column passes, which these shapes ran before the tall kernel covered them and still run
+    with the wgrad_tall switch off, are held to float64 in tests/test_gpu_dense.py.)"""
     from marl_amd import ops
     g = torch.Generator().manual_seed(9 + B + O)
     T, N = 50, 5                         # (T+1)-slot storage read through the row remap
@@ -475,6 +486,9 @@ def test_wgrad_large_rows_and_remap(dev, B, O):
         s = ops.src(cu(store.reshape(-1, O), dev), idx=cu(u.reshape(-1, 1), dev, torch.int32), nhot=1, hot_w=7, nid=N,
                     remap0=(T * N, (T + 1) * N, t0 * N), remapi=(T * N, T * N, uoff * N))
         dW, db = torch.zeros(64, K, device=dev), torch.zeros(64, device=dev)
+        plan = ops.linear_wgrad_plan(cu(dY, dev), 64, s, B * T * N, 64, K)
+        want = ("generic", (0, 0)) if B < 17 else ("tall", (6, 3) if K <= 96 else (10, 5) if K <= 160 else (14, 6))
+        assert (plan.family, plan.inst) == want, "the plan moved"
         ops.linear_wgrad(cu(dY, dev), s, dW, db, B * T * N, 64, K)
         close(dW, dY.t() @ Xfull, 2e-3, 1e-3)
         close(db, dY.sum(0), 2e-3, 1e-3)
@@ -496,6 +510,9 @@ def test_wgrad_split_state_and_encoder_columns(dev, M, S, E_):
     base_w, base_b = torch.randn(64, S + E_, generator=g), torch.randn(64, generator=g)
     gw, gb = cu(base_w, dev), cu(base_b, dev)
     ed = cu(torch.cat([e, torch.zeros(M, (-E_) % 4)], 1), dev)[:, :E_]       # rows padded to 16 bytes, as the kernels' scratch is
+    for xsrc, kk, inst in ((ops.src(cu(s, dev)), S, (10, 5) if S <= 160 else (14, 7) if S > 192 else (14, 6)), (ops.src(ed), E_, (6, 3))):
+        plan = ops.linear_wgrad_plan(cu(dY, dev), 64, xsrc, M, 64, kk)
+        assert (plan.family, plan.inst) == ("tall", inst), "the plan moved"
     ops.linear_wgrad(cu(dY, dev), ops.src(cu(s, dev)), gw[:, :S], gb, M, 64, S)
     ops.linear_wgrad(cu(dY, dev), ops.src(ed), gw[:, S:], None, M, 64, E_)
     ref = dY.double().t() @ torch.cat([s, e], 1).double()
