@@ -463,6 +463,27 @@ int marl_qtran_wgrad_rows(const marl_src_t* s, const float* s1, const float* e2,
                           const float* d_out, const float* dy1, const float* dy2, const float* de2, float* d_q0_w, long ld_q0,
                           float* d_q0_b, float* d_q2_w, float* d_q2_b, float* d_q4_w, float* d_q4_b, float* d_enc2_w, float* ws,
                           size_t ws_bytes, long BT, int S, int AE, void* stream);
+/* The launch plan of the entry points of qtran_fused.hip for these sizes, from the host functions the launches themselves decide
+ * with.  Host only: no GPU, no pointer is read (alignment refusals are the entry points' own).  Arguments a query does not use are
+ * ignored.  Returns 0 and fills plan[8], or the hipError_t the entry point returns for these sizes; BT <= 0 launches nothing:
+ * all-zero plan.
+ *   FWD / FWD2 / BWD (BT, N, A, AE): marl_qtran_head_fwd, _fwd2, _bwd
+ *     plan[0] FT feature tiles of the encoder (5 <-> qtran_*_kernel<5, ..>, 4)   plan[1] HOT: one-hot table   plan[2] DUAL: two action sets
+ *     plan[3] workgroups   plan[4] dynamic LDS bytes (BWD: of qtran_bwd_rows_kernel; plan[7]: of qtran_bwd_agents_kernel)
+ *     plan[5] rounds: 16-row tiles the busiest wave walks   plan[6] BWD: slabs qtran_reduce_kernel sums
+ *   STATE_PARTS (BT, S, nsets) / QMIX_TAIL (BT, S):
+ *     plan[0] KCT: 16-column chunks of the instantiation   plan[1] nsets   plan[3] workgroups   plan[4] LDS bytes
+ *     plan[5] rounds: 64-row blocks the busiest workgroup walks
+ *   WGRAD_ROWS (BT, S, AE):
+ *     plan[0] FT   plan[1] SMAX (224 / 384)   plan[2] 16x16 product tiles   plan[3] workgroups   plan[4] LDS bytes
+ *     plan[5] rounds: 32-row blocks the busiest workgroup walks   plan[6] slabs qtran_wgrad_reduce_kernel sums */
+#define MARL_QTRAN_PLAN_FWD 0
+#define MARL_QTRAN_PLAN_FWD2 1
+#define MARL_QTRAN_PLAN_BWD 2
+#define MARL_QTRAN_PLAN_STATE_PARTS 3
+#define MARL_QTRAN_PLAN_QMIX_TAIL 4
+#define MARL_QTRAN_PLAN_WGRAD_ROWS 5
+int marl_qtran_plan(int what, long BT, int N, int A, int AE, int S, int nsets, int* plan);
 
 /* QPLEX (DMAQer.forward + calc_v/calc_adv, mixer.py:211-288; DMAQ_SI_Weight tail :158-169).
  *  wv row = [w_raw (N) | v (N)] (outputs of hyper_w_final.2 / V.2);

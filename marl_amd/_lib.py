@@ -187,6 +187,7 @@ SIGNATURES = {
     "marl_qtran_wgrad_rows_workspace": (SZ, [I, I]),
     "marl_qtran_wgrad_rows": (I, [SRC] + [P] * 8 + [P, L, P, P, P, P, P, P, P, SZ, L, I, I, P]),
     "marl_qtran_head_bwd": (I, [QT, P, P, P, P, P, P, P, P, P, I, P, P, P, P, SZ, L, I, I, I, P]),
+    "marl_qtran_plan": (I, [I, L, I, I, I, I, I, P]),
     "marl_qplex_mix_fwd": (I, [P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, P]),
     "marl_qplex_mix_bwd": (I, [P, P, P, P, P, P, P, P, P, P, P, P, P, L, I, I, I, I, P]),
     "marl_first_terminated_len": (I, [P, L, I, I, P, P]),

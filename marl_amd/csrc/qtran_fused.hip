@@ -920,6 +920,54 @@ inline unsigned grid_for(long BT) {
 }
 // A = 0: no one-hot block (QtranV, AE = 64 -> 4 feature tiles); 1 <= A <= 16: joint-Q (AE = 64 + A -> 5 feature tiles)
 inline bool supported(int N, int A, int AE) { return N >= 1 && A >= 0 && A <= 16 && AE == HD + A; }
+
+// ---- launch plans: the one place each entry point decides its kernel, grid and LDS (marl_qtran_plan reports them)
+// heads: FT feature tiles, one-hot table or not, one or two action sets; every wave walks ceil(tiles / (NW grid)) row tiles at most.
+// The backward pair (rows kernel, agents kernel) shares the grid, which is also the slab count qtran_reduce_kernel sums.
+struct HeadPlan { int FT, hot, dual; unsigned grid; size_t lds, lds_agents; int rounds, slabs; };
+inline HeadPlan plan_head(int what, long BT, int A) {
+  HeadPlan p = {};
+  p.hot = A > 0; p.FT = p.hot ? 5 : 4; p.dual = what == MARL_QTRAN_PLAN_FWD2;
+  p.grid = grid_for(BT);
+  const long tiles = (BT + 15) / 16, step = (long)NW * p.grid;
+  p.rounds = (int)((tiles + step - 1) / step);
+  if (what == MARL_QTRAN_PLAN_BWD) { p.lds = rows_lds(p.FT); p.lds_agents = agents_lds(p.FT, p.hot); p.slabs = (int)p.grid; }
+  else p.lds = fwd_lds(p.FT, p.hot);
+  return p;
+}
+// state parts / QMIX tail: chunk bucket KCT (16-column chunks of s kept in registers), 64-row blocks in equal shares
+struct SpPlan { int KCT, nsets; unsigned grid; size_t lds; int rounds; };
+inline SpPlan plan_sp(long BT, int S, int nsets) {
+  SpPlan p = {};
+  const int kc = (S + 15) / 16;
+  const long nblk = (BT + 64 - 1) / 64;
+  static const int buckets[] = {4, 8, 12, 14, 16, 20, 24};
+  p.KCT = 24;
+  for (int b : buckets) if (kc <= b) { p.KCT = b; break; }
+  p.nsets = nsets;
+  p.lds = (size_t)64 * (16 * p.KCT + 4) * sizeof(float);
+  const long cap = 256;                                   // workgroups resident on the chip
+  // equal shares: every workgroup walks ceil(nblk / cap) blocks (a grid of cap would leave a partial last round)
+  const long rounds = (nblk + cap - 1) / cap;
+  p.grid = (unsigned)((nblk + rounds - 1) / rounds);
+  p.rounds = (int)((nblk + p.grid - 1) / p.grid);
+  return p;
+}
+// row-level weight gradients: FT x SMAX instantiation, 32-row blocks over at most 256 workgroups = slabs of the reduce
+inline int wg_ts(int S) { return (S + 15) / 16; }
+inline int wg_zw(int FT, int smax) { return 3 * 16 * FT + 4 * 64 + 4 + smax; }
+struct WgPlan { int FT, SMAX, TS, ntiles; unsigned grid; size_t lds; int rounds, slabs; };
+inline WgPlan plan_wg(long BT, int S, int AE) {
+  WgPlan p = {};
+  p.FT = ft_of(AE); p.SMAX = S > 224 ? 384 : 224; p.TS = wg_ts(S);
+  p.ntiles = 4 * p.TS + 4 * p.FT + 16 + p.FT * p.FT;
+  const long nblk = (BT + 32 - 1) / 32;
+  p.grid = (unsigned)(nblk < 256 ? nblk : 256);
+  p.lds = (size_t)32 * wg_zw(p.FT, p.SMAX) * sizeof(float);
+  p.rounds = (int)((nblk + p.grid - 1) / p.grid);
+  p.slabs = (int)p.grid;
+  return p;
+}
 inline void fill_w(QtArgs& a, const marl_qtran_weights_t* w) {
   a.We1 = w->enc0_w; a.be1 = w->enc0_b; a.We2 = w->enc2_w; a.be2 = w->enc2_b;
   a.Wq1 = w->q0_w; a.ldq1 = w->q0_ld; a.S = w->q0_s;
@@ -954,9 +1002,9 @@ extern "C" int marl_qtran_head_fwd(const marl_qtran_weights_t* w, const float* h
   a.hidden = hidden; a.u = u; a.sp = sp; a.out = out; a.s1 = s1; a.e2 = e2; a.y1 = y1; a.y2 = y2;
   a.BT = BT; a.N = N; a.A = A; a.AE = AE;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = grid_for(BT);
-  if (A > 0) return launch(qtran_fwd_kernel<5, true>, a, grid, fwd_lds(5, true), s);
-  return launch(qtran_fwd_kernel<4, false>, a, grid, fwd_lds(4, false), s);
+  const HeadPlan p = plan_head(MARL_QTRAN_PLAN_FWD, BT, A);
+  if (p.hot) return launch(qtran_fwd_kernel<5, true>, a, p.grid, p.lds, s);
+  return launch(qtran_fwd_kernel<4, false>, a, p.grid, p.lds, s);
 }
 
 extern "C" int marl_qtran_head_fwd2(const marl_qtran_weights_t* w, const float* hidden, const int* u, const int* u2, const float* sp,
@@ -971,22 +1019,19 @@ extern "C" int marl_qtran_head_fwd2(const marl_qtran_weights_t* w, const float* 
   fill_w(a, w);
   a.hidden = hidden; a.u = u; a.u2 = u2; a.sp = sp; a.out = out; a.out2 = out2; a.s1 = s1; a.e2 = e2; a.y1 = y1; a.y2 = y2;
   a.BT = BT; a.N = N; a.A = A; a.AE = AE;
-  return launch(qtran_fwd_kernel<5, true, true>, a, grid_for(BT), fwd_lds(5, true), (hipStream_t)stream);
+  const HeadPlan p = plan_head(MARL_QTRAN_PLAN_FWD2, BT, A);
+  return launch(qtran_fwd_kernel<5, true, true>, a, p.grid, p.lds, (hipStream_t)stream);
 }
 
 namespace {
 // launch of the row GEMM [BT, S] x [S, 64 per set] -> 16-feature tiles written where the descriptors say
 int sp_launch(SpArgs& a, int nsets, hipStream_t stream) {
+  static_assert(SPR == 64, "plan_sp counts 64-row blocks");
   a.kc = (a.S + 15) / 16;
-  const long nblk = (a.BT + SPR - 1) / SPR;
-  static const int buckets[] = {4, 8, 12, 14, 16, 20, 24};
-  int KCT = 24;
-  for (int b : buckets) if (a.kc <= b) { KCT = b; break; }
-  const size_t lds = (size_t)SPR * (16 * KCT + 4) * sizeof(float);
-  const long cap = 256;                                   // workgroups resident on the chip
-  // equal shares: every workgroup walks ceil(nblk / cap) blocks (a grid of cap would leave a partial last round)
-  const long rounds = (nblk + cap - 1) / cap;
-  const unsigned grid = (unsigned)((nblk + rounds - 1) / rounds);
+  const SpPlan p = plan_sp(a.BT, a.S, nsets);
+  const int KCT = p.KCT;
+  const size_t lds = p.lds;
+  const unsigned grid = p.grid;
   const void* fn = nullptr;
 #define SP_CASE(K) case K: fn = nsets == 2 ? (const void*)qtran_state_parts_kernel<K, 2> : (const void*)qtran_state_parts_kernel<K, 1>; break;
   switch (KCT) { SP_CASE(4) SP_CASE(8) SP_CASE(12) SP_CASE(14) SP_CASE(16) SP_CASE(20) SP_CASE(24) }
@@ -1039,11 +1084,6 @@ extern "C" int marl_qmix_tail_fwd(const marl_src_t* s, long rows, int S, const f
   return sp_launch(a, 1, (hipStream_t)stream);
 }
 
-namespace {
-inline int wg_ts(int S) { return (S + 15) / 16; }
-inline int wg_zw(int FT, int smax) { return 3 * 16 * FT + 4 * 64 + 4 + smax; }
-}  // namespace
-
 extern "C" int marl_qtran_wgrad_rows_supported(int S, int AE) {
   const int FT = ft_of(AE);
   return (S >= 4 && S % 4 == 0 && S <= 384 && (FT == 4 || FT == 5)) ? 1 : 0;
@@ -1064,12 +1104,13 @@ extern "C" int marl_qtran_wgrad_rows(const marl_src_t* s, const float* s1, const
   const int FT = ft_of(AE), AEP = 16 * FT;
   WgArgs a = {};
   a.s = state_src(s); a.e2 = e2; a.y1 = y1; a.s1 = s1; a.dy1 = dy1; a.dy2 = dy2; a.de2 = de2; a.y2 = y2; a.d_out = d_out;
-  a.slab = ws; a.BT = BT; a.S = S; a.AE = AE; a.TS = wg_ts(S);
-  a.ntiles = 4 * a.TS + 4 * FT + 16 + FT * FT;
-  const long nblk = (BT + WR - 1) / WR;
-  const unsigned grid = (unsigned)(nblk < 256 ? nblk : 256);
-  const bool big = S > 224;
-  const size_t lds = (size_t)WR * wg_zw(FT, big ? 384 : 224) * sizeof(float);
+  static_assert(WR == 32, "plan_wg counts 32-row blocks");
+  const WgPlan p = plan_wg(BT, S, AE);
+  a.slab = ws; a.BT = BT; a.S = S; a.AE = AE; a.TS = p.TS;
+  a.ntiles = p.ntiles;
+  const unsigned grid = p.grid;
+  const bool big = p.SMAX == 384;
+  const size_t lds = p.lds;
   const void* fn = FT == 5 ? (big ? (const void*)qtran_wgrad_rows_kernel<5, 384> : (const void*)qtran_wgrad_rows_kernel<5, 224>)
                            : (big ? (const void*)qtran_wgrad_rows_kernel<4, 384> : (const void*)qtran_wgrad_rows_kernel<4, 224>);
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -1080,7 +1121,7 @@ extern "C" int marl_qtran_wgrad_rows(const marl_src_t* s, const float* s1, const
   MARL_CHECK_LAUNCH();
   WgRedArgs r = {};
   r.slab = ws; r.dWq1 = d_q0_w; r.ldq1 = ld_q0; r.dbq1 = d_q0_b; r.dWq2 = d_q2_w; r.dbq2 = d_q2_b; r.dwq3 = d_q4_w; r.dbq3 = d_q4_b;
-  r.dWe2 = d_enc2_w; r.nwg = (int)grid; r.S = S; r.AE = AE; r.AEP = AEP; r.TS = a.TS;
+  r.dWe2 = d_enc2_w; r.nwg = p.slabs; r.S = S; r.AE = AE; r.AEP = AEP; r.TS = a.TS;
   const int total = wg_slab_elems(a.TS, AEP);
   hipLaunchKernelGGL(qtran_wgrad_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, (hipStream_t)stream, r);
   MARL_CHECK_LAUNCH();
@@ -1109,17 +1150,50 @@ extern "C" int marl_qtran_head_bwd(const marl_qtran_weights_t* w, const float* h
   a.ds1 = ws; a.slab1 = ws + (size_t)BT * AEP; a.slab2 = a.slab1 + (size_t)256 * AEP;
   a.BT = BT; a.N = N; a.A = A; a.AE = AE;
   hipStream_t s = (hipStream_t)stream;
-  const unsigned grid = grid_for(BT);
-  int rc = FT == 5 ? launch(qtran_bwd_rows_kernel<5>, a, grid, rows_lds(5), s) : launch(qtran_bwd_rows_kernel<4>, a, grid, rows_lds(4), s);
+  const HeadPlan p = plan_head(MARL_QTRAN_PLAN_BWD, BT, A);
+  int rc = p.FT == 5 ? launch(qtran_bwd_rows_kernel<5>, a, p.grid, p.lds, s) : launch(qtran_bwd_rows_kernel<4>, a, p.grid, p.lds, s);
   if (rc) return rc;
-  if (A > 0) rc = launch(qtran_bwd_agents_kernel<5, true>, a, grid, agents_lds(5, true), s);
-  else rc = launch(qtran_bwd_agents_kernel<4, false>, a, grid, agents_lds(4, false), s);
+  if (p.hot) rc = launch(qtran_bwd_agents_kernel<5, true>, a, p.grid, p.lds_agents, s);
+  else rc = launch(qtran_bwd_agents_kernel<4, false>, a, p.grid, p.lds_agents, s);
   if (rc) return rc;
   QtRedArgs r;
   r.slab1 = a.slab1; r.slab2 = a.slab2; r.dWe1 = d_enc0_w; r.dbe1 = d_enc0_b; r.dbe2 = d_enc2_b;
-  r.nwg = (int)grid; r.AE = AE; r.AEP = AEP; r.A = A; r.N = N;
+  r.nwg = p.slabs; r.AE = AE; r.AEP = AEP; r.A = A; r.N = N;
   const int total = AEP * KW + AEP;
   hipLaunchKernelGGL(qtran_reduce_kernel, dim3((total + 63) / 64), dim3(256), 0, s, r);
   MARL_CHECK_LAUNCH();
   return 0;
+}
+
+// The launch plan of the entry points above for these sizes, from the functions the launches decide with.  Host only.
+extern "C" int marl_qtran_plan(int what, long BT, int N, int A, int AE, int S, int nsets, int* plan) {
+  if (!plan) return (int)hipErrorInvalidValue;
+  for (int i = 0; i < 8; ++i) plan[i] = 0;
+  switch (what) {
+    case MARL_QTRAN_PLAN_FWD: case MARL_QTRAN_PLAN_FWD2: case MARL_QTRAN_PLAN_BWD: {
+      if (!supported(N, A, AE) || (what == MARL_QTRAN_PLAN_FWD2 && A <= 0)) return (int)hipErrorInvalidValue;
+      if (BT <= 0) return 0;
+      const HeadPlan p = plan_head(what, BT, A);
+      plan[0] = p.FT; plan[1] = p.hot; plan[2] = p.dual; plan[3] = (int)p.grid; plan[4] = (int)p.lds; plan[5] = p.rounds;
+      plan[6] = p.slabs; plan[7] = (int)p.lds_agents;
+      return 0;
+    }
+    case MARL_QTRAN_PLAN_STATE_PARTS: case MARL_QTRAN_PLAN_QMIX_TAIL: {
+      if (what == MARL_QTRAN_PLAN_QMIX_TAIL) nsets = 1;
+      if (!marl_qtran_state_parts_supported(S) || nsets < 1 || nsets > 2) return (int)hipErrorInvalidValue;
+      if (BT <= 0) return 0;
+      const SpPlan p = plan_sp(BT, S, nsets);
+      plan[0] = p.KCT; plan[1] = p.nsets; plan[3] = (int)p.grid; plan[4] = (int)p.lds; plan[5] = p.rounds;
+      return 0;
+    }
+    case MARL_QTRAN_PLAN_WGRAD_ROWS: {
+      if (!marl_qtran_wgrad_rows_supported(S, AE)) return (int)hipErrorInvalidValue;
+      if (BT <= 0) return 0;
+      const WgPlan p = plan_wg(BT, S, AE);
+      plan[0] = p.FT; plan[1] = p.SMAX; plan[2] = p.ntiles; plan[3] = (int)p.grid; plan[4] = (int)p.lds; plan[5] = p.rounds;
+      plan[6] = p.slabs;
+      return 0;
+    }
+  }
+  return (int)hipErrorInvalidValue;
 }

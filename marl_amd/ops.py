@@ -993,6 +993,30 @@ def qtran_wgrad_rows(s, s1, e2, y1, y2, d_out, dy1, dy2, de2, d_q0_w, d_q0_b, d_
                                     _p(ws), ws.numel() * 4, BT, S, AE, _stream()), "marl_qtran_wgrad_rows")
 
 
+QTRAN_PLANS = ("fwd", "fwd2", "bwd", "state_parts", "qmix_tail", "wgrad_rows")          # `what` of marl_qtran_plan (include/marl_hip.h)
+QtranHeadPlan = collections.namedtuple("QtranHeadPlan", "FT hot dual grid lds rounds slabs lds_agents")
+QtranStatePlan = collections.namedtuple("QtranStatePlan", "KCT nsets grid lds rounds")
+QtranWgradPlan = collections.namedtuple("QtranWgradPlan", "FT SMAX ntiles grid lds rounds slabs")
+
+
+def qtran_plan(what, BT, N=1, A=0, AE=64, S=4, nsets=1):
+    """The launch plan of a qtran_fused.hip entry point (`what` in QTRAN_PLANS) for these sizes, from the host functions the launches
+    themselves decide with - no GPU.  None where the entry point refuses the sizes.
+      fwd / fwd2 / bwd (BT, N, A, AE)            QtranHeadPlan(FT, hot, dual, grid, lds, rounds, slabs, lds_agents)
+      state_parts (BT, S, nsets) / qmix_tail    QtranStatePlan(KCT, nsets, grid, lds, rounds)
+      wgrad_rows (BT, S, AE)                     QtranWgradPlan(FT, SMAX, ntiles, grid, lds, rounds, slabs)"""
+    k = QTRAN_PLANS.index(what)
+    plan = (C.c_int * 8)()
+    if _lib.load().marl_qtran_plan(k, BT, N, A, AE, S, nsets, plan) != 0:
+        return None
+    p = tuple(plan)
+    if k <= 2:
+        return QtranHeadPlan(p[0], bool(p[1]), bool(p[2]), p[3], p[4], p[5], p[6], p[7])
+    if k <= 4:
+        return QtranStatePlan(p[0], p[1], p[3], p[4], p[5])
+    return QtranWgradPlan(p[0], p[1], p[2], p[3], p[4], p[5], p[6])
+
+
 def qtran_head_fwd2(w, hidden, u, u2, sp, out, out2, s1, e2, y1, y2, BT, N, A, AE):
     check(_lib.load().marl_qtran_head_fwd2(C.byref(w), _p(_f32(hidden)), _p(_i32(u)), _p(_i32(u2)), _p(_f32(sp)), _p(_f32(out)),
                                            _p(_f32(out2)), _p(s1), _p(e2), _p(y1), _p(y2), BT, N, A, AE, _stream()),

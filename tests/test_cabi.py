@@ -186,3 +186,46 @@ def test_qtran_row_kernel_predicates_and_workspace():
     for S, AE in ((216, 78), (120, 64), (384, 80)):
         aep, ts = (AE + 15) // 16 * 16, (S + 15) // 16
         assert ws(S, AE) == 256 * (64 * 16 * ts + 64 * aep + 64 * 64 + aep * aep + 256) * 4
+
+
+def test_qtran_plan_query():
+    """marl_qtran_plan (a host function, no GPU: the planners the launches of csrc/qtran_fused.hip themselves decide with) either
+    side of every step of the launch code: the head kernels' 256-workgroup cap (8 waves x 16 rows: a second round beyond 32 768
+    rows), the seven chunk buckets and the equal-share rounds of the state-part kernel (beyond 256 blocks of 64 rows), the four
+    instantiations and the 256-slab cap of the row-gradient kernel (beyond 8192 rows); and what the entry points refuse."""
+    from marl_amd import ops
+    q = ops.qtran_plan
+    fwd = lambda BT, A: q("fwd", BT, N=2, A=A, AE=64 + A)
+    lds5 = ((20 + 25 + 20 + 16) * 256 + 17 * 84 + 80 + 128) * 4
+    lds4 = ((16 + 16 + 16 + 16) * 256 + 68 + 64 + 128) * 4
+    assert fwd(1, 3) == (5, True, False, 1, lds5, 1, 0, 0) and fwd(1, 0) == (4, False, False, 1, lds4, 1, 0, 0)
+    assert fwd(128, 16)[3:6:2] == (1, 1) and fwd(129, 1)[3:6:2] == (2, 1)
+    assert fwd(32768, 3)[3:6:2] == (256, 1) and fwd(32769, 3)[3:6:2] == (256, 2) and fwd(65536, 0)[3:6:2] == (256, 2)
+    assert fwd(65536 + 5, 0)[3:6:2] == (256, 3)
+    assert q("fwd2", 32769, N=1, A=3, AE=67) == (5, True, True, 256, lds5, 2, 0, 0)
+    assert q("fwd2", 100, N=1, A=0, AE=64) is None and q("fwd", 100, N=0, A=3, AE=67) is None
+    assert q("fwd", 100, N=2, A=17, AE=81) is None and q("bwd", 100, N=2, A=3, AE=66) is None
+    b = q("bwd", 32769, N=2, A=3, AE=67)
+    assert (b.FT, b.hot, b.grid, b.rounds, b.slabs) == (5, True, 256, 2, 256)
+    assert b.lds == ((16 + 20 + 25) * 256 + 64 + 8 * 80) * 4
+    assert b.lds_agents == ((20 + 20) * 256 + 17 * 84 + 8 * 16 * 84 + 8 * 16 * 68 + 8 * 16) * 4
+    b = q("bwd", 17, N=1, A=0, AE=64)
+    assert (b.FT, b.hot, b.grid, b.rounds, b.slabs) == (4, False, 1, 1, 1) and b.lds_agents == ((16 + 16) * 256 + 68 + 8 * 16 * 68 * 2 + 128) * 4
+    assert q("fwd", 0, N=2, A=3, AE=67) == (0, False, False, 0, 0, 0, 0, 0)          # nothing to launch
+    sp = lambda BT, S, n=1: q("state_parts", BT, S=S, nsets=n)
+    for S, kct in ((1, 4), (64, 4), (65, 8), (128, 8), (129, 12), (192, 12), (193, 14), (224, 14), (225, 16), (256, 16), (257, 20), (320, 20),
+                   (321, 24), (384, 24)):
+        for n in (1, 2):
+            assert sp(65, S, n) == (kct, n, 2, 64 * (16 * kct + 4) * 4, 1), (S, n)
+    assert sp(16384, 4)[2::2] == (256, 1) and sp(16385, 4)[2::2] == (129, 2) and sp(16384 + 64 * 3 + 1, 4, 2)[2::2] == (130, 2)
+    assert sp(64 * 513, 4)[2::2] == (171, 3)
+    assert sp(10, 0) is None and sp(10, 385) is None and sp(10, 4, 3) is None
+    assert q("qmix_tail", 16385, S=322, nsets=2) == (24, 1, 129, 64 * 388 * 4, 2)
+    wg = lambda BT, S, AE: q("wgrad_rows", BT, S=S, AE=AE)
+    for S, AE, ft, smax in ((4, 64, 4, 224), (224, 80, 5, 224), (228, 64, 4, 384), (384, 65, 5, 384)):
+        p = wg(33, S, AE)
+        ts = (S + 15) // 16
+        assert p == (ft, smax, 4 * ts + 4 * ft + 16 + ft * ft, 2, 32 * (48 * ft + 260 + smax) * 4, 1, 2), (S, AE, p)
+    assert wg(8192, 4, 64)[3:] == (256, wg(1, 4, 64).lds, 1, 256) and wg(8193, 4, 64)[3:] == (256, wg(1, 4, 64).lds, 2, 256)
+    assert wg(8192 + 32 * 5 + 7, 224, 80)[5:] == (2, 256) and wg(31, 4, 64)[3] == 1 and wg(8160, 4, 64)[3] == 255
+    assert wg(10, 322, 74) is None and wg(10, 388, 78) is None and wg(10, 216, 81) is None and wg(10, 2, 64) is None

@@ -1577,6 +1577,15 @@ def test_rollout_kernels_match_numpy_env(dev):
         assert (alive.cpu().numpy() == (t + 1 < L)).all()
 
 
+_QTRAN_HEAD_PLANS = {
+    ("q", 37, 216): ((5, True, 1, 1), (14, 1), (5, 224, 2, 1)), ("q", 16, 120): ((5, True, 1, 1), (8, 1), (5, 224, 1, 1)),
+    ("q", 1, 1): ((5, True, 1, 1), (4, 1), None), ("q", 300, 40): ((5, True, 3, 1), (4, 5), (5, 224, 10, 1)),
+    ("v", 37, 216): ((4, False, 1, 1), (14, 1), (4, 224, 2, 1)), ("v", 129, 120): ((4, False, 2, 1), (8, 3), (4, 224, 5, 1)),
+    ("q", 4100, 216): ((5, True, 33, 1), (14, 65), (5, 224, 129, 1)), ("q", 700, 320): ((5, True, 6, 1), (20, 11), (5, 384, 22, 1)),
+    ("v", 333, 228): ((4, False, 3, 1), (16, 6), (4, 384, 11, 1)), ("v", 9000, 224): ((4, False, 71, 1), (14, 141), (4, 224, 256, 2)),
+    ("q", 64, 384): ((5, True, 1, 1), (24, 1), (5, 384, 2, 1))}
+
+
 @pytest.mark.parametrize("kind,BT,N,A,S", [("q", 37, 8, 14, 216), ("q", 16, 5, 11, 120), ("q", 1, 2, 3, 1), ("q", 300, 3, 16, 40),
                                             ("v", 37, 8, 14, 216), ("v", 129, 5, 11, 120), ("q", 4100, 8, 14, 216),
                                             ("q", 700, 3, 9, 320), ("v", 333, 4, 5, 228), ("v", 9000, 2, 5, 224), ("q", 64, 2, 16, 384)])
@@ -1588,6 +1597,15 @@ def test_qtran_fused_heads(dev, kind, BT, N, A, S):
     from marl_amd.network.mixer import QtranQBase, QtranV
     from marl_amd.hostutil import FlatParams
     args = types.SimpleNamespace(n_agents=N, n_actions=A, state_shape=S, rnn_hidden_dim=64, qtran_hidden_dim=64)
+    # the launch plan each shape was picked for: head backward (FT, one-hot table, workgroups, rounds), state parts (chunk bucket,
+    # workgroups), row gradients (FT, SMAX, workgroups, rounds; None: S % 4 != 0 -> marl_linear_wgrad)
+    from marl_amd import ops
+    a_ = A if kind == "q" else 0
+    hp = ops.qtran_plan("bwd", BT, N=N, A=a_, AE=64 + a_)
+    spp = ops.qtran_plan("state_parts", BT, S=S)
+    wgp = ops.qtran_plan("wgrad_rows", BT, S=S, AE=64 + a_)
+    got_plan = ((hp.FT, hp.hot, hp.grid, hp.rounds), (spp.KCT, spp.grid), wgp and (wgp.FT, wgp.SMAX, wgp.grid, wgp.rounds))
+    assert got_plan == _QTRAN_HEAD_PLANS[(kind, BT, S)], "the plan moved: %r" % (got_plan,)
     torch.manual_seed(BT + N + A)
     mod = (QtranQBase if kind == "q" else QtranV)(args)
     ref = (QtranQBase if kind == "q" else QtranV)(args)
@@ -1672,6 +1690,10 @@ def test_qtran_state_parts(dev, BT, S):
     from marl_amd.network.mixer import QtranQBase, QtranV
     from marl_amd import ops
     assert ops.qtran_state_parts_supported(S)
+    want_plan = {(37, 216): (14, 1), (4100, 216): (14, 65), (64, 4): (4, 1), (1000, 384): (24, 16), (129, 120): (8, 3)}[(BT, S)]
+    for n in (1, 2):          # (chunk bucket, weight sets, workgroups, LDS bytes, rounds)
+        pl = ops.qtran_plan("state_parts", BT, S=S, nsets=n)
+        assert pl == (want_plan[0], n, want_plan[1], 64 * (16 * want_plan[0] + 4) * 4, 1), "the plan moved: %r" % (pl,)
     args = types.SimpleNamespace(n_agents=3, n_actions=7, state_shape=S, rnn_hidden_dim=64, qtran_hidden_dim=64)
     torch.manual_seed(BT + S)
     qn, vn = QtranQBase(args).to(dev), QtranV(args).to(dev)
@@ -1697,6 +1719,8 @@ def test_qtran_state_parts_ignores_what_follows_a_row(dev, BT, S):
     from marl_amd import ops
     if not ops.qtran_state_parts_supported(S):
         pytest.skip("state width not covered by the row kernel")
+    pl = ops.qtran_plan("state_parts", BT, S=S)
+    assert (pl.KCT, pl.grid, pl.rounds) == {(100, 322): (24, 2, 1), (70, 50): (4, 2, 1), (33, 121): (8, 1, 1)}[(BT, S)], "the plan moved: %r" % (pl,)
     args = types.SimpleNamespace(n_agents=3, n_actions=7, state_shape=S, rnn_hidden_dim=64, qtran_hidden_dim=64)
     torch.manual_seed(BT + S)
     qn = QtranQBase(args).to(dev)
@@ -1723,6 +1747,9 @@ def test_qmix_two_hyper_tail(dev, rows, N, S, padded):
     from marl_amd.hostutil import FlatParams
     from marl_amd import ops
     args = types.SimpleNamespace(n_agents=N, state_shape=S, qmix_hidden_dim=32, hyper_hidden_dim=64, two_hyper_layers=True)
+    pl = ops.qtran_plan("qmix_tail", rows, S=S)
+    assert (pl.KCT, pl.nsets, pl.grid, pl.rounds) == {(37, 120): (8, 1, 1, 1), (2500, 322): (24, 1, 40, 1), (130, 48): (4, 1, 3, 1)}[(rows, S)], \
+        "the plan moved: %r" % (pl,)
     torch.manual_seed(rows + S)
     mod, ref = QMixMixer(args), QMixMixer(args)
     ref.load_state_dict(mod.state_dict())
@@ -1771,6 +1798,9 @@ def test_qtran_two_action_sets(dev, BT, N, A, S):
     import types
     from marl_amd.network.mixer import QtranQBase
     args = types.SimpleNamespace(n_agents=N, n_actions=A, state_shape=S, rnn_hidden_dim=64, qtran_hidden_dim=64)
+    from marl_amd import ops
+    pl = ops.qtran_plan("fwd2", BT, N=N, A=A, AE=64 + A)          # qtran_fwd_kernel<5, true, true>: workgroups, rounds
+    assert (pl.FT, pl.hot, pl.dual, pl.grid, pl.rounds) == (5, True, True, {37: 1, 4100: 33, 1: 1}[BT], 1), "the plan moved: %r" % (pl,)
     torch.manual_seed(BT + A)
     mod = QtranQBase(args).to(dev)
     g = torch.Generator().manual_seed(BT)
@@ -1804,6 +1834,10 @@ def test_qtran_row_kernels_reproducible_and_remapped(dev, kind, BT, S):
     N, A, T = 3, 6, 11
     B = (BT + T - 1) // T
     BT = B * T
+    wgp = ops.qtran_plan("wgrad_rows", BT, S=S, AE=64 + (A if kind == "q" else 0))          # (FT, SMAX, workgroups, rounds, slabs)
+    spp = ops.qtran_plan("state_parts", BT, S=S)
+    want_plan = {44: ((5, 224, 2, 1, 2), (14, 1, 1)), 8239: ((5, 224, 256, 2, 256), (14, 129, 1)), 2508: ((4, 384, 79, 1, 79), (24, 40, 1))}[BT]
+    assert ((wgp.FT, wgp.SMAX, wgp.grid, wgp.rounds, wgp.slabs), (spp.KCT, spp.grid, spp.rounds)) == want_plan, "the plan moved: %r %r" % (wgp, spp)
     args = types.SimpleNamespace(n_agents=N, n_actions=A, state_shape=S, rnn_hidden_dim=64, qtran_hidden_dim=64)
     torch.manual_seed(BT)
     mod = (QtranQBase if kind == "q" else QtranV)(args).to(dev)
