@@ -404,6 +404,19 @@ int marl_mlp3_x6_fwd_save(const marl_mlp3_weights_t* w, const marl_src_t* x, flo
 int marl_mlp3_x6_bwd_saved(const marl_mlp3_weights_t* w, const marl_src_t* x, const float* dY, long lddy, long gs_dy,
                            const marl_mlp3_weights_t* grads, float* ws, size_t ws_bytes, const float* hsave,
                            size_t hsave_floats, long M, int K1, int N3, int groups, void* stream);
+/* The launch plan of one of the four calls above for these arguments - a host function: no GPU, nothing is launched, and the pointers
+ * (in w, grads and x too) may be integers standing for addresses: only their alignment and whether they are NULL is read.
+ * what: 0 marl_mlp3_fwd_save, 1 marl_mlp3_bwd_saved, 2 marl_mlp3_x6_fwd_save, 3 marl_mlp3_x6_bwd_saved; Y / ldy / gs_y are dY's for
+ * the backwards, grads / ws_bytes are read by the backwards only; M >= 1.  These are the host functions the launches themselves
+ * decide with.  Returns 0, or an error where the entry point refuses the call (plan[0] = 1).  plan[19]:
+ *   [0] refused   [1] KC chunk bucket  [2] CF leading 16-byte chunks (runtime)  [3] compile-time CF variant, -1 if none
+ *   [4] kpad  [5] KV = K1 + kpad  [6] three-layer  [7] WIDE  [8] n3t output tiles  [9] kept (forward: writes hsave; backward: reads it)
+ *   [10] KH chunks of x^T per stage pass  [11] stage passes (forwards: KC, 1)  [12] workgroups per CU (1 / 2)
+ *   [13] nst stripes per group  [14] units per stripe (forwards: 16-row tiles; backwards: 64-row iterations)  [15] grid
+ *   [16] dynamic LDS bytes  [17] yvec (forwards)  [18] slabs per group the reduce sums (backwards) */
+int marl_mlp3_plan(int what, const marl_mlp3_weights_t* w, const marl_src_t* x, const void* Y, long ldy, long gs_y,
+                   const marl_mlp3_weights_t* grads, size_t ws_bytes, const void* hsave, size_t hsave_floats, long M, int K1,
+                   int N3, int groups, int* plan);
 
 /* ---- fused QTRAN-base heads (qtran_fused.hip) ------------------------------------------------
  * QtranQBase.forward (network/mixer.py:378-388, A = n_actions > 0, AE = 64 + A) and QtranV.forward (:411-418, A = 0,

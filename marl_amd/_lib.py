@@ -177,6 +177,7 @@ SIGNATURES = {
     "marl_mlp3_x6_supported": (I, [SRC, I, I, I, I, I]),
     "marl_mlp3_x6_fwd_save": (I, [M3, SRC, P, L, L, P, SZ, L, I, I, I, P]),
     "marl_mlp3_x6_bwd_saved": (I, [M3, SRC, P, L, L, M3, P, SZ, P, SZ, L, I, I, I, P]),
+    "marl_mlp3_plan": (I, [I, M3, SRC, P, L, L, M3, SZ, P, SZ, L, I, I, I, P]),
     "marl_qtran_supported": (I, [I, I, I]),
     "marl_qtran_head_fwd": (I, [QT, P, P, P, P, P, P, P, P, L, I, I, I, P]),
     "marl_qtran_head_fwd2": (I, [QT, P, P, P, P, P, P, P, P, P, P, L, I, I, I, P]),

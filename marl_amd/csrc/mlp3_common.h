@@ -5,6 +5,11 @@
 #include "common.h"
 #include "../../include/marl_hip.h"
 
+// the bf16x6 half of marl_mlp3_plan (mlp3_x6.hip; plain types: the structs below are private to each object)
+int mlp3_x6_plan_ints(int bwd, const marl_mlp3_weights_t* w, const marl_src_t* x, const void* Y, long ldy, long gs_y,
+                      const marl_mlp3_weights_t* grads, size_t ws_bytes, const void* hsave, size_t hsave_floats, long M, int K1,
+                      int N3, int groups, int* plan);
+
 namespace {
 
 
@@ -312,16 +317,59 @@ inline int stripes(long units, int groups, int wgs = 256) {
   return (int)(n < 1 ? 1 : n);
 }
 
-bool fill_args(Mlp3Args& a, const marl_mlp3_weights_t* w, const marl_src_t* x, long M, int K1, int N3, int groups) {
-  a.x = to_src3(x);
-  if (concat_width(a.x) != K1) return false;
+// ---- launch plans.  Each of the four entry points (fp32 / bf16x6, forward / backward) decides its refusal, kernel instantiation,
+// grid and LDS by calling its planner and launches from the result; marl_mlp3_plan reports the same struct (all int, in the order
+// of plan[] in include/marl_hip.h).
+struct Mlp3Call {
+  const marl_mlp3_weights_t* w; const marl_src_t* x;
+  const void* Y; long ldy, gs_y;                      // forward: outputs; backward: dY
+  const marl_mlp3_weights_t* grads; size_t ws_bytes;  // backward only
+  const void* hsave; size_t hsave_floats;
+  long M; int K1, N3, groups;
+};
+struct Mlp3Plan {
+  int refused;        // 1: the entry point returns an error and launches nothing (the other fields are then 0 / -1)
+  int KC, CF, CFT;    // chunk bucket, runtime leading 16-byte chunks, compile-time CF variant or -1
+  int kpad, KV;
+  int three, wide, n3t;
+  int kept;           // forward: writes hsave; backward: reads it (0: recomputes)
+  int KH, passes;     // backward: chunks of x^T per stage pass, passes (forward: KC, 1)
+  int wgpc;           // workgroups per CU the kernel is bounded for
+  int nst, per, grid; // stripes per group, units per stripe (forward: 16-row tiles; backward: 64-row iterations), workgroups
+  int lds;            // dynamic LDS bytes
+  int yvec;           // forward: 16-byte output stores
+  int slabs;          // backward: slabs per group the reduce sums (forward: 0)
+};
+constexpr int MLP3_PLAN_INTS = sizeof(Mlp3Plan) / sizeof(int);
+inline void plan_out(int* plan, const Mlp3Plan& p) {
+  const int* v = reinterpret_cast<const int*>(&p);
+  for (int i = 0; i < MLP3_PLAN_INTS; ++i) plan[i] = v[i];
+}
+inline Mlp3Plan plan_refused() { Mlp3Plan p = {}; p.refused = 1; p.CFT = -1; return p; }
+
+bool fill_args(Mlp3Args& a, const Mlp3Call& c, const Mlp3Plan& p) {
+  const marl_mlp3_weights_t* w = c.w;
+  a.x = to_src3(c.x);
+  if (concat_width(a.x) != c.K1) return false;
   a.W1 = w->w1; a.b1 = w->b1; a.W2 = w->w2; a.b2 = w->b2; a.W3 = w->w3; a.b3 = w->b3;
   a.gs_w1 = w->gs_w1; a.gs_b1 = w->gs_b1; a.gs_w2 = w->gs_w2; a.gs_b2 = w->gs_b2; a.gs_w3 = w->gs_w3; a.gs_b3 = w->gs_b3;
-  a.M = M; a.K1 = K1; a.N3 = N3; a.groups = groups;
-  a.kpad = kpad_of(x); a.KV = K1 + a.kpad;
-  a.CF = lead_chunks(x);
-  a.n3t = (N3 + 15) / 16; a.yvec = 0;
+  a.M = c.M; a.K1 = c.K1; a.N3 = c.N3; a.groups = c.groups;
+  a.kpad = p.kpad; a.KV = p.KV;
+  a.CF = p.CF;
+  a.n3t = p.n3t; a.yvec = p.yvec; a.nst = p.nst;
+  a.Y = const_cast<float*>(static_cast<const float*>(c.Y)); a.ldy = c.ldy; a.gs_y = c.gs_y;
+  a.hs = const_cast<float*>(static_cast<const float*>(c.hsave));
+  a.ws = nullptr;
   return true;
+}
+inline void fill_red(Mlp3RedArgs& r, const float* ws, const Mlp3Call& c, const Mlp3Plan& p) {
+  const marl_mlp3_weights_t* grads = c.grads;
+  r.ws = ws; r.dW1 = const_cast<float*>(grads->w1); r.db1 = const_cast<float*>(grads->b1);
+  r.dW2 = const_cast<float*>(grads->w2); r.db2 = const_cast<float*>(grads->b2);
+  r.dW3 = const_cast<float*>(grads->w3); r.db3 = const_cast<float*>(grads->b3);
+  r.gs_w1 = grads->gs_w1; r.gs_b1 = grads->gs_b1; r.gs_w2 = grads->gs_w2; r.gs_b2 = grads->gs_b2;
+  r.gs_w3 = grads->gs_w3; r.gs_b3 = grads->gs_b3;
+  r.K1 = c.K1; r.N3 = c.N3; r.groups = c.groups; r.nst = p.slabs;
 }
 
 }  // namespace

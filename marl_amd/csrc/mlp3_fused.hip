@@ -597,26 +597,94 @@ extern "C" size_t marl_mlp3_save_floats(long M, int three, int groups) {
   return M <= 0 ? 0 : (size_t)groups * (size_t)((M + 15) / 16) * (three ? 8 : 4) * 256;
 }
 
+// ---- launch plans of the fp32 pair (see Mlp3Plan in mlp3_common.h)
+namespace {
+
+bool bias_rows_ok(const marl_mlp3_weights_t* w, bool three) {      // bias rows are read with 16-byte loads
+  return aligned16(w->b1) && w->gs_b1 % 4 == 0 && (!three || (aligned16(w->b2) && w->gs_b2 % 4 == 0));
+}
+
+Mlp3Plan plan_fwd(const Mlp3Call& c) {
+  Mlp3Plan p = plan_refused();
+  const bool three = c.w->w2 != nullptr;
+  if (c.hsave && (c.hsave_floats < marl_mlp3_save_floats(c.M, three, c.groups) || !aligned16(c.hsave))) return p;
+  if (!marl_mlp3_supported(c.x, c.K1, HD, three ? HD : 0, c.N3, c.groups)) return p;
+  if (!bias_rows_ok(c.w, three)) return p;
+  if (concat_width(to_src3(c.x)) != c.K1) return p;
+  p.kpad = kpad_of(c.x); p.KV = c.K1 + p.kpad; p.KC = kc_bucket(p.KV); p.CF = lead_chunks(c.x);
+  p.three = three; p.wide = c.N3 > 16; p.n3t = (c.N3 + 15) / 16; p.kept = c.hsave != nullptr;
+  // (seven leading full chunks = a 120-wide dense segment 0: the QPLEX heads on 2s3z-sized maps get the compile-time variants)
+  p.CFT = (!p.wide && (p.KC == 8 || p.KC == 11) && p.CF == 7) ? 7 : -1;
+  p.KH = p.KC; p.passes = 1;
+  p.wgpc = (p.KC > 12 || p.wide) ? 1 : 2;
+  const long tiles = (c.M + 15) / 16;
+  p.nst = stripes((tiles + FNW - 1) / FNW, c.groups);
+  p.per = (int)((tiles + p.nst - 1) / p.nst);
+  p.grid = (p.nst + 7) / 8 * 8 * c.groups;
+  p.lds = (int)fwd_lds(p.KC, p.CF, p.wide);
+  p.yvec = (c.ldy % 4 == 0) && (c.gs_y % 4 == 0) && aligned16(c.Y) && (c.N3 % 4 == 0);
+  p.slabs = 0;
+  p.refused = 0;
+  return p;
+}
+
+Mlp3Plan plan_bwd(const Mlp3Call& c) {
+  Mlp3Plan p = plan_refused();
+  const bool three = c.w->w2 != nullptr;
+  if (c.hsave && (c.hsave_floats < marl_mlp3_save_floats(c.M, three, c.groups) || !aligned16(c.hsave))) return p;
+  if (!marl_mlp3_supported(c.x, c.K1, HD, three ? HD : 0, c.N3, c.groups)) return p;
+  if (!bias_rows_ok(c.w, three)) return p;
+  if (three != (c.grads->w2 != nullptr)) return p;
+  if (c.ws_bytes < marl_mlp3_bwd_workspace(c.M, c.K1, c.N3, c.groups)) return p;
+  if (concat_width(to_src3(c.x)) != c.K1) return p;
+  const int KC = kc_bucket(c.K1 + kpad_of(c.x));
+  const bool wide = c.N3 > 16, kept = c.hsave != nullptr;
+  if ((KC > 12 || wide) && !kept) return p;      // marl_mlp3_needs_kept(): no recomputing backward for these
+  if (wide && (c.ldy % 4 || c.gs_y % 4 || !aligned16(c.Y))) return p;      // dY tiles are 16-byte loads
+  p.kpad = kpad_of(c.x); p.KV = c.K1 + p.kpad; p.KC = KC; p.CF = lead_chunks(c.x);
+  p.three = three; p.wide = wide; p.n3t = (c.N3 + 15) / 16; p.kept = kept;
+  p.CFT = (!wide && (KC == 8 || KC == 11) && p.CF == 7) ? 7 : -1;
+  const bool two = kept && !wide && KC <= MLP3_BWD2_KC;      // (the same terms as the kernel's TWO / KH / NH)
+  p.KH = KC > 24 ? 16 : (two && KC > 8) ? 6 : KC; p.passes = (KC + p.KH - 1) / p.KH;
+  p.wgpc = two ? 2 : 1;
+  const long its = (c.M + 63) / 64;
+  p.nst = stripes(its, c.groups, two ? 512 : 256);
+  p.per = (int)((its + p.nst - 1) / p.nst);
+  p.grid = (p.nst + 7) / 8 * 8 * c.groups;
+  p.lds = (int)bwd_lds(KC, p.CF, kept, wide, three);
+  p.yvec = 0;
+  p.slabs = p.nst;
+  p.refused = 0;
+  return p;
+}
+
+}  // namespace
+
+extern "C" int marl_mlp3_plan(int what, const marl_mlp3_weights_t* w, const marl_src_t* x, const void* Y, long ldy, long gs_y,
+                              const marl_mlp3_weights_t* grads, size_t ws_bytes, const void* hsave, size_t hsave_floats, long M,
+                              int K1, int N3, int groups, int* plan) {
+  static_assert(MLP3_PLAN_INTS == 19, "plan[] of include/marl_hip.h");
+  if (what < 0 || what > 3 || !w || !x || !plan || ((what & 1) && !grads) || M <= 0) return (int)hipErrorInvalidValue;
+  if (what >= 2) return mlp3_x6_plan_ints(what & 1, w, x, Y, ldy, gs_y, grads, ws_bytes, hsave, hsave_floats, M, K1, N3, groups, plan);
+  const Mlp3Call c = {w, x, Y, ldy, gs_y, grads, ws_bytes, hsave, hsave_floats, M, K1, N3, groups};
+  const Mlp3Plan p = what ? plan_bwd(c) : plan_fwd(c);
+  plan_out(plan, p);
+  return p.refused ? (int)hipErrorInvalidValue : 0;
+}
+
 extern "C" int marl_mlp3_fwd_save(const marl_mlp3_weights_t* w, const marl_src_t* x, float* Y, long ldy, long gs_y,
                                   float* hsave, size_t hsave_floats, long M, int K1, int N3, int groups, void* stream) {
   if (M <= 0) return 0;
-  const bool three = w->w2 != nullptr;
-  if (hsave && (hsave_floats < marl_mlp3_save_floats(M, three, groups) || !aligned16(hsave))) return (int)hipErrorInvalidValue;
-  if (!marl_mlp3_supported(x, K1, HD, three ? HD : 0, N3, groups)) return (int)hipErrorInvalidValue;
-  // bias rows are read with 16-byte loads
-  if (!aligned16(w->b1) || w->gs_b1 % 4 || (three && (!aligned16(w->b2) || w->gs_b2 % 4))) return (int)hipErrorInvalidValue;
+  const Mlp3Call c = {w, x, Y, ldy, gs_y, nullptr, 0, hsave, hsave_floats, M, K1, N3, groups};
+  const Mlp3Plan p = plan_fwd(c);
+  if (p.refused) return (int)hipErrorInvalidValue;
   Mlp3Args a;
-  if (!fill_args(a, w, x, M, K1, N3, groups)) return (int)hipErrorInvalidValue;
-  a.Y = Y; a.ldy = ldy; a.gs_y = gs_y; a.ws = nullptr; a.hs = hsave;
-  const long tiles = (M + 15) / 16;
-  a.nst = stripes((tiles + FNW - 1) / FNW, groups);
-  const int KC = kc_bucket(a.KV);
-  const bool wide = N3 > 16;
-  a.yvec = (ldy % 4 == 0) && (gs_y % 4 == 0) && aligned16(Y) && (N3 % 4 == 0);
-  const size_t lds = fwd_lds(KC, a.CF, wide);
-// (seven leading full chunks = a 120-wide dense segment 0: the QPLEX heads on 2s3z-sized maps get the compile-time variants)
-#define MLP3_PICK(K, ...) (KC == 4 ? (const void*)K<4, __VA_ARGS__> : KC == 8 ? (a.CF == 7 ? (const void*)K<8, MLP3_CF7(__VA_ARGS__)> : (const void*)K<8, __VA_ARGS__>) \
-                           : KC == 11 ? (a.CF == 7 ? (const void*)K<11, MLP3_CF7(__VA_ARGS__)> : (const void*)K<11, __VA_ARGS__>) : (const void*)K<12, __VA_ARGS__>)
+  if (!fill_args(a, c, p)) return (int)hipErrorInvalidValue;
+  const int KC = p.KC;
+  const bool three = p.three, wide = p.wide;
+  const size_t lds = (size_t)p.lds;
+#define MLP3_PICK(K, ...) (KC == 4 ? (const void*)K<4, __VA_ARGS__> : KC == 8 ? (p.CFT == 7 ? (const void*)K<8, MLP3_CF7(__VA_ARGS__)> : (const void*)K<8, __VA_ARGS__>) \
+                           : KC == 11 ? (p.CFT == 7 ? (const void*)K<11, MLP3_CF7(__VA_ARGS__)> : (const void*)K<11, __VA_ARGS__>) : (const void*)K<12, __VA_ARGS__>)
 #define MLP3_PICK_BIG(K, ...) (KC == 16 ? (const void*)K<16, __VA_ARGS__> : KC == 24 ? (const void*)K<24, __VA_ARGS__> : (const void*)K<32, __VA_ARGS__>)
 #define MLP3_PICK_WIDE(K, ...) (KC == 8 ? (const void*)K<8, __VA_ARGS__> : KC == 16 ? (const void*)K<16, __VA_ARGS__> : (const void*)K<24, __VA_ARGS__>)
   const void* fn = wide ? MLP3_PICK_WIDE(mlp3_fwd_kernel, false, -1, true)
@@ -624,7 +692,7 @@ extern "C" int marl_mlp3_fwd_save(const marl_mlp3_weights_t* w, const marl_src_t
                              : (three ? MLP3_PICK(mlp3_fwd_kernel, true, -1) : MLP3_PICK(mlp3_fwd_kernel, false, -1));
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
-  dim3 grid((unsigned)((a.nst + 7) / 8 * 8 * groups)), block(64 * FNW);
+  dim3 grid((unsigned)p.grid), block(64 * FNW);
   void* kargs[] = {(void*)&a};
   e = hipLaunchKernel(fn, grid, block, kargs, lds, (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
@@ -646,39 +714,28 @@ extern "C" int marl_mlp3_bwd_saved(const marl_mlp3_weights_t* w, const marl_src_
                                    const marl_mlp3_weights_t* grads, float* ws, size_t ws_bytes, const float* hsave,
                                    size_t hsave_floats, long M, int K1, int N3, int groups, void* stream) {
   if (M <= 0) return 0;
-  const bool three = w->w2 != nullptr;
-  if (hsave && (hsave_floats < marl_mlp3_save_floats(M, three, groups) || !aligned16(hsave))) return (int)hipErrorInvalidValue;
-  if (!marl_mlp3_supported(x, K1, HD, three ? HD : 0, N3, groups)) return (int)hipErrorInvalidValue;
-  if (!aligned16(w->b1) || w->gs_b1 % 4 || (three && (!aligned16(w->b2) || w->gs_b2 % 4))) return (int)hipErrorInvalidValue;
-  if (three != (grads->w2 != nullptr)) return (int)hipErrorInvalidValue;
-  if (ws_bytes < marl_mlp3_bwd_workspace(M, K1, N3, groups)) return (int)hipErrorInvalidValue;
+  const Mlp3Call c = {w, x, dY, lddy, gs_dy, grads, ws_bytes, hsave, hsave_floats, M, K1, N3, groups};
+  const Mlp3Plan p = plan_bwd(c);
+  if (p.refused) return (int)hipErrorInvalidValue;
   Mlp3Args a;
-  if (!fill_args(a, w, x, M, K1, N3, groups)) return (int)hipErrorInvalidValue;
-  a.Y = const_cast<float*>(dY); a.ldy = lddy; a.gs_y = gs_dy; a.ws = ws; a.hs = const_cast<float*>(hsave);
-  const int KC = kc_bucket(a.KV);
-  const bool wide = N3 > 16;
-  a.nst = stripes((M + 63) / 64, groups, (hsave && !wide && KC <= MLP3_BWD2_KC) ? 512 : 256);
-  if ((KC > 12 || wide) && !hsave) return (int)hipErrorInvalidValue;      // marl_mlp3_needs_kept(): no recomputing backward for these
-  if (wide && (lddy % 4 || gs_dy % 4 || !aligned16(dY))) return (int)hipErrorInvalidValue;      // dY tiles are 16-byte loads
-  const size_t lds = bwd_lds(KC, a.CF, hsave != nullptr, wide, three);
+  if (!fill_args(a, c, p)) return (int)hipErrorInvalidValue;
+  a.ws = ws;
+  const int KC = p.KC;
+  const bool three = p.three, wide = p.wide, kept = p.kept;
+  const size_t lds = (size_t)p.lds;
   const void* fn = wide ? MLP3_PICK_WIDE(mlp3_bwd_kernel, false, -1, true, true) : KC > 12 ? (three ? MLP3_PICK_BIG(mlp3_bwd_kernel, true, -1, true) : MLP3_PICK_BIG(mlp3_bwd_kernel, false, -1, true))
-                   : hsave ? (three ? MLP3_PICK(mlp3_bwd_kernel, true, -1, true) : MLP3_PICK(mlp3_bwd_kernel, false, -1, true))
-                           : (three ? MLP3_PICK(mlp3_bwd_kernel, true, -1, false) : MLP3_PICK(mlp3_bwd_kernel, false, -1, false));
+                   : kept ? (three ? MLP3_PICK(mlp3_bwd_kernel, true, -1, true) : MLP3_PICK(mlp3_bwd_kernel, false, -1, true))
+                          : (three ? MLP3_PICK(mlp3_bwd_kernel, true, -1, false) : MLP3_PICK(mlp3_bwd_kernel, false, -1, false));
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
-  dim3 grid((unsigned)((a.nst + 7) / 8 * 8 * groups)), block(64 * BNW);
+  dim3 grid((unsigned)p.grid), block(64 * BNW);
   void* kargs[] = {(void*)&a};
   hipStream_t s = (hipStream_t)stream;
   e = hipLaunchKernel(fn, grid, block, kargs, lds, s);
   if (e != hipSuccess) return (int)e;
   MARL_CHECK_LAUNCH();
   Mlp3RedArgs r;
-  r.ws = ws; r.dW1 = const_cast<float*>(grads->w1); r.db1 = const_cast<float*>(grads->b1);
-  r.dW2 = const_cast<float*>(grads->w2); r.db2 = const_cast<float*>(grads->b2);
-  r.dW3 = const_cast<float*>(grads->w3); r.db3 = const_cast<float*>(grads->b3);
-  r.gs_w1 = grads->gs_w1; r.gs_b1 = grads->gs_b1; r.gs_w2 = grads->gs_w2; r.gs_b2 = grads->gs_b2;
-  r.gs_w3 = grads->gs_w3; r.gs_b3 = grads->gs_b3;
-  r.K1 = K1; r.N3 = N3; r.groups = groups; r.nst = a.nst;
+  fill_red(r, ws, c, p);
   const long total = mlp3_slab_floats(K1, N3) * groups;
   hipLaunchKernelGGL(mlp3_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, r);
   MARL_CHECK_LAUNCH();

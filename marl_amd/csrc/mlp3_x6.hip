@@ -539,27 +539,73 @@ extern "C" int marl_mlp3_x6_supported(const marl_src_t* x, int K1, int H1, int H
   return x6_fwd_lds(KC, CF, true) <= 160 * 1024 && x6_bwd_lds(KC, CF) <= 160 * 1024;
 }
 
+// ---- launch plans of the split pair (see Mlp3Plan in mlp3_common.h)
+namespace {
+
+Mlp3Plan plan_x6(bool bwd, const Mlp3Call& c) {
+  Mlp3Plan p = plan_refused();
+  if (!c.w->w2 || !marl_mlp3_x6_supported(c.x, c.K1, HD, HD, c.N3, c.groups)) return p;
+  if (bwd) {
+    if (!c.grads->w2 || !c.hsave) return p;
+    if (c.hsave_floats < marl_mlp3_save_floats(c.M, 1, c.groups) || !aligned16(c.hsave)) return p;
+    if (c.ws_bytes < marl_mlp3_bwd_workspace(c.M, c.K1, c.N3, c.groups)) return p;
+  } else {
+    if (c.hsave && (c.hsave_floats < marl_mlp3_save_floats(c.M, 1, c.groups) || !aligned16(c.hsave))) return p;
+    if (!aligned16(c.w->b1) || c.w->gs_b1 % 4 || !aligned16(c.w->b2) || c.w->gs_b2 % 4) return p;
+  }
+  if (concat_width(to_src3(c.x)) != c.K1) return p;
+  p.kpad = kpad_of(c.x); p.KV = c.K1 + p.kpad; p.KC = kc_bucket_x6(p.KV); p.CF = lead_chunks_nat(c.x);
+  // (six leading full chunks = a 120-wide dense segment 0: the QPLEX heads on 2s3z-sized maps get the compile-time variants)
+  p.CFT = ((p.KC == 8 || p.KC == 12) && p.CF == 6) ? 6 : -1;
+  p.three = 1; p.wide = 0; p.n3t = (c.N3 + 15) / 16; p.kept = c.hsave != nullptr;
+  p.wgpc = 2;
+  if (bwd) {
+    const long its = (c.M + XR - 1) / XR;
+    p.KH = 4; p.passes = p.KC / 4;                          // dW1: one pass per 64 columns of x
+    p.nst = stripes(its, c.groups, 512);                    // two workgroups per CU
+    p.per = (int)((its + p.nst - 1) / p.nst);
+    p.lds = (int)x6_bwd_lds(p.KC, p.CF);
+    p.yvec = 0; p.slabs = p.nst;
+  } else {
+    const long tiles = (c.M + 15) / 16;
+    p.KH = p.KC; p.passes = 1;
+    p.nst = stripes((tiles + FNW - 1) / FNW, c.groups);
+    p.per = (int)((tiles + p.nst - 1) / p.nst);
+    p.lds = (int)x6_fwd_lds(p.KC, p.CF, true);
+    p.yvec = 0; p.slabs = 0;
+  }
+  p.grid = (p.nst + 7) / 8 * 8 * c.groups;
+  p.refused = 0;
+  return p;
+}
+
+}  // namespace
+
+int mlp3_x6_plan_ints(int bwd, const marl_mlp3_weights_t* w, const marl_src_t* x, const void* Y, long ldy, long gs_y,
+                      const marl_mlp3_weights_t* grads, size_t ws_bytes, const void* hsave, size_t hsave_floats, long M, int K1,
+                      int N3, int groups, int* plan) {
+  const Mlp3Call c = {w, x, Y, ldy, gs_y, grads, ws_bytes, hsave, hsave_floats, M, K1, N3, groups};
+  const Mlp3Plan p = plan_x6(bwd != 0, c);
+  plan_out(plan, p);
+  return p.refused ? (int)hipErrorInvalidValue : 0;
+}
+
 extern "C" int marl_mlp3_x6_fwd_save(const marl_mlp3_weights_t* w, const marl_src_t* x, float* Y, long ldy, long gs_y,
                                      float* hsave, size_t hsave_floats, long M, int K1, int N3, int groups, void* stream) {
   if (M <= 0) return 0;
-  if (!w->w2 || !marl_mlp3_x6_supported(x, K1, HD, HD, N3, groups)) return (int)hipErrorInvalidValue;
-  if (hsave && (hsave_floats < marl_mlp3_save_floats(M, 1, groups) || !aligned16(hsave))) return (int)hipErrorInvalidValue;
-  if (!aligned16(w->b1) || w->gs_b1 % 4 || !aligned16(w->b2) || w->gs_b2 % 4) return (int)hipErrorInvalidValue;
+  const Mlp3Call c = {w, x, Y, ldy, gs_y, nullptr, 0, hsave, hsave_floats, M, K1, N3, groups};
+  const Mlp3Plan p = plan_x6(false, c);
+  if (p.refused) return (int)hipErrorInvalidValue;
   Mlp3Args a;
-  if (!fill_args(a, w, x, M, K1, N3, groups)) return (int)hipErrorInvalidValue;
-  a.Y = Y; a.ldy = ldy; a.gs_y = gs_y; a.ws = nullptr; a.hs = hsave;
-  const long tiles = (M + 15) / 16;
-  a.nst = stripes((tiles + FNW - 1) / FNW, groups);
-  const int KC = kc_bucket_x6(a.KV);
-  a.CF = lead_chunks_nat(x);
-  const size_t lds = x6_fwd_lds(KC, a.CF, true);
-// (six leading full chunks = a 120-wide dense segment 0: the QPLEX heads on 2s3z-sized maps get the compile-time variants)
-#define X6_PICK(K) (KC == 4 ? (const void*)K<4, true, -1> : KC == 8 ? (a.CF == 6 ? (const void*)K<8, true, 6> : (const void*)K<8, true, -1>) \
-                    : (a.CF == 6 ? (const void*)K<12, true, 6> : (const void*)K<12, true, -1>))
+  if (!fill_args(a, c, p)) return (int)hipErrorInvalidValue;
+  const int KC = p.KC;
+  const size_t lds = (size_t)p.lds;
+#define X6_PICK(K) (KC == 4 ? (const void*)K<4, true, -1> : KC == 8 ? (p.CFT == 6 ? (const void*)K<8, true, 6> : (const void*)K<8, true, -1>) \
+                    : (p.CFT == 6 ? (const void*)K<12, true, 6> : (const void*)K<12, true, -1>))
   const void* fn = X6_PICK(mlp3x6_fwd_kernel);
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
-  dim3 grid((unsigned)((a.nst + 7) / 8 * 8 * groups)), block(64 * FNW);
+  dim3 grid((unsigned)p.grid), block(64 * FNW);
   void* kargs[] = {(void*)&a};
   e = hipLaunchKernel(fn, grid, block, kargs, lds, (hipStream_t)stream);
   if (e != hipSuccess) return (int)e;
@@ -571,32 +617,25 @@ extern "C" int marl_mlp3_x6_bwd_saved(const marl_mlp3_weights_t* w, const marl_s
                                       const marl_mlp3_weights_t* grads, float* ws, size_t ws_bytes, const float* hsave,
                                       size_t hsave_floats, long M, int K1, int N3, int groups, void* stream) {
   if (M <= 0) return 0;
-  if (!w->w2 || !grads->w2 || !hsave || !marl_mlp3_x6_supported(x, K1, HD, HD, N3, groups)) return (int)hipErrorInvalidValue;
-  if (hsave_floats < marl_mlp3_save_floats(M, 1, groups) || !aligned16(hsave)) return (int)hipErrorInvalidValue;
-  if (ws_bytes < marl_mlp3_bwd_workspace(M, K1, N3, groups)) return (int)hipErrorInvalidValue;
+  const Mlp3Call c = {w, x, dY, lddy, gs_dy, grads, ws_bytes, hsave, hsave_floats, M, K1, N3, groups};
+  const Mlp3Plan p = plan_x6(true, c);
+  if (p.refused) return (int)hipErrorInvalidValue;
   Mlp3Args a;
-  if (!fill_args(a, w, x, M, K1, N3, groups)) return (int)hipErrorInvalidValue;
-  a.Y = const_cast<float*>(dY); a.ldy = lddy; a.gs_y = gs_dy; a.ws = ws; a.hs = const_cast<float*>(hsave);
-  const int KC = kc_bucket_x6(a.KV);
-  a.CF = lead_chunks_nat(x);
-  a.nst = stripes((M + XR - 1) / XR, groups, 512);      // two workgroups per CU
-  const size_t lds = x6_bwd_lds(KC, a.CF);
+  if (!fill_args(a, c, p)) return (int)hipErrorInvalidValue;
+  a.ws = ws;
+  const int KC = p.KC;
+  const size_t lds = (size_t)p.lds;
   const void* fn = X6_PICK(mlp3x6_bwd_kernel);
   hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return (int)e;
-  dim3 grid((unsigned)((a.nst + 7) / 8 * 8 * groups)), block(64 * XNW);
+  dim3 grid((unsigned)p.grid), block(64 * XNW);
   void* kargs[] = {(void*)&a};
   hipStream_t s = (hipStream_t)stream;
   e = hipLaunchKernel(fn, grid, block, kargs, lds, s);
   if (e != hipSuccess) return (int)e;
   MARL_CHECK_LAUNCH();
   Mlp3RedArgs r;
-  r.ws = ws; r.dW1 = const_cast<float*>(grads->w1); r.db1 = const_cast<float*>(grads->b1);
-  r.dW2 = const_cast<float*>(grads->w2); r.db2 = const_cast<float*>(grads->b2);
-  r.dW3 = const_cast<float*>(grads->w3); r.db3 = const_cast<float*>(grads->b3);
-  r.gs_w1 = grads->gs_w1; r.gs_b1 = grads->gs_b1; r.gs_w2 = grads->gs_w2; r.gs_b2 = grads->gs_b2;
-  r.gs_w3 = grads->gs_w3; r.gs_b3 = grads->gs_b3;
-  r.K1 = K1; r.N3 = N3; r.groups = groups; r.nst = a.nst;
+  fill_red(r, ws, c, p);
   const long total = mlp3_slab_floats(K1, N3) * groups;
   hipLaunchKernelGGL(mlp3_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, r);
   MARL_CHECK_LAUNCH();

@@ -934,6 +934,40 @@ def mlp3_bwd(w, x, dY, grads, M, K1, N3, groups, hsave=None, x6=False):
              hp, hn, M, K1, N3, groups, _stream()), "marl_mlp3_x6_bwd" if x6 else "marl_mlp3_bwd")
 
 
+MLP3_CALLS = ("fwd", "bwd", "x6_fwd", "x6_bwd")          # `what` of marl_mlp3_plan (include/marl_hip.h)
+Mlp3Plan = collections.namedtuple("Mlp3Plan", "KC CF CFT kpad KV three wide n3t kept KH passes wgpc nst per grid lds yvec slabs")
+
+
+def mlp3_plan(what, w, x, M, K1, N3, groups, Y=0, ld=None, gs=None, grads=None, hsave=None, hsave_floats=None, ws_bytes=None):
+    """The launch plan of mlp3_fwd / mlp3_bwd (`what` in MLP3_CALLS) for these arguments, from the host functions the launches
+    themselves decide with - no GPU.  None where the entry point refuses the call.  w / grads: MarlMlp3Weights (pointer fields may
+    be integers standing for addresses); Y (dY for the backwards) / hsave: tensors or such integers; ld / gs default to the
+    (M, groups * N3) layout; hsave_floats to mlp3_save_floats where hsave is given; ws_bytes to what mlp3_bwd() would pass now -
+    the shared grow-only buffer, grown to this call's need."""
+    lib = _lib.load()
+    k = MLP3_CALLS.index(what)
+    three = bool(w.w2)
+    if ld is None or gs is None:
+        ld0, gs0 = (_head_layout(Y, M, N3, groups) if isinstance(Y, torch.Tensor) else (groups * N3, N3))
+        ld, gs = (ld0 if ld is None else ld), (gs0 if gs is None else gs)
+    if hsave is not None and hsave_floats is None:
+        hsave_floats = hsave.numel() if isinstance(hsave, torch.Tensor) else lib.marl_mlp3_save_floats(M, 1 if three else 0, groups)
+    if ws_bytes is None:
+        ws_bytes = lib.marl_mlp3_bwd_workspace(M, K1, N3, groups)
+        have = WS.bufs.get("mlp3")
+        if have is not None:
+            ws_bytes = max((ws_bytes + 3) // 4 * 4, have.numel() * 4)
+    plan = (C.c_int * 19)()
+    if grads is None:
+        grads = w
+    if lib.marl_mlp3_plan(k, C.byref(w), C.byref(x), _pv(Y), ld, gs, C.byref(grads), ws_bytes, _pv(hsave), hsave_floats or 0,
+                          M, K1, N3, groups, plan) != 0:
+        return None
+    p = tuple(plan)
+    return Mlp3Plan(p[1], p[2], p[3], p[4], p[5], bool(p[6]), bool(p[7]), p[8], bool(p[9]), p[10], p[11], p[12], p[13], p[14],
+                    p[15], p[16], bool(p[17]), p[18])
+
+
 # ---- fused QTRAN-base heads (csrc/qtran_fused.hip)
 def qtran_supported(N, A, AE):
     return bool(_lib.load().marl_qtran_supported(N, A, AE))

@@ -229,3 +229,57 @@ def test_qtran_plan_query():
     assert wg(8192, 4, 64)[3:] == (256, wg(1, 4, 64).lds, 1, 256) and wg(8193, 4, 64)[3:] == (256, wg(1, 4, 64).lds, 2, 256)
     assert wg(8192 + 32 * 5 + 7, 224, 80)[5:] == (2, 256) and wg(31, 4, 64)[3] == 1 and wg(8160, 4, 64)[3] == 255
     assert wg(10, 322, 74) is None and wg(10, 388, 78) is None and wg(10, 216, 81) is None and wg(10, 2, 64) is None
+
+
+def test_mlp3_plan_query():
+    """marl_mlp3_plan (a host function, no GPU: the planners the four launches of csrc/mlp3_fused.hip and csrc/mlp3_x6.hip themselves
+    decide with; integers stand for the addresses) on QPLEX's action extractors of a 2s3z-sized map - [state 120 | 5 x 11 one-hot],
+    10 heads, 3073 rows: the compile-time CF variants, the 6 + 5 stage passes of the kept backward, the stripe arithmetic with its
+    empty stripes, the LDS bytes; the bucket steps; and what the entry points refuse."""
+    from marl_amd import ops
+    from marl_amd._lib import MarlMlp3Weights, MarlSrc
+
+    def weights(three=True, b1=1 << 20):
+        w = MarlMlp3Weights()
+        w.w1 = w.w3 = w.b3 = 1 << 21
+        w.b1 = b1
+        if three:
+            w.w2 = w.b2 = 1 << 22
+        return w
+
+    def src(k0, nhot=0, hot_w=0, ld0=None, p0=4096):
+        s = MarlSrc()
+        s.p0, s.ld0, s.k0 = p0, (k0 + 3) // 4 * 4 if ld0 is None else ld0, k0
+        if nhot:
+            s.idx, s.nhot, s.hot_w = 8192, nhot, hot_w
+        return s
+    q = lambda what, M=3073, G=10, N3=5, s=None, **kw: ops.mlp3_plan(what, kw.pop("w", weights()), s or src(120, 5, 11), M,
+                                                                    ops.src_width(s or src(120, 5, 11)), N3, G, Y=1 << 24, **kw)
+    f = q("fwd", hsave=1 << 26)
+    assert f == (11, 7, 7, 0, 175, True, False, 1, True, 11, 1, 2, 24, 9, 240, (4 * 11 * 256 + 16 * 256 + 4 * 256) * 4 + 4 * 128, False, 0)
+    assert q("fwd")._replace(kept=True) == f
+    b = q("bwd", hsave=1 << 26)
+    assert (b.KC, b.CFT, b.kept, b.KH, b.passes, b.wgpc, b.nst, b.per, b.grid, b.slabs) == (11, 7, True, 6, 2, 2, 48, 2, 480, 48)
+    assert b.lds == (16 * 256 + 16 * 64 + max(16 * 6 + 64, 192 + 16) * 68) * 4 + 4 * 128
+    r = q("bwd")
+    assert (r.kept, r.KH, r.passes, r.wgpc, r.nst, r.per, r.slabs) == (False, 11, 1, 1, 24, 3, 24)
+    xf, xb = q("x6_fwd", hsave=1 << 26), q("x6_bwd", hsave=1 << 26)
+    assert (xf.KC, xf.CF, xf.CFT, xf.nst, xf.per, xf.lds) == (12, 6, 6, 24, 9, (4 * 6 + 8 + 2) * 768 * 4 + 6 * 128)
+    assert (xb.KC, xb.CFT, xb.KH, xb.passes, xb.wgpc, xb.nst, xb.per, xb.slabs) == (12, 6, 4, 3, 2, 48, 2, 48)
+    assert q("x6_bwd") is None                                         # the split backward reads kept activations only
+    for k0, kc in ((64, 4), (68, 8), (128, 8), (132, 12), (160, 12), (164, 11), (176, 11), (180, 12), (192, 12), (196, 16), (256, 16),
+                   (260, 24), (384, 24), (388, 32), (512, 32)):
+        assert q("fwd", M=65, G=2, s=src(k0)).KC == kc, k0
+    assert q("fwd", M=65, G=2, s=src(516)) is None and q("fwd", M=65, G=2, s=src(508, 1, 5)) is None          # K1 + kpad = 513
+    assert q("fwd", M=65, G=2, s=src(509)).KV == 512
+    assert q("bwd", M=65, G=2, s=src(196)) is None and q("bwd", M=65, G=2, s=src(196), hsave=1 << 26).KH == 16
+    assert q("fwd", M=65, G=2, s=src(120, ld0=121)).CF == 0 and q("fwd", M=65, G=2, s=src(120, p0=4100)).CFT == -1
+    wide = lambda s, N3=160, **kw: q("bwd", M=65, G=2, N3=N3, s=s, w=weights(False), grads=weights(False), hsave=1 << 26, **kw)
+    w24 = wide(src(322))
+    assert (w24.wide, w24.KC, w24.CF, w24.n3t, w24.lds) == (True, 24, 20, 10, 165888 - 128 * 20)
+    assert wide(src(322, ld0=323)) is None                           # CF = 0: 165 888 bytes of LDS
+    assert wide(src(322), ld=321) is None and wide(src(72), N3=162) is None
+    assert q("fwd", w=weights(b1=(1 << 20) + 4)) is None and q("fwd", hsave=(1 << 26) + 4) is None
+    assert q("fwd", hsave=1 << 26, hsave_floats=ops.mlp3_save_floats(3073, True, 10) - 1) is None
+    assert q("bwd", hsave=1 << 26, ws_bytes=8) is None and q("bwd", hsave=1 << 26, grads=weights(False)) is None
+    assert q("fwd", M=0) is None

@@ -235,6 +235,32 @@ def test_wgrad_one_output_column(dev, M, K):
     close(db - 0.25, 2.0 * dY.sum(0), 1e-3, 1e-4)
 
 
+def _mlp3_plan_is(ops, what, w, xs, Y, rows, S, K1, N3, G, nl, hs, grads=None):
+    """the plan marl_mlp3_plan reports for a call of the three tests below is the one its shape is listed for: chunk bucket, leading
+    16-byte chunks (the state rows on the 16-byte grid or not), compile-time CF variant, depth, WIDE, kept - and, for the backward,
+    the stage passes and workgroups per CU that follow from them"""
+    p = ops.mlp3_plan(what, w, xs, rows, K1, N3, G, Y=Y, grads=grads, hsave=hs)
+    assert p is not None, "the plan moved: %s refused" % what
+    KV = K1 + (-S) % 4
+    vec = xs.ld0 % 4 == 0 and xs.p0 % 16 == 0
+    if what.startswith("x6"):
+        KC, CF = (KV + 63) // 64 * 4, (S // 32 * 2 if vec else 0)
+        want = (KC, CF, 6 if (KC in (8, 12) and CF == 6) else -1, True, False, hs is not None)
+    else:
+        kc = (KV + 15) // 16
+        KC = 11 if kc == 11 else (kc + 3) // 4 * 4 if kc <= 12 else 16 if kc <= 16 else (kc + 7) // 8 * 8
+        CF = S // 16 if vec else 0
+        want = (KC, CF, 7 if (N3 <= 16 and KC in (8, 11) and CF == 7) else -1, nl == 3, N3 > 16, hs is not None)
+    assert (p.KC, p.CF, p.CFT, p.three, p.wide, p.kept) == want and (p.kpad, p.KV) == ((-S) % 4, KV), "the plan moved: %s runs %r" % (what, p)
+    if what == "bwd":
+        two = p.kept and not p.wide and KC <= 11
+        KH = 16 if KC > 24 else 6 if (two and KC > 8) else KC
+        assert (p.wgpc, p.KH, p.passes) == (2 if two else 1, KH, (KC + KH - 1) // KH), "the plan moved: %s runs %r" % (what, p)
+        units = (rows + 63) // 64
+        assert p.slabs == p.nst == max(1, min(units, max((512 if two else 256) // G // 8 * 8, 8))) and p.per == (units + p.nst - 1) // p.nst
+    return p
+
+
 @pytest.mark.parametrize("rows,S,NH,HW,N3,G,remap,nl", [(333, 120, 0, 0, 1, 10, False, 3), (1000, 120, 5, 11, 5, 10, False, 3),
                                                         (70, 24, 2, 3, 2, 3, False, 3), (4100, 120, 5, 11, 5, 4, True, 3),
                                                         (129, 72, 0, 0, 16, 2, False, 3), (50, 36, 4, 9, 3, 1, False, 3),
@@ -267,8 +293,10 @@ def test_mlp3_fused(dev, rows, S, NH, HW, N3, G, remap, nl):
         x0_src = ops.Rows(cu(store.reshape(-1, S), dev), (T, T + 1, 1), cu(emap, dev, torch.int32))
     else:
         x0 = torch.randn(rows, S, generator=g)
-        # S = 36 / 72: rows at an odd stride - no 16-byte loads, every chunk takes the element path
+        # S a multiple of 8 (24, 72, 120): contiguous rows on the 16-byte grid - S // 16 leading vector chunks
         # S = 322 with rows = 700 / 333 / 500: rows padded to 16 bytes (how the replay stores MMM2 states) - 20 vector chunks
+        # else rows one float longer than S: S = 28 / 30 / 36 / 250 / 322 at an odd stride - no 16-byte loads, every chunk takes the
+        # element path; S = 203 lands on a stride of 204 floats and keeps its 12 vector chunks
         if S % 8 == 0:
             x0_src = cu(x0, dev)
         elif S == 322 and rows > 100:
@@ -313,8 +341,13 @@ def test_mlp3_fused(dev, rows, S, NH, HW, N3, G, remap, nl):
     kept_only = ops.mlp3_needs_kept(xs, K1, N3)      # K1 > 192 or wide outputs: no recomputing backward
     assert kept_only == ((K1 + (-S) % 4 + 15) // 16 > 12 or N3 > 16)
     hs = torch.full((ops.mlp3_save_floats(rows, nl == 3, G),), float("nan"), device=dev)
+    _mlp3_plan_is(ops, "fwd", ops.mlp3_weights(heads), xs, Y, rows, S, K1, N3, G, nl, hs if kept_only else None)
     ops.mlp3_fwd(ops.mlp3_weights(heads), xs, Y, rows, K1, N3, G, hsave=hs if kept_only else None)
     dY = torch.randn(rows, G * N3, generator=g)
+    for h_ in ((hs,) if kept_only else (None, hs)):
+        _mlp3_plan_is(ops, "bwd", ops.mlp3_weights(heads), xs, cu(dY, dev), rows, S, K1, N3, G, nl, h_, ops.mlp3_weights(heads, grad=True))
+    if kept_only:
+        assert ops.mlp3_plan("bwd", ops.mlp3_weights(heads), xs, rows, K1, N3, G, Y=cu(dY, dev), grads=ops.mlp3_weights(heads, grad=True)) is None
     if kept_only:
         with pytest.raises(Exception):
             ops.mlp3_bwd(ops.mlp3_weights(heads), xs, cu(dY, dev), ops.mlp3_weights(heads, grad=True), rows, K1, N3, G)
@@ -426,6 +459,9 @@ def test_mlp3_x6_split(dev, rows, S, NH, HW, N3, G, remap):
     for x6 in (True, False):
         Y = torch.full((rows, G * N3), 7.0, device=dev)
         hs = torch.full((ops.mlp3_save_floats(rows, True, G),), float("nan"), device=dev)
+        for what in ("fwd", "bwd"):
+            _mlp3_plan_is(ops, ("x6_" if x6 else "") + what, ops.mlp3_weights(heads), xs, Y if what == "fwd" else cu(dY, dev), rows, S, K1, N3,
+                          G, 3, hs, ops.mlp3_weights(heads, grad=True))
         ops.mlp3_fwd(ops.mlp3_weights(heads), xs, Y, rows, K1, N3, G, hsave=hs, x6=x6)
         if x6:      # without keeping (target mixer): the same outputs
             Y0 = torch.full((rows, G * N3), 7.0, device=dev)
@@ -2027,6 +2063,9 @@ def test_mlp3_wide_head_in_column_blocks(dev, rows, S, N3):
     wid = N3 + 96
     hy = torch.full((rows, wid), 7.0, device=dev)
     hs = torch.empty(ops.mlp3_save_floats(rows, False, G), device=dev)
+    for what in ("fwd", "bwd"):      # WIDE kept pair on 16-byte state rows, N3 / 160 column blocks of 160 / 128 outputs, yvec stores
+        p = _mlp3_plan_is(ops, what, w, xs, hy[:, 32:32 + N3], rows, S, S, n3g, G, 2, hs, ops.mlp3_wide_head(d0, d2, grad=True)[0])
+        assert (p.n3t, p.yvec) == ((n3g + 15) // 16, what == "fwd"), "the plan moved: %r" % (p,)
     ops.mlp3_fwd(w, xs, hy[:, 32:32 + N3], rows, S, n3g, G, hsave=hs)
     assert bool((hy[:, :32] == 7).all()) and bool((hy[:, 32 + N3:] == 7).all())
     y = l2(torch.relu(l0(x)))
