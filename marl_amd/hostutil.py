@@ -2,6 +2,8 @@
 a dense-layer helper that maps an nn.Linear onto the HIP kernels, and the device batch."""
 from __future__ import annotations
 
+import weakref
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -61,6 +63,77 @@ class Scratch:
             t = (torch.zeros if zero else torch.empty)(*shape, dtype=dtype, device=device)
             self.d[key] = t
         return t
+
+    def get_flat(self, name, n, device):
+        """>= n floats, grow-only and keyed by NAME alone: the kept-activation buffers of the fused head families are gigabytes
+        at the large batches, and max_episode_len - hence `rows` - may differ from update to update (one buffer per distinct
+        shape would pile them up)."""
+        key = (name, "flat")
+        t = self.d.get(key)
+        if t is None or t.device != device or t.numel() < n:
+            if t is not None:
+                # a captured hipGraph (algorithm/common.py:GraphedUpdate) has the old buffer's address baked in: moving the
+                # shared workspace generation makes it drop the graph and capture again instead of writing into freed storage
+                ops.WS.retire()
+            t = torch.empty(max(int(n), 1), dtype=torch.float32, device=device)
+            self.d[key] = t
+        return t
+
+    def get_rows(self, name, rows, width, device):
+        """(rows, width) fp32 view whose row stride is rounded up to 4 floats: every row starts on a 16-byte boundary,
+        so the GEMM kernels take their vector-load paths (QTRAN's 78-wide intermediates)."""
+        ld = (width + 3) // 4 * 4
+        return self.get(name, (rows, ld), device)[:, :width]
+
+
+# owner -> {struct name: (tensors, their data pointers, the ctypes struct)}: the struct a launch passes by reference holds raw
+# pointers, so it is rebuilt only when a tensor's storage moved (flat-buffer adoption, .to(), load_state_dict into new storage,
+# a replaced .grad) - rebuilding it on every launch cost ~15 us, five times per update.  Weak keys: a deep copy of the owner
+# (a target network) is another object and starts without entries.
+_STRUCTS = weakref.WeakKeyDictionary()
+
+
+def _struct_hit(owner, name, tensors=None):
+    """the cached struct while every one of `tensors` (None: the tensors it was stored with) sits where it sat then, else None"""
+    c = _STRUCTS.get(owner, {}).get(name)
+    if c is not None:
+        tlist, ptrs, w = c
+        tensors = tlist if tensors is None else tensors
+        if len(tensors) == len(ptrs) and all(q.data_ptr() == o and q.is_cuda for q, o in zip(tensors, ptrs)):
+            return w
+    return None
+
+
+def _struct_store(owner, name, tensors, w):
+    _STRUCTS.setdefault(owner, {})[name] = (tensors, [q.data_ptr() for q in tensors], w)
+    return w
+
+
+def cached_struct(owner, name, tensors, build):
+    """``build()`` kept under (owner, name).  ``tensors``: exactly the tensors whose pointers build() bakes into the struct (for
+    a gradient struct the .grad tensors); when one of them has moved the struct is rebuilt.  Nothing is moved or copied here."""
+    tensors = list(tensors)
+    w = _struct_hit(owner, name, tensors)
+    return w if w is not None else _struct_store(owner, name, tensors, build())
+
+
+def cached_module_struct(module, name, build, buffers=False):
+    """``build(dict name -> tensor)`` over the module's current parameter storage (with ``buffers``: and its buffers), for the
+    agent networks.  On a miss the module is moved to the device and its parameters are made contiguous first."""
+    w = _struct_hit(module, name)
+    if w is not None:
+        return w
+    if next(module.parameters()).device.type != "cuda":
+        module.to(require_cuda("RNNQNet"))
+    tracked = dict(module.named_parameters())      # the Parameter objects: `p.data = ...` (flat-buffer adoption) shows in them
+    for v in tracked.values():
+        if not v.data.is_contiguous():
+            v.data = v.data.contiguous()
+    tensors = {k: v.data for k, v in tracked.items()}
+    if buffers:
+        tracked.update(module.named_buffers())
+        tensors.update(module.named_buffers())
+    return _struct_store(module, name, list(tracked.values()), build(tensors))
 
 
 def flatten_module(module: nn.Module, device, with_grad=False):

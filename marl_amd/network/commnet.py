@@ -24,7 +24,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .q_network import cached_struct
+from ..hostutil import cached_module_struct
 
 FRONT_A = 1      # actions of the dummy fc2 the unroll kernels are fed: the smallest count they accept
 
@@ -65,14 +65,14 @@ class CommNetAgent(nn.Module):
     # ------------------------------------------------------------------ what the ops need
     def front_weights(self):
         """marl_agent_weights_t of the recurrence: identity fc1, rnn = f_obs, the zero dummy fc2"""
-        return cached_struct(self, "front", lambda t: ops.agent_weights({
+        return cached_module_struct(self, "front", lambda t: ops.agent_weights({
             "fc1.weight": t["_front_w"], "fc1.bias": t["_front_b"], "rnn.weight_ih": t["f_obs.weight_ih"],
             "rnn.weight_hh": t["f_obs.weight_hh"], "rnn.bias_ih": t["f_obs.bias_ih"], "rnn.bias_hh": t["f_obs.bias_hh"],
             "fc2.weight": t["_dummy_w"], "fc2.bias": t["_dummy_b"]}), buffers=True)
 
     def head_weights(self):
         """marl_commnet_weights_t: f_comm and decoding"""
-        return cached_struct(self, "head", ops.commnet_weights)
+        return cached_module_struct(self, "head", ops.commnet_weights)
 
     def head_grads(self):
         """marl_commnet_grads_t over the .grad views of f_comm and decoding"""

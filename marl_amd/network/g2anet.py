@@ -31,7 +31,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from .q_network import cached_struct
+from ..hostutil import cached_module_struct
 
 TAU = 0.01       # the published temperature of the hard attention
 
@@ -105,14 +105,14 @@ class G2ANetAgent(nn.Module):
     # ------------------------------------------------------------------ what the ops need
     def front_weights(self):
         """marl_agent_weights_t of the recurrence: fc1 = encoding, rnn = h, the zero dummy fc2"""
-        return cached_struct(self, "front", lambda t: ops.agent_weights({
+        return cached_module_struct(self, "front", lambda t: ops.agent_weights({
             "fc1.weight": t["encoding.weight"], "fc1.bias": t["encoding.bias"], "rnn.weight_ih": t["h.weight_ih"],
             "rnn.weight_hh": t["h.weight_hh"], "rnn.bias_ih": t["h.bias_ih"], "rnn.bias_hh": t["h.bias_hh"],
             "fc2.weight": t["_dummy_w"], "fc2.bias": t["_dummy_b"]}), buffers=True)
 
     def head_weights(self):
         """marl_g2anet_weights_t: the sixteen tensors behind the recurrence"""
-        return cached_struct(self, "head", ops.g2anet_weights)
+        return cached_module_struct(self, "head", ops.g2anet_weights)
 
     def head_grads(self):
         """marl_g2anet_grads_t over the .grad views of the head's tensors"""

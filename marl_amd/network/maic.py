@@ -17,7 +17,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..hostutil import require_cuda
-from .q_network import RNNQNet, cached_struct
+from ..hostutil import cached_module_struct
+from .q_network import RNNQNet
 
 
 class MAICAgent(RNNQNet):
@@ -48,7 +49,7 @@ class MAICAgent(RNNQNet):
 
     def maic_weights(self):
         """marl_maic_weights_t over the current parameter and buffer storage (rebuilt only when one moved, as weights())."""
-        return cached_struct(self, "maic", ops.maic_weights, buffers=True)
+        return cached_module_struct(self, "maic", ops.maic_weights, buffers=True)
 
     def head(self, h, q, bs, test_mode, eps=None, **outs):
         """q (bs*N, A) += the gated messages from h (bs*N, 64), BatchNorm in this module's mode (csrc/maic_head.hip)"""
@@ -78,7 +79,7 @@ class MAICAgent(RNNQNet):
 
     def infer_weights(self):
         """marl_maic_infer_t over inference_net's current parameter and buffer storage"""
-        return cached_struct(self, "maic_infer", ops.maic_infer_weights, buffers=True)
+        return cached_module_struct(self, "maic_infer", ops.maic_infer_weights, buffers=True)
 
     def infer_grads(self):
         """marl_maic_infer_grads_t over inference_net's .grad views"""

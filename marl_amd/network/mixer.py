@@ -14,43 +14,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..hostutil import Lin, lin_of, require_cuda, to_dev, onehot_to_index
-
-
-class _Scratch:
-    """Cached device buffers keyed by (name, shape)."""
-
-    def __init__(self):
-        self.d = {}
-
-    def get(self, name, shape, device, dtype=torch.float32):
-        key = (name, tuple(shape), dtype)
-        t = self.d.get(key)
-        if t is None or t.device != device:
-            t = torch.empty(*shape, dtype=dtype, device=device)
-            self.d[key] = t
-        return t
-
-    def get_flat(self, name, n, device):
-        """>= n floats, grow-only and keyed by NAME alone: the kept-activation buffers of the fused head families are gigabytes
-        at the large batches, and max_episode_len - hence `rows` - may differ from update to update (one buffer per distinct
-        shape would pile them up)."""
-        key = (name, "flat")
-        t = self.d.get(key)
-        if t is None or t.device != device or t.numel() < n:
-            if t is not None:
-                # a captured hipGraph (algorithm/common.py:GraphedUpdate) has the old buffer's address baked in: moving the
-                # shared workspace generation makes it drop the graph and capture again instead of writing into freed storage
-                ops.WS.gen += 1
-            t = torch.empty(max(int(n), 1), dtype=torch.float32, device=device)
-            self.d[key] = t
-        return t
-
-    def get_rows(self, name, rows, width, device):
-        """(rows, width) fp32 view whose row stride is rounded up to 4 floats: every row starts on a 16-byte boundary,
-        so the GEMM kernels take their vector-load paths (QTRAN's 78-wide intermediates)."""
-        ld = (width + 3) // 4 * 4
-        return self.get(name, (rows, ld), device)[:, :width]
+from ..hostutil import Lin, Scratch, cached_struct, lin_of, require_cuda, to_dev, onehot_to_index
 
 
 class _Precision:
@@ -95,7 +59,7 @@ class VDNMixer(_Precision, nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
-        self._s = _Scratch()
+        self._s = Scratch()
 
     def hip_forward(self, q, s, rows, ctx=None, tag="e"):
         out = self._s.get("qtot" + tag, (rows,), q.device)
@@ -130,7 +94,7 @@ class QMixMixer(_Precision, nn.Module):
             self.hyper_w2 = nn.Linear(S, E)
         self.hyper_b1 = nn.Linear(S, E)
         self.hyper_b2 = _mlp(None, [S, E, 1])
-        self._s = _Scratch()
+        self._s = Scratch()
 
     def _fused_ok(self, xs):
         a = self.args
@@ -169,23 +133,7 @@ class QMixMixer(_Precision, nn.Module):
     def _fused_struct(self, grad=False):
         """marl_qmix_weights_t of the parameters (or their gradients), rebuilt only when a tensor's storage moved"""
         t = self._fused_tensors(grad)
-        key = tuple(v.data_ptr() for v in t.values())
-        cache = self.__dict__.setdefault("_fs_cache", {})
-        c = cache.get(grad)
-        if c is None or c[0] != key:
-            c = cache[grad] = (key, ops.qmix_weights(t))
-        return c[1]
-
-    def __deepcopy__(self, memo):
-        # the cached ctypes structs point at THIS module's storage: a copy (target mixer) starts without them
-        cls = self.__class__
-        new = cls.__new__(cls)
-        memo[id(self)] = new
-        import copy as _copy
-        for k, v in self.__dict__.items():
-            if k != "_fs_cache":
-                new.__dict__[k] = _copy.deepcopy(v, memo)
-        return new
+        return cached_struct(self, ("qmix", grad), t.values(), lambda: ops.qmix_weights(t))
 
     def hip_forward(self, q, s, rows, ctx=None, tag="e"):
         a = self.args
@@ -389,15 +337,9 @@ def _keep_hidden():
     return experiments.get("mlp3_keep") != 0
 
 
-def _head_stride(mods, attr):
-    """element stride between consecutive heads' tensors if uniform (flat parameter buffer), else None."""
-    ts = [getattr(m, attr) for m in mods]
-    if len(ts) == 1:
-        return 0
-    d = [(ts[i + 1].data_ptr() - ts[i].data_ptr()) for i in range(len(ts) - 1)]
-    if any(x != d[0] for x in d) or d[0] % 4 != 0 or d[0] <= 0:
-        return None
-    return d[0] // 4
+def _head_strides(lins):
+    """element strides (weight, bias) between the consecutive heads of a grouped marl_linear; None where not uniform"""
+    return ops.uniform_stride([l.weight for l in lins], 4), ops.uniform_stride([l.bias for l in lins], 4)
 
 
 class DMAQer(_Precision, nn.Module):
@@ -415,13 +357,13 @@ class DMAQer(_Precision, nn.Module):
         self.hyper_w_final = _mlp(None, [self.state_dim, HE, self.n_agents])
         self.V = _mlp(None, [self.state_dim, HE, self.n_agents])
         self.si_weight = DMAQ_SI_Weight(args)
-        self._s = _Scratch()
+        self._s = Scratch()
 
     # ---- grouped dense layer over the K heads of one extractor family
     def _layer(self, mods, li, x, x_gs, Y, y_gs, rows, act):
         lins = [_linears(m)[li] for m in mods]
         K = len(lins)
-        gw, gb = _head_stride(lins, "weight"), _head_stride(lins, "bias")
+        gw, gb = _head_strides(lins)
         N_, K_ = lins[0].weight.shape
         if gw is not None and gb is not None:
             grp = ops.group(K, x0=x_gs, w=gw, b=gb, y=y_gs)
@@ -592,15 +534,14 @@ class DMAQer(_Precision, nn.Module):
             dcur, dcur_gs, gate = douts[name], nout, None
             for li in range(nl - 1, -1, -1):
                 lins = [_linears(m)[li] for m in mods]
-                gw, gb = _head_stride(lins, "weight"), _head_stride(lins, "bias")
+                gw, gb = _head_strides(lins)
                 N_, K_ = lins[0].weight.shape
                 if li > 0:
                     xin, xin_gs = ops.src(hs[li - 1], k0=K_), AE
                 else:
                     xin, xin_gs = x_in, 0
                 assert gw is not None and gb is not None, "QPLEX heads must live in one flat parameter buffer"
-                ggw = _head_stride(lins, "weight")
-                grp = ops.group(K, x0=xin_gs, w=ggw, b=gb, y=dcur_gs, m0=dcur_gs)
+                grp = ops.group(K, x0=xin_gs, w=gw, b=gb, y=dcur_gs, m0=dcur_gs)
                 # gradient buffers follow the parameter layout (views of the learner's flat grad)
                 ops.linear_wgrad(dcur, xin, lins[0].weight.grad, lins[0].bias.grad, rows, N_, K_, Yact=gate, grp=grp, bf16=self._bf16())
                 if li > 0:
@@ -649,22 +590,11 @@ class _QtranFusedHead:
                 and hidden.data_ptr() % 16 == 0)
 
     def _qt_struct(self):
-        ls = self._qt_layers()
-        key = tuple(p.data_ptr() for l in ls for p in (l.weight, l.bias))
-        c = self.__dict__.get("_qt_cache")
-        if c is None or c[0] != key:
-            c = self.__dict__["_qt_cache"] = (key, ops.qtran_weights(*ls, self.args.state_shape))
-        return c[1]
-
-    def __deepcopy__(self, memo):
-        # the cached ctypes struct points at THIS module's storage: a copy (target mixer) starts without it
-        import copy as _copy
-        new = self.__class__.__new__(self.__class__)
-        memo[id(self)] = new
-        for k, v in self.__dict__.items():
-            if k != "_qt_cache":
-                new.__dict__[k] = _copy.deepcopy(v, memo)
-        return new
+        """marl_qtran_weights_t of the parameters, rebuilt only when a tensor's storage moved"""
+        layers = zip(("enc0", "enc2", "q0", "q2", "q4"), self._qt_layers())
+        t = {k + "." + a: getattr(l, a).data for k, l in layers for a in ("weight", "bias")}
+        baked = [t[name] for _, name, _ in ops.QTRAN_FIELDS]          # all but the bias of q.0 / v.0: the state part adds it
+        return cached_struct(self, "qtran", baked, lambda: ops.qtran_weights(t, self.args.state_shape))
 
     def state_part(self, s, BT, tag="e", other=None):
         """sp = W_0[:, :S] s + b_0 (BT, 64): the state columns of the head's first layer.  Independent of hidden
@@ -752,7 +682,7 @@ class QtranQBase(_QtranFusedHead, _Precision, nn.Module):
         self.hidden_action_encoding = _mlp(None, [ae, ae, ae])
         q_in = args.state_shape + args.n_actions + args.rnn_hidden_dim
         self.q = _mlp(None, [q_in, args.qtran_hidden_dim, args.qtran_hidden_dim, 1])
-        self._s = _Scratch()
+        self._s = Scratch()
 
     def _qt_layers(self):
         return tuple(_linears(self.hidden_action_encoding) + _linears(self.q))
@@ -850,7 +780,7 @@ class QtranV(_QtranFusedHead, _Precision, nn.Module):
         H = args.rnn_hidden_dim
         self.hidden_encoding = _mlp(None, [H, H, H])
         self.v = _mlp(None, [args.state_shape + H, args.qtran_hidden_dim, args.qtran_hidden_dim, 1])
-        self._s = _Scratch()
+        self._s = Scratch()
 
     def _qt_layers(self):
         return tuple(_linears(self.hidden_encoding) + _linears(self.v))

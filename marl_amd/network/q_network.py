@@ -4,43 +4,11 @@ The nn.Linear / nn.GRUCell members are parameter containers only (state_dict key
 fc2.* as in the reference); the arithmetic is the persistent HIP unroll kernel
 (marl_amd/csrc/agent.hip) called with T = 1.
 """
-import weakref
-
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..hostutil import require_cuda
-
-
-# module -> {struct name: (parameters and buffers, their data pointers, the ctypes struct)}: a struct is rebuilt only when
-# a tensor's storage moved (flat-buffer adoption, .to(), load_state_dict into new storage) - walking named_parameters()
-# on every launch cost ~15 us, five times per update
-_STRUCTS = weakref.WeakKeyDictionary()
-
-
-def cached_struct(module, name, build, buffers=False):
-    """``build(dict name -> tensor)`` over the module's current parameter storage (with ``buffers``: and its buffers).
-    On a miss the module is moved to the device and its parameters are made contiguous first."""
-    c = _STRUCTS.get(module, {}).get(name)
-    if c is not None:
-        tlist, ptrs, w = c
-        if all(q.data_ptr() == o and q.is_cuda for q, o in zip(tlist, ptrs)):
-            return w
-    if next(module.parameters()).device.type != "cuda":
-        module.to(require_cuda("RNNQNet"))
-    tracked = dict(module.named_parameters())      # the Parameter objects: `p.data = ...` (flat-buffer adoption) shows in them
-    for v in tracked.values():
-        if not v.data.is_contiguous():
-            v.data = v.data.contiguous()
-    tensors = {k: v.data for k, v in tracked.items()}
-    if buffers:
-        tracked.update(module.named_buffers())
-        tensors.update(module.named_buffers())
-    w = build(tensors)
-    tlist = list(tracked.values())
-    _STRUCTS.setdefault(module, {})[name] = (tlist, [q.data_ptr() for q in tlist], w)
-    return w
+from ..hostutil import cached_module_struct, require_cuda
 
 
 class RNNQNet(nn.Module):
@@ -56,7 +24,7 @@ class RNNQNet(nn.Module):
 
     def weights(self):
         """marl_agent_weights_t over the current parameter storage."""
-        return cached_struct(self, "agent", ops.agent_weights)
+        return cached_module_struct(self, "agent", ops.agent_weights)
 
     def forward(self, obs, hidden_state):
         """obs (rows, input_shape) already concatenated; hidden (rows, H) -> (q, h)."""

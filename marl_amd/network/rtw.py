@@ -11,7 +11,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..hostutil import require_cuda
-from .q_network import RNNQNet, cached_struct
+from ..hostutil import cached_module_struct
+from .q_network import RNNQNet
 
 
 class RTWAgent(RNNQNet):
@@ -32,7 +33,7 @@ class RTWAgent(RNNQNet):
 
     def rtw_weights(self):
         """marl_rtw_weights_t over the current parameter storage (rebuilt only when a parameter moved, as weights())."""
-        return cached_struct(self, "rtw", ops.rtw_weights)
+        return cached_module_struct(self, "rtw", ops.rtw_weights)
 
     def forward(self, inputs, hidden_state, obs, obs_next, u, avail_u, target=False, test_mode=False, agent_num=0):
         """reference RTW.py:59-203: (q, h) with test_mode, else (q, h, loss_t, loss_w) with both losses 0."""

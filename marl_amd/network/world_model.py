@@ -10,7 +10,8 @@ import torch.nn as nn
 
 from .. import ops
 from ..hostutil import require_cuda
-from .q_network import RNNQNet, cached_struct
+from ..hostutil import cached_module_struct
+from .q_network import RNNQNet
 
 
 class WorldModel(nn.Module):
@@ -36,7 +37,7 @@ class Agent(RNNQNet):
 
     def world_weights(self):
         """marl_world_weights_t over the current parameter storage (rebuilt only when a parameter moved, as weights())."""
-        return cached_struct(self, "world", ops.world_weights)
+        return cached_module_struct(self, "world", ops.world_weights)
 
     def world_grads(self):
         """marl_world_grads_t over the parameters' .grad views (the learner's flat gradient buffer)."""

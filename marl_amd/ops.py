@@ -35,6 +35,26 @@ def _i32(t):
     return t
 
 
+def _dense_on_device(t, dtype=torch.float32, align=1):
+    """t is a contiguous device tensor of `dtype` that starts on an `align`-byte boundary"""
+    return t is not None and t.is_contiguous() and t.dtype == dtype and t.is_cuda and t.data_ptr() % align == 0
+
+
+def _linear_fields(keys):
+    return [(short + suf, name + key, torch.float32) for short, name in keys for suf, key in (("_w", ".weight"), ("_b", ".bias"))]
+
+
+def _fill_struct(cls, tensors, fields):
+    """cls() with every (field, tensor name, dtype) of `fields` set to the data pointer of tensors[name]"""
+    w = cls()
+    for field, name, dt in fields:
+        t = tensors[name]
+        assert _dense_on_device(t, dt), name
+        setattr(w, field, t.data_ptr())
+    w._keep = tensors
+    return w
+
+
 class Workspace:
     """Grow-only scratch buffers keyed by name (no allocation in steady state).  ``gen`` counts (re)allocations:
     a captured hipGraph holds raw pointers into these buffers, so its owner records ``gen`` at capture time, keeps
@@ -51,8 +71,12 @@ class Workspace:
         if b is None or b.numel() < n or b.device != device:
             b = torch.empty(max(n, 1), dtype=torch.float32, device=device)
             self.bufs[name] = b
-            self.gen += 1
+            self.retire()
         return b
+
+    def retire(self):
+        """a buffer whose address a captured graph may hold has been replaced, here or in a hostutil.Scratch.get_flat"""
+        self.gen += 1
 
     def snapshot(self):
         return list(self.bufs.values())
@@ -197,17 +221,14 @@ def linear_wgrad_plan(dY, lddy, x, M, N, K, Yact=None, ldya=0, grp=None, bf16=Fa
     return WgradPlan(WGRAD_FAMILIES[p[0]], (p[1], p[2]), p[3], p[4], bool(p[5]), bool(p[6]), p[7])
 
 
+_AGENT_FIELDS = _linear_fields((("fc1", "fc1"), ("fc2", "fc2"))) + [
+    (field, "rnn." + name, torch.float32) for field, name in (("w_ih", "weight_ih"), ("w_hh", "weight_hh"), ("b_ih", "bias_ih"), ("b_hh", "bias_hh"))]
+
+
 def agent_weights(params):
     """params: dict name -> tensor with RNNQNet keys."""
-    w = MarlAgentWeights()
-    w.fc1_w, w.fc1_b = params["fc1.weight"].data_ptr(), params["fc1.bias"].data_ptr()
-    w.w_ih, w.w_hh = params["rnn.weight_ih"].data_ptr(), params["rnn.weight_hh"].data_ptr()
-    w.b_ih, w.b_hh = params["rnn.bias_ih"].data_ptr(), params["rnn.bias_hh"].data_ptr()
-    w.fc2_w, w.fc2_b = params["fc2.weight"].data_ptr(), params["fc2.bias"].data_ptr()
+    w = _fill_struct(MarlAgentWeights, params, _AGENT_FIELDS)
     w.H = params["rnn.weight_hh"].shape[1]
-    for k in ("fc1.weight", "rnn.weight_ih", "rnn.weight_hh", "fc2.weight"):
-        assert params[k].is_contiguous() and params[k].dtype == torch.float32 and params[k].is_cuda
-    w._keep = params
     return w
 
 
@@ -758,13 +779,7 @@ def qmix_fused_supported(N, S, E):
 
 def qmix_weights(t):
     """t: dict with tensors w1,w1_b,b1,b1_b,w2,w2_b,h,h_b,b2_w,b2_b (weights or their gradients)."""
-    w = MarlQmixWeights()
-    for k in ("w1", "w1_b", "b1", "b1_b", "w2", "w2_b", "h", "h_b", "b2_w", "b2_b"):
-        v = t[k]
-        assert v.is_contiguous() and v.dtype == torch.float32 and v.is_cuda
-        setattr(w, k, v.data_ptr())
-    w._keep = t
-    return w
+    return _fill_struct(MarlQmixWeights, t, [(k, k, torch.float32) for k, _ in MarlQmixWeights._fields_])
 
 
 def qmix_fused_fwd(w, s, q, q_tot, rows, N, S, E, x6=False):
@@ -829,12 +844,13 @@ def qmix_wide_bwd(w, s, q, dq_tot, dq, grads, rows, N, S, E, bf16=False, wgrad_b
                                  ws.numel() * 4, rows, N, S, E, _wide_flags(bf16, wgrad_bf16), _stream()), "marl_qmix_wide_bwd")
 
 
-def _uniform_stride(ts):
-    """element stride between consecutive heads' tensors (one flat parameter buffer), None if not uniform."""
+def uniform_stride(ts, align):
+    """element stride between consecutive heads' fp32 tensors (one flat parameter buffer; 0 for a single head), None if it is
+    not uniform, not positive or not a multiple of `align` bytes: 16 for the fused heads (vector loads), 4 for grouped marl_linear"""
     if len(ts) == 1:
         return 0
     d = [ts[i + 1].data_ptr() - ts[i].data_ptr() for i in range(len(ts) - 1)]
-    if any(x != d[0] for x in d) or d[0] <= 0 or d[0] % 16 != 0:
+    if any(x != d[0] for x in d) or d[0] <= 0 or d[0] % align != 0:
         return None
     return d[0] // 4
 
@@ -851,10 +867,10 @@ def mlp3_weights(heads, grad=False):
     for li, (wn, bn) in enumerate(names):
         for name, attr in ((wn, "weight"), (bn, "bias")):
             ts = [pick(getattr(h[li], attr)) for h in heads]
-            if any(t is None or not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda for t in ts):
+            if not _dense_on_device(ts[0], align=16) or not all(_dense_on_device(t) for t in ts):
                 return None
-            st = _uniform_stride(ts)
-            if st is None or ts[0].data_ptr() % 16 != 0:
+            st = uniform_stride(ts, 16)
+            if st is None:
                 return None
             setattr(w, name, ts[0].data_ptr())
             setattr(w, "gs_" + name, st)
@@ -868,7 +884,7 @@ def mlp3_wide_head(l0, l2, grad=False):
     ``groups`` column blocks that share layer 1: returns (marl_mlp3_weights_t, groups, outputs per group) or None."""
     pick = (lambda p: p.grad) if grad else (lambda p: p.data)
     ts = [pick(l0.weight), pick(l0.bias), pick(l2.weight), pick(l2.bias)]
-    if any(t is None or not t.is_contiguous() or t.dtype != torch.float32 or not t.is_cuda or t.data_ptr() % 16 for t in ts):
+    if not all(_dense_on_device(t, align=16) for t in ts):
         return None
     N3 = l2.out_features
     G = (N3 + 159) // 160
@@ -973,16 +989,14 @@ def qtran_supported(N, A, AE):
     return bool(_lib.load().marl_qtran_supported(N, A, AE))
 
 
-def qtran_weights(enc0, enc2, q0, q2, q4, S):
-    """nn.Linear layers of hidden(_action)_encoding.{0,2} and q.{0,2,4} (or hidden_encoding / v) -> marl_qtran_weights_t"""
-    w = MarlQtranWeights()
-    for name, lin in (("enc0", enc0), ("enc2", enc2), ("q2", q2), ("q4", q4)):
-        for suf, t in (("_w", lin.weight.data), ("_b", lin.bias.data)):
-            assert t.is_contiguous() and t.dtype == torch.float32 and t.is_cuda
-            setattr(w, name + suf, t.data_ptr())
-    assert q0.weight.data.is_contiguous()
-    w.q0_w, w.q0_ld, w.q0_s = q0.weight.data.data_ptr(), q0.weight.shape[1], S
-    w._keep = (enc0, enc2, q0, q2, q4)
+QTRAN_FIELDS = _linear_fields((k, k) for k in ("enc0", "enc2", "q2", "q4")) + [("q0_w", "q0.weight", torch.float32)]
+
+
+def qtran_weights(t, S):
+    """t: dict with the tensors of QTRAN_FIELDS - enc0 / enc2: hidden(_action)_encoding.{0,2}; q0 / q2 / q4: q.{0,2,4} (or
+    hidden_encoding / v); q.0 gives its weight only -> marl_qtran_weights_t"""
+    w = _fill_struct(MarlQtranWeights, t, QTRAN_FIELDS)
+    w.q0_ld, w.q0_s = t["q0.weight"].shape[1], S
     return w
 
 
@@ -1074,21 +1088,6 @@ RTW_KEYS = (("t0", "teammate_net.0"), ("t2", "teammate_net.2"), ("w0", "world_ne
 
 def rtw_supported(N, O, A, H=64, hidden_dim=64, attn_dim=64):
     return bool(_lib.load().marl_rtw_supported(N, O, A, H, hidden_dim, attn_dim))
-
-
-def _linear_fields(keys):
-    return [(short + suf, name + key, torch.float32) for short, name in keys for suf, key in (("_w", ".weight"), ("_b", ".bias"))]
-
-
-def _fill_struct(cls, tensors, fields):
-    """cls() with every (field, tensor name, dtype) of `fields` set to the data pointer of tensors[name]"""
-    w = cls()
-    for field, name, dt in fields:
-        t = tensors[name]
-        assert t.is_contiguous() and t.dtype == dt and t.is_cuda, name
-        setattr(w, field, t.data_ptr())
-    w._keep = tensors
-    return w
 
 
 def rtw_weights(params):

@@ -3,6 +3,9 @@ the ctypes table lists exactly those symbols.  No compute is called."""
 import ctypes
 import os
 import re
+import shutil
+import struct
+import subprocess
 
 import pytest
 
@@ -13,6 +16,30 @@ def declared_symbols():
     txt = open(os.path.join(ROOT, "include", "marl_hip.h")).read()
     txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
     return sorted(set(re.findall(r"\b(marl_[a-z0-9_]+)\s*\(", txt)))
+
+
+def exported_symbols(path):
+    """names of the defined symbols in the dynamic symbol table of an ELF64 little-endian shared object"""
+    blob = open(path, "rb").read()
+    assert blob[:6] == b"\x7fELF\x02\x01", "not a 64-bit little-endian ELF file"
+    shoff, = struct.unpack_from("<Q", blob, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
+    secs = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, sh_type, _, _, off, size, link, _, _, entsize in secs:
+        if sh_type == 11:                                   # SHT_DYNSYM; its sh_link is the string table
+            strtab = secs[link][4]
+            for k in range(size // entsize):
+                st_name, _, _, st_shndx = struct.unpack_from("<IBBH", blob, off + k * entsize)
+                if st_shndx != 0:                           # defined here, not imported
+                    names.add(blob[strtab + st_name:blob.index(b"\0", strtab + st_name)].decode())
+    return names
+
+
+# exported with C linkage but no part of the C ABI: the accessor of the experiment-switch table that the library's own objects
+# share (csrc/common.h declares it, optim.hip defines it; it returns a C++ struct the public header does not know).  Callers use
+# marl_experiment_set / marl_experiment_get.
+LIBRARY_INTERNAL = {"marl_switches"}
 
 
 def test_library_exports_every_declared_symbol():
@@ -26,8 +53,116 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(lib, s), "missing export " + s
     assert set(_lib.SIGNATURES) == set(syms), set(_lib.SIGNATURES) ^ set(syms)
+    # ... and the other way round: nothing the library exports under the project's prefix is without a signature
+    exported = {s for s in exported_symbols(_lib.LIB_PATH) if s.startswith("marl_")}
+    assert LIBRARY_INTERNAL <= exported                        # (the exception list cannot go stale)
+    assert exported - LIBRARY_INTERNAL == set(_lib.SIGNATURES), exported ^ set(_lib.SIGNATURES)
     _lib.load()
     assert b"gfx950" in _lib.load().marl_hip_version()
+
+
+def _host_cc():
+    """the host C compiler: cc, else the clang that ships beside hipcc"""
+    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
+    beside = os.path.dirname(os.path.realpath(hipcc))
+    for c in ("cc", os.path.join(beside, "clang"), os.path.join(beside, "amdclang"),
+              os.path.join(beside, "..", "lib", "llvm", "bin", "clang")):
+        if shutil.which(c):
+            return shutil.which(c)
+    return None
+
+
+def test_struct_layouts_match_the_host_c_compiler(tmp_path):
+    """sizeof / offsetof of every struct of the header as the C compiler lays it out, against the ctypes classes _lib derives
+    from the same header.  The C side never passes through _lib's type mapping: a reader that takes a `long` for an `int` (or drops
+    a field) shows here as a moved offset."""
+    from marl_amd import _lib
+    cc = _host_cc()
+    assert cc is not None, "no host C compiler (cc, or clang beside hipcc): build() needs one as well"
+    assert len(_lib.STRUCTS) >= 18 and _lib.STRUCTS["marl_src_t"] is _lib.MarlSrc
+    assert _lib.STRUCTS["marl_maic_infer_grads_t"] is _lib.MarlMaicInferGrads and _lib.MarlG2anetWeights.__name__ == "MarlG2anetWeights"
+    prog = ["#include <stdio.h>", "#include <stddef.h>", '#include "marl_hip.h"', "int main(void) {"]
+    want = {}
+    for cname, cls in _lib.STRUCTS.items():
+        prog.append('  printf("%s %%zu\\n", sizeof(%s));' % (cname, cname))
+        want[cname] = ctypes.sizeof(cls)
+        for field, _ in cls._fields_:
+            prog.append('  printf("%s.%s %%zu\\n", offsetof(%s, %s));' % (cname, field, cname, field))
+            want[cname + "." + field] = getattr(cls, field).offset
+    prog += ["  return 0;", "}", ""]
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text("\n".join(prog))
+    subprocess.run([cc, "-I", os.path.join(ROOT, "include"), "-o", str(exe), str(src)], check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout
+    got = {k: int(v) for k, v in (line.split() for line in out.splitlines())}
+    assert got == want
+    assert got["marl_src_t"] == 144 and got["marl_src_t.emap0"] == 136          # (a 64-bit host: what the library is built for)
+
+
+DEMO_HEADER = """/* a comment
+ * over two lines */
+#ifndef DEMO_H
+#define DEMO_H
+#include <stddef.h>
+#ifdef __cplusplus
+extern "C" {
+#endif
+typedef struct {
+  const float *a, *b;   /* two declarators on one line */
+  long long* n;
+  long x, y; int k;
+} marl_demo_t;
+#define MARL_DEMO_FLAG 1   /* a constant */
+int marl_demo(const marl_demo_t* w, marl_demo_t* g, const char* name, const long long* idx, unsigned k, size_t n,
+              double d, float f, long m, const void* y, void* stream);
+size_t marl_demo_bytes(int n);
+const char* marl_demo_version(void);
+#ifdef __cplusplus
+}
+#endif
+#endif
+"""
+
+
+def test_header_reader_reads_the_headers_grammar_and_nothing_else():
+    """parse_header on a small header: the positive cases (several declarators on a line, `long long*`, struct pointers, const char*),
+    then one foreign construct at a time - each must raise and name the line it stands on, never guess."""
+    from marl_amd import _lib
+    P, I, L, F, U, SZ, D = _lib.P, _lib.I, _lib.L, _lib.F, _lib.U, _lib.SZ, _lib.D
+    structs, sigs = _lib.parse_header(DEMO_HEADER)
+    demo = structs["marl_demo_t"]
+    assert list(structs) == ["marl_demo_t"] and demo.__name__ == "MarlDemo" and issubclass(demo, ctypes.Structure)
+    assert demo._fields_ == [("a", P), ("b", P), ("n", P), ("x", L), ("y", L), ("k", I)]
+    assert sigs == {"marl_demo": (I, [ctypes.POINTER(demo), ctypes.POINTER(demo), ctypes.c_char_p, P, U, SZ, D, F, L, P, P]),
+                    "marl_demo_bytes": (SZ, [I]), "marl_demo_version": (ctypes.c_char_p, [])}
+
+    def refused(old, new, line, word):
+        assert DEMO_HEADER.count(old) == 1
+        with pytest.raises(_lib.MarlHipError, match=r"line %d: .*%s" % (line, word)):
+            _lib.parse_header(DEMO_HEADER.replace(old, new))
+    refused("long x, y;", "short x, y;", 12, "short")                                      # an unknown scalar type: a field ...
+    refused("unsigned k, size_t n", "unsigned k, uint64_t n", 15, "uint64_t")              # ... and an argument
+    refused("marl_demo_t* g,", "marl_demo_t g,", 15, "marl_demo_t g")                      # a struct by value
+    refused("size_t marl_demo_bytes(int n);", "size_t marl_demo_bytes(int (*cb)(int), int n);", 17, "marl_demo_bytes")   # cannot be split
+    refused("size_t marl_demo_bytes(int n);", "size_t marl_demo_bytes(int n[4]);", 17, r"n\[4\]")
+    refused("size_t marl_demo_bytes(int n);", "size_t marl_demo_bytes(int);", 17, "int")          # (every argument is named)
+    refused("const char* marl_demo_version", "char* marl_demo_version", 18, "char")
+    refused("float f, long m", "float** f, long m", 16, "float")
+    refused("const void* y", "const marl_other_t* y", 16, "marl_other_t")                   # a struct the header does not define
+    refused("#define MARL_DEMO_FLAG 1 ", "#define MARL_DEMO_FLAG \\\n 1 ", 14, "MARL_DEMO_FLAG")
+    refused("} marl_demo_t;", "} demo_t;", 9, "typedef")
+
+
+def test_header_is_found_beside_the_package():
+    from marl_amd import _lib
+    assert os.path.samefile(_lib.HEADER_PATH, os.path.join(ROOT, "include", "marl_hip.h"))
+    missing = os.path.join(ROOT, "include", "no_such_header.h")
+    old, _lib.HEADER_PATH = _lib.HEADER_PATH, missing
+    try:
+        with pytest.raises(_lib.MarlHipError, match="not found"):
+            _lib._read_header()
+    finally:
+        _lib.HEADER_PATH = old
 
 
 def test_product_fails_loudly_without_gpu():

@@ -53,6 +53,67 @@ def test_scratch_is_one_class_and_zero_fills_at_allocation_only():
     assert buf.get("z", (3, 2), cpu) is not z and buf.get("z", (2, 3), cpu, torch.int32) is not z   # one per (name, shape, dtype)
 
 
+def test_scratch_row_and_flat_buffers():
+    """The one Scratch class behind the learners, the controllers and the mixers: `get` hands back the same tensor for the same
+    (name, shape, dtype); `get_rows` pads the row pitch to 16 bytes; `get_flat` is keyed by name alone, only grows, and moves the
+    shared workspace generation exactly when it REPLACES a buffer (a captured graph holds the old address)."""
+    from marl_amd import hostutil, ops
+    buf, cpu = hostutil.Scratch(), torch.device("cpu")
+    a = buf.get("a", (3, 5), cpu)
+    assert buf.get("a", (3, 5), cpu) is a and buf.get("a", [3, 5], cpu, torch.float32) is a
+    r = buf.get_rows("r", 7, 78, cpu)
+    assert r.shape == (7, 78) and r.dtype == torch.float32 and r.stride() == (80, 1) and r.stride(0) * r.element_size() % 16 == 0
+    assert buf.get_rows("r", 7, 78, cpu).data_ptr() == r.data_ptr()
+    assert buf.get_rows("r4", 7, 64, cpu).stride() == (64, 1)                   # already a multiple of 4 floats: no pad
+    gen = ops.WS.gen
+    f = buf.get_flat("f", 10, cpu)
+    assert f.dtype == torch.float32 and f.dim() == 1 and f.numel() >= 10 and ops.WS.gen == gen      # a first allocation replaces nothing
+    assert buf.get_flat("f", 4, cpu) is f and buf.get_flat("f", 10, cpu) is f and buf.get_flat("f", 0, cpu) is f and ops.WS.gen == gen
+    f2 = buf.get_flat("f", 11, cpu)
+    assert f2 is not f and f2.numel() >= 11 and ops.WS.gen == gen + 1
+    assert buf.get_flat("f", 10, cpu) is f2 and ops.WS.gen == gen + 1           # grow-only
+    assert buf.get_flat("h", 0, cpu).numel() >= 1 and buf.get_flat("h", 1, cpu) is not f2 and ops.WS.gen == gen + 1
+    ops.WS.retire()
+    assert ops.WS.gen == gen + 2
+
+
+def test_struct_cache_follows_the_pointers_and_not_the_copies():
+    """hostutil.cached_struct: one entry per (owner, name), rebuilt exactly when a tracked pointer has moved; a deep copy of the
+    owner (a target mixer) starts without entries, and an owner that goes away takes its entries along."""
+    import copy
+    import gc
+    from marl_amd import hostutil
+
+    class At:          # stands for a device tensor at an address
+        is_cuda = True
+
+        def __init__(self, ptr):
+            self.ptr = ptr
+
+        def data_ptr(self):
+            return self.ptr
+
+    class Owner:
+        pass
+    owner, built = Owner(), []
+
+    def build():
+        built.append(object())
+        return built[-1]
+    a = hostutil.cached_struct(owner, "w", [At(16), At(32)], build)
+    assert hostutil.cached_struct(owner, "w", [At(16), At(32)], build) is a and len(built) == 1      # fresh tensor objects, same storage
+    b = hostutil.cached_struct(owner, "w", [At(16), At(48)], build)
+    assert b is not a and len(built) == 2 and hostutil.cached_struct(owner, "w", [At(16), At(48)], build) is b
+    g = hostutil.cached_struct(owner, ("w", True), [At(64), At(80)], build)                          # e.g. the gradient struct
+    assert g is not b and len(built) == 3 and hostutil.cached_struct(owner, "w", [At(16), At(48)], build) is b
+    twin = copy.deepcopy(owner)
+    assert hostutil.cached_struct(twin, "w", [At(16), At(48)], build) is not b and len(built) == 4
+    n = len(hostutil._STRUCTS)
+    del owner, twin
+    gc.collect()
+    assert len(hostutil._STRUCTS) == n - 2
+
+
 DROPIN_TOP = ("rollout", "runner", "controller", "algorithm", "common", "network", "env", "utils", "smac")
 
 
