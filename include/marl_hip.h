@@ -607,6 +607,35 @@ int marl_policy_sample(const float* logits, const float* avail, long avail_es, c
                        unsigned rseed, int env0, const int* tg, int tg0, int* act_out, long act_es,
                        int E, int N, int A, void* stream);
 
+/* ---- MAPPO: the clipped surrogate (policy.hip) and advantage standardisation (ppo.hip) -----------
+ * marl_ppo_loss_bwd: marl_policy_loss_bwd_ex's pass under PPO's clipped surrogate.  Rows, m, "has a policy", pi, log pi, H and
+ * their gradients (eps mixing included) are marl_policy_loss_bwd_ex's.  adv (rows / N) stands where G / v stood (a constant of the
+ * gradient), logp_old (rows) is log pi(u) under the policy the batch's first pass saw (NULL: that pass itself), clip = c in (0, 1).
+ * For a row with a policy and m = 1:
+ *   rho = exp(min(logp - logp_old, 80))  (logp_old NULL: rho = 1 exactly),
+ *   s = rho adv,  k = clamp(rho, 1 - c, 1 + c) adv,  clipped = k < s  (the minimum takes the clamped term, strictly),
+ *   L_row = - min(s, k) - beta H,
+ *   dlogits = - (clipped ? 0 : adv rho) d log pi(u) / dz - beta dH / dz,
+ *   logp[r] = log pi_r(u_r),  ent[r] = H_r (ent may be NULL),
+ *   out4 = { sum m L_row,  sum_r m = N sum m,  sum m H,  sum m [clipped] }  (un-normalised).
+ * A row with m = 0 or without a policy contributes nothing, its dlogits are exact zeros, logp = ent = 0, and its logits and
+ * logp_old are never looked at (nor is a padded step's adv).  A row with one available action has rho = 1 and no gradient; it
+ * still contributes - adv to the numerator.  logp comes from the row's scalars before the one gradient walk, whose scale is
+ * - m adv rho (0 when clipped).  With logp_old NULL, dlogits, logp and ent are marl_policy_loss_bwd_ex's with G = adv and v NULL
+ * bit for bit, and out4[3] = 0.  fp32, fixed-order sums, no float atomics: two calls give the same bits.  ws: marl_loss_workspace()
+ * bytes (four partials per workgroup).  dlogits may be logits itself, not avail; logp may be logp_old.  A NULL required pointer,
+ * rows % N != 0, c outside (0, 1), beta < 0 or dlogits == avail: hipErrorInvalidValue.  rows <= 0: returns 0, no launch.
+ *
+ * marl_masked_standardize: over x (rows) and padded (rows), m = 1 - padded, M = sum m:
+ *   mean = sum m x / M,  var = sum m (x - mean)^2 / M  (a pass each: never E[x^2] - mean^2),  out = m (x - mean) / (sqrt(var) + 1e-5).
+ * Padded rows get exact zeros and their x is never looked at; M = 0 gives all zeros and stats3 = 0.  stats3 = { mean, var, M }.
+ * out may be x itself, not padded.  ws: marl_loss_workspace() bytes.  Fixed-order sums: two calls give the same bits.
+ * rows <= 0: returns 0, no launch. */
+int marl_ppo_loss_bwd(const float* logits, const float* avail, const int* u, const float* adv, const float* logp_old,
+                      const float* padded, float eps, float beta, float clip, float* dlogits, float* logp, float* ent,
+                      float* out4, float* ws, long rows, int N, int A, void* stream);
+int marl_masked_standardize(const float* x, const float* padded, float* out, float* stats3, float* ws, long rows, void* stream);
+
 /* ---- COMA: the counterfactual critic (coma.hip; the reference ships the argument table only - the definitions are this
  * project's own, from the published algorithm) ----------------------------------------------------------------------------
  * Rows r = (b T + t) N + i: agent i at step t of episode b; R = B T N; u (R) int32 the taken actions; D = critic_dim.  The critic is

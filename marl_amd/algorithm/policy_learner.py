@@ -5,8 +5,9 @@ optimizer of ``args.optimizer``'s kind at lr_actor, the eval unroll with saved p
 backward on the dense gradient of the logits at its end, the entropy weight beta = ``args.policy_entropy_coef``, eager launches (no
 hipGraph replay, no launch ahead of max_episode_len), one rank, no target actor.  A learner with a critic defines ``_make_critic``:
 the frame then keeps the critic and its target copy in flat buffers of their own, a second optimizer at lr_critic, the target sync
-every ``target_update_cycle`` updates, the critic's model file and its part of the resume state.  A learner provides
-``_forward_backward(db)`` between ``_actor_unroll`` and ``_actor_backward``.
+every ``target_update_cycle`` updates, the critic's model file and its part of the resume state.  A learner whose critic
+bootstraps from itself sets ``has_target_critic = False`` (PPOLearner): no target copy is built, synced or carried in the resume
+state.  A learner provides ``_forward_backward(db)`` between ``_actor_unroll`` and ``_actor_backward``.
 """
 from __future__ import annotations
 
@@ -31,6 +32,7 @@ class PolicyLearner(Learner):
     mixer = target_mixer = None
     critic = target_critic = None
     _make_critic = None           # a learner with a critic: _make_critic(args) -> the nn.Module (and "critic" in extra_nets)
+    has_target_critic = True      # False (PPOLearner): the critic has no target copy
     _no_q_table = None            # the sentence get_q_and_q_tot_table refuses with
 
     def __init__(self, mac, args):
@@ -52,7 +54,8 @@ class PolicyLearner(Learner):
         self.eval_net.cuda()
         if self._make_critic is not None:
             self.critic = self._make_critic(args)
-            self.target_critic = copy.deepcopy(self.critic)
+            if self.has_target_critic:
+                self.target_critic = copy.deepcopy(self.critic)
         self.cuda()
         self.optimizer = FusedOptimizer(self._flat, args.optimizer, args.lr_actor, args.grad_norm_clip)
         if self.critic is not None:
@@ -75,7 +78,8 @@ class PolicyLearner(Learner):
         self.eval_net.agent.to(dev)
         if self.critic is not None:
             self.critic.to(dev)
-            self.target_critic.to(dev)
+            if self.target_critic is not None:
+                self.target_critic.to(dev)
         self.params = list(self.eval_net.parameters())
         self._flat = LearnerParams(self.params, dev)                              # the actor's buffer: stats = {numerator, N M, sum m H}
         self.eval_net.agent._flat = FlatView(self._flat.flat, self.eval_net.agent.parameters(), 0)
@@ -83,7 +87,8 @@ class PolicyLearner(Learner):
         if self.critic is not None:
             self._cflat = LearnerParams(list(self.critic.parameters()), dev)      # the critic's: stats = {numerator, denominator}
             self.critic._flat = FlatView(self._cflat.flat, self.critic.parameters(), 0)
-            flatten_module(self.target_critic, dev)
+            if self.target_critic is not None:
+                flatten_module(self.target_critic, dev)
 
     def _update_targets(self):
         self.target_critic._flat.flat.copy_(self._cflat.flat)
@@ -126,7 +131,7 @@ class PolicyLearner(Learner):
             cs = self._cflat.stats
             self.critic_optimizer.step(den=cs[1:2])
         self.optimizer.step(den=st[1:2])
-        if cs is not None and train_step > 0 and train_step % self.args.target_update_cycle == 0:
+        if self.target_critic is not None and train_step > 0 and train_step % self.args.target_update_cycle == 0:
             self._update_targets()
         self.last_stats, self.actor_stats = (st if cs is None else cs), st
         if cs is not None:
@@ -141,7 +146,7 @@ class PolicyLearner(Learner):
     # ------------------------------------------------------------------ resume state (checkpoints: Learner's, no mixer file)
     def _target_flats(self):
         """ResumeMixin: there is no target actor"""
-        return {} if self.critic is None else {"target_critic": self.target_critic._flat.flat}
+        return {} if self.target_critic is None else {"target_critic": self.target_critic._flat.flat}
 
     def resume_state(self):
         sd = super().resume_state()

@@ -34,6 +34,11 @@ def get_common_args(argv=None):
     # the +g2anet actors: hard attention on / off and its temperature; absent = get_g2anet_args' True and the published 0.01
     p.add_argument('--g2anet_hard', type=_bool, default=None)
     p.add_argument('--g2anet_tau', type=float, default=None)
+    # --alg mappo: the surrogate's clip c in (0, 1), the passes over one rollout and whether the advantage is standardised over the
+    # live steps; absent = get_mappo_args' 0.2, 5 and True
+    p.add_argument('--ppo_clip', type=float, default=None)
+    p.add_argument('--ppo_epochs', type=int, default=None)
+    p.add_argument('--ppo_norm_adv', type=_bool, default=None)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')
@@ -130,6 +135,14 @@ def get_coma_args(args):
 def get_centralv_args(args):
     """reference :151-177"""
     return _assign(args, dict(_ACTOR_CRITIC, td_lambda=0.8, target_update_cycle=200))
+
+
+def get_mappo_args(args):
+    """This project's own table (the reference ships none for PPO): the actor-critic fields of central-V, td_lambda = 0.95 (with
+    adv = G - V that is GAE(0.95)), clip 0.2, five passes over a rollout, standardised advantages.  There is no target network, so
+    no target_update_cycle is set here.  ``args.optimizer`` stays as given: the MAPPO paper's Adam at 5e-4 is not imposed - the
+    learning rates are the table's lr_actor / lr_critic with whichever optimizer the user named."""
+    return _assign(args, dict(_ACTOR_CRITIC, td_lambda=0.95, ppo_clip=0.2, ppo_epochs=5, ppo_norm_adv=True))
 
 
 def get_reinforce_args(args):

@@ -1,5 +1,5 @@
-// Stochastic policy head of the policy-gradient learners (central-V, REINFORCE; include/marl_hip.h has the definition).  A row is one agent at one
-// step: logits z (A, the agent's fc2 output), availability a in {0,1}^A, exploration rate eps:
+// Stochastic policy head of the policy-gradient learners (central-V, REINFORCE, MAPPO; include/marl_hip.h has the definition).
+// A row is one agent at one step: logits z (A, the agent's fc2 output), availability a in {0,1}^A, exploration rate eps:
 //   p = softmax(z),  n = sum a,  pt_k = a_k ((1 - eps) p_k + eps / n),  pi_k = pt_k / sum_j pt_j.
 // The kernels shift by mx = the largest AVAILABLE logit (any shift gives the same p): with e_k = exp(min(z_k - mx, 80)),
 // S = sum e, Sa = sum a e, w_k = (1 - eps) e_k + eps S / n and D = (1 - eps) Sa + eps S the policy is pi_k = a_k w_k / D, where
@@ -14,6 +14,7 @@
 // workgroup barrier.  The LDS walk is at a lane stride of A dwords: conflict-free for odd A, two-way for A = 14 or 18.  From
 // A = 29 the tiles of four waves pass 56 KiB and the row-per-lane kernel runs instead (same arithmetic in the same order).
 // The sampler runs once per lock-step over E N rows (25 600 at most in the measured set-ups): one lane per row, like select_kernel.
+#include <type_traits>
 #include "synth_env.h"
 #include "policy_rows.h"
 #include "../../include/marl_hip.h"
@@ -31,6 +32,13 @@ struct PolicyArgs {
   long rows;
   int N, A, vec;
 };
+// ppo_loss_bwd: G holds adv and v is unused.  Its two scalars ride behind PolicyArgs in a type of their own, so that the kernel
+// argument of the other instantiations is the struct it was (and their code with it)
+struct PpoArgs : PolicyArgs {
+  const float* logp_old;             // (rows) or NULL
+  float clip;                        // c in (0, 1)
+};
+template <bool PPO> using ArgsOf = std::conditional_t<PPO, PpoArgs, PolicyArgs>;
 
 // one row of the loss: m = 1 - padded, Adv = G - v of the row's (episode, step); out = -m Adv d log pi_u / dz
 __device__ __forceinline__ void loss_row(const PolicyArgs& p, long r, const float* z, const float* a, float* out, float (&acc)[2]) {
@@ -68,16 +76,49 @@ __device__ __forceinline__ void loss_row_ex(const PolicyArgs& p, long r, const f
   acc[1] += m;
 }
 
-// EX (with LOSS): loss_row_ex and its three partial sums
-template <bool LOSS, bool EX = false>
-__global__ __launch_bounds__(TPB) void policy_tiled_kernel(PolicyArgs p) {
+// loss_row_ex's row under the clipped surrogate: Adv = adv[bt], rho = exp(log pi_u - logp_old) (1 exactly without logp_old, and on a
+// row with one available action), s = rho Adv, k = clamp(rho, 1 - c, 1 + c) Adv, clipped = k < s.  log pi_u comes from the row
+// scalars (one exp and two logs beside row_policy's walk), so that the gradient walk already knows its scale:
+// out = -(clipped ? 0 : m Adv rho) d log pi_u / dz - beta m dH / dz,  acc = { -m min(s, k) - beta m H, m, m H, m [clipped] }
+__device__ __forceinline__ void loss_row_ppo(const PpoArgs& p, long r, const float* z, const float* a, float* out, float (&acc)[4]) {
+  const long bt = r / p.N;
+  const float m = 1.f - p.padded[bt];
+  float lp = 0.f, H = 0.f;
+  if (m == 0.f) {
+    for (int k = 0; k < p.A; ++k) out[k] = 0.f;          // a padded step: its logits, adv and logp_old are never looked at
+  } else {
+    const float adv = p.G[bt];
+    const int u = p.u[r];
+    const RowPolicy rp = row_policy(z, a, p.A, p.eps);
+    float rho = 1.f;
+    if (p.logp_old && rp.n > 1 && u >= 0 && u < p.A && a[u] != 0.f) {
+      const float wu = rp.cw * row_e(rp, z[u]) + rp.ew;
+      rho = expf(fminf(logf(wu) - logf(rp.D) - p.logp_old[r], EXP_CLAMP));
+    }
+    const float s = rho * adv, k = fminf(fmaxf(rho, 1.f - p.clip), 1.f + p.clip) * adv;
+    const bool clipped = k < s;
+    if (row_logp_ent_grad_of<true>(rp, z, a, out, p.A, u, clipped ? 0.f : -m * adv * rho, p.beta * m, lp, H)) {
+      acc[0] += -m * fminf(s, k);
+      if (p.beta != 0.f) acc[0] -= p.beta * m * H;
+      acc[2] += m * H;
+      if (clipped) acc[3] += m;
+    }
+  }
+  p.logp[r] = lp;
+  if (p.ent) p.ent[r] = H;
+  acc[1] += m;
+}
+
+// EX (with LOSS): loss_row_ex and its three partial sums; PPO (with LOSS and EX): loss_row_ppo and its four
+template <bool LOSS, bool EX = false, bool PPO = false>
+__global__ __launch_bounds__(TPB) void policy_tiled_kernel(ArgsOf<PPO> p) {
   extern __shared__ __attribute__((aligned(16))) float pt_smem[];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int A = p.A;
   const int TS = (PT_ROWS * A + 3) & ~3;                  // floats per tile (16-byte multiple)
   float* Sz = pt_smem + (size_t)wave * 2 * TS;
   float* Sa = Sz + TS;
-  float acc[EX ? 3 : 2] = {};
+  float acc[PPO ? 4 : EX ? 3 : 2] = {};
   const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
   for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
     const long r0 = tile * PT_ROWS;
@@ -96,7 +137,8 @@ __global__ __launch_bounds__(TPB) void policy_tiled_kernel(PolicyArgs p) {
     __builtin_amdgcn_wave_barrier();
     const long r = r0 + lane;
     if (r < p.rows) {
-      if constexpr (EX) loss_row_ex(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
+      if constexpr (PPO) loss_row_ppo(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
+      else if constexpr (EX) loss_row_ex(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
       else if constexpr (LOSS) loss_row(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
       else row_probs(Sz + lane * A, Sa + lane * A, Sz + lane * A, A, p.eps);
     }
@@ -107,37 +149,38 @@ __global__ __launch_bounds__(TPB) void policy_tiled_kernel(PolicyArgs p) {
     __builtin_amdgcn_s_waitcnt(0xC07F);                   // the tile is read out before the next trip overwrites it
     __builtin_amdgcn_wave_barrier();
   }
-  if (LOSS) block_partials<EX ? 3 : 2>(acc, p.ws);
+  if (LOSS) block_partials<PPO ? 4 : EX ? 3 : 2>(acc, p.ws);
 }
 
 // row-per-lane form for action counts whose tiles do not fit: same arithmetic in the same order
-template <bool LOSS, bool EX = false>
-__global__ __launch_bounds__(TPB) void policy_rows_kernel(PolicyArgs p) {
-  float acc[EX ? 3 : 2] = {};
+template <bool LOSS, bool EX = false, bool PPO = false>
+__global__ __launch_bounds__(TPB) void policy_rows_kernel(ArgsOf<PPO> p) {
+  float acc[PPO ? 4 : EX ? 3 : 2] = {};
   for (long r = (long)blockIdx.x * TPB + threadIdx.x; r < p.rows; r += (long)gridDim.x * TPB) {
     const float* z = p.logits + r * p.A;
     const float* a = p.avail + r * p.A;
     float* out = p.out + r * p.A;
-    if constexpr (EX) loss_row_ex(p, r, z, a, out, acc);
+    if constexpr (PPO) loss_row_ppo(p, r, z, a, out, acc);
+    else if constexpr (EX) loss_row_ex(p, r, z, a, out, acc);
     else if constexpr (LOSS) loss_row(p, r, z, a, out, acc);
     else row_probs(z, a, out, p.A, p.eps);
   }
-  if (LOSS) block_partials<EX ? 3 : 2>(acc, p.ws);
+  if (LOSS) block_partials<PPO ? 4 : EX ? 3 : 2>(acc, p.ws);
 }
 
-template <bool LOSS, bool EX = false>
-int launch_policy(PolicyArgs p, hipStream_t s, int& nb) {
+template <bool LOSS, bool EX = false, bool PPO = false>
+int launch_policy(ArgsOf<PPO> p, hipStream_t s, int& nb) {
   const size_t lds = (size_t)4 * 2 * ((PT_ROWS * p.A + 3) & ~3) * sizeof(float);
   if (lds <= 56 * 1024) {            // (block_partials keeps a few floats of its own)
     const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
     long b = (tiles + 3) / 4;
     nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
     p.vec = ((reinterpret_cast<uintptr_t>(p.logits) | reinterpret_cast<uintptr_t>(p.avail) | reinterpret_cast<uintptr_t>(p.out)) & 15) == 0;
-    hipLaunchKernelGGL((policy_tiled_kernel<LOSS, EX>), dim3((unsigned)nb), dim3(TPB), lds, s, p);
+    hipLaunchKernelGGL((policy_tiled_kernel<LOSS, EX, PPO>), dim3((unsigned)nb), dim3(TPB), lds, s, p);
   } else {
     long b = (p.rows + TPB - 1) / TPB;
     nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
-    hipLaunchKernelGGL((policy_rows_kernel<LOSS, EX>), dim3((unsigned)nb), dim3(TPB), 0, s, p);
+    hipLaunchKernelGGL((policy_rows_kernel<LOSS, EX, PPO>), dim3((unsigned)nb), dim3(TPB), 0, s, p);
   }
   MARL_CHECK_LAUNCH();
   return 0;
@@ -225,6 +268,24 @@ extern "C" int marl_policy_loss_bwd_ex(const float* logits, const float* avail, 
   const int rc = launch_policy<true, true>(p, (hipStream_t)stream, nb);
   if (rc) return rc;
   hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, (const float*)ws, nb, 3, out3);
+  MARL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int marl_ppo_loss_bwd(const float* logits, const float* avail, const int* u, const float* adv, const float* logp_old,
+                                 const float* padded, float eps, float beta, float clip, float* dlogits, float* logp, float* ent,
+                                 float* out4, float* ws, long rows, int N, int A, void* stream) {
+  if (rows <= 0 || A <= 0) return 0;
+  if (!logits || !avail || !u || !adv || !padded || !dlogits || !logp || !out4 || !ws || N <= 0 || rows % N != 0 ||
+      dlogits == avail || !(beta >= 0.f) || !(clip > 0.f && clip < 1.f))
+    return (int)hipErrorInvalidValue;
+  PpoArgs p = {};
+  p.logits = logits; p.avail = avail; p.u = u; p.G = adv; p.logp_old = logp_old; p.padded = padded; p.eps = eps; p.beta = beta;
+  p.clip = clip; p.out = dlogits; p.logp = logp; p.ent = ent; p.ws = ws; p.rows = rows; p.N = N; p.A = A;
+  int nb;
+  const int rc = launch_policy<true, true, true>(p, (hipStream_t)stream, nb);
+  if (rc) return rc;
+  hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, (const float*)ws, nb, 4, out4);
   MARL_CHECK_LAUNCH();
   return 0;
 }

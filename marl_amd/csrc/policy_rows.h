@@ -94,7 +94,12 @@ __device__ __forceinline__ bool row_logp_grad(const float* z, const float* a, fl
 // eps = 0 once z_k sits about 104 below mx) and, for hs != 0, out = scale d log pi_u / dz - hs dH / dz.  With
 // L1 = sum a_k e_k log pi_k and Hn = sum pi_k log pi_k = -H (one walk, before out - which may be z - is written):
 //   dH/dz_i = -c2 (a_i e_i log pi_i - e_i L1 / S) + c2 e_i (a_i - Pa) Hn          (the second walk; -pi_i (log pi_i + H) at eps = 0).
-// hs = 0 takes row_logp_grad's own walk: the same bits.  A row with n = 1 has H = 0 and no gradient
+// hs = 0 takes row_logp_grad's own walk: the same bits.  A row with n = 1 has H = 0 and no gradient.
+// SPLIT (marl_ppo_loss_bwd): the last combine rounds scale * (..) and hs * dH each before they are subtracted.  That is the form the
+// compiler gives the marl_policy_loss_bwd_ex instantiations of its own accord (their ISA: a packed multiply, then a subtract), while
+// it fused hs * dH into the subtraction in the PPO ones - and the PPO pass without logp_old is held to the _ex pass bit for bit
+// (tests/test_gpu_ppo.py).  The callers without SPLIT compile the statement they always had
+template <bool SPLIT = false>
 __device__ __forceinline__ bool row_logp_ent_grad_of(const RowPolicy& p, const float* z, const float* a, float* out, int A, int u,
                                                      float scale, float hs, float& logp, float& H) {
   H = 0.f;
@@ -119,7 +124,15 @@ __device__ __forceinline__ bool row_logp_ent_grad_of(const RowPolicy& p, const f
     const float w = p.cw * e + p.ew;
     const float elp = (ak != 0.f && w > 0.f) ? e * (logf(w) - logD) : 0.f;
     const float dH = c2 * (e * (ak - Pa) * Hn - (elp - e * L1S));
-    out[k] = scale * (c1 * ((k == u ? 1.f : 0.f) - e * invS) - c2 * e * (ak - Pa)) - hs * dH;
+    if constexpr (SPLIT) {
+      const float g = c1 * ((k == u ? 1.f : 0.f) - e * invS) - c2 * e * (ak - Pa);
+      {
+#pragma clang fp contract(off)
+        out[k] = scale * g - hs * dH;
+      }
+    } else {
+      out[k] = scale * (c1 * ((k == u ? 1.f : 0.f) - e * invS) - c2 * e * (ak - Pa)) - hs * dH;
+    }
   }
   return true;
 }

@@ -5,6 +5,7 @@
     python -m marl_amd.main --map 2s3z --alg central_v --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg coma --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg reinforce --policy_entropy_coef 0.01 --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --map 2s3z --alg mappo --ppo_epochs 5 --ppo_clip 0.2 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg reinforce+commnet --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg central_v+commnet --commnet_k 2 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg coma+commnet --n_envs 64 --n_steps 200000
@@ -21,7 +22,7 @@ import sys
 from collections import namedtuple
 
 from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
-    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args
+    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .runner import Runner
@@ -92,6 +93,14 @@ def build(argv=None):
             args.td_lambda = given
     elif base == 'reinforce':
         get_reinforce_args(args)
+    elif base == 'mappo':               # (an actor suffix on it was refused above: _POLICY_ALGS does not hold the name)
+        given = {k: getattr(args, k) for k in ('td_lambda', 'ppo_clip', 'ppo_epochs', 'ppo_norm_adv')}
+        get_mappo_args(args)
+        for k, v in given.items():      # the table's values are defaults, not overrides of the switches
+            if v is not None:
+                setattr(args, k, v)
+        from .algorithm.ppo import ppo_settings_of
+        ppo_settings_of(args)           # a bad --ppo_clip / --ppo_epochs is refused before the environment is made
     if actor is not None:
         actor.table(args)
         if getattr(args, actor.switch, None) is not None:
@@ -122,13 +131,17 @@ def build(argv=None):
 
 def make_runner(args, env, logger=None):
     """the Runner of a built (args, env).  ``--alg coma`` names its learner here: the runner's own table of on-policy learners
-    holds central_v and reinforce, and a Runner built on the bare name 'coma' still refuses it.  The algorithms with an actor suffix
+    holds central_v and reinforce, and a Runner built on the bare name 'coma' still refuses it; ``--alg mappo`` likewise (PPOLearner;
+    with RTW, world_model or MAIC the runner refuses it as it refuses central_v).  The algorithms with an actor suffix
     get their learner class and their actor's controller (``mac_cls``, the _ACTORS entry's) the same way."""
     learner_cls = mac_cls = None
     base, actor = actor_base(args.alg, entry=True)
     if base == 'coma':
         from .algorithm.coma import COMALearner
         learner_cls = COMALearner
+    elif base == 'mappo':
+        from .algorithm.ppo import PPOLearner
+        learner_cls = PPOLearner
     elif actor is not None:             # the names with an actor suffix are the launcher's: the runner's own table does not hold them
         from .algorithm.central_v import CentralVLearner
         from .algorithm.reinforce import ReinforceLearner

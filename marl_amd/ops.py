@@ -524,6 +524,34 @@ def policy_loss_bwd_ex(logits, avail, u, G, v, padded, eps, beta, dlogits, logp,
                                       _p(logp), _p(ent), _p(_f32(out3)), _p(ws), rows, N, A, _stream()), "marl_policy_loss_bwd_ex")
 
 
+def ppo_loss_bwd(logits, avail, u, adv, logp_old, padded, eps, beta, clip, dlogits, logp, ent, out4, rows, N, A):
+    """policy_loss_bwd_ex's pass under PPO's clipped surrogate (csrc/policy.hip): ``adv`` (rows / N) in the place of G - v,
+    ``logp_old`` (rows) or None (rho = 1 exactly: the batch's first pass), ``clip`` = c in (0, 1).  out4 = {- sum m min(rho adv,
+    clamp(rho, 1 - c, 1 + c) adv) - beta sum m H, N sum m, sum m H, sum m [clipped]}, ent (rows) = H or None, and
+    dlogits = - m (clipped ? 0 : adv rho) dlogp/dz - beta m dH/dz.  logp_old None: policy_loss_bwd_ex's dlogits, logp and ent with
+    G = adv and no v, bit for bit."""
+    lib = _lib.load()
+    for t, n in ((logits, rows * A), (avail, rows * A), (dlogits, rows * A), (logp, rows), (adv, rows // N), (padded, rows // N)) + \
+            (() if logp_old is None else ((logp_old, rows),)) + (() if ent is None else ((ent, rows),)):
+        assert _f32(t).is_contiguous() and t.numel() >= n
+    assert _i32(u).is_contiguous() and u.numel() >= rows and out4.numel() >= 4
+    ws = WS.get("loss", lib.marl_loss_workspace(rows), logits.device)
+    check(lib.marl_ppo_loss_bwd(_p(logits), _p(avail), _p(u), _p(adv), _p(logp_old), _p(padded), float(eps), float(beta), float(clip),
+                                _p(dlogits), _p(logp), _p(ent), _p(_f32(out4)), _p(ws), rows, N, A, _stream()), "marl_ppo_loss_bwd")
+
+
+def masked_standardize(x, padded, out, stats3, rows):
+    """out = m (x - mean) / (sqrt(var) + 1e-5) over the live rows (m = 1 - padded; csrc/ppo.hip): exact zeros on padded rows, all
+    zeros when none is live; stats3 = {mean, var, sum m}.  ``out`` may be ``x``."""
+    lib = _lib.load()
+    for t in (x, padded, out):
+        assert _f32(t).is_contiguous() and t.numel() >= rows
+    assert _f32(stats3).numel() >= 3
+    ws = WS.get("loss", lib.marl_loss_workspace(rows), x.device)
+    check(lib.marl_masked_standardize(_p(x), _p(padded), _p(out), _p(stats3), _p(ws), rows, _stream()), "marl_masked_standardize")
+    return out
+
+
 def policy_sample(logits, avail, avail_es, alive, eps, rseed, env0, tg, tg0, act_out, act_es, E, N, A):
     """select_actions' arguments; draws every live agent's action from the stochastic policy"""
     check(_lib.load().marl_policy_sample(_p(_f32(logits)), _p(_f32(avail)), avail_es, _p(alive), float(eps),
