@@ -7,7 +7,8 @@ Written from the formulas, not from the reference's code: a row is agent i of on
           s_j = (query / 8) . (Wk m_j + bk) (self at -1e9), p = softmax(s), v_j = V2 relu(V0 [h_i ; m_j] + b) + b,
           q_i += sum_j p_j v_j
   given : m_j = onehot(u_j) (self zeroed), o_hat -> the real o_next, and v_j from h_j (RTW.py:122 h_repeat[b,i,j] = h[b,j])
-The parameters are dicts name -> tensor with RTWAgent's state_dict keys.  Also: the batched lock-step RTW rollout, a copy
+The parameters are dicts name -> tensor with RTWAgent's state_dict keys; act_head, given_head and _reflect compute in the dtype
+of their inputs (params_t(sd, torch.float64) and float64 inputs give the float64 statement the kernel tests compare against).  Also: the batched lock-step RTW rollout, a copy
 of oracle.rollout.batched_rollout with the head between the agent step and the selection.
 """
 from __future__ import annotations
@@ -28,8 +29,8 @@ def _mlp(p, name, x):
     return _lin(p, name + ".2", torch.relu(_lin(p, name + ".0", x)))
 
 
-def params_t(sd):
-    return {k: torch.as_tensor(np.asarray(v), dtype=torch.float32) for k, v in sd.items()}
+def params_t(sd, dtype=torch.float32):
+    return {k: torch.as_tensor(np.asarray(v), dtype=dtype) for k, v in sd.items()}
 
 
 def _reflect(p, h_val, o, o2, m, N, not_self):
@@ -53,7 +54,7 @@ def act_head(p, h, o, avail, N, not_self=True):
     G = h.shape[0] // N
     H, O, A = h.shape[1], o.shape[1], avail.shape[-1]
     hr = h.view(G, N, 1, H).expand(G, N, N, H)
-    e = torch.eye(N).view(1, 1, N, N).expand(G, N, N, N)
+    e = torch.eye(N, dtype=h.dtype).view(1, 1, N, N).expand(G, N, N, N)
     x = torch.cat([hr, e], -1).clone()
     if not_self:
         idx = torch.arange(N)
@@ -64,7 +65,7 @@ def act_head(p, h, o, avail, N, not_self=True):
     a = tm.argmax(-1)                                                     # first index of the maximum
     top2 = tm.topk(min(2, A), -1).values
     gap = (top2[..., 0] - top2[..., 1]) if A > 1 else torch.full_like(top2[..., 0], float("inf"))
-    m = F.one_hot(a, A).float()
+    m = F.one_hot(a, A).to(h.dtype)
     if not_self:
         idx = torch.arange(N)
         m[:, idx, idx] = 0.0
@@ -81,7 +82,7 @@ def given_head(p, hs, o, on, u, N, not_self=True):
     A = p["w_k.weight"].shape[1]
     hr = hs.view(G, 1, N, H).expand(G, N, N, H)                           # row i, teammate j: h_j
     uj = u.view(G, 1, N).expand(G, N, N).clamp(min=0).long()
-    m = F.one_hot(uj, A).float()
+    m = F.one_hot(uj, A).to(hs.dtype)
     if not_self:
         idx = torch.arange(N)
         m[:, idx, idx] = 0.0

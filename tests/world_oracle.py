@@ -1,8 +1,9 @@
 """CPU restatement of the world-model agent's head and prediction loss (TEST INFRASTRUCTURE; reference
 network/world_model.py:7-75, algorithm/q_learner_state.py:94-187).
 
-``head`` is the WorldModel forward in float64; ``head_backward`` its gradients by autograd for a given gradient on r (the
-TD loss reaching q = fc2(h) + r) and on o_hat (the prediction loss).  ``train`` restates QLearnerWithState.train on the
+``head`` is the WorldModel forward in the dtype of its arguments (float64 wherever a kernel is judged; ``params_t`` converts
+the weights, ``pre_activations`` returns the two ReLU inputs); ``head_backward`` its gradients by autograd, in float64 unless
+told otherwise, for a given gradient on r (the TD loss reaching q = fc2(h) + r) and on o_hat (the prediction loss).  ``train`` restates QLearnerWithState.train on the
 oracle's LearnerState (oracle/learners.py) with the agent's world.* tensors in ``state.agent``: the q_forward schedule with
 r added to every Q tensor, plus mean((o_next - o_hat)^2) from the eval pass."""
 from __future__ import annotations
@@ -31,14 +32,26 @@ def head(p, h):
     return lin(e, WORLD[2]), lin(e, WORLD[3]), lin(e, WORLD[4])
 
 
-def head_backward(p, h, dr, dohat):
-    """float64 gradients of sum(r * dr) + sum(o_hat * dohat): (dh, {param name: grad})"""
-    p64 = {k: torch.tensor(np.asarray(v), dtype=torch.float64, requires_grad=True) for k, v in p.items()
+def params_t(p, dtype=torch.float64):
+    """the world.* tensors of a numpy state dict in `dtype` (float64: the reference; float32: the yardstick)"""
+    return {k: torch.tensor(np.asarray(v), dtype=dtype) for k, v in p.items() if k.startswith("world.")}
+
+
+def pre_activations(p, h):
+    """the two ReLU inputs of `head`, (W1 h + b1, W2 z + b2): where a caller counts values near the kink at 0"""
+    lin = lambda x, n: x @ p[n + ".weight"].T + p[n + ".bias"]
+    zp = lin(h, WORLD[0])
+    return zp, lin(torch.relu(zp), WORLD[1])
+
+
+def head_backward(p, h, dr, dohat, dtype=torch.float64):
+    """gradients of sum(r * dr) + sum(o_hat * dohat), computed in `dtype` (float64 unless told): (dh, {param name: grad})"""
+    p64 = {k: torch.tensor(np.asarray(v), dtype=dtype, requires_grad=True) for k, v in p.items()
            if k.startswith("world.")}
-    h64 = torch.tensor(np.asarray(h), dtype=torch.float64, requires_grad=True)
+    h64 = torch.tensor(np.asarray(h), dtype=dtype, requires_grad=True)
     r, ohat, _ = head(p64, h64)
-    obj = (r * torch.as_tensor(np.asarray(dr), dtype=torch.float64)).sum() + \
-        (ohat * torch.as_tensor(np.asarray(dohat), dtype=torch.float64)).sum()
+    obj = (r * torch.as_tensor(np.asarray(dr), dtype=dtype)).sum() + \
+        (ohat * torch.as_tensor(np.asarray(dohat), dtype=dtype)).sum()
     names = list(p64)
     gs = torch.autograd.grad(obj, [h64] + [p64[n] for n in names], allow_unused=True)
     return gs[0].numpy(), {n: (g.numpy() if g is not None else np.zeros(p64[n].shape)) for n, g in zip(names, gs[1:])}
