@@ -558,6 +558,36 @@ size_t marl_loss_workspace(long rows);
 int marl_td_lambda_returns(const float* q_next_tot, const float* r, const float* term, const float* padded,
                            float gamma, float lambda, float* ret, int B, int T, void* stream);
 
+/* ---- independent Q-learning (iql.hip; the reference ships no IQL: the definition is this project's own) -----------------------
+ * Rows r = (b T + t) N + i: agent i at step t of episode b; R = B T N; m = 1 - padded[b, t].  q (R, A) the eval unroll's Qs, u (R)
+ * int32 the taken actions (>= 0; an index outside [0, A) reads 0), q_sel / q_tgt / avail_next (R, A), r / term / padded (B T):
+ *   q_taken[r] = q[r, u[r]],
+ *   q_next[r]  = q_tgt[r, a*] masked with avail_next (mask_val where it is 0), a* the first-index argmax of q_sel[r, :] masked the
+ *                same way - marl_q_double_select's comparisons; q_sel NULL: a* is taken on q_tgt itself, which gives
+ *                marl_q_masked_max's value; avail_next NULL: everything is available; a live row with nothing available: mask_val,
+ *   y[r]       = r[b,t] + gamma (1 - term[b,t]) q_next[r]        (ret NULL),       y[r] = ret[b, i, t]        (ret given, (B, N, T)),
+ *   td = y - q_taken,   dq_val[r] = - 2 m td (un-normalised, as marl_td_loss's dq_tot),   out2 = { sum_r m td^2, sum_r m = N sum m }.
+ * A row with m = 0 contributes nothing, its dq_val, q_taken, q_next are exact zeros and its q, q_sel, q_tgt, avail_next (and ret)
+ * entries never enter a computation: they may hold NaN.
+ *
+ * marl_iql_loss_bwd, ret NULL: gather, selection, target, loss partials and the sparse gradient (the dq_val of
+ *   marl_agent_unroll_bwd with dq_idx = u) in ONE pass over the rows, then the fixed-order finish of the two sums.  q_taken and
+ *   q_next (R) are optional outputs.  ret given: the target is ret; q_sel, q_tgt, avail_next, r and term are not read and q_next is
+ *   not written.
+ * marl_iql_select: the first half alone, for TD(lambda): q_taken (R, optional) and q_next written in (B, N, T) layout,
+ *   q_next_bnt[(b N + i) T + t] - the layout marl_td_lambda_returns scans on B N sequences.  Same bits as the fused call's.
+ * Up to A = 21 (three row operands; 31 with two, 63 with one) a wave stages 64 rows of each operand through LDS, beyond that a lane
+ * scans its row in global memory: same comparisons, same bits.  fp32, fixed-order sums (ws: marl_loss_workspace() bytes), no float
+ * atomics: two calls give the same bits.  A NULL required pointer, A < 1, N < 1, B T N >= 2^31 or an output overlapping an input or
+ * another output: hipErrorInvalidValue.  B <= 0 or T <= 0: returns 0, no launch. */
+int marl_iql_loss_bwd(const float* q, const int* u, const float* q_sel, const float* q_tgt, const float* avail_next,
+                      const float* ret, const float* r, const float* term, const float* padded, float gamma, float mask_val,
+                      float* dq_val, float* q_taken, float* q_next, float* out2, float* ws, int B, int T, int N, int A,
+                      void* stream);
+int marl_iql_select(const float* q, const int* u, const float* q_sel, const float* q_tgt, const float* avail_next,
+                    const float* padded, float mask_val, float* q_taken, float* q_next_bnt, int B, int T, int N, int A,
+                    void* stream);
+
 /* ---- stochastic policy of the policy-gradient learners (policy.hip; central-V, REINFORCE) --------
  * A row is one agent at one step: logits z (A floats, the agent's fc2 output), availability a in {0,1}^A, exploration rate eps:
  *   p = softmax(z) over all A actions,  n = sum_k a_k,  pt_k = a_k ((1 - eps) p_k + eps / n),  pi_k = pt_k / sum_j pt_j.

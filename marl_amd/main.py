@@ -2,6 +2,7 @@
 
     python -m marl_amd.main --alg qmix --map 2s3z --n_envs 1024 --n_steps 500000
     python -m marl_amd.main --env matrix --alg qplex --n_envs 32 --n_steps 20000
+    python -m marl_amd.main --map 2s3z --alg iql --n_envs 1024 --n_steps 500000
     python -m marl_amd.main --map 2s3z --alg central_v --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg coma --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg reinforce --policy_entropy_coef 0.01 --n_envs 64 --n_steps 200000

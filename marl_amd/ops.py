@@ -488,6 +488,36 @@ def td_lambda_returns(q_next_tot, r, term, padded, gamma, lam, out, B, T):
     return out
 
 
+def _iql_rows(B, T, N, A, per_row_a, per_row, per_step):
+    R = B * T * N
+    for t, n in [(x, R * A) for x in per_row_a] + [(x, R) for x in per_row] + [(x, B * T) for x in per_step]:
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() >= n), "iql: contiguous device arrays of the rows' sizes"
+
+
+def iql_loss_bwd(q, u, q_sel, q_tgt, avail_next, ret, r, term, padded, gamma, mask_val, dq_val, out2, B, T, N, A,
+                 q_taken=None, q_next=None):
+    """Independent Q-learning's loss tail over the R = B T N agent rows (csrc/iql.hip): the taken actions' Qs, the double-Q
+    selection (q_sel None: the masked max of q_tgt), the one-step target, out2 = {sum m td^2, N sum m} and the sparse gradient
+    dq_val = -2 m td in one row pass; with ``ret`` (B, N, T) the target is ret and no selection runs."""
+    lib = _lib.load()
+    _iql_rows(B, T, N, A, (q, q_sel, q_tgt, avail_next), (u, ret, dq_val, q_taken, q_next), (r, term, padded))
+    ws = WS.get("loss", lib.marl_loss_workspace(B * T * N), q.device)
+    check(lib.marl_iql_loss_bwd(_p(_f32(q)), _p(_i32(u)), _p(q_sel), _p(q_tgt), _p(avail_next), _p(ret), _p(r), _p(term),
+                                _p(_f32(padded)), float(gamma), float(mask_val), _p(_f32(dq_val)), _p(q_taken), _p(q_next),
+                                _p(_f32(out2)), _p(ws), int(B), int(T), int(N), int(A), _stream()), "marl_iql_loss_bwd")
+    return dq_val
+
+
+def iql_select(q, u, q_sel, q_tgt, avail_next, padded, mask_val, q_taken, q_next_bnt, B, T, N, A):
+    """the selection half of iql_loss_bwd alone: q_taken (R, optional) and q_next in (B, N, T) layout, the one
+    td_lambda_returns scans on B N sequences"""
+    _iql_rows(B, T, N, A, (q, q_sel, q_tgt, avail_next), (u, q_taken, q_next_bnt), (padded,))
+    check(_lib.load().marl_iql_select(_p(_f32(q)), _p(_i32(u)), _p(q_sel), _p(_f32(q_tgt)), _p(avail_next), _p(_f32(padded)),
+                                      float(mask_val), _p(q_taken), _p(_f32(q_next_bnt)), int(B), int(T), int(N), int(A),
+                                      _stream()), "marl_iql_select")
+    return q_next_bnt
+
+
 def policy_probs(logits, avail, eps, pi, rows, A):
     """pi (rows, A) of the stochastic policy (csrc/policy.hip): softmax of the logits, mixed with eps of the uniform policy over the
     available actions, renormalised over them; a row without an available action is all zeros"""

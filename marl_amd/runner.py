@@ -41,6 +41,10 @@ own table; everything above holds for it.  The launcher passes COMALearner (algo
 launcher passes the GroupHeadMAC subclass of its actor table (CommNetMAC for the three ``+commnet`` algorithms, G2ANetMAC for the three
 ``+g2anet`` ones); a Runner built on a bare ``+commnet`` / ``+g2anet`` name answers 'cannot find!' too.
 
+``args.alg == 'iql'`` (no agent switch on): SharedMAC, the replay buffer and IQLLearner (algorithm/iql.py), independent Q-learning
+without a mixer.  With an agent switch the name is answered as before: world_model refuses it as an unknown mixer, RTW and MAIC
+end in 'learner iql cannot find!'.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -63,6 +67,7 @@ from .algorithm.maic_q_learner import MAICQLearner
 from .algorithm.maic_td_learner import MAICTDLearner
 from .algorithm.central_v import CentralVLearner
 from .algorithm.reinforce import ReinforceLearner
+from .algorithm.iql import IQLLearner
 from .utils.logging import Logger
 
 
@@ -148,6 +153,8 @@ class Runner:
             self.learner = make_learner(self.mac, logger, args)
         elif _qtran(args):
             self.learner = QTRANLearner(self.mac, args)
+        elif args.alg == 'iql' and not on:
+            self.learner = IQLLearner(self.mac, args)
         else:
             raise ValueError('learner {} cannot find!'.format(args.alg))
         if args.load_model:

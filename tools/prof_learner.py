@@ -31,6 +31,7 @@ def main():
     from marl_amd.common.arguments import get_centralv_args
     from marl_amd.algorithm.q_learner import QLearner
     from marl_amd.algorithm.qtran_learner import QTRANLearner
+    from marl_amd.algorithm.iql import IQLLearner
     from marl_amd.rollout import RolloutWorker
     from marl_amd.env.synthetic_smac import SyntheticSMACEnv
     args = bench.make_args(o.alg, o.shape, o.T)
@@ -47,7 +48,8 @@ def main():
         learner = CentralVLearner(mac, args)
     else:
         mac = SharedMAC(args)
-        learner = QTRANLearner(mac, args) if o.alg.startswith("qtran") else QLearner(mac, args)
+        cls = QTRANLearner if o.alg.startswith("qtran") else {"iql": IQLLearner}.get(o.alg, QLearner)
+        learner = cls(mac, args)
     env = SyntheticSMACEnv(o.envs, args.n_agents, args.obs_shape, args.state_shape, args.n_actions, args.episode_limit,
                            seed=1, fixed_length=True)
     w = RolloutWorker(env, mac, args)
