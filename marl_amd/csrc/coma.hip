@@ -14,14 +14,15 @@
 //     a register (the id column): no two lanes ever touch the same word, so there is no barrier and no atomic.  The tables go to a
 //     workspace; one more launch adds the slabs in order into fc1.weight.grad's columns (lane = (column, d), d fastest).
 //   q_taken: one lane per output element.
-//   loss_bwd: policy_tiled_kernel's row staging with a third tile for Q: a wave stages 64 rows of logits, availability and Q
-//     into LDS, every lane walks its own row, dlogits and dQ are written over the logits and Q tiles and stored as contiguous runs.
-//     From A = 19 the twelve tiles of a workgroup pass 56 KiB and the row-per-lane form runs (same arithmetic in the same order).
+//   loss_bwd: row_tile.h's staging with three tiles (logits, availability, Q); dlogits and dQ are written over the logits and Q
+//     tiles and stored back.  From A = 19 the twelve tiles of a workgroup pass 56 KiB and the row-per-lane form runs.
 // fp32, fixed-order sums, no float atomics: two calls give the same bits.  An action index outside [0, A) is an all-zero one-hot.
 #include "policy_rows.h"
+#include "row_tile.h"
 #include "../../include/marl_hip.h"
 
 namespace {
+namespace rt = row_tile;
 
 constexpr int TPB = SUMS_TPB;
 constexpr int SLAB_STEPS_MIN = 8;     // steps per slab of the scatter at least; 256 slabs at most
@@ -203,42 +204,24 @@ __device__ __forceinline__ void coma_row(const ComaArgs& p, long r, const float*
 
 __global__ __launch_bounds__(TPB) void coma_loss_tiled_kernel(ComaArgs p) {
   extern __shared__ __attribute__((aligned(16))) float ct_smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int A = p.A;
-  const int TS = (PT_ROWS * A + 3) & ~3;                  // floats per tile (16-byte multiple)
-  float* Sz = ct_smem + (size_t)wave * 3 * TS;
+  const int TS = rt::tile_floats(A);
+  float* Sz = rt::wave_tiles(ct_smem, 3, A);
   float* Sa = Sz + TS;
   float* Sq = Sa + TS;
   float acc[4] = {};
-  const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
-  for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
-    const long r0 = tile * PT_ROWS;
-    const int n = (int)((p.rows - r0 < PT_ROWS ? p.rows - r0 : PT_ROWS) * A);
-    const float* gz = p.logits + r0 * A;
-    const float* ga = p.avail + r0 * A;
-    const float* gq = p.q + r0 * A;
-    float* oz = p.dlogits + r0 * A;
-    float* oq = p.dq + r0 * A;
-    const int n4 = p.vec ? n >> 2 : 0;
-    for (int e = lane; e < n4; e += 64) {
-      reinterpret_cast<f32x4*>(Sz)[e] = reinterpret_cast<const f32x4*>(gz)[e];
-      reinterpret_cast<f32x4*>(Sa)[e] = reinterpret_cast<const f32x4*>(ga)[e];
-      reinterpret_cast<f32x4*>(Sq)[e] = reinterpret_cast<const f32x4*>(gq)[e];
-    }
-    for (int e = 4 * n4 + lane; e < n; e += 64) { Sz[e] = gz[e]; Sa[e] = ga[e]; Sq[e] = gq[e]; }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                   // this wave's LDS writes (lgkmcnt(0)); no cross-wave sharing
-    __builtin_amdgcn_wave_barrier();
+  const long tiles = rt::tiles(p.rows);
+  for (long tile = rt::first_tile(); tile < tiles; tile += rt::tile_step()) {
+    const long r0 = tile * rt::ROWS;
+    const int n = rt::tile_len(p.rows, r0, A);
+    rt::copy<3>({Sz, Sa, Sq}, {p.logits + r0 * A, p.avail + r0 * A, p.q + r0 * A}, n, p.vec);
+    rt::lds_done_fenced();
     const long r = r0 + lane;
     if (r < p.rows) coma_row(p, r, Sz + lane * A, Sa + lane * A, Sq + lane * A, Sz + lane * A, Sq + lane * A, acc);
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
-    for (int e = lane; e < n4; e += 64) {
-      reinterpret_cast<f32x4*>(oz)[e] = reinterpret_cast<const f32x4*>(Sz)[e];
-      reinterpret_cast<f32x4*>(oq)[e] = reinterpret_cast<const f32x4*>(Sq)[e];
-    }
-    for (int e = 4 * n4 + lane; e < n; e += 64) { oz[e] = Sz[e]; oq[e] = Sq[e]; }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                   // the tiles are read out before the next trip overwrites them
-    __builtin_amdgcn_wave_barrier();
+    rt::lds_done_fenced();
+    rt::copy<2>({p.dlogits + r0 * A, p.dq + r0 * A}, {Sz, Sq}, n, p.vec);
+    rt::lds_done_fenced();                                // the tiles are read out before the next trip overwrites them
   }
   block_partials<4>(acc, p.ws);
 }
@@ -252,27 +235,14 @@ __global__ __launch_bounds__(TPB) void coma_loss_rows_kernel(ComaArgs p) {
 
 // the four sums in block order, then critic = { s0, s1 }, actor = { s2, s1, s3 }
 __global__ void coma_finish_kernel(const float* ws, int nblocks, float* out_c2, float* out_a3) {
-  __shared__ float sh[SUMS_TPB];
   float tot[4];
-  for (int i = 0; i < 4; ++i) {
-    float s = 0.f;
-    for (int b = threadIdx.x; b < nblocks; b += SUMS_TPB) s += ws[(long)b * 4 + i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = SUMS_TPB / 2; o > 0; o >>= 1) {
-      if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-      __syncthreads();
-    }
-    tot[i] = sh[0];
-    __syncthreads();
-  }
+  for (int i = 0; i < 4; ++i) tot[i] = block_tree_sum(ws, nblocks, 4, i);
   if (threadIdx.x == 0) {
     out_c2[0] = tot[0]; out_c2[1] = tot[1];
     out_a3[0] = tot[2]; out_a3[1] = tot[1]; out_a3[2] = tot[3];
   }
 }
 
-inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline unsigned blocks_for(long total) {
   long b = (total + TPB - 1) / TPB;
   return (unsigned)(b > 4096 ? 4096 : (b < 1 ? 1 : b));
@@ -298,7 +268,7 @@ extern "C" int marl_coma_onehot_cols(const float* W, long ldw, int col0, float* 
 extern "C" int marl_coma_fc1_fwd(const float* pre_s, const float* Wt, const int* u, float* h1, int B, int T, int N, int A, int D,
                                  void* stream) {
   if (B <= 0 || T <= 0 || N <= 0 || A <= 0 || D <= 0) return 0;
-  if (!pre_s || !Wt || !u || !h1 || !dim_ok(D) || !al16(pre_s) || !al16(Wt) || !al16(h1)) return (int)hipErrorInvalidValue;
+  if (!pre_s || !Wt || !u || !h1 || !dim_ok(D) || !aligned16(pre_s) || !aligned16(Wt) || !aligned16(h1)) return (int)hipErrorInvalidValue;
   const long BT = (long)B * T;
   const int D4 = D / 4, SPB = TPB / D4;
   hipLaunchKernelGGL(coma_fc1_fwd_kernel, dim3((unsigned)((BT + SPB - 1) / SPB)), dim3(TPB), 0, (hipStream_t)stream,
@@ -318,7 +288,7 @@ extern "C" int marl_coma_fc1_bwd(const float* dh1, const float* h1, const int* u
   if (B <= 0 || T <= 0 || N <= 0 || A <= 0 || D <= 0) return 0;
   const int C = 2 * N * A + N;
   const size_t lds = (size_t)2 * A * D * sizeof(float);
-  if (!dh1 || !h1 || !u || !dpre || !dsum || !dW || !ws || !dim_ok(D) || !al16(dh1) || !al16(h1) || !al16(dpre) || !al16(dsum) ||
+  if (!dh1 || !h1 || !u || !dpre || !dsum || !dW || !ws || !dim_ok(D) || !aligned16(dh1) || !aligned16(h1) || !aligned16(dpre) || !aligned16(dsum) ||
       col0 < 0 || lddw < (long)col0 + C || lds > 64 * 1024 || ws_bytes < marl_coma_fc1_bwd_workspace(B, T, N, A, D))
     return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
@@ -362,16 +332,13 @@ extern "C" int marl_coma_loss_bwd(const float* logits, const float* avail, const
   p.rows = (long)B * T * N; p.T = T; p.N = N; p.A = A;
   hipStream_t s = (hipStream_t)stream;
   int nb;
-  const size_t lds = (size_t)4 * 3 * ((PT_ROWS * A + 3) & ~3) * sizeof(float);
-  if (lds <= 56 * 1024) {            // (block_partials keeps a few floats of its own)
-    const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
-    const long b = (tiles + 3) / 4;
-    nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
-    p.vec = al16(logits) && al16(avail) && al16(q) && al16(dlogits) && al16(dq);
-    hipLaunchKernelGGL(coma_loss_tiled_kernel, dim3((unsigned)nb), dim3(TPB), lds, s, p);
+  const rt::Plan pl = rt::plan(p.rows, A, 3, 56 * 1024, rt::PARTIAL_ROWS, {logits, avail, q, dlogits, dq});   // (block_partials keeps a few floats of its own)
+  if (pl.tiled) {
+    nb = pl.blocks;
+    p.vec = pl.vec;
+    hipLaunchKernelGGL(coma_loss_tiled_kernel, dim3((unsigned)nb), dim3(TPB), pl.lds_bytes, s, p);
   } else {
-    const long b = (p.rows + TPB - 1) / TPB;
-    nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
+    nb = rt::partial_blocks(p.rows);
     hipLaunchKernelGGL(coma_loss_rows_kernel, dim3((unsigned)nb), dim3(TPB), 0, s, p);
   }
   MARL_CHECK_LAUNCH();

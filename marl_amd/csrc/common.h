@@ -344,4 +344,7 @@ static __device__ unsigned long long* marl_stamp_buf;   // one per translation u
 #define ST_DUMP_AT(n, col)
 #endif
 
+// 16-byte loads and stores (f32x4, global_load_lds) need this of their base; NULL counts as aligned
+inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
 #define MARL_CHECK_LAUNCH() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return (int)e_; } while (0)

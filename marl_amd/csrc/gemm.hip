@@ -1163,8 +1163,6 @@ inline ConcatSrc to_src(const marl_src_t* s) {
   return c;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // ---- launch plans.  marl_linear / marl_linear_wgrad decide by calling these and launch from the result; marl_linear_plan /
 // marl_linear_wgrad_plan hand the same result to the caller.  Host arithmetic on sizes, strides and pointer VALUES only.
 struct LinPlan { int amode, nc, gate, kmajor, bf, wvec; dim3 grid; };

@@ -5,27 +5,23 @@
 //   td = y - q_taken;   dq_val = - 2 m td;   partial sums { m td^2, m }.
 // A row with m = 0 writes exact zeros and none of its row operands enters a computation.
 //
-// Lane mapping: one lane per row, a wave per tile of 64 consecutive rows, four waves per workgroup, tiles in a grid-stride loop.
-// The row operands of the selection (q_sel, q_tgt, avail_next: A floats per row, 44 bytes at 2s3z) are what the pass moves; read a
-// row per lane they waste most of every 64-byte request, so a wave copies its tile of each operand into LDS as it lies (one
-// contiguous run of 64 A floats, 16 bytes per lane: mixers.hip's q_double_select_kernel idiom) and every lane then scans its own row
-// there.  The taken action's Q is one float per row and is read from global memory directly, with the row's other scalars, before
-// the staging so that those loads fly beside it.  The staged form holds
-// 4 waves x (operands given) x 64 A floats and runs while that fits 64 KiB less the sums' 64 static bytes: up to A = 21 with three operands (the switch of
-// marl_q_double_select), up to A = 31 with two (q_sel or avail_next NULL), any A <= 63 with one; beyond that the same lanes scan their
-// rows in global memory - the same comparisons in the same order, so the same bits.  The ret mode reads no row operand but the
-// gather and never stages.
+// Lane mapping: row_tile.h's - the row operands of the selection (q_sel, q_tgt, avail_next) are what the pass moves, and only those
+// given are staged, one after the other.  The taken action's Q is one float per row and is read from global memory directly, with
+// the row's other scalars, before the staging so that those loads fly beside it.  The staged form runs while its tiles fit 64 KiB
+// less the sums' 64 static bytes: up to A = 21 with three operands (the switch of marl_q_double_select), up to A = 31 with two
+// (q_sel or avail_next NULL), any A <= 63 with one; beyond that the same lanes scan their rows in global memory.  The ret mode
+// reads no row operand but the gather and never stages.
 //
 // Sums: sums.h - every workgroup leaves { sum m td^2, sum m } in the workspace, one single-workgroup launch adds the rows in a
 // fixed order.  No float atomics: two calls give the same bits.
 #include "sums.h"
+#include "row_tile.h"
 #include "../../include/marl_hip.h"
 
 namespace {
+namespace rt = row_tile;
 
 constexpr int TPB = SUMS_TPB;
-constexpr int IQ_ROWS = 64;              // rows per wave-tile
-constexpr int IQ_MAX_BLOCKS = 1024;      // the loss workspace holds 1024 rows of four partials
 constexpr size_t IQ_LDS_MAX = 64 * 1024 - 64;   // 64 KiB less the static words of block_partials
 
 struct IqlArgs {
@@ -41,20 +37,9 @@ struct IqlArgs {
 
 // the lane's row of the (staged or global) operands: first-index argmax of the masked sel, the masked val there
 __device__ __forceinline__ float iql_select_row(const float* sel, const float* val, const float* av, float mask_val, int A) {
-  float best = 0.f; int arg = 0;
-  for (int a = 0; a < A; ++a) {
-    float v = sel[a];
-    if (av && av[a] == 0.f) v = mask_val;
-    if (a == 0 || v > best) { best = v; arg = a; }       // strict >: first index wins ties (torch)
-  }
+  float best;
+  const int arg = rt::masked_argmax_row(sel, av, mask_val, A, &best);
   return (av && av[arg] == 0.f) ? mask_val : val[arg];
-}
-
-// a wave copies n floats of its tile as they lie: 16 bytes per lane where the operand is 16-byte aligned
-__device__ __forceinline__ void iql_stage(float* S, const float* g, int n, int vec, int lane) {
-  const int n4 = vec ? n >> 2 : 0;
-  for (int e = lane; e < n4; e += 64) reinterpret_cast<f32x4*>(S)[e] = reinterpret_cast<const f32x4*>(g)[e];
-  for (int e = 4 * n4 + lane; e < n; e += 64) S[e] = g[e];
 }
 
 template <bool STAGED>
@@ -64,14 +49,16 @@ __global__ __launch_bounds__(TPB) void iql_rows_kernel(IqlArgs a) {
   const int A = a.A;
   const bool select = a.q_tgt != nullptr;
   const int nops = (a.q_sel ? 1 : 0) + 1 + (a.avail ? 1 : 0);
-  const int TS = (IQ_ROWS * A + 3) & ~3;                  // floats per operand tile (16-byte multiple)
+  const int TS = rt::tile_floats(A);
+  // rt::wave_tiles written out: through the helper the compiler orders this kernel's prologue another way, and the staged form then
+  // measures 1.2 % slower at A = 14 and 18 with the same loop body (DESIGN, the section on row_tile.h)
   float* Sv = iq_smem + (size_t)wave * nops * TS;          // q_tgt, then q_sel, then avail - those that are given
   float* Sq = a.q_sel ? Sv + TS : Sv;
   float* Sa = a.avail ? Sv + (a.q_sel ? 2 : 1) * TS : nullptr;
   float acc[2] = {0.f, 0.f};
-  const long tiles = (a.rows + IQ_ROWS - 1) / IQ_ROWS;
-  for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
-    const long r0 = tile * IQ_ROWS;
+  const long tiles = rt::tiles(a.rows);
+  for (long tile = rt::first_tile(); tile < tiles; tile += rt::tile_step()) {
+    const long r0 = tile * rt::ROWS;
     // the row's own scalars first: their loads fly while the tiles are staged (the taken action's Q hangs on u, the target on both)
     const long row = r0 + lane;
     const bool in = row < a.rows;
@@ -92,11 +79,11 @@ __global__ __launch_bounds__(TPB) void iql_rows_kernel(IqlArgs a) {
       }
     }
     if (STAGED) {
-      const int n = (int)((a.rows - r0 < IQ_ROWS ? a.rows - r0 : IQ_ROWS) * A);
-      iql_stage(Sv, a.q_tgt + r0 * A, n, a.vec, lane);
-      if (a.q_sel) iql_stage(Sq, a.q_sel + r0 * A, n, a.vec, lane);
-      if (a.avail) iql_stage(Sa, a.avail + r0 * A, n, a.vec, lane);
-      __builtin_amdgcn_s_waitcnt(0xC07F);                 // this wave's LDS writes (lgkmcnt(0)); no cross-wave sharing
+      const int n = rt::tile_len(a.rows, r0, A);
+      rt::copy(Sv, a.q_tgt + r0 * A, n, a.vec);
+      if (a.q_sel) rt::copy(Sq, a.q_sel + r0 * A, n, a.vec);
+      if (a.avail) rt::copy(Sa, a.avail + r0 * A, n, a.vec);
+      rt::lds_done();
     }
     if (in) {
       float qn = 0.f, dq = 0.f;
@@ -152,19 +139,16 @@ int iql_launch(IqlArgs a, float* out2, int B, int T, int N, int A, hipStream_t s
     for (int p = 0; p < o; ++p)
       if (iql_overlap(outs[o], outb[o], outs[p], outb[p])) return (int)hipErrorInvalidValue;
   }
-  const long tiles = (rows + IQ_ROWS - 1) / IQ_ROWS;
-  long nb = (tiles + 3) / 4;
-  if (nb > IQ_MAX_BLOCKS) nb = IQ_MAX_BLOCKS;
   const int nops = (a.q_sel ? 1 : 0) + 1 + (a.avail ? 1 : 0);
-  const size_t lds = (size_t)4 * nops * ((IQ_ROWS * A + 3) & ~3) * sizeof(float);
-  a.vec = ((reinterpret_cast<uintptr_t>(a.q_sel) | reinterpret_cast<uintptr_t>(a.q_tgt) | reinterpret_cast<uintptr_t>(a.avail)) & 15) == 0;
-  if (select && lds <= IQ_LDS_MAX)
-    hipLaunchKernelGGL(iql_rows_kernel<true>, dim3((unsigned)nb), dim3(TPB), lds, s, a);
-  else
-    hipLaunchKernelGGL(iql_rows_kernel<false>, dim3((unsigned)nb), dim3(TPB), 0, s, a);
+  const rt::Plan pl = rt::plan(rows, A, nops, IQ_LDS_MAX, rt::PARTIAL_ROWS, {a.q_sel, a.q_tgt, a.avail});
+  a.vec = pl.vec;
+  if (select && pl.tiled)
+    hipLaunchKernelGGL(iql_rows_kernel<true>, dim3((unsigned)pl.blocks), dim3(TPB), pl.lds_bytes, s, a);
+  else                                 // the row-per-lane twin keeps the tile loop, and so the grid
+    hipLaunchKernelGGL(iql_rows_kernel<false>, dim3((unsigned)pl.blocks), dim3(TPB), 0, s, a);
   MARL_CHECK_LAUNCH();
   if (a.ws) {
-    hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, s, (const float*)a.ws, (int)nb, 2, out2);
+    hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, s, (const float*)a.ws, pl.blocks, 2, out2);
     MARL_CHECK_LAUNCH();
   }
   return 0;

@@ -3,9 +3,11 @@
 // coalesced over the row axis, reductions by wave shuffles, deterministic two-stage sums.
 #include "common.h"
 #include "sums.h"
+#include "row_tile.h"
 #include "../../include/marl_hip.h"
 
 namespace {
+namespace rt = row_tile;
 
 constexpr int TPB = 256;
 static_assert(TPB == SUMS_TPB, "the loss kernels launch sums.h's workgroup size");
@@ -29,13 +31,8 @@ __global__ void q_gather_kernel(const float* q, const int* idx, const float* ava
 __global__ void q_masked_max_kernel(const float* q, const float* avail, float mask_val, float* out_max,
                                     int* out_arg, long rows, int A) {
   for (long r = (long)blockIdx.x * TPB + threadIdx.x; r < rows; r += (long)gridDim.x * TPB) {
-    float best = 0.f;
-    int arg = 0;
-    for (int a = 0; a < A; ++a) {
-      float v = q[r * A + a];
-      if (avail && avail[r * A + a] == 0.f) v = mask_val;
-      if (a == 0 || v > best) { best = v; arg = a; }   // strict >: first index wins ties (torch)
-    }
+    float best;
+    const int arg = rt::masked_argmax_row(q + r * A, avail ? avail + r * A : nullptr, mask_val, A, &best);
     if (out_max) out_max[r] = best;
     if (out_arg) out_arg[r] = arg;
   }
@@ -43,99 +40,60 @@ __global__ void q_masked_max_kernel(const float* q, const float* avail, float ma
 
 // Double-Q selection in one pass (reference q_learner.py:104-117): arg = first-index argmax over the available
 // actions of q_sel (the eval net on the next observations), out = q_val (target net) at arg, masked the same way.
-// A wave stages 64 rows of each operand through LDS with fully coalesced loads (rows are A floats = 44 B for
-// 2s3z, a thread-per-row global read pattern wastes most of every 64-byte request); stride A is odd or the
-// tile is padded to an odd stride, so the per-row LDS reads are conflict-free.
-constexpr int DS_ROWS = 64;      // rows per wave-tile
+// Staged by row_tile.h: three tiles per wave, and the availability tile holds 1 where no avail is given.
 __global__ __launch_bounds__(256) void q_double_select_kernel(const float* q_sel, const float* q_val, const float* avail,
                                                               float mask_val, float* out_val, int* out_arg, long rows, int A, int vec) {
   extern __shared__ __attribute__((aligned(16))) float ds_smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int TS = (DS_ROWS * A + 3) & ~3;                  // floats per operand tile (16-byte multiple)
-  float* Sq = ds_smem + (size_t)wave * 3 * TS;
+  const int lane = threadIdx.x & 63;
+  const int TS = rt::tile_floats(A);
+  float* Sq = rt::wave_tiles(ds_smem, 3, A);
   float* Sv = Sq + TS;
   float* Sa = Sv + TS;
-  const long tiles = (rows + DS_ROWS - 1) / DS_ROWS;
-  for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
-    const long r0 = tile * DS_ROWS;
-    const int n = (int)((rows - r0 < DS_ROWS ? rows - r0 : DS_ROWS) * A);
-    // the tile is one contiguous run of n floats (64 rows x A): copied as it lies, 16 bytes per lane, no index math
-    // (r0 * A * 4 is a multiple of 16, the operands themselves are 16-byte aligned - checked on the host)
-    const float* gq = q_sel + r0 * A;
-    const float* gv = q_val + r0 * A;
-    const float* ga = avail ? avail + r0 * A : nullptr;
-    const int n4 = vec ? n >> 2 : 0;                   // (operands not 16-byte aligned: plain element copy)
-    for (int e = lane; e < n4; e += 64) {
-      reinterpret_cast<f32x4*>(Sq)[e] = reinterpret_cast<const f32x4*>(gq)[e];
-      reinterpret_cast<f32x4*>(Sv)[e] = reinterpret_cast<const f32x4*>(gv)[e];
-      reinterpret_cast<f32x4*>(Sa)[e] = ga ? reinterpret_cast<const f32x4*>(ga)[e] : (f32x4){1.f, 1.f, 1.f, 1.f};
-    }
-    for (int e = 4 * n4 + lane; e < n; e += 64) {
-      Sq[e] = gq[e]; Sv[e] = gv[e]; Sa[e] = ga ? ga[e] : 1.f;
-    }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                   // this wave's LDS writes (lgkmcnt(0)); no cross-wave sharing
+  const long tiles = rt::tiles(rows);
+  for (long tile = rt::first_tile(); tile < tiles; tile += rt::tile_step()) {
+    const long r0 = tile * rt::ROWS;
+    rt::copy<3, true>({Sq, Sv, Sa}, {q_sel + r0 * A, q_val + r0 * A, avail ? avail + r0 * A : nullptr}, rt::tile_len(rows, r0, A), vec);
+    rt::lds_done();
     const long r = r0 + lane;
     if (r < rows) {
-      float best = 0.f; int arg = 0;
-      for (int a = 0; a < A; ++a) {
-        float v = Sq[lane * A + a];
-        if (Sa[lane * A + a] == 0.f) v = mask_val;
-        if (a == 0 || v > best) { best = v; arg = a; }   // strict >: first index wins ties (torch)
-      }
+      float best;
+      __builtin_assume(Sa != nullptr);                     // the availability tile is always there (ones without avail)
+      const int arg = rt::masked_argmax_row(Sq + lane * A, Sa + lane * A, mask_val, A, &best);
       out_val[r] = Sa[lane * A + arg] == 0.f ? mask_val : Sv[lane * A + arg];
       if (out_arg) out_arg[r] = arg;
     }
   }
 }
 
-// Row-per-thread form of the same selection for action counts whose staged tiles do not fit (4 waves x 3 operands x 64 rows x A
-// floats exceeds 64 KiB from A = 22): same comparisons in the same order, so the same results bit for bit.
+// Row-per-thread form of the same selection for action counts whose staged tiles do not fit (from A = 22)
 __global__ void q_double_select_rows_kernel(const float* q_sel, const float* q_val, const float* avail, float mask_val,
                                             float* out_val, int* out_arg, long rows, int A) {
   for (long r = (long)blockIdx.x * TPB + threadIdx.x; r < rows; r += (long)gridDim.x * TPB) {
-    float best = 0.f;
-    int arg = 0;
-    for (int a = 0; a < A; ++a) {
-      float v = q_sel[r * A + a];
-      if (avail && avail[r * A + a] == 0.f) v = mask_val;
-      if (a == 0 || v > best) { best = v; arg = a; }   // strict >: first index wins ties (torch)
-    }
+    float best;
+    const int arg = rt::masked_argmax_row(q_sel + r * A, avail ? avail + r * A : nullptr, mask_val, A, &best);
     out_val[r] = (avail && avail[r * A + arg] == 0.f) ? mask_val : q_val[r * A + arg];
     if (out_arg) out_arg[r] = arg;
   }
 }
 
-// q_masked_max with the staging of q_double_select_kernel: a wave copies 64 rows of q (and avail) into LDS with 16-byte coalesced
-// loads, then one lane per row scans its A values (the thread-per-row kernel above reads 44 - 72 byte rows at a lane stride of a
-// row: 50 us for 614 400 rows x 14 actions where the bytes are worth 12 us).  Same results (strict >: first index wins ties).
+// q_masked_max with the same staging (the thread-per-row kernel above reads 44 - 72 byte rows at a lane stride of a row: 50 us for
+// 614 400 rows x 14 actions where the bytes are worth 12 us).  No vec argument: the host sends unaligned bases to the row kernel.
 __global__ __launch_bounds__(256) void q_masked_max_tiled_kernel(const float* q, const float* avail, float mask_val, float* out_max,
                                                                  int* out_arg, long rows, int A) {
   extern __shared__ __attribute__((aligned(16))) float ds_smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int TS = (DS_ROWS * A + 3) & ~3;
-  float* Sq = ds_smem + (size_t)wave * 2 * TS;
-  float* Sa = Sq + TS;
-  const long tiles = (rows + DS_ROWS - 1) / DS_ROWS;
-  for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
-    const long r0 = tile * DS_ROWS;
-    const int n = (int)((rows - r0 < DS_ROWS ? rows - r0 : DS_ROWS) * A);
-    const float* gq = q + r0 * A;
-    const float* ga = avail ? avail + r0 * A : nullptr;
-    const int n4 = n >> 2;
-    for (int e = lane; e < n4; e += 64) {
-      reinterpret_cast<f32x4*>(Sq)[e] = reinterpret_cast<const f32x4*>(gq)[e];
-      reinterpret_cast<f32x4*>(Sa)[e] = ga ? reinterpret_cast<const f32x4*>(ga)[e] : (f32x4){1.f, 1.f, 1.f, 1.f};
-    }
-    for (int e = 4 * n4 + lane; e < n; e += 64) { Sq[e] = gq[e]; Sa[e] = ga ? ga[e] : 1.f; }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                   // this wave's LDS writes (lgkmcnt(0)); no cross-wave sharing
+  const int lane = threadIdx.x & 63;
+  float* Sq = rt::wave_tiles(ds_smem, 2, A);
+  float* Sa = Sq + rt::tile_floats(A);
+  const long tiles = rt::tiles(rows);
+  for (long tile = rt::first_tile(); tile < tiles; tile += rt::tile_step()) {
+    const long r0 = tile * rt::ROWS;
+    rt::copy<2, true>({Sq, Sa}, {q + r0 * A, avail ? avail + r0 * A : nullptr}, rt::tile_len(rows, r0, A), 1);
+    rt::lds_done();
     const long r = r0 + lane;
     if (r < rows) {
-      float best = 0.f; int arg = 0;
-      for (int a = 0; a < A; ++a) {
-        float v = Sq[lane * A + a];
-        if (Sa[lane * A + a] == 0.f) v = mask_val;
-        if (a == 0 || v > best) { best = v; arg = a; }
-      }
+      float best;
+      __builtin_assume(Sa != nullptr);                     // the availability tile is always there (ones without avail)
+      const int arg = rt::masked_argmax_row(Sq + lane * A, Sa + lane * A, mask_val, A, &best);
       if (out_max) out_max[r] = best;
       if (out_arg) out_arg[r] = arg;
     }
@@ -457,7 +415,7 @@ __global__ __launch_bounds__(TPB) void qplex_mix_bwd_tiled_kernel(const float* w
 
 // rows per workgroup of the tiled kernels (0: shape not covered, use the row-per-thread kernels)
 inline int qplex_tile_rows(int N, int K, const void* a, const void* b, const void* c) {
-  if (((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b) | reinterpret_cast<uintptr_t>(c)) & 15) != 0) return 0;
+  if (!aligned16(a) || !aligned16(b) || !aligned16(c)) return 0;
   for (int qr = 128; qr >= 32; qr >>= 1)
     if ((size_t)qr * (2 * K * N + K + 2 * N) * 4 <= 64 * 1024) return qr;
   return 0;
@@ -502,13 +460,6 @@ __global__ void qtran_loss_kernel(const float* jq, const float* jq_tgt, const fl
   block_partials<4>(acc, ws);
 }
 
-inline int loss_blocks(long rows) {
-  long b = (rows + TPB - 1) / TPB;
-  if (b > 1024) b = 1024;
-  if (b < 1) b = 1;
-  return (int)b;
-}
-
 }  // namespace
 
 extern "C" int marl_q_gather(const float* q, const int* idx, const float* avail, float mask_val, float* out,
@@ -524,13 +475,10 @@ extern "C" int marl_q_masked_max(const float* q, const float* avail, float mask_
                                  long rows, int A, void* stream) {
   if (rows <= 0) return 0;
   // 16-byte aligned operands (64 rows x A floats is a multiple of 16 bytes): the LDS-staged kernel
-  const size_t lds = (size_t)4 * 2 * ((DS_ROWS * A + 3) & ~3) * sizeof(float);
-  if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(avail)) & 15) == 0 && lds <= 64 * 1024 && rows >= 4096) {
-    const long tiles = (rows + DS_ROWS - 1) / DS_ROWS;
-    long nb = (tiles + 3) / 4;
-    if (nb > 2048) nb = 2048;
-    hipLaunchKernelGGL(q_masked_max_tiled_kernel, dim3((unsigned)nb), dim3(256), lds, (hipStream_t)stream, q, avail, mask_val,
-                       out_max, out_arg, rows, A);
+  const rt::Plan pl = rt::plan(rows, A, 2, 64 * 1024, 2048, {q, avail});
+  if (pl.tiled && pl.vec && rows >= 4096) {
+    hipLaunchKernelGGL(q_masked_max_tiled_kernel, dim3((unsigned)pl.blocks), dim3(256), pl.lds_bytes, (hipStream_t)stream, q, avail,
+                       mask_val, out_max, out_arg, rows, A);
     MARL_CHECK_LAUNCH();
     return 0;
   }
@@ -543,19 +491,15 @@ extern "C" int marl_q_masked_max(const float* q, const float* avail, float mask_
 extern "C" int marl_q_double_select(const float* q_sel, const float* q_val, const float* avail, float mask_val,
                                     float* out_val, int* out_arg, long rows, int A, void* stream) {
   if (rows <= 0) return 0;
-  const long tiles = (rows + DS_ROWS - 1) / DS_ROWS;
-  long nb = (tiles + 3) / 4;
-  if (nb > 2048) nb = 2048;
-  const size_t lds = (size_t)4 * 3 * ((DS_ROWS * A + 3) & ~3) * sizeof(float);
-  if (lds > 64 * 1024) {             // A >= 22: the tiles do not fit, one thread per row (as marl_q_masked_max falls back)
+  const rt::Plan pl = rt::plan(rows, A, 3, 64 * 1024, 2048, {q_sel, q_val, avail});
+  if (!pl.tiled) {                   // A >= 22: the tiles do not fit, one thread per row (as marl_q_masked_max falls back)
     hipLaunchKernelGGL(q_double_select_rows_kernel, dim3(nblk(rows)), dim3(TPB), 0, (hipStream_t)stream, q_sel, q_val, avail,
                        mask_val, out_val, out_arg, rows, A);
     MARL_CHECK_LAUNCH();
     return 0;
   }
-  const int vec = ((reinterpret_cast<uintptr_t>(q_sel) | reinterpret_cast<uintptr_t>(q_val) | reinterpret_cast<uintptr_t>(avail)) & 15) == 0;
-  hipLaunchKernelGGL(q_double_select_kernel, dim3((unsigned)nb), dim3(256), lds, (hipStream_t)stream, q_sel, q_val, avail,
-                     mask_val, out_val, out_arg, rows, A, vec);
+  hipLaunchKernelGGL(q_double_select_kernel, dim3((unsigned)pl.blocks), dim3(256), pl.lds_bytes, (hipStream_t)stream, q_sel, q_val,
+                     avail, mask_val, out_val, out_arg, rows, A, pl.vec);
   MARL_CHECK_LAUNCH();
   return 0;
 }
@@ -640,7 +584,7 @@ extern "C" int marl_qplex_mix_bwd(const float* w_raw, const float* q, const floa
                                   int weighted_head, int minus_one, void* stream) {
   if (rows <= 0) return 0;
   int qr = qplex_tile_rows(N, K, key, ag, ac);
-  if (qr && ((reinterpret_cast<uintptr_t>(dkey) | reinterpret_cast<uintptr_t>(dag) | reinterpret_cast<uintptr_t>(dac)) & 15) != 0) qr = 0;
+  if (qr && (!aligned16(dkey) || !aligned16(dag) || !aligned16(dac))) qr = 0;
   if (qr) {
     long nb = (rows + qr - 1) / qr; if (nb > 4096) nb = 4096;
     hipLaunchKernelGGL(qplex_mix_bwd_tiled_kernel, dim3((unsigned)nb), dim3(TPB), (size_t)qr * (2 * K * N + K + 2 * N) * 4,
@@ -759,13 +703,13 @@ extern "C" int marl_replay_gather(const long long* idx, int B, int T, int N, int
   return 0;
 }
 
-extern "C" size_t marl_loss_workspace(long rows) { return (size_t)1024 * 4 * sizeof(float); }
+extern "C" size_t marl_loss_workspace(long rows) { return (size_t)rt::PARTIAL_ROWS * 4 * sizeof(float); }
 
 extern "C" int marl_td_loss(const float* q_tot, const float* q_tot_tgt, const float* r, const float* term,
                             const float* padded, float gamma, float* dq_tot, float* out2, float* ws, long rows,
                             void* stream) {
   if (rows <= 0) return 0;
-  const int nb = loss_blocks(rows);
+  const int nb = rt::partial_blocks(rows);
   hipLaunchKernelGGL(td_loss_kernel, dim3(nb), dim3(TPB), 0, (hipStream_t)stream, q_tot, q_tot_tgt, r, term, padded,
                      gamma, dq_tot, ws, rows);
   MARL_CHECK_LAUNCH();
@@ -780,7 +724,7 @@ extern "C" int marl_qtran_loss(const float* jq, const float* jq_tgt, const float
                                float* d_v, float* d_qsum_opt, float* d_qsum_nopt, float* out4, float* ws, long rows,
                                void* stream) {
   if (rows <= 0) return 0;
-  const int nb = loss_blocks(rows);
+  const int nb = rt::partial_blocks(rows);
   hipLaunchKernelGGL(qtran_loss_kernel, dim3(nb), dim3(TPB), 0, (hipStream_t)stream, jq, jq_tgt, v, jq_hat, qsum_opt,
                      qsum_nopt, r, term, padded, gamma, lam_opt, lam_nopt, d_jq, d_v, d_qsum_opt, d_qsum_nopt, ws,
                      rows);

@@ -266,8 +266,6 @@ __global__ __launch_bounds__(256) void mlp3_reduce_kernel(Mlp3RedArgs a) {
   else a.db3[g * a.gs_b3 + n] += s;
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 inline ConcatSrc to_src3(const marl_src_t* s) {
   ConcatSrc c;
   c.p0 = s->p0; c.ld0 = s->ld0; c.k0 = s->k0;

@@ -7,19 +7,18 @@
 // Gradient of log pi_u by z_i (through pt and the renormalisation; delta_ui - pi_i at eps = 0):
 //   g_i = (1 - eps) [ e_u (delta_ui - e_i / S) / w_u  -  e_i (a_i - Sa / S) / D ].
 //
-// Lane mapping of the two batch kernels (probs, loss_bwd): rows are A consecutive floats (44 bytes at A = 11), so one lane per row
-// against global memory would spend most of every 64-byte request.  A wave stages 64 rows of logits and availability - one
-// contiguous run of 64 A floats each - into LDS with 16-byte coalesced loads, every lane then walks its own row in LDS, writes the
-// result over the logits tile, and the wave stores that tile back as one contiguous run.  The tiles are private to a wave: no
-// workgroup barrier.  The LDS walk is at a lane stride of A dwords: conflict-free for odd A, two-way for A = 14 or 18.  From
-// A = 29 the tiles of four waves pass 56 KiB and the row-per-lane kernel runs instead (same arithmetic in the same order).
+// Lane mapping of the two batch kernels (probs, loss_bwd): row_tile.h's staging with two tiles, logits and availability; every lane
+// writes its result over its row of the logits tile, and the wave stores that tile back.  From A = 29 the tiles of four waves pass
+// 56 KiB and the row-per-lane kernel runs instead.
 // The sampler runs once per lock-step over E N rows (25 600 at most in the measured set-ups): one lane per row, like select_kernel.
 #include <type_traits>
 #include "synth_env.h"
 #include "policy_rows.h"
+#include "row_tile.h"
 #include "../../include/marl_hip.h"
 
 namespace {
+namespace rt = row_tile;
 
 constexpr int TPB = SUMS_TPB;
 
@@ -113,28 +112,17 @@ __device__ __forceinline__ void loss_row_ppo(const PpoArgs& p, long r, const flo
 template <bool LOSS, bool EX = false, bool PPO = false>
 __global__ __launch_bounds__(TPB) void policy_tiled_kernel(ArgsOf<PPO> p) {
   extern __shared__ __attribute__((aligned(16))) float pt_smem[];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
   const int A = p.A;
-  const int TS = (PT_ROWS * A + 3) & ~3;                  // floats per tile (16-byte multiple)
-  float* Sz = pt_smem + (size_t)wave * 2 * TS;
-  float* Sa = Sz + TS;
+  float* Sz = rt::wave_tiles(pt_smem, 2, A);
+  float* Sa = Sz + rt::tile_floats(A);
   float acc[PPO ? 4 : EX ? 3 : 2] = {};
-  const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
-  for (long tile = (long)blockIdx.x * 4 + wave; tile < tiles; tile += (long)gridDim.x * 4) {
-    const long r0 = tile * PT_ROWS;
-    const int n = (int)((p.rows - r0 < PT_ROWS ? p.rows - r0 : PT_ROWS) * A);
-    // the tile is one contiguous run of n floats: copied as it lies (r0 A 4 is a multiple of 16; the host checked the bases)
-    const float* gz = p.logits + r0 * A;
-    const float* ga = p.avail + r0 * A;
-    float* go = p.out + r0 * A;
-    const int n4 = p.vec ? n >> 2 : 0;
-    for (int e = lane; e < n4; e += 64) {
-      reinterpret_cast<f32x4*>(Sz)[e] = reinterpret_cast<const f32x4*>(gz)[e];
-      reinterpret_cast<f32x4*>(Sa)[e] = reinterpret_cast<const f32x4*>(ga)[e];
-    }
-    for (int e = 4 * n4 + lane; e < n; e += 64) { Sz[e] = gz[e]; Sa[e] = ga[e]; }
-    __builtin_amdgcn_s_waitcnt(0xC07F);                   // this wave's LDS writes (lgkmcnt(0)); no cross-wave sharing
-    __builtin_amdgcn_wave_barrier();
+  const long tiles = rt::tiles(p.rows);
+  for (long tile = rt::first_tile(); tile < tiles; tile += rt::tile_step()) {
+    const long r0 = tile * rt::ROWS;
+    const int n = rt::tile_len(p.rows, r0, A);
+    rt::copy<2>({Sz, Sa}, {p.logits + r0 * A, p.avail + r0 * A}, n, p.vec);
+    rt::lds_done_fenced();
     const long r = r0 + lane;
     if (r < p.rows) {
       if constexpr (PPO) loss_row_ppo(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
@@ -142,12 +130,9 @@ __global__ __launch_bounds__(TPB) void policy_tiled_kernel(ArgsOf<PPO> p) {
       else if constexpr (LOSS) loss_row(p, r, Sz + lane * A, Sa + lane * A, Sz + lane * A, acc);
       else row_probs(Sz + lane * A, Sa + lane * A, Sz + lane * A, A, p.eps);
     }
-    __builtin_amdgcn_s_waitcnt(0xC07F);
-    __builtin_amdgcn_wave_barrier();
-    for (int e = lane; e < n4; e += 64) reinterpret_cast<f32x4*>(go)[e] = reinterpret_cast<const f32x4*>(Sz)[e];
-    for (int e = 4 * n4 + lane; e < n; e += 64) go[e] = Sz[e];
-    __builtin_amdgcn_s_waitcnt(0xC07F);                   // the tile is read out before the next trip overwrites it
-    __builtin_amdgcn_wave_barrier();
+    rt::lds_done_fenced();
+    rt::copy(p.out + r0 * A, Sz, n, p.vec);
+    rt::lds_done_fenced();                                // the tile is read out before the next trip overwrites it
   }
   if (LOSS) block_partials<PPO ? 4 : EX ? 3 : 2>(acc, p.ws);
 }
@@ -170,16 +155,13 @@ __global__ __launch_bounds__(TPB) void policy_rows_kernel(ArgsOf<PPO> p) {
 
 template <bool LOSS, bool EX = false, bool PPO = false>
 int launch_policy(ArgsOf<PPO> p, hipStream_t s, int& nb) {
-  const size_t lds = (size_t)4 * 2 * ((PT_ROWS * p.A + 3) & ~3) * sizeof(float);
-  if (lds <= 56 * 1024) {            // (block_partials keeps a few floats of its own)
-    const long tiles = (p.rows + PT_ROWS - 1) / PT_ROWS;
-    long b = (tiles + 3) / 4;
-    nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
-    p.vec = ((reinterpret_cast<uintptr_t>(p.logits) | reinterpret_cast<uintptr_t>(p.avail) | reinterpret_cast<uintptr_t>(p.out)) & 15) == 0;
-    hipLaunchKernelGGL((policy_tiled_kernel<LOSS, EX, PPO>), dim3((unsigned)nb), dim3(TPB), lds, s, p);
+  const rt::Plan pl = rt::plan(p.rows, p.A, 2, 56 * 1024, rt::PARTIAL_ROWS, {p.logits, p.avail, p.out});   // (block_partials keeps a few floats of its own)
+  if (pl.tiled) {
+    nb = pl.blocks;
+    p.vec = pl.vec;
+    hipLaunchKernelGGL((policy_tiled_kernel<LOSS, EX, PPO>), dim3((unsigned)nb), dim3(TPB), pl.lds_bytes, s, p);
   } else {
-    long b = (p.rows + TPB - 1) / TPB;
-    nb = (int)(b > PT_MAX_BLOCKS ? PT_MAX_BLOCKS : b);
+    nb = rt::partial_blocks(p.rows);
     hipLaunchKernelGGL((policy_rows_kernel<LOSS, EX, PPO>), dim3((unsigned)nb), dim3(TPB), 0, s, p);
   }
   MARL_CHECK_LAUNCH();

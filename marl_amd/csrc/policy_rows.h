@@ -6,8 +6,6 @@
 
 namespace {
 
-constexpr int PT_ROWS = 64;          // rows per wave tile
-constexpr int PT_MAX_BLOCKS = 1024;  // one grid pass covers 1024 x 4 x 64 = 262 144 rows (and the loss workspace holds 1024 rows of partials)
 constexpr float EXP_CLAMP = 80.f;
 
 struct RowPolicy { float mx, S, Sa, D, cw, ew; int n; };     // w_k = cw e_k + ew

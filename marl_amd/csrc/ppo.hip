@@ -7,13 +7,13 @@
 // at most its first half), so nothing reads stats3 and the third pass may write it.  rows is B*T (491 520 at the full size): plain
 // grid-stride loops, one float per lane.
 #include "sums.h"
+#include "row_tile.h"
 #include "../../include/marl_hip.h"
 
 namespace {
 
 constexpr int TPB = SUMS_TPB;
-constexpr int PS_MAX_BLOCKS = 1024;                      // the loss workspace holds 1024 rows of four partials
-constexpr int PS_RAW = PS_MAX_BLOCKS * 4 - 4;            // { sum m x, M, sum m (x - mean)^2 } behind the partials
+constexpr int PS_RAW = row_tile::PARTIAL_ROWS * 4 - 4;   // { sum m x, M, sum m (x - mean)^2 } behind the partials
 constexpr float PS_EPS = 1e-5f;
 
 __device__ __forceinline__ float ps_mean(const float* raw) { return raw[1] > 0.f ? raw[0] / raw[1] : 0.f; }
@@ -64,8 +64,7 @@ extern "C" int marl_masked_standardize(const float* x, const float* padded, floa
   if (rows <= 0) return 0;
   if (!x || !padded || !out || !stats3 || !ws || out == padded) return (int)hipErrorInvalidValue;
   hipStream_t s = (hipStream_t)stream;
-  const long b = (rows + TPB - 1) / TPB;
-  const int nb = (int)(b > PS_MAX_BLOCKS ? PS_MAX_BLOCKS : b);
+  const int nb = row_tile::partial_blocks(rows);
   hipLaunchKernelGGL(ps_sum_kernel, dim3((unsigned)nb), dim3(TPB), 0, s, x, padded, ws, rows);
   MARL_CHECK_LAUNCH();
   hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, s, (const float*)ws, nb, 2, ws + PS_RAW);

@@ -885,7 +885,6 @@ __global__ __launch_bounds__(256) void qtran_reduce_kernel(QtRedArgs a) {
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // the states as the callers hold them: dense (BT, S) or rows of the (T+1)-slot episode storage through a row remap and an
 // optional episode map (replay samples read in place); one dense segment, rows 16-byte aligned
 inline bool state_src_ok(const marl_src_t* s, int S) {

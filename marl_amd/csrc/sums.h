@@ -23,19 +23,27 @@ __device__ __forceinline__ void block_partials(float (&v)[NV], float* ws) {
   }
 }
 
-__global__ void finish_sums_kernel(const float* ws, int nblocks, int nv, float* out) {
+// the fixed-order tree of the finish pass, called by every thread of ONE workgroup of SUMS_TPB: column i of nblocks workspace rows
+// of nv partials - a strided sum per thread, then the LDS halving; every thread gets the total
+__device__ __forceinline__ float block_tree_sum(const float* ws, int nblocks, int nv, int i) {
   __shared__ float sh[SUMS_TPB];
+  float s = 0.f;
+  for (int b = threadIdx.x; b < nblocks; b += SUMS_TPB) s += ws[(long)b * nv + i];
+  sh[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = SUMS_TPB / 2; o > 0; o >>= 1) {
+    if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
+    __syncthreads();
+  }
+  const float tot = sh[0];
+  __syncthreads();                     // sh is free for the next column
+  return tot;
+}
+
+__global__ void finish_sums_kernel(const float* ws, int nblocks, int nv, float* out) {
   for (int i = 0; i < nv; ++i) {
-    float s = 0.f;
-    for (int b = threadIdx.x; b < nblocks; b += SUMS_TPB) s += ws[(long)b * nv + i];
-    sh[threadIdx.x] = s;
-    __syncthreads();
-    for (int o = SUMS_TPB / 2; o > 0; o >>= 1) {
-      if (threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) out[i] = sh[0];
-    __syncthreads();
+    const float tot = block_tree_sum(ws, nblocks, nv, i);
+    if (threadIdx.x == 0) out[i] = tot;
   }
 }
 
