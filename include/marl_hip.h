@@ -753,6 +753,12 @@ int marl_synth_step(unsigned seed, int env0, int episode, int t, const int* len,
 int marl_synth_fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const int* len,
                           const float* q, float* obs, float* state, long state_ld, float* avail, int* u, float* r,
                           float* term, float* padded, int E, int T, int N, int O, int S, int A, void* stream);
+/* marl_synth_fused_step with the choice drawn from the stochastic policy of the agent's row of q (logits) and its availability at
+ * slot t: marl_policy_sample's definition with eps as the mixing epsilon and x = u01(hash(rseed, SAMPLE, env0 + e, tg, n)).  Same
+ * arguments; everything after the choice is marl_synth_fused_step's. */
+int marl_synth_fused_step_sample(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const int* len,
+                                 const float* q, float* obs, float* state, long state_ld, float* avail, int* u, float* r,
+                                 float* term, float* padded, int E, int T, int N, int O, int S, int A, void* stream);
 
 /* The WHOLE rollout of the synthetic env in one persistent launch (rollout_fused.hip): agent step,
  * epsilon-greedy choice, env step and next observation for all T lock-steps; weights and hidden state
@@ -766,6 +772,17 @@ int marl_synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rs
                        float* r, float* term, float* padded, int* length, int* won, float* h_out,
                        float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int O, int S,
                        int A, int last_action, int reuse_network, void* stream);
+/* marl_synth_rollout with every action drawn from the stochastic policy of the step's logits instead of the epsilon-greedy choice:
+ * marl_synth_rollout's argument list and meaning, the same marl_synth_rollout_supported() shapes and launch plan.  eps(t) - the
+ * eps vector or the fp64 schedule - is the policy's mixing epsilon of lock-step t.  With x = u01(hash(rseed, SAMPLE, env, tg, n))
+ * (one draw per environment, agent and global step tg) the action is marl_policy_sample's: with row_policy's scalars of the row, the
+ * first k in index order with a_k = 1 whose running fp32 sum of (cw e_k + ew) / D over the available actions up to k exceeds x; the
+ * last available action when rounding leaves none.  Rows past the episode's end get -1. */
+int marl_synth_rollout_sample(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
+                              int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
+                              float* r, float* term, float* padded, int* length, int* won, float* h_out,
+                              float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int O, int S,
+                              int A, int last_action, int reuse_network, void* stream);
 
 /* The same whole rollout with the agent step (network/q_network.py:16-21) as bf16x6 split products (rollout_x6.hip; args.gemm_mode =
  * "bf16x6"): same arguments, same environment, same epsilon-greedy choice, same record - the integer fields agree with

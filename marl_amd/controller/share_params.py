@@ -269,8 +269,9 @@ class SharedMACWithState(SharedMAC):
 class PolicyMAC(SharedMAC):
     """The actor of the actor-critic learners (central-V): SharedMAC over the unchanged RNNQNet, whose fc2 output is read as the
     logits of a stochastic policy (csrc/policy.hip: the softmax mixed with epsilon of the uniform policy over the available
-    actions).  Training rollouts sample from it - ``stochastic`` sends them down the per-step path with ops.policy_sample in the
-    place of ops.select_actions; evaluation is greedy, and the policy's argmax over the available actions is the masked argmax of
+    actions).  Training rollouts sample from it - ``stochastic`` makes the whole-rollout kernel and the fused step draw from the
+    policy, and the unfused path call ops.policy_sample in the place of ops.select_actions (one rule, one stream of draws:
+    marl_amd/rollout.py); evaluation is greedy, and the policy's argmax over the available actions is the masked argmax of
     the logits, so an evaluation rollout is SharedMAC's at epsilon 0, the whole-rollout kernel included."""
 
     stochastic = True

@@ -17,6 +17,7 @@
 //   loss_bwd: row_tile.h's staging with three tiles (logits, availability, Q); dlogits and dQ are written over the logits and Q
 //     tiles and stored back.  From A = 19 the twelve tiles of a workgroup pass 56 KiB and the row-per-lane form runs.
 // fp32, fixed-order sums, no float atomics: two calls give the same bits.  An action index outside [0, A) is an all-zero one-hot.
+#include "sums.h"
 #include "policy_rows.h"
 #include "row_tile.h"
 #include "../../include/marl_hip.h"

@@ -13,6 +13,7 @@
 // The sampler runs once per lock-step over E N rows (25 600 at most in the measured set-ups): one lane per row, like select_kernel.
 #include <type_traits>
 #include "synth_env.h"
+#include "sums.h"
 #include "policy_rows.h"
 #include "row_tile.h"
 #include "../../include/marl_hip.h"
@@ -182,16 +183,7 @@ __global__ void policy_sample_kernel(const float* logits, const float* avail, lo
     const RowPolicy p = row_policy(z, av, A, eps);
     const unsigned tgl = (unsigned)(tg ? tg[e] : tg0);
     const float u = u01(hkey(rseed, ST_SAMPLE, (unsigned)(env0 + e), tgl, (unsigned)n));
-    const float inv = 1.f / p.D;
-    int arg = -1, last = 0;          // no action available: cannot happen for a live agent; action 0, as select_kernel
-    float cum = 0.f;
-    for (int k = 0; k < A; ++k) {
-      if (av[k] == 0.f) continue;
-      last = k;
-      cum += (p.cw * row_e(p, z[k]) + p.ew) * inv;
-      if (cum > u) { arg = k; break; }
-    }
-    *out = arg >= 0 ? arg : last;    // rounding left the running sum at or below u: the last available action
+    *out = row_sample(p, z, av, A, u);
   }
 }
 

@@ -1,8 +1,8 @@
 // Row helpers of the stochastic policy (policy.hip has the definition and the derivation): the scalars of a row, pi, log pi(u) and
-// the entropy with their gradients by the logits.  Shared by policy.hip and coma.hip; a row's A logits / availability flags may
-// lie in LDS or in global memory.
+// the entropy with their gradients by the logits, and the sampler's ordered walk.  Shared by policy.hip, coma.hip and the rollout
+// kernels (rollout.hip, rollout_fused.hip); a row's A logits / availability flags may lie in LDS or in global memory.
 #pragma once
-#include "sums.h"
+#include "common.h"
 
 namespace {
 
@@ -33,6 +33,47 @@ __device__ __forceinline__ RowPolicy row_policy(const float* z, const float* a, 
   return p;
 }
 __device__ __forceinline__ float row_e(const RowPolicy& p, float z) { return expf(fminf(z - p.mx, EXP_CLAMP)); }
+
+// row_policy of a row whose e_k = row_e(z_k) a caller already holds (e: all A columns, computed against the row's mx): the same
+// ordered fp32 sums S (all columns) and Sa (the available ones) and the same statements for n, cw, ew and D; mx is not needed again
+__device__ __forceinline__ RowPolicy row_policy_e(const float* e, const float* a, int A, float eps) {
+  RowPolicy p;
+  p.n = 0; p.mx = 0.f;
+  for (int k = 0; k < A; ++k)
+    if (a[k] != 0.f) ++p.n;
+  p.S = 0.f; p.Sa = 0.f; p.D = 1.f; p.cw = 0.f; p.ew = 0.f;
+  if (p.n == 0) return p;
+  for (int k = 0; k < A; ++k) {
+    const float ek = e[k];
+    p.S += ek;
+    if (a[k] != 0.f) p.Sa += ek;
+  }
+  p.cw = 1.f - eps;
+  p.ew = eps * p.S / (float)p.n;
+  p.D = p.cw * p.Sa + eps * p.S;
+  return p;
+}
+
+// the sampler's walk (marl_policy_sample, include/marl_hip.h): the running fp32 sum of (cw e_k + ew) / D over the available actions
+// in index order; the first k whose sum exceeds the draw u, the last available action when rounding leaves none (action 0 when no
+// action is available: cannot happen for a live agent).  E_ROW: z holds the row's e_k (row_policy_e) instead of its logits
+template <bool E_ROW = false>
+__device__ __forceinline__ int row_walk(const RowPolicy& p, const float* z, const float* av, int A, float u) {
+  const float inv = 1.f / p.D;
+  int arg = -1, last = 0;
+  float cum = 0.f;
+  for (int k = 0; k < A; ++k) {
+    if (av[k] == 0.f) continue;
+    last = k;
+    cum += (p.cw * (E_ROW ? z[k] : row_e(p, z[k])) + p.ew) * inv;
+    if (cum > u) { arg = k; break; }
+  }
+  return arg >= 0 ? arg : last;
+}
+// one draw from the policy of a row: row_policy's scalars, then the walk
+__device__ __forceinline__ int row_sample(const RowPolicy& p, const float* z, const float* av, int A, float u) {
+  return row_walk<false>(p, z, av, A, u);
+}
 
 // pi of one row, written over out (out may be z)
 __device__ __forceinline__ void row_probs(const float* z, const float* a, float* out, int A, float eps) {

@@ -4,6 +4,7 @@
 // is a pure function of (seed, stream, env, step, index) through a 32-bit hash, so the numpy
 // restatement in oracle/rollout.py reproduces it bit for bit.
 #include "synth_env.h"
+#include "policy_rows.h"
 #include "../../include/marl_hip.h"
 
 namespace {
@@ -89,6 +90,9 @@ __global__ void synth_step_kernel(unsigned seed, int env0, int episode, int t, c
 }
 // One launch per lock-step for the synthetic env: epsilon-greedy choice (same rule as select_kernel),
 // env step (reward / terminated / padded / u) and the observation of slot t+1.  One block per env.
+// SAMPLE: the choice is a draw from the stochastic policy of the agent's row instead (policy_sample_kernel's rule: row_policy with
+// eps as the mixing epsilon, the ST_SAMPLE draw, row_sample); everything after the choice is the same code.
+template <bool SAMPLE>
 __global__ void synth_fused_step_kernel(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps,
                                         const int* len, const float* q, float* obs, float* state, long SL,
                                         float* avail, int* u, float* r, float* term, float* padded, int E, int T, int N,
@@ -104,22 +108,27 @@ __global__ void synth_fused_step_kernel(unsigned seed, unsigned rseed, int env0,
     if (live) {
       const float* qa = q + ((long)e * N + n) * A;
       const float* av = avail + (((long)e * (T + 1) + t) * N + n) * A;
-      float best = 0.f; int navail = 0;
-      for (int a = 0; a < A; ++a) {
-        if (av[a] == 0.f) continue;
-        ++navail;
-        if (arg < 0 || qa[a] > best) { best = qa[a]; arg = a; }
-      }
-      if (arg < 0) arg = 0;
-      const bool explore = u01(hkey(rseed, ST_EXPLORE, env, tg, (unsigned)n)) < eps;
-      if (explore && navail > 0) {
-        int k;
-        env_pick(u01(hkey(rseed, ST_PICK, env, tg, (unsigned)n)), navail, k);
-        int c = 0;
+      if constexpr (SAMPLE) {
+        const RowPolicy p = row_policy(qa, av, A, eps);
+        arg = row_sample(p, qa, av, A, u01(hkey(rseed, ST_SAMPLE, env, tg, (unsigned)n)));
+      } else {
+        float best = 0.f; int navail = 0;
         for (int a = 0; a < A; ++a) {
           if (av[a] == 0.f) continue;
-          if (c == k) { arg = a; break; }
-          ++c;
+          ++navail;
+          if (arg < 0 || qa[a] > best) { best = qa[a]; arg = a; }
+        }
+        if (arg < 0) arg = 0;
+        const bool explore = u01(hkey(rseed, ST_EXPLORE, env, tg, (unsigned)n)) < eps;
+        if (explore && navail > 0) {
+          int k;
+          env_pick(u01(hkey(rseed, ST_PICK, env, tg, (unsigned)n)), navail, k);
+          int c = 0;
+          for (int a = 0; a < A; ++a) {
+            if (av[a] == 0.f) continue;
+            if (c == k) { arg = a; break; }
+            ++c;
+          }
         }
       }
     }
@@ -152,16 +161,32 @@ __global__ void synth_fused_step_kernel(unsigned seed, unsigned rseed, int env0,
 }
 }  // namespace
 
+template <bool SAMPLE>
+static int fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const int* len, const float* q,
+                      float* obs, float* state, long state_ld, float* avail, int* u, float* r, float* term, float* padded, int E,
+                      int T, int N, int O, int S, int A, void* stream) {
+  if (E <= 0) return 0;
+  if (N > 64 || state_ld < S) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(synth_fused_step_kernel<SAMPLE>, dim3(E), dim3(TPB), 0, (hipStream_t)stream, seed, rseed, env0, episode,
+                     t, eps, len, q, obs, state, state_ld, avail, u, r, term, padded, E, T, N, O, S, A);
+  MARL_CHECK_LAUNCH();
+  return 0;
+}
+
 extern "C" int marl_synth_fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps,
                                      const int* len, const float* q, float* obs, float* state, long state_ld,
                                      float* avail, int* u, float* r, float* term, float* padded, int E, int T, int N,
                                      int O, int S, int A, void* stream) {
-  if (E <= 0) return 0;
-  if (N > 64 || state_ld < S) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(synth_fused_step_kernel, dim3(E), dim3(TPB), 0, (hipStream_t)stream, seed, rseed, env0, episode,
-                     t, eps, len, q, obs, state, state_ld, avail, u, r, term, padded, E, T, N, O, S, A);
-  MARL_CHECK_LAUNCH();
-  return 0;
+  return fused_step<false>(seed, rseed, env0, episode, t, eps, len, q, obs, state, state_ld, avail, u, r, term, padded, E, T, N, O,
+                           S, A, stream);
+}
+
+extern "C" int marl_synth_fused_step_sample(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps,
+                                            const int* len, const float* q, float* obs, float* state, long state_ld,
+                                            float* avail, int* u, float* r, float* term, float* padded, int E, int T, int N,
+                                            int O, int S, int A, void* stream) {
+  return fused_step<true>(seed, rseed, env0, episode, t, eps, len, q, obs, state, state_ld, avail, u, r, term, padded, E, T, N, O,
+                          S, A, stream);
 }
 
 extern "C" int marl_select_actions(const float* q, const float* avail, long avail_es, const int* alive, float eps,

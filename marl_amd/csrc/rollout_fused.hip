@@ -10,6 +10,7 @@
 // env of synth_env.h, so the episode record is bit-identical to the launch-per-step path and to the
 // numpy oracle.
 #include "synth_rollout.h"
+#include "policy_rows.h"
 
 namespace {
 
@@ -35,7 +36,9 @@ struct RollArgs {
   long R;
 };
 
-template <int AC>
+// SAMPLE: the choice block draws from the stochastic policy of the row's logits (policy_rows.h; marl_policy_sample's rule with
+// eps(t) as the mixing epsilon and the ST_SAMPLE draw) instead of the epsilon-greedy choice; nothing else differs
+template <int AC, bool SAMPLE>
 __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -205,8 +208,12 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
   gen_prefix(1);          // consumed by gen_slot(1) after the first barrier of step 0
   if (tid < rows) {       // uniforms of the first choice; tile counters
     const unsigned env = (unsigned)(a.env0 + b0 + rowe[tid]), tg0 = env_tg(a.episode, T, 0);
-    uex[tid] = u01(hkey(a.rseed, ST_EXPLORE, env, tg0, (unsigned)rown[tid]));
-    uex[rows + tid] = u01(hkey(a.rseed, ST_PICK, env, tg0, (unsigned)rown[tid]));
+    if constexpr (SAMPLE) {      // one uniform per (env, agent, step): the policy's draw; uex[rows + r] stays unused
+      uex[tid] = u01(hkey(a.rseed, ST_SAMPLE, env, tg0, (unsigned)rown[tid]));
+    } else {
+      uex[tid] = u01(hkey(a.rseed, ST_EXPLORE, env, tg0, (unsigned)rown[tid]));
+      uex[rows + tid] = u01(hkey(a.rseed, ST_PICK, env, tg0, (unsigned)rown[tid]));
+    }
     if (tid < 4) tilecnt[tid] = 0;
   }
 
@@ -389,38 +396,79 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
     // ---------------- epsilon-greedy choice (share_params.py:66-70): 16*AC lanes per (env, agent) row, lane = action;
     // first-index argmax over the available actions by a lane-group max + ballot, the explored action is the
     // kk-th set bit of the availability mask (the serial per-thread form of this took 13-35 % of a lock-step)
+    // SAMPLE: a draw from the row's stochastic policy in two phases (below)
     const unsigned tg = env_tg(a.episode, T, t);
     {
       constexpr int LG = 16 * AC;
       constexpr unsigned GM = LG == 32 ? 0xffffffffu : ((1u << LG) - 1u);
       const int gl = lane & (LG - 1), sh = lane & ~(LG - 1);
-      for (int base = wave * (64 / LG); base < vrows; base += (RNT / 64) * (64 / LG)) {
-        const int r = base + lane / LG;
-        const bool valid = r < vrows;
-        const int rr = valid ? r : vrows - 1;
-        const int4 mt = rmeta[rr];
-        const int n = mt.w;
-        const bool on = gl < A && AvC[rr * A + (gl < A ? gl : 0)] != 0.f;
-        const float v = on ? Qs[rr * AS + gl] : -3.0e38f;
-        float mx = group_max16(v);
-        if (LG == 32) mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        const unsigned am = (unsigned)(__ballot(on) >> sh) & GM;
-        const unsigned em = (unsigned)(__ballot(on && v == mx) >> sh) & GM;
-        const int navail = __popc(am);
-        int arg = em ? __ffs(em) - 1 : (am ? __ffs(am) - 1 : 0);
-        const bool explore = uex[rr] < eps;
-        int kk;
-        env_pick(uex[rows + rr], navail, kk);
-        const bool sel = explore && on && __popc(am & ((1u << gl) - 1u)) == kk;
-        const unsigned sm = (unsigned)(__ballot(sel) >> sh) & GM;
-        if (sm) arg = __ffs(sm) - 1;
-        if (!(t < mt.z)) arg = -1;
-        if (valid) {
-          if (gl == 0) {
+      if constexpr (SAMPLE) {
+        constexpr int G = 64 / LG;                      // rows of one pass of a wave
+        // phase A, the greedy block's lane mapping: the row's max over the available actions (order-free) and each lane's
+        // e_k = exp(min(z_k - mx, 80)), written over the row in Qs, which nothing reads after the choice
+        for (int base = wave * G; base < vrows; base += (RNT / 64) * G) {
+          const int r = base + lane / LG;
+          const bool valid = r < vrows;
+          const int rr = valid ? r : vrows - 1;
+          const int gk = gl < A ? gl : 0;
+          const float z = Qs[rr * AS + gk];
+          const bool on = gl < A && AvC[rr * A + gk] != 0.f;
+          float mx = group_max16(on ? z : -3.0e38f);
+          if (LG == 32) mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+          const float ek = expf(fminf(z - mx, EXP_CLAMP));
+          if (valid && gl < A) Qs[r * AS + gl] = ek;       // (a padding group would write over the row it duplicates)
+        }
+        __builtin_amdgcn_wave_barrier();
+        // phase B, one lane per row, ONCE for all rows this wave handled in phase A (lane l: row l % G of pass l / G; a wave's
+        // LDS accesses complete in order, so no workgroup barrier): the sums and the walk keep index order, as row_policy and
+        // row_sample do - the serial part is A steps deep per lock-step, not A steps per pass
+        {
+          const int r = (wave + (RNT / 64) * (lane / G)) * G + lane % G;
+          if (r < vrows) {
+            const int4 mt = rmeta[r];
+            const RowPolicy p = row_policy_e(Qs + r * AS, AvC + r * A, A, eps);
+            int arg = row_walk<true>(p, Qs + r * AS, AvC + r * A, A, uex[r]);
+            if (!(t < mt.z)) arg = -1;
             act[r] = arg;
-            a.u[((long)(b0 + rowe[rr]) * T + t) * N + n] = arg;
+            a.u[((long)(b0 + rowe[r]) * T + t) * N + mt.w] = arg;
           }
-          if (a.has_act && gl < A) In[r * KS + O + gl] = (gl == arg) ? 1.f : 0.f;      // one-hot fed to step t+1
+        }
+        __builtin_amdgcn_wave_barrier();
+        if (a.has_act) {                                   // one-hot fed to step t+1, phase A's mapping again
+          for (int base = wave * G; base < vrows; base += (RNT / 64) * G) {
+            const int r = base + lane / LG;
+            if (r < vrows && gl < A) In[r * KS + O + gl] = (gl == act[r]) ? 1.f : 0.f;
+          }
+        }
+      } else {
+        for (int base = wave * (64 / LG); base < vrows; base += (RNT / 64) * (64 / LG)) {
+          const int r = base + lane / LG;
+          const bool valid = r < vrows;
+          const int rr = valid ? r : vrows - 1;
+          const int4 mt = rmeta[rr];
+          const int n = mt.w;
+          const bool on = gl < A && AvC[rr * A + (gl < A ? gl : 0)] != 0.f;
+          const float v = on ? Qs[rr * AS + gl] : -3.0e38f;
+          float mx = group_max16(v);
+          if (LG == 32) mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+          const unsigned am = (unsigned)(__ballot(on) >> sh) & GM;
+          const unsigned em = (unsigned)(__ballot(on && v == mx) >> sh) & GM;
+          const int navail = __popc(am);
+          int arg = em ? __ffs(em) - 1 : (am ? __ffs(am) - 1 : 0);
+          const bool explore = uex[rr] < eps;
+          int kk;
+          env_pick(uex[rows + rr], navail, kk);
+          const bool sel = explore && on && __popc(am & ((1u << gl) - 1u)) == kk;
+          const unsigned sm = (unsigned)(__ballot(sel) >> sh) & GM;
+          if (sm) arg = __ffs(sm) - 1;
+          if (!(t < mt.z)) arg = -1;
+          if (valid) {
+            if (gl == 0) {
+              act[r] = arg;
+              a.u[((long)(b0 + rowe[rr]) * T + t) * N + n] = arg;
+            }
+            if (a.has_act && gl < A) In[r * KS + O + gl] = (gl == arg) ? 1.f : 0.f;      // one-hot fed to step t+1
+          }
         }
       }
     }
@@ -432,8 +480,12 @@ __global__ __launch_bounds__(RNT, 2) void synth_rollout_kernel(RollArgs a) {
     if (tid >= RNT - 128 && tid - (RNT - 128) < rows) {
       const int r = tid - (RNT - 128);
       const unsigned env = (unsigned)(a.env0 + b0 + rowe[r]), nn_ = (unsigned)rown[r];
-      uex[r] = u01(hkey(a.rseed, ST_EXPLORE, env, tg + 1u, nn_));
-      uex[rows + r] = u01(hkey(a.rseed, ST_PICK, env, tg + 1u, nn_));
+      if constexpr (SAMPLE) {
+        uex[r] = u01(hkey(a.rseed, ST_SAMPLE, env, tg + 1u, nn_));
+      } else {
+        uex[r] = u01(hkey(a.rseed, ST_EXPLORE, env, tg + 1u, nn_));
+        uex[rows + r] = u01(hkey(a.rseed, ST_PICK, env, tg + 1u, nn_));
+      }
     }
     // one lane per (env, agent) hashes its reward term; the env's lane sums them in agent order (the serial form -
     // one thread per env looping over the agents' hashes - was 4-12 % of a lock-step on the critical path)
@@ -503,11 +555,11 @@ extern "C" int marl_synth_rollout_supported(int N, int O, int A) {
   return 16 * max_rt(O + A + N, A) >= N ? 1 : 0;
 }
 
-extern "C" int marl_synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                                  int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
-                                  float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                                  float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
-                                  int O, int S, int A, int last_action, int reuse_network, void* stream) {
+template <bool SAMPLE>
+static int synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, int fixed_len,
+                         const float* eps, float* obs, float* state, long state_ld, float* avail, int* u, float* r, float* term,
+                         float* padded, int* length, int* won, float* h_out, float* stats, double eps0, double eps_anneal,
+                         double eps_min, int E, int T, int N, int O, int S, int A, int last_action, int reuse_network, void* stream) {
   if (E <= 0 || T <= 0) return 0;
   if (A > 32 || A < 1 || N < 1 || N > 64) return (int)hipErrorInvalidValue;
   RollArgs a;
@@ -523,6 +575,24 @@ extern "C" int marl_synth_rollout(const marl_agent_weights_t* w, unsigned seed, 
   if (epw * N > 16 * rt_max) epw = (16 * rt_max) / N;
   a.EPW = epw;
   a.RT = (epw * N + 15) / 16;
-  return launch_rollout(A <= 16 ? (const void*)synth_rollout_kernel<1> : (const void*)synth_rollout_kernel<2>, (E + epw - 1) / epw,
-                        roll_lds(a.I, A, a.RT), a, stream);
+  return launch_rollout(A <= 16 ? (const void*)synth_rollout_kernel<1, SAMPLE> : (const void*)synth_rollout_kernel<2, SAMPLE>,
+                        (E + epw - 1) / epw, roll_lds(a.I, A, a.RT), a, stream);
+}
+
+extern "C" int marl_synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
+                                  int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
+                                  float* r, float* term, float* padded, int* length, int* won, float* h_out,
+                                  float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
+                                  int O, int S, int A, int last_action, int reuse_network, void* stream) {
+  return synth_rollout<false>(w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded, length,
+                              won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network, stream);
+}
+
+extern "C" int marl_synth_rollout_sample(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
+                                         int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail,
+                                         int* u, float* r, float* term, float* padded, int* length, int* won, float* h_out,
+                                         float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
+                                         int O, int S, int A, int last_action, int reuse_network, void* stream) {
+  return synth_rollout<true>(w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded, length,
+                             won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network, stream);
 }

@@ -793,12 +793,17 @@ def synth_step(seed, env0, episode, t, length, act, u, r, term, padded, alive_ne
                                       E, T, N, A, _stream()), "marl_synth_step")
 
 
-def synth_fused_step(seed, rseed, env0, episode, t, eps, length, q, obs, state, avail, u, r, term, padded, E, T, N, O, S, A):
-    check(_lib.load().marl_synth_fused_step(int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, t, float(eps),
-                                            _p(_i32(length)), _p(_f32(q)), _p(_f32(obs)), _p(_f32(state)), state.stride(-2),
-                                            _p(_f32(avail)),
-                                            _p(_i32(u)), _p(_f32(r)), _p(_f32(term)), _p(_f32(padded)), E, T, N, O, S, A,
-                                            _stream()), "marl_synth_fused_step")
+def synth_fused_step(seed, rseed, env0, episode, t, eps, length, q, obs, state, avail, u, r, term, padded, E, T, N, O, S, A,
+                     sample=False):
+    """sample: the actions are drawn from the stochastic policy of q (logits) with eps as its mixing epsilon (policy_sample's rule)"""
+    lib = _lib.load()
+    fn, name = (lib.marl_synth_fused_step_sample, "marl_synth_fused_step_sample") if sample else \
+        (lib.marl_synth_fused_step, "marl_synth_fused_step")
+    check(fn(int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, t, float(eps),
+             _p(_i32(length)), _p(_f32(q)), _p(_f32(obs)), _p(_f32(state)), state.stride(-2),
+             _p(_f32(avail)),
+             _p(_i32(u)), _p(_f32(r)), _p(_f32(term)), _p(_f32(padded)), E, T, N, O, S, A,
+             _stream()), name)
 
 
 def synth_rollout_supported(N, O, A):
@@ -817,18 +822,21 @@ def synth_rollout_x6_plan(E, N, O, A, last_action=True, reuse_network=True):
 
 
 def synth_rollout(w, seed, rseed, env0, episode, fixed_len, eps, rec, h_out, E, T, N, O, S, A, last_action, reuse_network,
-                  stats=None, eps_sched=None, x6=False):
+                  stats=None, eps_sched=None, x6=False, sample=False):
     """eps: device (T,) epsilon per lock-step, or None with eps_sched = (eps0, anneal, eps_min): the per-step anneal of
-    rollout.py:100-101 is then evaluated inside the kernel (fp64, like the host loop) and no schedule crosses PCIe."""
+    rollout.py:100-101 is then evaluated inside the kernel (fp64, like the host loop) and no schedule crosses PCIe.
+    sample: the actions are drawn from the stochastic policy of the step's logits, eps(t) its mixing epsilon; always the fp32
+    kernel (x6 is ignored)."""
     e0, ea, em = (0.0, 0.0, 0.0) if eps_sched is None else eps_sched
     assert (eps is None) != (eps_sched is None)
-    fn = _lib.load().marl_synth_rollout_x6 if x6 else _lib.load().marl_synth_rollout       # x6: the agent step as bf16x6 split products
+    lib = _lib.load()
+    fn = lib.marl_synth_rollout_sample if sample else lib.marl_synth_rollout_x6 if x6 else lib.marl_synth_rollout   # x6: the agent step as bf16x6 split products
     check(fn(C.byref(w), int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode,
                                          1 if fixed_len else 0, _p(_f32(eps)) if eps is not None else None, _p(_f32(rec.obs)), _p(_f32(rec.state)),
                                          rec.state.stride(-2), _p(_f32(rec.avail)), _p(_i32(rec.u)), _p(_f32(rec.r)), _p(_f32(rec.term)),
                                          _p(_f32(rec.padded)), _p(_i32(rec.length)), _p(_i32(rec.won)), _p(h_out),
                                          _p(_f32(stats)) if stats is not None else None, float(e0), float(ea), float(em), E, T, N, O, S, A, 1 if last_action else 0, 1 if reuse_network else 0, _stream()),
-          "marl_synth_rollout")
+          "marl_synth_rollout_sample" if sample else "marl_synth_rollout")
 
 
 def qmix_fused_supported(N, S, E):

@@ -9,8 +9,11 @@
   With an RTW controller (RTWMAC) the reflection head (csrc/rtw_head.hip, act mode) runs between the agent step and the
   selection; such rollouts always take this per-step path (the whole-rollout kernels have no head).  The world-model head
   (SharedMACWithState) and the MAIC message head (MAICMAC, csrc/maic_head.hip; test mode = ``evaluate``) run at the same place.
-  With a stochastic controller (PolicyMAC) a TRAINING rollout takes this per-step path too, unfused, and draws its actions with
-  ops.policy_sample (csrc/policy.hip; the ST_SAMPLE stream keyed by (rseed, env, global step, agent)); evaluation is untouched.
+  With a stochastic controller a TRAINING rollout draws its actions from the policy (the ST_SAMPLE stream keyed by (rseed, env,
+  global step, agent); evaluation is untouched).  PolicyMAC: the whole-rollout kernel samples in place (csrc/rollout_fused.hip,
+  one launch; the fp32 kernel in either gemm_mode), where the env has it and covers the shape; else the fused step samples
+  (csrc/rollout.hip: agent step + fused step per lock-step).  The controllers with a head (CommNetMAC, G2ANetMAC) keep the
+  per-step path with ops.policy_sample (csrc/policy.hip) unless ``rollout_mode = "fused_step"`` asks for the sampling fused step.
   MAIC's sampled latents (training rollouts) take their noise from the counter hash keyed by (rseed, env, global step, agent,
   column) through a Box-Muller transform (ops.maic_noise), so a rollout is a pure function of its seeds.
 """
@@ -159,10 +162,10 @@ class RolloutWorker:
         if a.replay_dir != '' and evaluate:
             env.close()
         mode = getattr(self, "rollout_mode", "whole")      # "whole" | "fused_step" | "unfused" (tests)
-        # a stochastic controller (PolicyMAC) samples its training actions: the per-step path with ops.policy_sample, unfused
+        # a stochastic controller samples its training actions: inside the whole-rollout kernel, inside the fused step, or with
+        # ops.policy_sample on the unfused path - the same rule and the same draws
         sample = mac.stochastic and not evaluate
-        if mode == "whole" and mac.head_name is None and not sample and hasattr(env, "whole_rollout") \
-                and env.supports_whole_rollout():
+        if mode == "whole" and mac.head_name is None and hasattr(env, "whole_rollout") and env.supports_whole_rollout():
             # the persistent kernel writes every field of the record, so training rollouts can be
             # played straight into the replay ring (record_sink = the ReplayBuffer; zero-copy store)
             sink = getattr(self, "record_sink", None)
@@ -186,7 +189,9 @@ class RolloutWorker:
         if a.epsilon_anneal_scale == 'episode':
             epsilon = epsilon - self.anneal_epsilon if epsilon > self.min_epsilon else epsilon
         w = mac.rollout_weights()
-        fused = hasattr(env, "fused_step") and mode != "unfused" and not sample
+        # (a sampling controller with a head takes the fused step only when asked to: its default stays the three-launch tail)
+        fused = hasattr(env, "fused_step") and mode != "unfused" and \
+            (not sample or mode == "fused_step" or mac.head_name is None)
         select = ops.policy_sample if sample else ops.select_actions
         env.observe(0, rec)
         for t in range(T):
@@ -194,7 +199,7 @@ class RolloutWorker:
             mac.rollout_step(w, rec, t, h, q, E)
             mac.rollout_head(h, q, rec, t, E, evaluate, self.rseed, env)     # q += the controller's head term, if it has one
             if fused:
-                env.fused_step(t, q, epsilon, self.rseed, rec)
+                env.fused_step(t, q, epsilon, self.rseed, rec, sample=sample)
             else:
                 select(q, rec.avail[:, t], (T + 1) * N * A, alive, epsilon, self.rseed, env.env0, None,
                        env.global_step(t), act, N, E, N, A)
@@ -236,9 +241,10 @@ class RolloutWorker:
             for t in range(T):
                 epsilon = epsilon - self.anneal_epsilon if epsilon > self.min_epsilon else epsilon
         mac.init_hidden(E)
-        x6 = x6_mode(a)      # the agent step as split products (csrc/rollout_x6.hip)
+        sample = mac.stochastic and not evaluate      # the fp32 kernel draws from the policy: the same record in either gemm_mode
+        x6 = x6_mode(a) and not sample      # the agent step as split products (csrc/rollout_x6.hip)
         env.whole_rollout(mac.agent.weights(), None, self.rseed, rec, a.last_action, a.reuse_network,
-                          h_out=mac.hidden_states.view(E * N, H), eps_sched=sched, x6=x6)
+                          h_out=mac.hidden_states.view(E * N, H), eps_sched=sched, x6=x6, sample=sample)
         if not evaluate:
             self.epsilon = epsilon
         return rec, evaluate
