@@ -544,6 +544,36 @@ int marl_qtran_loss(const float* jq, const float* jq_tgt, const float* v, const 
                     void* stream);
 size_t marl_loss_workspace(long rows);
 
+/* ---- Qatten mixer (qatten.hip; Yang et al. 2020 - the reference ships no Qatten: the definition is this project's own) ---------
+ * Per row, with the unit features u_i = s[i U : (i + 1) U] (i < N) read in place from the state row, H heads and scale = 1/sqrt(D):
+ *   l_{h,i} = scale (p_h . u_i),   lam_{h,.} = softmax_i(l_{h,.}) (maximum subtracted),   y_h = sum_i lam_{h,i} q_i,
+ *   q_tot = sum_h |w_raw_h| y_h + c.
+ * p_h = Wk_h^T e_h is the bias-free key layer applied to the query e_h (e_h . (Wk_h u_i) = p_h . u_i), so the kernel has no weight
+ * of its own.  hy (rows, ldh): [p (H U) | w_raw (H) | c (1)] per row; q (rows, N); s: segment 0 of a marl_src_t with k0 >= N U (row
+ * remap and episode map honoured; columns from N U on are never read).  Backward, g = dL/dq_tot:
+ *   dq_i = g sum_h |w_raw_h| lam_{h,i},  dw_raw_h = g y_h sign(w_raw_h) (sign(0) = 0),  dp_h = scale sum_i g |w_raw_h| lam_{h,i} (q_i - y_h) u_i,
+ * dc = g is the caller's.  dhy (rows, lddh): [dp (H U) | dw_raw (H)] per row, nothing else of a row is written.  lam is recomputed.
+ * marl_qatten_loss_bwd: forward, the TD loss of marl_td_loss (same expressions: dq_tot = -2 mask (mask td), out2 = {sum (mask td)^2,
+ *   sum mask} written through the fixed-order finish on ws = marl_loss_workspace() bytes) and the backward in one launch; q_tot is
+ *   optional.  Its q_tot is marl_qatten_mix_fwd's and its dq, dhy, dq_tot are those of mix_fwd -> marl_td_loss -> mix_bwd, bit for
+ *   bit.  A row with padded = 1 and finite inputs gets exact zeros in dq, dhy, dq_tot and adds nothing to either sum.
+ * fp32 only, no float atomics: two calls give the same bits.  Supported: 1 <= N <= 16, 1 <= U <= 64, 1 <= H <= 8 and a source of
+ * segment 0 alone (no second segment, one-hot block, agent-id block or gate); marl_qatten_supported reports it, and the entry points
+ * return hipErrorInvalidValue for what it rejects, for a NULL required pointer, ldh < H U + H + 1, lddh < H U + H or rows >= 2^31,
+ * and write nothing then.  rows <= 0: returns 0, no launch.
+ * marl_qatten_plan (host only), plan[4]: [0] rows of a workgroup's LDS tile  [1] workgroups  [2] dynamic LDS bytes
+ *   [3] tiles the busiest workgroup walks. */
+int marl_qatten_supported(const marl_src_t* s, int N, int U, int H);
+int marl_qatten_plan(long rows, int N, int U, int H, int* plan);
+int marl_qatten_mix_fwd(const marl_src_t* s, const float* hy, long ldh, const float* q, float scale, float* q_tot,
+                        long rows, int N, int U, int H, void* stream);
+int marl_qatten_mix_bwd(const marl_src_t* s, const float* hy, long ldh, const float* q, float scale, const float* dq_tot,
+                        float* dq, float* dhy, long lddh, long rows, int N, int U, int H, void* stream);
+int marl_qatten_loss_bwd(const marl_src_t* s, const float* hy, long ldh, const float* q, float scale,
+                         const float* q_tot_tgt, const float* r, const float* term, const float* padded, float gamma,
+                         float* q_tot, float* dq, float* dhy, long lddh, float* dq_tot, float* out2, float* ws, long rows,
+                         int N, int U, int H, void* stream);
+
 /* TD(lambda) returns (td_lambda.hip; utils/rl_utils.py:4-14, build_td_lambda_targets - a function the reference ships and never
  * calls).  Per episode b over the T steps of the batch, q[t] = q_next_tot[b, t] (the target network's value at the next state of
  * step t), m = 1 - padded:

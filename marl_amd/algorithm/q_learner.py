@@ -1,4 +1,4 @@
-"""QLearner for VDN / QMIX / QPLEX (mirror of reference algorithm/q_learner.py:10-262).
+"""QLearner for VDN / QMIX / QPLEX and Qatten (mirror of reference algorithm/q_learner.py:10-262).
 
 ``train(batch, train_step)`` keeps the reference contract (returns the float loss, syncs targets
 every ``target_update_cycle``), but is an explicit forward/backward schedule of HIP kernels:
@@ -7,6 +7,8 @@ Reference quirks Q1 (double-Q pass continues from the eval net's final hidden st
 (get_max_episode_len ignores unterminated episodes), Q4/Q5 (mask constant, first-index argmax) and
 Q6 (target sync rule) are reproduced.  With ``args.td_lambda`` set the TD target is the lambda-return of q_tot_target
 (Learner._td_inputs; quirk Q15) instead of the one-step bootstrap; unset, not one call differs.
+``args.alg == 'qatten'`` (this project's own; the reference ships no Qatten) mixes with QattenMixer on the same schedule, its
+eval forward, the TD loss and the attention backward folded into one launch as QMIX's are (``args.no_loss_fold`` unfolds both).
 """
 from __future__ import annotations
 
@@ -17,7 +19,7 @@ import torch
 
 from .. import ops, experiments
 from ..hostutil import flatten_module
-from ..network.mixer import VDNMixer, QMixMixer, DMAQer
+from ..network.mixer import VDNMixer, QMixMixer, DMAQer, QattenMixer
 from .common import MASK_BIG, LearnerParams, FlatView, Learner, agent_backward
 
 
@@ -30,6 +32,8 @@ class QLearner(Learner):
             self.mixer = QMixMixer(args)
         elif args.alg == 'qplex':
             self.mixer = DMAQer(args)
+        elif args.alg == 'qatten':
+            self.mixer = QattenMixer(args)
         else:
             raise ValueError("Mixer {} not recognised.".format(args.alg))
         self.target_mixer = copy.deepcopy(self.mixer)
@@ -118,7 +122,7 @@ class QLearner(Learner):
         return q_chosen, q_tgt_chosen, cur_max
 
     def _mix(self, db, q_evals, q_tgt, q_chosen, q_tgt_chosen, cur_max):
-        """Eval and target mixer forwards.  Returns q_tot, q_tot_tgt, the eval mixer's ctx and `fold`: QMIX's eval forward
+        """Eval and target mixer forwards.  Returns q_tot, q_tot_tgt, the eval mixer's ctx and `fold`: QMIX's and Qatten's eval forward
         is left to the loss stage, where it is one launch with the TD loss and the mixer backward."""
         a, g = self.args, self._g
         N, BT, A = db.N, db.B * db.T, db.A
@@ -140,7 +144,7 @@ class QLearner(Learner):
             else:
                 q_tot_tgt, _ = self.target_mixer.hip_forward(qtc, db.s_next, BT, tag="t")
         else:
-            fold = a.alg == 'qmix' and getattr(self.mixer, "loss_backward_fused", None) is not None and \
+            fold = a.alg in ('qmix', 'qatten') and getattr(self.mixer, "loss_backward_fused", None) is not None and \
                 self.mixer.loss_backward_fused(db.s) and not getattr(a, "no_loss_fold", False)
             q_tot = g("q_tot", (BT,)) if fold else self.mixer.hip_forward(qc, db.s, BT, ctx=ctx)
             q_tot_tgt = self.target_mixer.hip_forward(qtc, db.s_next, BT, tag="t")
@@ -152,7 +156,7 @@ class QLearner(Learner):
         BT = db.B * db.T
         r, gamma = self._td_inputs(db, q_tot_tgt)        # args.td_lambda set: the lambda-returns as r, and gamma = 0
         if fold:
-            # fused QMIX: eval-mixer forward, TD loss and mixer backward are ONE launch (the backward recomputes q_tot anyway)
+            # fused QMIX / Qatten: eval-mixer forward, TD loss and mixer backward are ONE launch (the backward recomputes q_tot anyway)
             return self.mixer.hip_loss_backward(q_chosen.view(BT, db.N), db.s, BT, q_tot_tgt, r, db.term, db.padded, gamma,
                                                 self._flat.stats[:2], q_tot=q_tot)
         dq_tot = self._g("dq_tot", (BT,))

@@ -39,6 +39,11 @@ def get_common_args(argv=None):
     p.add_argument('--ppo_clip', type=float, default=None)
     p.add_argument('--ppo_epochs', type=int, default=None)
     p.add_argument('--ppo_norm_adv', type=_bool, default=None)
+    # --alg qatten: attention heads, embedding width and the width of an agent's unit features in the state row; absent =
+    # get_qatten_args' 4, 32 and state_shape // n_agents
+    p.add_argument('--qatten_heads', type=int, default=None)
+    p.add_argument('--qatten_embed_dim', type=int, default=None)
+    p.add_argument('--qatten_unit_dim', type=int, default=None)
     p.add_argument('--env', type=str, default='smac')
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')
@@ -162,3 +167,14 @@ def get_commnet_args(args):
 def get_g2anet_args(args):
     """reference :212-215"""
     return _assign(args, dict(attention_dim=32, hard=True))
+
+
+def get_qatten_args(args):
+    """This project's own table for the Qatten mixer (the reference ships none): 4 heads, embedding width 32, and the unit features
+    of agent i are columns [i U, (i + 1) U) of the state row with U = state_shape // n_agents (24 at 2s3z, 27 at 3s5z, 32 at MMM2,
+    whose last 2 of 322 state columns are then no unit's).  Called once the environment's sizes are known; values the caller set
+    (not None) are kept."""
+    for k, v in dict(qatten_heads=4, qatten_embed_dim=32, qatten_unit_dim=args.state_shape // args.n_agents).items():
+        if getattr(args, k, None) is None:
+            setattr(args, k, v)
+    return args

@@ -3,6 +3,7 @@
     python -m marl_amd.main --alg qmix --map 2s3z --n_envs 1024 --n_steps 500000
     python -m marl_amd.main --env matrix --alg qplex --n_envs 32 --n_steps 20000
     python -m marl_amd.main --map 2s3z --alg iql --n_envs 1024 --n_steps 500000
+    python -m marl_amd.main --map 2s3z --alg qatten --qatten_heads 4 --n_envs 1024 --n_steps 500000
     python -m marl_amd.main --map 2s3z --alg central_v --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg coma --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg reinforce --policy_entropy_coef 0.01 --n_envs 64 --n_steps 200000
@@ -23,7 +24,7 @@ import sys
 from collections import namedtuple
 
 from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
-    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args
+    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .runner import Runner
@@ -79,6 +80,15 @@ def commnet_base(alg):
     return base if actor == 'commnet' else None
 
 
+def _qatten(args):
+    """get_qatten_args' table (4 heads, embedding 32, U = state_shape // n_agents; --qatten_* values stay) and the mixer's shape check:
+    a state too narrow for a block of at least one column per agent (the matrix game), N U > S or a shape outside the row kernel's
+    range is a ValueError here"""
+    from .network.mixer import qatten_shape_of
+    get_qatten_args(args)
+    qatten_shape_of(args)
+
+
 def build(argv=None):
     args = get_common_args(argv)
     get_mixer_args(args)
@@ -110,6 +120,9 @@ def build(argv=None):
         _share(actor.check)(args, n_agents=n, n_actions=a)      # refused before the environment is made
     get_RTW_args(args)
     get_maic_args(args)
+    if args.alg == 'qatten':            # the sizes the environment will report are the map's (the matrix game: 2 agents, state width 1):
+        args.n_agents, args.state_shape = (MAPS[args.map][0], MAPS[args.map][2]) if args.env in ('smac', 'synthetic') else (2, 1)
+        _qatten(args)                   # refused before the environment is made
     if args.env == 'smac':
         args.env = 'synthetic'
     if args.env == 'synthetic':
@@ -125,6 +138,8 @@ def build(argv=None):
     args.state_shape, args.obs_shape, args.episode_limit = info["state_shape"], info["obs_shape"], info["episode_limit"]
     args.batch_size = max(args.batch_size, args.n_envs)
     args.buffer_size = max(2 * args.n_envs, min(args.buffer_size, 8 * args.n_envs))
+    if args.alg == 'qatten':
+        _qatten(args)                   # ... and with the environment's own sizes
     if actor is not None:
         _share(actor.check)(args)       # ... and the environment's agent and action counts with it, before a controller is built
     return args, env

@@ -572,6 +572,157 @@ class DMAQer(_Precision, nn.Module):
 
 
 # =====================================================================================
+QATTEN_MAX = dict(n_agents=16, qatten_unit_dim=64, qatten_heads=8)       # the support range of csrc/qatten.hip (marl_qatten_supported)
+
+
+def qatten_shape_of(args):
+    """(N, U, H, D, S) of the Qatten mixer from args (unset qatten_* fields take get_qatten_args' defaults), or ValueError: the unit
+    features are N blocks of U >= 1 state columns (N U <= S), and the row kernel covers N <= 16, U <= 64, H <= 8 - nothing else
+    runs them.  The launcher calls this before anything is built, the mixer at construction."""
+    S, N = int(np.prod(args.state_shape)), args.n_agents
+    H, D, U = (v if v is not None else d for v, d in ((getattr(args, "qatten_heads", None), 4),
+                                                      (getattr(args, "qatten_embed_dim", None), 32),
+                                                      (getattr(args, "qatten_unit_dim", None), S // N)))
+    if U < 1 or N * U > S:
+        raise ValueError("qatten: %d agents x %d unit features do not fit a state of width %d (the state row must hold a block of "
+                         "at least one column per agent)" % (N, U, S))
+    if D < 1:
+        raise ValueError("qatten: qatten_embed_dim = %d, it must be at least 1" % D)
+    for name, v in (("n_agents", N), ("qatten_unit_dim", U), ("qatten_heads", H)):
+        if not 1 <= v <= QATTEN_MAX[name]:
+            raise ValueError("qatten: %s = %d is outside the row kernel's range 1..%d" % (name, v, QATTEN_MAX[name]))
+    return N, U, H, D, S
+
+
+class QattenMixer(_Precision, nn.Module):
+    """Qatten (Yang et al. 2020; the reference ships none): multi-head attention over per-agent unit features of the state gives
+    the mixing weights.  Per row, u_i = s[i U : (i + 1) U]:
+        e_h = query.h(s),  l_{h,i} = e_h . (key.h u_i) / sqrt(D),  lam_h = softmax_i l_h,  y_h = sum_i lam_{h,i} q_i,
+        q_tot = sum_h |head_weight(s)_h| y_h + const(s)            (monotone in every q_i: lam >= 0, |.| >= 0)
+    The keys are never built: p_h = key.h^T e_h is the key layer run on the query side (Lin.bwd_x), its weight gradient is
+    Lin.wgrad(e_h, dp_h) and the query's gradient Lin.fwd(dp_h); the row kernel (csrc/qatten.hip) does logits, softmax, head
+    weighting and mix - and, in the update, the TD loss - out of p, the state rows and q.  key.h has no bias: the softmax removes a
+    term common to all agents.  Every dense layer goes through ``self._lin``, so args.mixer_dtype = "bf16" reaches them; the
+    attention kernel is fp32 only, and args.gemm_mode = "bf16x6" leaves this mixer's products on fp32 (no split kernel exists for
+    them).  There is no fused-head path: ``no_fused`` is accepted and changes nothing.  Out of scope: the paper's regularisers, the
+    dead-agent mask, a non-linear key."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        N, U, H, D, S = qatten_shape_of(args)
+        HE = args.hypernet_embed
+        self.n_heads, self.embed_dim, self.unit_dim, self.state_dim = H, D, U, S
+        self.query = nn.ModuleList([_mlp(None, [S, HE, D]) for _ in range(H)])
+        self.key = nn.ModuleList([nn.Linear(U, D, bias=False) for _ in range(H)])
+        self.head_weight = _mlp(None, [S, HE, H])
+        self.const = _mlp(None, [S, D, 1])
+        self._s = Scratch()
+
+    def _dims(self):
+        return self.args.n_agents, self.unit_dim, self.n_heads, self.embed_dim, self.args.hypernet_embed
+
+    def _scale(self):
+        return 1.0 / float(np.sqrt(self.embed_dim))
+
+    def _key(self, h):
+        return Lin(self.key[h].weight, None, self._bf16())
+
+    def _dense_forward(self, s, rows, tag):
+        """hy (rows, H U + H + 1) = [p | w_raw | c] and the activations the backward needs, as a ctx dict"""
+        N, U, H, D, HE = self._dims()
+        dev = s.device
+        xs = ops.src(s)
+        hy = self._s.get_rows("hy" + tag, rows, H * U + H + 1, dev)
+        hq = self._s.get("hq" + tag, (rows, H * HE), dev)
+        e = self._s.get("e" + tag, (rows, H * D), dev)
+        hw = self._s.get("hw" + tag, (rows, HE), dev)
+        hc = self._s.get("hc" + tag, (rows, D), dev)
+        for h in range(H):
+            q0, q2 = _linears(self.query[h])
+            hq_h, e_h = hq[:, h * HE:(h + 1) * HE], e[:, h * D:(h + 1) * D]
+            self._lin(q0).fwd(xs, hq_h, rows, act=1)
+            self._lin(q2).fwd(ops.src(hq_h), e_h, rows)
+            self._key(h).bwd_x(e_h, hy[:, h * U:(h + 1) * U], rows)                  # p_h = e_h Wk_h
+        w0, w2 = _linears(self.head_weight)
+        self._lin(w0).fwd(xs, hw, rows, act=1)
+        self._lin(w2).fwd(ops.src(hw), hy[:, H * U:H * U + H], rows)
+        c0, c2 = _linears(self.const)
+        self._lin(c0).fwd(xs, hc, rows, act=1)
+        self._lin(c2).fwd(ops.src(hc), hy[:, H * U + H:], rows)
+        return dict(s=s, hy=hy, hq=hq, e=e, hw=hw, hc=hc)
+
+    def _dense_backward(self, ctx, dhy, dc, rows):
+        """the dense chain behind the row kernel: dhy (rows, >= H U + H) = [dp | dw_raw], dc (rows) = dL/dq_tot"""
+        N, U, H, D, HE = self._dims()
+        dev = dhy.device
+        xs = ops.src(ctx["s"])
+        for seq, hbuf, dout, width in ((self.const, ctx["hc"], dc.view(rows, 1), D),
+                                       (self.head_weight, ctx["hw"], dhy[:, H * U:H * U + H], HE)):
+            l0, l2 = _linears(seq)
+            self._lin(l2).wgrad(dout, ops.src(hbuf), rows)
+            dh = self._s.get("dh%d" % width, (rows, width), dev)
+            self._lin(l2).bwd_x(dout, dh, rows)
+            self._lin(l0).wgrad(dh, xs, rows, Yact=hbuf)
+        de = self._s.get("de", (rows, D), dev)
+        dhq = self._s.get("dh%d" % HE, (rows, HE), dev)
+        for h in range(H):
+            q0, q2 = _linears(self.query[h])
+            hq_h, e_h, dp_h = ctx["hq"][:, h * HE:(h + 1) * HE], ctx["e"][:, h * D:(h + 1) * D], dhy[:, h * U:(h + 1) * U]
+            self._key(h).wgrad(e_h, ops.src(dp_h), rows)                             # dWk_h += e_h^T dp_h
+            self._key(h).fwd(ops.src(dp_h), de, rows)                                # de_h = dp_h Wk_h^T
+            self._lin(q2).wgrad(de, ops.src(hq_h), rows)
+            self._lin(q2).bwd_x(de, dhq, rows)
+            self._lin(q0).wgrad(dhq, xs, rows, Yact=hq_h)
+
+    def hip_forward(self, q, s, rows, ctx=None, tag="e"):
+        N, U, H, D, HE = self._dims()
+        kept = self._dense_forward(s, rows, tag)
+        qtot = self._s.get("qtot" + tag, (rows,), q.device)
+        ops.qatten_mix_fwd(ops.src(s), kept["hy"], q, self._scale(), qtot, rows, N, U, H)
+        if ctx is not None:
+            ctx.update(kept, q=q)
+        return qtot
+
+    def _grad_rows(self, rows, dev):
+        N, U, H, D, HE = self._dims()
+        return self._s.get("dq", (rows, N), dev), self._s.get_rows("dhy", rows, H * U + H, dev)
+
+    def hip_backward(self, ctx, dq_tot, rows):
+        N, U, H, D, HE = self._dims()
+        dq, dhy = self._grad_rows(rows, dq_tot.device)
+        ops.qatten_mix_bwd(ops.src(ctx["s"]), ctx["hy"], ctx["q"], self._scale(), dq_tot, dq, dhy, rows, N, U, H)
+        self._dense_backward(ctx, dhy, dq_tot, rows)
+        return dq
+
+    def loss_backward_fused(self, s):
+        """True when hip_loss_backward covers this source (the row kernel reads segment 0 alone)."""
+        N, U, H, D, HE = self._dims()
+        return ops.qatten_supported(s, N, U, H)
+
+    def hip_loss_backward(self, q, s, rows, q_tot_tgt, r, term, padded, gamma, loss2, q_tot=None):
+        """Forward + TD loss + backward of the attention mix in ONE launch (csrc/qatten.hip: marl_qatten_loss_bwd) between the dense
+        forward and the dense backward chain.  loss2 (2 floats, written): sum (mask td)^2, sum mask.  Returns dL/dq (rows, N); the
+        parameter gradients are accumulated into .grad; q_tot (rows) is written when given."""
+        N, U, H, D, HE = self._dims()
+        ctx = self._dense_forward(s, rows, "e")
+        dq, dhy = self._grad_rows(rows, q.device)
+        dq_tot = self._s.get("dq_tot", (rows,), q.device)
+        ops.qatten_loss_bwd(ops.src(s), ctx["hy"], q, self._scale(), q_tot_tgt, r, term, padded, gamma, q_tot, dq, dhy, dq_tot, loss2,
+                            rows, N, U, H)
+        self._dense_backward(ctx, dhy, dq_tot, rows)
+        return dq
+
+    def forward(self, q_values, states):
+        dev = require_cuda("QattenMixer")
+        self.to(dev)
+        B = q_values.shape[0]
+        q = to_dev(q_values, dev).reshape(-1, self.args.n_agents)
+        s = to_dev(states, dev).reshape(-1, self.state_dim)
+        return self.hip_forward(q, s, q.shape[0]).clone().view(B, -1, 1)
+
+
+# =====================================================================================
 class _QtranFusedHead:
     """Fused path shared by QtranQBase (one-hot actions, A = n_actions) and QtranV (A = 0): csrc/qtran_fused.hip.
     The subclass provides ``_qt_layers()`` -> (enc.0, enc.2, head.0, head.2, head.4) and ``_qt_actions()``."""

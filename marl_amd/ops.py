@@ -426,6 +426,42 @@ def qplex_mix_bwd(w_raw, q, max_q, key, ag, ac, g, dq, dw_raw, dv, dkey, dag, da
                                          int(minus_one), _stream()), "marl_qplex_mix_bwd")
 
 
+def qatten_supported(s, N, U, H):
+    """csrc/qatten.hip covers the shape (N <= 16, U <= 64, H <= 8) and the source s (a marl_src_t, Rows or a dense 2-D tensor)"""
+    x = s if isinstance(s, MarlSrc) else src(s)
+    return bool(_lib.load().marl_qatten_supported(C.byref(x), N, U, H))
+
+
+def qatten_plan(rows, N, U, H):
+    """(rows of a workgroup's tile, workgroups, LDS bytes, tiles the busiest workgroup walks) of the Qatten row kernel"""
+    plan = (C.c_int * 4)()
+    check(_lib.load().marl_qatten_plan(rows, N, U, H, plan), "marl_qatten_plan")
+    return tuple(plan)
+
+
+def qatten_mix_fwd(s, hy, q, scale, q_tot, rows, N, U, H):
+    """q_tot of the Qatten mixer; hy (rows, >= H U + H + 1): [p | w_raw | c] per row, s: the states (marl_src_t)"""
+    check(_lib.load().marl_qatten_mix_fwd(C.byref(s), _p(_f32(hy)), hy.stride(0), _p(_f32(q)), float(scale), _p(_f32(q_tot)), rows,
+                                          N, U, H, _stream()), "marl_qatten_mix_fwd")
+
+
+def qatten_mix_bwd(s, hy, q, scale, dq_tot, dq, dhy, rows, N, U, H):
+    """dq (rows, N) and dhy (rows, >= H U + H): [dp | dw_raw] per row, from dq_tot; the softmax weights are recomputed"""
+    check(_lib.load().marl_qatten_mix_bwd(C.byref(s), _p(_f32(hy)), hy.stride(0), _p(_f32(q)), float(scale), _p(_f32(dq_tot)),
+                                          _p(_f32(dq)), _p(_f32(dhy)), dhy.stride(0), rows, N, U, H, _stream()), "marl_qatten_mix_bwd")
+
+
+def qatten_loss_bwd(s, hy, q, scale, q_tot_tgt, r, term, padded, gamma, q_tot, dq, dhy, dq_tot, out2, rows, N, U, H):
+    """Qatten forward + TD loss + backward in one launch (include/marl_hip.h); out2: 2-element device view written,
+    q_tot optional"""
+    lib = _lib.load()
+    ws = WS.get("loss", lib.marl_loss_workspace(rows), q.device)
+    check(lib.marl_qatten_loss_bwd(C.byref(s), _p(_f32(hy)), hy.stride(0), _p(_f32(q)), float(scale), _p(_f32(q_tot_tgt)),
+                                   _p(_f32(r)), _p(_f32(term)), _p(_f32(padded)), float(gamma), _p(q_tot), _p(_f32(dq)),
+                                   _p(_f32(dhy)), dhy.stride(0), _p(_f32(dq_tot)), _p(_f32(out2)), _p(ws), rows, N, U, H, _stream()),
+          "marl_qatten_loss_bwd")
+
+
 _FT_OUT = {}
 
 

@@ -45,6 +45,9 @@ launcher passes the GroupHeadMAC subclass of its actor table (CommNetMAC for the
 without a mixer.  With an agent switch the name is answered as before: world_model refuses it as an unknown mixer, RTW and MAIC
 end in 'learner iql cannot find!'.
 
+``args.alg == 'qatten'`` (no agent switch on): SharedMAC, the replay buffer and QLearner with QattenMixer (network/mixer.py).  With
+RTW, world_model or MAIC it raises ValueError before anything is built: their learners keep their own three-mixer tables.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -117,6 +120,8 @@ class Runner:
             raise ValueError("mi_loss_weight / entropy_loss_weight are terms of MAICTDLearner's loss: they need MAIC_train")
         mac_cls, make_learner = SharedMAC, lambda mac, logger, args: QLearner(mac, args)
         on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
+        if args.alg == 'qatten' and on:      # their learners keep their own three-mixer tables
+            raise ValueError("qatten mixes the plain shared agent's values in QLearner: not with %s" % on[0].name)
         self.on_policy = learner_cls is not None or args.alg in _ON_POLICY
         if self.on_policy:
             if on:
@@ -153,6 +158,8 @@ class Runner:
             self.learner = make_learner(self.mac, logger, args)
         elif _qtran(args):
             self.learner = QTRANLearner(self.mac, args)
+        elif args.alg == 'qatten':
+            self.learner = QLearner(self.mac, args)
         elif args.alg == 'iql' and not on:
             self.learner = IQLLearner(self.mac, args)
         else:

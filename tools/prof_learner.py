@@ -16,7 +16,7 @@ import bench  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--envs", type=int, default=4096)
-    ap.add_argument("--alg", default="qmix")
+    ap.add_argument("--alg", default="qmix", help="vdn, qmix, qplex, qatten, qtran_base, iql or central_v")
     ap.add_argument("--shape", default="2s3z")
     ap.add_argument("--T", type=int, default=0)
     ap.add_argument("--updates", type=int, default=3)
