@@ -574,6 +574,43 @@ int marl_qatten_loss_bwd(const marl_src_t* s, const float* hy, long ldh, const f
                          float* q_tot, float* dq, float* dhy, long lddh, float* dq_tot, float* out2, float* ws, long rows,
                          int N, int U, int H, void* stream);
 
+/* ---- LICA's mixing critic (lica.hip; Zhou et al., NeurIPS 2020 - the reference ships no LICA: the definitions are this project's
+ * own) ------------------------------------------------------------------------------------------------------------------------
+ * A critic row is one step (b, t), rows = B T.  K = N A, E = mixing_embed_dim.  hy (rows, ldh), the outputs of four hypernetworks
+ * of the state, holds per row [ W1 (K E, k-major: W1[k, e] at k E + e) | b1 (E) | wf (E) | b2 (1) ], ldh >= K E + 2 E + 1.  The
+ * input is x (rows, K), agent-major x[i A + k] - the agents' action distributions - or the taken actions u (rows N) int32, which
+ * stand for the one-hot vector with one 1 per agent block (an index outside [0, A): that block all zero).  Exactly one of x and u is
+ * non-NULL; with u only the N taken rows of W1 are read and the one-hot vector is never built.
+ *   pre_e = b1_e + sum_k x_k W1[k, e],   h_e = relu(pre_e),   Q = sum_e h_e wf_e + b2       (no abs(): the critic is not monotonic)
+ * marl_lica_mix_fwd: q (rows) = Q.
+ * marl_lica_mix_bwd: with g = dq[row] and dpre_e = g wf_e [pre_e > 0] (pre is recomputed),
+ *   dhy (rows, lddh >= K E + 2 E): [ dW1[k, e] = x_k dpre_e | db1 = dpre | dwf_e = g h_e ]; db2 = g is the caller's.  All K E + 2 E
+ *     columns of a row are written - with u, dpre in the blocks of the taken actions (the row's db1 bit for bit) and exact zeros in
+ *     the others - and nothing beyond them;
+ *   dx (rows, K): dx_k = sum_e W1[k, e] dpre_e.
+ *   Either output may be NULL, not both.
+ * marl_lica_loss_bwd: the forward on the taken actions, the TD loss of marl_td_loss (same expressions: dq_tot = -2 m (m td) with
+ *   m = 1 - padded, td = r + gamma q_tgt (1 - term) - Q, un-normalised) and the backward to dhy in one row launch; out2 = {sum (m td)^2,
+ *   sum m} comes from a pass over the q it wrote that keeps marl_td_loss's partition of the rows, then the fixed-order finish on
+ *   ws = marl_loss_workspace() bytes.  q, dhy, dq_tot and out2 equal mix_fwd -> marl_td_loss -> mix_bwd bit for bit.  A row with
+ *   padded = 1 gets exact zeros in dhy and dq_tot and adds nothing to either sum; its hy, u, r and q_tgt enter no computation but its
+ *   own q (they may hold NaN, and q[row] is then NaN too).  q is required.
+ * Sums run in a fixed order (pre over k ascending from b1, Q over e ascending then + b2, dx over e ascending); fp32, no float atomics:
+ * two calls give the same bits.  Supported: 1 <= N <= 16, 1 <= A <= 32, 1 <= E <= 64 (marl_lica_supported).  An unsupported shape,
+ * a NULL required pointer, both or neither of x and u, both of dhy and dx NULL, a short ldh / lddh or rows >= 2^31:
+ * hipErrorInvalidValue and nothing written.  rows <= 0: returns 0, no launch.
+ * marl_lica_plan (host only), plan[4]: [0] rows of a workgroup's tile  [1] workgroups  [2] dynamic LDS bytes
+ *   [3] tiles the busiest workgroup walks. */
+int marl_lica_supported(int N, int A, int E);
+int marl_lica_plan(long rows, int N, int A, int E, int* plan);
+int marl_lica_mix_fwd(const float* hy, long ldh, const float* x, const int* u, float* q, long rows, int N, int A, int E,
+                      void* stream);
+int marl_lica_mix_bwd(const float* hy, long ldh, const float* x, const int* u, const float* dq, float* dhy, long lddh, float* dx,
+                      long rows, int N, int A, int E, void* stream);
+int marl_lica_loss_bwd(const float* hy, long ldh, const int* u, const float* q_tgt, const float* r, const float* term,
+                       const float* padded, float gamma, float* q, float* dhy, long lddh, float* dq_tot, float* out2, float* ws,
+                       long rows, int N, int A, int E, void* stream);
+
 /* TD(lambda) returns (td_lambda.hip; utils/rl_utils.py:4-14, build_td_lambda_targets - a function the reference ships and never
  * calls).  Per episode b over the T steps of the batch, q[t] = q_next_tot[b, t] (the target network's value at the next state of
  * step t), m = 1 - padded:
@@ -695,6 +732,24 @@ int marl_ppo_loss_bwd(const float* logits, const float* avail, const int* u, con
                       const float* padded, float eps, float beta, float clip, float* dlogits, float* logp, float* ent,
                       float* out4, float* ws, long rows, int N, int A, void* stream);
 int marl_masked_standardize(const float* x, const float* padded, float* out, float* stats3, float* ws, long rows, void* stream);
+
+/* ---- LICA's actor pass (policy.hip): the transpose-Jacobian of the policy by its logits applied to a vector ----------------------
+ * marl_policy_probs_bwd: rows = B T N agent rows, row r of step r / N; pi, m, H, dH/dz and "no policy" (n = 0) are those above.
+ * gpi (rows, A) is dL/dpi, read on available actions only.  With e_k = exp(z_k - mx), S = sum e, Sa = sum a e,
+ * D = (1 - eps) Sa + eps S, n = sum a:
+ *   (J^T g)_i = (e_i / D) [ (1 - eps) a_i g_i + (eps / n) sum_k a_k g_k - ((1 - eps) a_i + eps) sum_k pi_k g_k ]
+ *   (at eps = 0: pi_i (g_i - sum_k pi_k g_k) on available actions, exactly 0 elsewhere).
+ * For an agent row with m = 1 and a policy:  dlogits = J^T gpi - beta dH/dz,  ent[r] = H_r (ent may be NULL),
+ *   out3 = { - sum_r m q_pi[r / N] - beta sum_r m H_r,  sum_r m,  sum_r m H_r }  (un-normalised; q_pi (rows / N) may be NULL: that
+ *   term is 0.  Every live agent row adds - q_pi of its step once, which gives a factor N).
+ * A row with m = 0 or without a policy: exact zero dlogits, ent = 0, its logits and gpi never looked at; such a row still adds
+ * - q_pi when m = 1.  A row with one available action: dlogits exactly 0, H = 0.  dlogits may be logits or gpi itself, not avail.
+ * fp32, fixed-order sums (ws: marl_loss_workspace() bytes, three partials per workgroup), no float atomics: two calls give the same
+ * bits.  A NULL required pointer, rows % N != 0, beta < 0 or dlogits == avail: hipErrorInvalidValue.  rows <= 0: returns 0, no
+ * launch. */
+int marl_policy_probs_bwd(const float* logits, const float* avail, const float* gpi, const float* q_pi, const float* padded,
+                          float eps, float beta, float* dlogits, float* ent, float* out3, float* ws, long rows, int N, int A,
+                          void* stream);
 
 /* ---- COMA: the counterfactual critic (coma.hip; the reference ships the argument table only - the definitions are this
  * project's own, from the published algorithm) ----------------------------------------------------------------------------

@@ -142,6 +142,12 @@ def get_centralv_args(args):
     return _assign(args, dict(_ACTOR_CRITIC, td_lambda=0.8, target_update_cycle=200))
 
 
+def get_lica_args(args):
+    """This project's own table for LICA (the reference ships none): the actor-critic fields of central-V, td_lambda = 0.8 and a
+    target critic that follows every 200 updates.  The critic's widths, mixing_embed_dim and hypernet_embed, stay get_mixer_args'."""
+    return _assign(args, dict(_ACTOR_CRITIC, td_lambda=0.8, target_update_cycle=200))
+
+
 def get_mappo_args(args):
     """This project's own table (the reference ships none for PPO): the actor-critic fields of central-V, td_lambda = 0.95 (with
     adv = G - V that is GAE(0.95)), clip 0.2, five passes over a rollout, standardised advantages.  There is no target network, so

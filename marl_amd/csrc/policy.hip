@@ -10,6 +10,8 @@
 // Lane mapping of the two batch kernels (probs, loss_bwd): row_tile.h's staging with two tiles, logits and availability; every lane
 // writes its result over its row of the logits tile, and the wave stores that tile back.  From A = 29 the tiles of four waves pass
 // 56 KiB and the row-per-lane kernel runs instead.
+// marl_policy_probs_bwd (LICA: the transpose-Jacobian of pi applied to dL/dpi, policy_rows.h: row_probs_bwd) stages a third tile,
+// the gradient, and takes the row-per-lane form from A = 19.
 // The sampler runs once per lock-step over E N rows (25 600 at most in the measured set-ups): one lane per row, like select_kernel.
 #include <type_traits>
 #include "synth_env.h"
@@ -169,6 +171,66 @@ int launch_policy(ArgsOf<PPO> p, hipStream_t s, int& nb) {
   return 0;
 }
 
+// marl_policy_probs_bwd (LICA's actor pass): gpi is a third row operand, so the tiled form stages three tiles (it fits up to A = 18)
+struct ProbsBwdArgs {
+  const float *logits, *avail, *gpi;     // (rows, A)
+  const float *q_pi, *padded;            // (rows / N); q_pi may be NULL
+  float eps, beta;
+  float *out, *ent, *ws;                 // (rows, A); (rows) or NULL; partial sums
+  long rows;
+  int N, A, vec;
+};
+
+// one agent row: out = J^T gpi - beta m dH/dz, acc = { -m q_pi - beta m H, m, m H }; a padded step: exact zeros, nothing of it looked at
+__device__ __forceinline__ void probs_bwd_row(const ProbsBwdArgs& p, long r, const float* z, const float* a, const float* g, float* out,
+                                              float (&acc)[3]) {
+  const long bt = r / p.N;
+  const float m = 1.f - p.padded[bt];
+  float H = 0.f;
+  if (m == 0.f) {
+    for (int k = 0; k < p.A; ++k) out[k] = 0.f;
+  } else {
+    if (p.q_pi) acc[0] -= m * p.q_pi[bt];
+    if (row_probs_bwd(row_policy(z, a, p.A, p.eps), z, a, g, out, p.A, p.eps, p.beta * m, H)) {
+      if (p.beta != 0.f) acc[0] -= p.beta * m * H;
+      acc[2] += m * H;
+    }
+  }
+  if (p.ent) p.ent[r] = H;
+  acc[1] += m;
+}
+
+__global__ __launch_bounds__(TPB) void probs_bwd_tiled_kernel(ProbsBwdArgs p) {
+  extern __shared__ __attribute__((aligned(16))) float pb_smem[];
+  const int lane = threadIdx.x & 63;
+  const int A = p.A;
+  float* Sz = rt::wave_tiles(pb_smem, 3, A);
+  float* Sa = Sz + rt::tile_floats(A);
+  float* Sg = Sa + rt::tile_floats(A);
+  float acc[3] = {};
+  const long tiles = rt::tiles(p.rows);
+  for (long tile = rt::first_tile(); tile < tiles; tile += rt::tile_step()) {
+    const long r0 = tile * rt::ROWS;
+    const int n = rt::tile_len(p.rows, r0, A);
+    rt::copy<3>({Sz, Sa, Sg}, {p.logits + r0 * A, p.avail + r0 * A, p.gpi + r0 * A}, n, p.vec);
+    rt::lds_done_fenced();
+    const long r = r0 + lane;
+    if (r < p.rows) probs_bwd_row(p, r, Sz + lane * A, Sa + lane * A, Sg + lane * A, Sz + lane * A, acc);
+    rt::lds_done_fenced();
+    rt::copy(p.out + r0 * A, Sz, n, p.vec);
+    rt::lds_done_fenced();                                // the tile is read out before the next trip overwrites it
+  }
+  block_partials<3>(acc, p.ws);
+}
+
+// row-per-lane form for action counts whose tiles do not fit: same arithmetic in the same order
+__global__ __launch_bounds__(TPB) void probs_bwd_rows_kernel(ProbsBwdArgs p) {
+  float acc[3] = {};
+  for (long r = (long)blockIdx.x * TPB + threadIdx.x; r < p.rows; r += (long)gridDim.x * TPB)
+    probs_bwd_row(p, r, p.logits + r * p.A, p.avail + r * p.A, p.gpi + r * p.A, p.out + r * p.A, acc);
+  block_partials<3>(acc, p.ws);
+}
+
 // marl_select_actions' argument shape; the draw is the ST_SAMPLE stream's
 __global__ void policy_sample_kernel(const float* logits, const float* avail, long avail_es, const int* alive, float eps,
                                      unsigned rseed, int env0, const int* tg, int tg0, int* act_out, long act_es, int E,
@@ -260,6 +322,32 @@ extern "C" int marl_ppo_loss_bwd(const float* logits, const float* avail, const 
   const int rc = launch_policy<true, true, true>(p, (hipStream_t)stream, nb);
   if (rc) return rc;
   hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, (const float*)ws, nb, 4, out4);
+  MARL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int marl_policy_probs_bwd(const float* logits, const float* avail, const float* gpi, const float* q_pi, const float* padded,
+                                     float eps, float beta, float* dlogits, float* ent, float* out3, float* ws, long rows, int N,
+                                     int A, void* stream) {
+  if (rows <= 0 || A <= 0) return 0;
+  if (!logits || !avail || !gpi || !padded || !dlogits || !out3 || !ws || N <= 0 || rows % N != 0 || dlogits == avail ||
+      !(beta >= 0.f))
+    return (int)hipErrorInvalidValue;
+  ProbsBwdArgs p = {};
+  p.logits = logits; p.avail = avail; p.gpi = gpi; p.q_pi = q_pi; p.padded = padded; p.eps = eps; p.beta = beta;
+  p.out = dlogits; p.ent = ent; p.ws = ws; p.rows = rows; p.N = N; p.A = A;
+  const rt::Plan pl = rt::plan(rows, A, 3, 56 * 1024, rt::PARTIAL_ROWS, {logits, avail, gpi, dlogits});
+  int nb;
+  if (pl.tiled) {
+    nb = pl.blocks;
+    p.vec = pl.vec;
+    hipLaunchKernelGGL(probs_bwd_tiled_kernel, dim3((unsigned)nb), dim3(TPB), pl.lds_bytes, (hipStream_t)stream, p);
+  } else {
+    nb = rt::partial_blocks(rows);
+    hipLaunchKernelGGL(probs_bwd_rows_kernel, dim3((unsigned)nb), dim3(TPB), 0, (hipStream_t)stream, p);
+  }
+  MARL_CHECK_LAUNCH();
+  hipLaunchKernelGGL(finish_sums_kernel, dim3(1), dim3(TPB), 0, (hipStream_t)stream, (const float*)ws, nb, 3, out3);
   MARL_CHECK_LAUNCH();
   return 0;
 }

@@ -138,6 +138,11 @@ __device__ __forceinline__ bool row_logp_grad(const float* z, const float* a, fl
 // compiler gives the marl_policy_loss_bwd_ex instantiations of its own accord (their ISA: a packed multiply, then a subtract), while
 // it fused hs * dH into the subtraction in the PPO ones - and the PPO pass without logp_old is held to the _ex pass bit for bit
 // (tests/test_gpu_ppo.py).  The callers without SPLIT compile the statement they always had
+// dH/dz_k of the comment above, from the row's scalars and column k's e, a and w = cw e + ew
+__device__ __forceinline__ float row_dH(float e, float ak, float w, float logD, float c2, float Pa, float Hn, float L1S) {
+  const float elp = (ak != 0.f && w > 0.f) ? e * (logf(w) - logD) : 0.f;
+  return c2 * (e * (ak - Pa) * Hn - (elp - e * L1S));
+}
 template <bool SPLIT = false>
 __device__ __forceinline__ bool row_logp_ent_grad_of(const RowPolicy& p, const float* z, const float* a, float* out, int A, int u,
                                                      float scale, float hs, float& logp, float& H) {
@@ -161,8 +166,7 @@ __device__ __forceinline__ bool row_logp_ent_grad_of(const RowPolicy& p, const f
     const float e = row_e(p, z[k]);
     const float ak = a[k] != 0.f ? 1.f : 0.f;
     const float w = p.cw * e + p.ew;
-    const float elp = (ak != 0.f && w > 0.f) ? e * (logf(w) - logD) : 0.f;
-    const float dH = c2 * (e * (ak - Pa) * Hn - (elp - e * L1S));
+    const float dH = row_dH(e, ak, w, logD, c2, Pa, Hn, L1S);
     if constexpr (SPLIT) {
       const float g = c1 * ((k == u ? 1.f : 0.f) - e * invS) - c2 * e * (ak - Pa);
       {
@@ -178,6 +182,43 @@ __device__ __forceinline__ bool row_logp_ent_grad_of(const RowPolicy& p, const f
 __device__ __forceinline__ bool row_logp_ent_grad(const float* z, const float* a, float* out, int A, float eps, int u, float scale,
                                                   float hs, float& logp, float& H) {
   return row_logp_ent_grad_of(row_policy(z, a, A, eps), z, a, out, A, u, scale, hs, logp, H);
+}
+
+// The transpose-Jacobian of pi by the logits applied to g (A values, read on available actions only), less hs dH/dz:
+//   (J^T g)_i = (e_i / D) [ (1 - eps) a_i g_i + (eps / n) sum_k a_k g_k - ((1 - eps) a_i + eps) sum_k pi_k g_k ]
+// (pi_i (g_i - sum_k pi_k g_k) on available actions and 0 elsewhere at eps = 0), written over out, which may be z or g: column k of
+// both is read before out[k] is written, the sums before any.  H: the row's entropy (row_ent_sums).  A row without a policy
+// (n = 0) returns `false`; it and a row with one available action (pi = 1 whatever the logits hold) get exact zeros and H = 0
+__device__ __forceinline__ bool row_probs_bwd(const RowPolicy& p, const float* z, const float* a, const float* g, float* out, int A,
+                                              float eps, float hs, float& H) {
+  H = 0.f;
+  if (p.n <= 1) {
+    for (int k = 0; k < A; ++k) out[k] = 0.f;
+    return p.n == 1;
+  }
+  const float invD = 1.f / p.D;
+  float sag = 0.f, spg = 0.f;
+  for (int k = 0; k < A; ++k) {
+    if (a[k] == 0.f) continue;
+    const float gk = g[k];
+    sag += gk;
+    spg += (p.cw * row_e(p, z[k]) + p.ew) * invD * gk;
+  }
+  const float2 s = row_ent_sums(p, z, a, A);
+  const float Hn = s.y;
+  H = -Hn;
+  const float logD = logf(p.D);
+  const float invS = 1.f / p.S, Pa = p.Sa * invS, c2 = p.cw / p.D, L1S = s.x * invS;
+  const float us = eps / (float)p.n * sag;
+  for (int k = 0; k < A; ++k) {
+    const float e = row_e(p, z[k]);
+    const float ak = a[k] != 0.f ? 1.f : 0.f;
+    const float gk = ak != 0.f ? g[k] : 0.f;
+    float v = e * invD * (p.cw * ak * gk + us - (p.cw * ak + eps) * spg);
+    if (hs != 0.f) v -= hs * row_dH(e, ak, p.cw * e + p.ew, logD, c2, Pa, Hn, L1S);
+    out[k] = v;
+  }
+  return true;
 }
 
 }  // namespace

@@ -8,6 +8,7 @@
     python -m marl_amd.main --map 2s3z --alg coma --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg reinforce --policy_entropy_coef 0.01 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg mappo --ppo_epochs 5 --ppo_clip 0.2 --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --map 2s3z --alg lica --policy_entropy_coef 0.01 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg reinforce+commnet --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg central_v+commnet --commnet_k 2 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg coma+commnet --n_envs 64 --n_steps 200000
@@ -24,7 +25,7 @@ import sys
 from collections import namedtuple
 
 from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
-    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args
+    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args, get_lica_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .runner import Runner
@@ -89,6 +90,12 @@ def _qatten(args):
     qatten_shape_of(args)
 
 
+def _lica(args):
+    """the LICA critic's shape check: agents, actions or mixing_embed_dim outside the row kernels' range are a ValueError here"""
+    from .algorithm.lica import lica_shape_of
+    lica_shape_of(args)
+
+
 def build(argv=None):
     args = get_common_args(argv)
     get_mixer_args(args)
@@ -97,9 +104,9 @@ def build(argv=None):
         on = [sw for sw in ('RTW', 'world_model', 'MAIC') if getattr(args, sw, False)]
         if on:
             raise ValueError("%s trains the %s actor as a policy: not with %s" % (args.alg, actor.title, on[0]))
-    if base in ('central_v', 'coma'):
+    if base in ('central_v', 'coma', 'lica'):      # (an actor suffix on lica was refused above: _POLICY_ALGS does not hold the name)
         given = args.td_lambda
-        (get_centralv_args if base == 'central_v' else get_coma_args)(args)
+        {'central_v': get_centralv_args, 'coma': get_coma_args, 'lica': get_lica_args}[base](args)
         if given is not None:           # the table's 0.8 is the default, not an override of --td_lambda
             args.td_lambda = given
     elif base == 'reinforce':
@@ -123,6 +130,10 @@ def build(argv=None):
     if args.alg == 'qatten':            # the sizes the environment will report are the map's (the matrix game: 2 agents, state width 1):
         args.n_agents, args.state_shape = (MAPS[args.map][0], MAPS[args.map][2]) if args.env in ('smac', 'synthetic') else (2, 1)
         _qatten(args)                   # refused before the environment is made
+    if args.alg == 'lica':              # likewise: the map's agent, action and state sizes (the matrix game: 2 agents, 3 actions, width 1)
+        args.n_agents, args.n_actions, args.state_shape = (MAPS[args.map][0], MAPS[args.map][3], MAPS[args.map][2]) \
+            if args.env in ('smac', 'synthetic') else (2, 3, 1)
+        _lica(args)                     # refused before the environment is made
     if args.env == 'smac':
         args.env = 'synthetic'
     if args.env == 'synthetic':
@@ -140,6 +151,8 @@ def build(argv=None):
     args.buffer_size = max(2 * args.n_envs, min(args.buffer_size, 8 * args.n_envs))
     if args.alg == 'qatten':
         _qatten(args)                   # ... and with the environment's own sizes
+    if args.alg == 'lica':
+        _lica(args)
     if actor is not None:
         _share(actor.check)(args)       # ... and the environment's agent and action counts with it, before a controller is built
     return args, env
@@ -147,8 +160,8 @@ def build(argv=None):
 
 def make_runner(args, env, logger=None):
     """the Runner of a built (args, env).  ``--alg coma`` names its learner here: the runner's own table of on-policy learners
-    holds central_v and reinforce, and a Runner built on the bare name 'coma' still refuses it; ``--alg mappo`` likewise (PPOLearner;
-    with RTW, world_model or MAIC the runner refuses it as it refuses central_v).  The algorithms with an actor suffix
+    holds central_v and reinforce, and a Runner built on the bare name 'coma' still refuses it; ``--alg mappo`` (PPOLearner) and
+    ``--alg lica`` (LICALearner) likewise (with RTW, world_model or MAIC the runner refuses them as it refuses central_v).  The algorithms with an actor suffix
     get their learner class and their actor's controller (``mac_cls``, the _ACTORS entry's) the same way."""
     learner_cls = mac_cls = None
     base, actor = actor_base(args.alg, entry=True)
@@ -158,6 +171,9 @@ def make_runner(args, env, logger=None):
     elif base == 'mappo':
         from .algorithm.ppo import PPOLearner
         learner_cls = PPOLearner
+    elif base == 'lica':
+        from .algorithm.lica import LICALearner
+        learner_cls = LICALearner
     elif actor is not None:             # the names with an actor suffix are the launcher's: the runner's own table does not hold them
         from .algorithm.central_v import CentralVLearner
         from .algorithm.reinforce import ReinforceLearner

@@ -462,6 +462,47 @@ def qatten_loss_bwd(s, hy, q, scale, q_tot_tgt, r, term, padded, gamma, q_tot, d
           "marl_qatten_loss_bwd")
 
 
+def lica_supported(N, A, E):
+    """csrc/lica.hip covers the shape: N <= 16, A <= 32, E <= 64"""
+    return bool(_lib.load().marl_lica_supported(N, A, E))
+
+
+def lica_plan(rows, N, A, E):
+    """(rows of a workgroup's tile, workgroups, LDS bytes, tiles the busiest workgroup walks) of the LICA row kernel"""
+    plan = (C.c_int * 4)()
+    check(_lib.load().marl_lica_plan(rows, N, A, E, plan), "marl_lica_plan")
+    return tuple(plan)
+
+
+def _lica_in(x, u):
+    return _p(None if x is None else _f32(x)), _p(None if u is None else _i32(u))
+
+
+def lica_mix_fwd(hy, x, u, q, rows, N, A, E):
+    """Q (rows) of LICA's mixing critic; hy (rows, >= K E + 2 E + 1): [W1 | b1 | wf | b2] per row; the input is dense x (rows, K) or
+    the taken actions u (rows N) int32 - exactly one of them, the other None"""
+    px, pu = _lica_in(x, u)
+    check(_lib.load().marl_lica_mix_fwd(_p(_f32(hy)), hy.stride(0), px, pu, _p(_f32(q)), rows, N, A, E, _stream()), "marl_lica_mix_fwd")
+
+
+def lica_mix_bwd(hy, x, u, dq, dhy, dx, rows, N, A, E):
+    """dhy (rows, >= K E + 2 E): [dW1 | db1 | dwf] per row and dx (rows, K) from dq (rows); either output may be None, not both"""
+    px, pu = _lica_in(x, u)
+    check(_lib.load().marl_lica_mix_bwd(_p(_f32(hy)), hy.stride(0), px, pu, _p(_f32(dq)), _p(None if dhy is None else _f32(dhy)),
+                                        0 if dhy is None else dhy.stride(0), _p(None if dx is None else _f32(dx)), rows, N, A, E,
+                                        _stream()), "marl_lica_mix_bwd")
+
+
+def lica_loss_bwd(hy, u, q_tgt, r, term, padded, gamma, q, dhy, dq_tot, out2, rows, N, A, E):
+    """LICA's critic on the taken actions + TD loss + backward to dhy in one row launch (include/marl_hip.h); out2: 2-element
+    device view written"""
+    lib = _lib.load()
+    ws = WS.get("loss", lib.marl_loss_workspace(rows), hy.device)
+    check(lib.marl_lica_loss_bwd(_p(_f32(hy)), hy.stride(0), _p(_i32(u)), _p(_f32(q_tgt)), _p(_f32(r)), _p(_f32(term)),
+                                 _p(_f32(padded)), float(gamma), _p(_f32(q)), _p(_f32(dhy)), dhy.stride(0), _p(_f32(dq_tot)),
+                                 _p(_f32(out2)), _p(ws), rows, N, A, E, _stream()), "marl_lica_loss_bwd")
+
+
 _FT_OUT = {}
 
 
@@ -588,6 +629,20 @@ def policy_loss_bwd_ex(logits, avail, u, G, v, padded, eps, beta, dlogits, logp,
     ws = WS.get("loss", lib.marl_loss_workspace(rows), logits.device)
     check(lib.marl_policy_loss_bwd_ex(_p(logits), _p(avail), _p(u), _p(G), _p(v), _p(padded), float(eps), float(beta), _p(dlogits),
                                       _p(logp), _p(ent), _p(_f32(out3)), _p(ws), rows, N, A, _stream()), "marl_policy_loss_bwd_ex")
+
+
+def policy_probs_bwd(logits, avail, gpi, q_pi, padded, eps, beta, dlogits, ent, out3, rows, N, A):
+    """LICA's actor pass (csrc/policy.hip): dlogits (rows, A) = J^T gpi - beta m dH/dz, the transpose-Jacobian of the policy by its
+    logits applied to gpi = dL/dpi; ent (rows) = H or None; out3 = {- sum m q_pi - beta sum m H, N sum m, sum m H} with q_pi
+    (rows / N) or None.  dlogits may be logits or gpi."""
+    lib = _lib.load()
+    for t, n in ((logits, rows * A), (avail, rows * A), (gpi, rows * A), (dlogits, rows * A), (padded, rows // N)) + \
+            (() if q_pi is None else ((q_pi, rows // N),)) + (() if ent is None else ((ent, rows),)):
+        assert _f32(t).is_contiguous() and t.numel() >= n
+    assert out3.numel() >= 3
+    ws = WS.get("loss", lib.marl_loss_workspace(rows), logits.device)
+    check(lib.marl_policy_probs_bwd(_p(logits), _p(avail), _p(gpi), _p(q_pi), _p(padded), float(eps), float(beta), _p(dlogits),
+                                    _p(ent), _p(_f32(out3)), _p(ws), rows, N, A, _stream()), "marl_policy_probs_bwd")
 
 
 def ppo_loss_bwd(logits, avail, u, adv, logp_old, padded, eps, beta, clip, dlogits, logp, ent, out4, rows, N, A):

@@ -36,7 +36,9 @@ exploration rate they were drawn at.  With RTW / world_model / MAIC it raises Va
 NotImplementedError (an on-policy update needs the weights the last one wrote) - before anything is built.
 ``learner_cls`` (a constructor argument): a further on-policy learner over PolicyMAC, named by the caller instead of by the runner's
 own table; everything above holds for it.  The launcher passes COMALearner (algorithm/coma.py) for ``--alg coma``
-(``main.make_runner``); a Runner built without it keeps answering 'learner coma cannot find!', as it always has.
+(``main.make_runner``); a Runner built without it keeps answering 'learner coma cannot find!', as it always has.  ``--alg lica``
+gets LICALearner (algorithm/lica.py) the same way: PolicyMAC, on-policy batches, and a Runner on the bare name answers
+'learner lica cannot find!'.
 ``mac_cls`` (a constructor argument, with ``learner_cls``): the stochastic controller that learner trains in the place of PolicyMAC - the
 launcher passes the GroupHeadMAC subclass of its actor table (CommNetMAC for the three ``+commnet`` algorithms, G2ANetMAC for the three
 ``+g2anet`` ones); a Runner built on a bare ``+commnet`` / ``+g2anet`` name answers 'cannot find!' too.
