@@ -1149,6 +1149,30 @@ int marl_g2anet_head_bwd(const marl_g2anet_weights_t* w, const marl_g2anet_grads
  * T = 1 with tg0 = the global step, so one call over T steps from an episode's first global step gives the per-step draws. */
 int marl_g2anet_noise(unsigned seed, int env0, unsigned tg0, float* noise, int E, int T, int N, void* stream);
 
+/* ---- battle environment (battle.hip; rules: csrc/battle_env.h) ----------------------------------------------
+ * A deterministic micro-combat simulator in SMAC's layout: N allies against M = N enemies of the same types on a 32 x 32 grid.
+ * types: two bits per unit of a side, unit 0 lowest (0 marine, 1 stalker, 2 zealot); shield (0 / 1) and type_bits (0 .. 2) say
+ * which feature columns the map has, A = 6 + M; observation width O = 4 + (M + N - 1)(5 + shield + type_bits) + 1 + shield +
+ * type_bits, state width S = N (4 + shield + type_bits) + M (3 + shield + type_bits) + N A.  units (E, N + M, 5) int32: x, y, hp,
+ * shield, cooldown, allies first.  The record is the synthetic environment's: obs (E,T+1,N,O), state (E,T+1,state_ld >= S), avail
+ * (E,T+1,N,A), u (E,T,N), r / term / padded (E,T), length / won (E).  marl_battle_supported(): 1 <= n_allies = n_enemies <= 16
+ * and A = 6 + n_enemies; the two entries return hipErrorInvalidValue for anything else (and for a type without a bit, state_ld
+ * < S, t outside 0 .. T - 1) and launch nothing. */
+int marl_battle_supported(int n_allies, int n_enemies, int A);
+/* start of episode `episode`: unit state (positions from the counter hash of (seed, env0 + e, episode, unit), streams 16 .. 19),
+ * length = T, won = 0, and slot 0 of obs / state / avail */
+int marl_battle_reset(unsigned seed, int env0, int episode, unsigned types, int shield, int type_bits, int* units, int* length,
+                      int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N, int M, int A,
+                      void* stream);
+/* lock-step t in one launch: reads act (E,N); writes u / r / term / padded of step t, length = t + 1 and won where the episode
+ * ends here, alive_next (E; may be NULL) = 0 from the terminating step on, the new unit state and slot t + 1 of obs / state /
+ * avail (the final observation at the terminating step).  Environments whose episode is over (t >= length) get u = -1, r = 0,
+ * term = 1, padded = 1 and a zero slot.  r = (float)points * scale with points = hp + shield removed from enemies + 10 per kill +
+ * 200 for the win; scale = 20 / (sum of enemy hp + shield + 10 M + 200) in fp32, from the caller. */
+int marl_battle_step(unsigned types, int shield, int type_bits, float scale, int t, const int* act, int* units, int* u, float* r,
+                     float* term, float* padded, int* length, int* won, int* alive_next, float* obs, float* state, long state_ld,
+                     float* avail, int E, int T, int N, int M, int A, void* stream);
+
 const char* marl_hip_version(void);
 
 /* Experiment switches (A/B measurements, variant tests): one table per process; NO entry point reads the environment.

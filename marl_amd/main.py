@@ -16,9 +16,12 @@
     python -m marl_amd.main --map 2s3z --alg central_v+g2anet --g2anet_hard False --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg coma+g2anet --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --MAIC True --load_model True --evaluate True --evaluate_epoch 1 --n_envs 64
+    python -m marl_amd.main --env battle --map 3m --alg qmix --n_envs 64 --n_steps 200000
 
 ``--env synthetic`` (default) uses the synthetic SMAC-shaped device env with the dims of ``--map``;
-``--env matrix`` the batched two-agent matrix game.  StarCraft II itself is not vendored by the reference."""
+``--env matrix`` the batched two-agent matrix game; ``--env battle`` the micro-combat simulator in SMAC's layout (env/battle.py:
+maps 3m, 2s3z, 3s5z), the one environment here whose outcome depends on the actions.  StarCraft II itself is not vendored by the
+reference."""
 from __future__ import annotations
 
 import sys
@@ -28,6 +31,7 @@ from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get
     get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args, get_lica_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
+from .env.battle import BattleEnv, battle_shapes
 from .runner import Runner
 from .utils.logging import Logger
 
@@ -39,9 +43,18 @@ G2ANET = '+g2anet'
 _POLICY_ALGS = ('central_v', 'coma', 'reinforce')
 
 
+def _map_shapes(args):
+    """(agents, observation, state, actions, episode limit) of --map, known before the environment is made: ``MAPS`` for the synthetic
+    environment, the battle environment's own table for ``--env battle`` (a map it does not have is a ValueError); None otherwise"""
+    if args.env == 'battle':
+        return battle_shapes(args.map)
+    return MAPS[args.map] if args.env in ('smac', 'synthetic') else None
+
+
 def _map_counts(args):
     """(agents, actions) of --map, known before the environment is made; (2, 1) where no map says them"""
-    return (MAPS[args.map][0], MAPS[args.map][3]) if args.env in ('smac', 'synthetic') else (2, 1)
+    shapes = _map_shapes(args)
+    return (shapes[0], shapes[3]) if shapes is not None else (2, 1)
 
 
 # What the launcher does for an actor suffix.  table: the argument table (commnet: k = 2 on map 3m, otherwise 3; g2anet: attention_dim =
@@ -99,6 +112,8 @@ def _lica(args):
 def build(argv=None):
     args = get_common_args(argv)
     get_mixer_args(args)
+    if args.env == 'battle':
+        battle_shapes(args.map)         # a map the battle environment does not have is refused before anything is built
     base, actor = actor_base(args.alg, entry=True)           # raises on a Q-learning algorithm with an actor suffix
     if actor is not None:
         on = [sw for sw in ('RTW', 'world_model', 'MAIC') if getattr(args, sw, False)]
@@ -128,17 +143,20 @@ def build(argv=None):
     get_RTW_args(args)
     get_maic_args(args)
     if args.alg == 'qatten':            # the sizes the environment will report are the map's (the matrix game: 2 agents, state width 1):
-        args.n_agents, args.state_shape = (MAPS[args.map][0], MAPS[args.map][2]) if args.env in ('smac', 'synthetic') else (2, 1)
+        shapes = _map_shapes(args)
+        args.n_agents, args.state_shape = (shapes[0], shapes[2]) if shapes is not None else (2, 1)
         _qatten(args)                   # refused before the environment is made
     if args.alg == 'lica':              # likewise: the map's agent, action and state sizes (the matrix game: 2 agents, 3 actions, width 1)
-        args.n_agents, args.n_actions, args.state_shape = (MAPS[args.map][0], MAPS[args.map][3], MAPS[args.map][2]) \
-            if args.env in ('smac', 'synthetic') else (2, 3, 1)
+        shapes = _map_shapes(args)
+        args.n_agents, args.n_actions, args.state_shape = (shapes[0], shapes[3], shapes[2]) if shapes is not None else (2, 3, 1)
         _lica(args)                     # refused before the environment is made
     if args.env == 'smac':
         args.env = 'synthetic'
     if args.env == 'synthetic':
         n, o, s, a, t = MAPS[args.map]
         env = SyntheticSMACEnv(args.n_envs, n, o, s, a, t, seed=args.seed)
+    elif args.env == 'battle':
+        env = BattleEnv(args.n_envs, args.map, seed=args.seed)
     elif args.env == 'matrix':
         env = BatchedMatrixGame([[8, -12, -12], [-12, 0, 0], [-12, 0, 0]], args.n_envs, seed=args.seed)
         args.map = 'MatrixGame'

@@ -897,6 +897,26 @@ def synth_fused_step(seed, rseed, env0, episode, t, eps, length, q, obs, state, 
              _stream()), name)
 
 
+def battle_supported(n_allies, n_enemies, A):
+    return bool(_lib.load().marl_battle_supported(n_allies, n_enemies, A))
+
+
+def battle_reset(seed, env0, episode, types, shield, type_bits, units, rec, E, T, N, M, A):
+    """start of an episode of the battle environment (csrc/battle.hip): unit state, length, won and slot 0 of the record"""
+    check(_lib.load().marl_battle_reset(int(seed) & 0xFFFFFFFF, env0, episode, types, int(shield), type_bits, _p(_i32(units)),
+                                        _p(_i32(rec.length)), _p(_i32(rec.won)), _p(_f32(rec.obs)), _p(_f32(rec.state)),
+                                        rec.state.stride(-2), _p(_f32(rec.avail)), E, T, N, M, A, _stream()), "marl_battle_reset")
+
+
+def battle_step(types, shield, type_bits, scale, t, act, units, rec, alive_next, E, T, N, M, A):
+    """lock-step t of the battle environment in one launch: step t of the record, the unit state and slot t + 1"""
+    check(_lib.load().marl_battle_step(types, int(shield), type_bits, float(scale), t, _p(_i32(act)), _p(_i32(units)),
+                                       _p(_i32(rec.u)), _p(_f32(rec.r)), _p(_f32(rec.term)), _p(_f32(rec.padded)),
+                                       _p(_i32(rec.length)), _p(_i32(rec.won)), _p(alive_next), _p(_f32(rec.obs)),
+                                       _p(_f32(rec.state)), rec.state.stride(-2), _p(_f32(rec.avail)), E, T, N, M, A, _stream()),
+          "marl_battle_step")
+
+
 def synth_rollout_supported(N, O, A):
     return bool(_lib.load().marl_synth_rollout_supported(N, O, A))
 
