@@ -1172,6 +1172,40 @@ int marl_battle_reset(unsigned seed, int env0, int episode, unsigned types, int 
 int marl_battle_step(unsigned types, int shield, int type_bits, float scale, int t, const int* act, int* units, int* u, float* r,
                      float* term, float* padded, int* length, int* won, int* alive_next, float* obs, float* state, long state_ld,
                      float* avail, int E, int T, int N, int M, int A, void* stream);
+/* The action choice and marl_battle_step in one launch.  q (E,1,N,A): ally n of a live environment chooses from its row and slot t's
+ * availability in the record with marl_select_actions' epsilon-greedy rule and draws, keyed by (rseed, env0 + e, tg = episode (T + 1)
+ * + t, n); -1 wherever t >= length[e].  Then the step, as marl_battle_step does it (no alive_next).  _sample: the choice is
+ * marl_policy_sample's draw from the stochastic policy of the row instead, eps its mixing epsilon. */
+int marl_battle_fused_step(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0, int episode, int t,
+                           float eps, const float* q, int* units, int* u, float* r, float* term, float* padded, int* length,
+                           int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N, int M, int A,
+                           void* stream);
+int marl_battle_fused_step_sample(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0, int episode,
+                                  int t, float eps, const float* q, int* units, int* u, float* r, float* term, float* padded,
+                                  int* length, int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N,
+                                  int M, int A, void* stream);
+/* Whole battle rollout, ONE persistent launch (csrc/battle_rollout.hip): marl_battle_reset and, for t = 0 .. T - 1, the agent step
+ * (fp32 MFMA, marl_synth_rollout's sequences: q bit for bit the T = 1 unroll's), the choice and marl_battle_step, with the unit state
+ * and the hidden state in LDS.  Writes every element of obs / state (S columns of a row) / avail / u / r / term / padded / length /
+ * won - the zeros after an episode's end included - the final unit state to units, stats ([3][E], optional): sum_t r in step order |
+ * won | length, and h_out (E N, 64; optional): the final hidden state.  Epsilon follows marl_synth_rollout's fp64 schedule
+ * (eps0, eps_anneal, eps_min).  _sample: marl_synth_rollout_sample's draw instead of the epsilon-greedy choice.
+ * marl_battle_rollout_supported(N, O, A): marl_battle_supported(N, N, A) and N within the 16-row tiles (at most 8) that 160 KB of
+ * LDS hold with last action and agent id appended; the launch returns hipErrorInvalidValue for a shape no plan places, and for what
+ * marl_battle_step refuses, and writes nothing.  marl_battle_rollout_plan: plan[0] = workgroups, plan[1] = environments per
+ * workgroup (ceil(E / 256) until the row tiles are full), plan[2] = row tiles, plan[3] = dynamic LDS bytes. */
+int marl_battle_rollout_supported(int N, int O, int A);
+int marl_battle_rollout_plan(int E, int N, int O, int A, int last_action, int reuse_network, int* plan);
+int marl_battle_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, unsigned types,
+                        int shield, int type_bits, float scale, int* units, float* obs, float* state, long state_ld, float* avail,
+                        int* u, float* r, float* term, float* padded, int* length, int* won, float* h_out, float* stats,
+                        double eps0, double eps_anneal, double eps_min, int E, int T, int N, int M, int A, int last_action,
+                        int reuse_network, void* stream);
+int marl_battle_rollout_sample(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, unsigned types,
+                               int shield, int type_bits, float scale, int* units, float* obs, float* state, long state_ld,
+                               float* avail, int* u, float* r, float* term, float* padded, int* length, int* won, float* h_out,
+                               float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int M, int A,
+                               int last_action, int reuse_network, void* stream);
 
 const char* marl_hip_version(void);
 

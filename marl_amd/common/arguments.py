@@ -45,6 +45,8 @@ def get_common_args(argv=None):
     p.add_argument('--qatten_embed_dim', type=int, default=None)
     p.add_argument('--qatten_unit_dim', type=int, default=None)
     p.add_argument('--env', type=str, default='smac')
+    # --env battle: the environment with the fused step and the whole-rollout kernel (env/battle.py: FusedBattleEnv)
+    p.add_argument('--battle_fused', type=_bool, default=False)
     p.add_argument('--difficulty', type=str, default='7')
     p.add_argument('--game_version', type=str, default='latest')
     p.add_argument('--map', type=str, default='2s3z')

@@ -1,9 +1,10 @@
-// The battle environment's two kernels (rules: battle_env.h): reset, and one launch per lock-step that applies the step and writes
-// slot t + 1 of the record.  A wave per environment, BT_WPB environments per workgroup; the units sit on lanes 0 .. N + M - 1 for the
+// The battle environment's per-step kernels (rules: battle_env.h): reset, one launch per lock-step that applies the step and writes
+// slot t + 1 of the record, and the same launch with the action choice in front (the whole rollout in one launch: battle_rollout.hip).  A wave per environment, BT_WPB environments per workgroup; the units sit on lanes 0 .. N + M - 1 for the
 // dynamics (the unit state of the workgroup's environments lives in LDS), damage and points are integer LDS atomics (any order gives
 // the same sum), then all 64 lanes write the slot's N O + S + N A floats as three contiguous runs, 16 bytes a lane where a run's
 // address allows (a run starts on any 4-byte boundary: N O is 90 floats on 3m).
 #include "battle_env.h"
+#include "policy_rows.h"
 #include "../../include/marl_hip.h"
 
 namespace {
@@ -56,50 +57,53 @@ __global__ __launch_bounds__(BT_WPB * MARL_WAVE) void battle_reset_kernel(Battle
   if (valid) write_slot(c, s_un[w], nullptr, true, obs, state, SL, avail, e, T, 0, lane);
 }
 
-__global__ __launch_bounds__(BT_WPB * MARL_WAVE) void battle_step_kernel(BattleCfg c, float scale, int t, const int* act, int* units,
-                                                                        int* u, float* r, float* term, float* padded, int* length,
-                                                                        int* won, int* alive_next, float* obs, float* state, long SL,
-                                                                        float* avail, int E, int T) {
-  __shared__ int s_un[BT_WPB][BT_UNITS * BT_F];      // the pre-step state, then the post-step state
-  __shared__ int s_dmg[BT_WPB][BT_UNITS];
-  __shared__ int s_act[BT_WPB][BT_MAX_SIDE];
-  __shared__ int s_pts[BT_WPB];
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const long e = (long)blockIdx.x * BT_WPB + w;
-  const bool valid = e < E;
-  const bool live = valid && t < length[e];          // an episode that ended at step t' has length t' + 1 <= t
+// The shared memory of a step: the unit state of the workgroup's environments (pre-step, then post-step), the damage and points
+// accumulators and the step's recorded actions
+struct BattleStepLds {
+  int un[BT_WPB][BT_UNITS * BT_F];
+  int dmg[BT_WPB][BT_UNITS];
+  int act[BT_WPB][BT_MAX_SIDE];
+  int pts[BT_WPB];
+};
+
+// Lock-step t of environment e by its wave (every thread of the workgroup calls this: it holds workgroup barriers).  a: the action of
+// ally `lane` as given (lanes < N of a live environment; anything elsewhere); live: t < length[e] as read before the step
+__device__ __forceinline__ void battle_step_body(const BattleCfg& c, BattleStepLds& s, float scale, int t, int a, bool valid, bool live,
+                                                 long e, int w, int lane, int* units, int* u, float* r, float* term, float* padded,
+                                                 int* length, int* won, int* alive_next, float* obs, float* state, long SL,
+                                                 float* avail, int T) {
   const int N = c.N, NU = c.N + c.M;
   const bool unit = valid && lane < NU;
   int me[BT_F] = {0, 0, 0, 0, 0};
   if (unit) {
-    for (int f = 0; f < BT_F; ++f) s_un[w][lane * BT_F + f] = me[f] = units[(e * NU + lane) * BT_F + f];
-    s_dmg[w][lane] = 0;
+    for (int f = 0; f < BT_F; ++f) s.un[w][lane * BT_F + f] = me[f] = units[(e * NU + lane) * BT_F + f];
+    s.dmg[w][lane] = 0;
   }
   if (valid && lane < N) {
-    const int a = live ? act[e * N + lane] : -1;     // the record keeps the action as given
-    s_act[w][lane] = a;
+    a = live ? a : -1;                                // the record keeps the action as given
+    s.act[w][lane] = a;
     u[(e * T + t) * N + lane] = a;
   }
-  if (lane == 0) s_pts[w] = 0;
+  if (lane == 0) s.pts[w] = 0;
   __syncthreads();
   // 1. every unit's action, from the pre-step state
   int dx = 0, dy = 0, target = -1;
   const int type = unit ? bt_type(c, lane) : 0;
   if (live && unit) {
-    if (lane < N) bt_ally_decide(c, s_un[w], lane, s_act[w][lane], dx, dy, target);
-    else bt_enemy_decide(c, s_un[w], lane - N, dx, dy, target);
-    if (target >= 0) atomicAdd(&s_dmg[w][target], bt_damage(type));
+    if (lane < N) bt_ally_decide(c, s.un[w], lane, s.act[w][lane], dx, dy, target);
+    else bt_enemy_decide(c, s.un[w], lane - N, dx, dy, target);
+    if (target >= 0) atomicAdd(&s.dmg[w][target], bt_damage(type));
   }
   __syncthreads();
   // 2. - 4. movers move, damage lands (a unit killed this step has dealt its own), cooldowns
   if (live && unit) {
     const int hp0 = me[BT_HP];
     me[BT_X] += dx; me[BT_Y] += dy;
-    const int removed = bt_hit(s_dmg[w][lane], me[BT_HP], me[BT_SH]);
+    const int removed = bt_hit(s.dmg[w][lane], me[BT_HP], me[BT_SH]);
     me[BT_CD] = target >= 0 ? bt_cooldown(type) : (me[BT_CD] > 0 ? me[BT_CD] - 1 : 0);
-    if (lane >= N && removed > 0) atomicAdd(&s_pts[w], removed + (hp0 > 0 && me[BT_HP] <= 0 ? BT_KILL : 0));
+    if (lane >= N && removed > 0) atomicAdd(&s.pts[w], removed + (hp0 > 0 && me[BT_HP] <= 0 ? BT_KILL : 0));
     for (int f = 0; f < BT_F; ++f) {
-      s_un[w][lane * BT_F + f] = me[f];
+      s.un[w][lane * BT_F + f] = me[f];
       units[(e * NU + lane) * BT_F + f] = me[f];
     }
   }
@@ -109,27 +113,78 @@ __global__ __launch_bounds__(BT_WPB * MARL_WAVE) void battle_step_kernel(BattleC
   if (valid && lane == 0) {
     const bool win = live && !enemies && allies;
     const bool over = !live || !enemies || !allies || t + 1 == T;
-    r[e * T + t] = live ? (float)(s_pts[w] + (win ? BT_WIN : 0)) * scale : 0.f;
+    r[e * T + t] = live ? (float)(s.pts[w] + (win ? BT_WIN : 0)) * scale : 0.f;
     term[e * T + t] = over ? 1.f : 0.f;
     padded[e * T + t] = live ? 0.f : 1.f;
     if (live && over) { length[e] = t + 1; won[e] = win ? 1 : 0; }
     if (alive_next) alive_next[e] = over ? 0 : 1;
   }
   // slot t + 1: the final observation at the terminating step, zeros after
-  if (valid) write_slot(c, s_un[w], s_act[w], live, obs, state, SL, avail, e, T, t + 1, lane);
+  if (valid) write_slot(c, s.un[w], s.act[w], live, obs, state, SL, avail, e, T, t + 1, lane);
 }
 
-// hipErrorInvalidValue unless the shape is one the kernels cover; cfg: the feature widths
-int battle_cfg(int N, int M, int A, int shield, int type_bits, unsigned types, long state_ld, int T, BattleCfg& cfg) {
-  if (!bt_supported(N, M, A) || (shield != 0 && shield != 1) || type_bits < 0 || type_bits > BT_TYPES - 1 || T < 1)
-    return (int)hipErrorInvalidValue;
-  cfg = bt_cfg(N, M, A, shield, type_bits, types);
-  for (int i = 0; i < N; ++i) {
-    const int type = bt_type(cfg, i);
-    if (type >= BT_TYPES || type > type_bits) return (int)hipErrorInvalidValue;     // a type the one-hot has no bit for
-  }
-  return state_ld < cfg.S ? (int)hipErrorInvalidValue : 0;
+__global__ __launch_bounds__(BT_WPB * MARL_WAVE) void battle_step_kernel(BattleCfg c, float scale, int t, const int* act, int* units,
+                                                                        int* u, float* r, float* term, float* padded, int* length,
+                                                                        int* won, int* alive_next, float* obs, float* state, long SL,
+                                                                        float* avail, int E, int T) {
+  __shared__ BattleStepLds s;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long e = (long)blockIdx.x * BT_WPB + w;
+  const bool valid = e < E;
+  const bool live = valid && t < length[e];          // an episode that ended at step t' has length t' + 1 <= t
+  const int a = live && lane < c.N ? act[e * c.N + lane] : -1;
+  battle_step_body(c, s, scale, t, a, valid, live, e, w, lane, units, u, r, term, padded, length, won, alive_next, obs, state, SL,
+                   avail, T);
 }
+
+// The action choice and the step in one launch: ally lane n of a live environment chooses from its row of q (E,1,N,A) and slot t's
+// availability in the record - select_kernel's epsilon-greedy rule and draws (rollout.hip), or with SAMPLE policy_sample's draw from
+// the stochastic policy of the row (policy_rows.h) - keyed by (rseed, env0 + e, env_tg(episode, T, t), n); then battle_step_body
+template <bool SAMPLE>
+__global__ __launch_bounds__(BT_WPB * MARL_WAVE) void battle_fused_step_kernel(BattleCfg c, float scale, unsigned rseed, int env0,
+                                                                              int episode, int t, float eps, const float* q,
+                                                                              int* units, int* u, float* r, float* term, float* padded,
+                                                                              int* length, int* won, float* obs, float* state, long SL,
+                                                                              float* avail, int E, int T) {
+  __shared__ BattleStepLds s;
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long e = (long)blockIdx.x * BT_WPB + w;
+  const bool valid = e < E;
+  const bool live = valid && t < length[e];
+  const int N = c.N, A = c.A;
+  int arg = -1;
+  if (live && lane < N) {
+    const unsigned env = (unsigned)(env0 + (int)e), tg = env_tg(episode, T, t);
+    const float* qa = q + (e * N + lane) * A;
+    const float* av = avail + ((e * (T + 1) + t) * N + lane) * A;
+    if constexpr (SAMPLE) {
+      const RowPolicy p = row_policy(qa, av, A, eps);
+      arg = row_sample(p, qa, av, A, u01(hkey(rseed, ST_SAMPLE, env, tg, (unsigned)lane)));
+    } else {
+      float best = 0.f; int navail = 0;
+      for (int k = 0; k < A; ++k) {
+        if (av[k] == 0.f) continue;
+        ++navail;
+        if (arg < 0 || qa[k] > best) { best = qa[k]; arg = k; }
+      }
+      if (arg < 0) arg = 0;
+      const bool explore = u01(hkey(rseed, ST_EXPLORE, env, tg, (unsigned)lane)) < eps;
+      if (explore && navail > 0) {
+        int kk;
+        env_pick(u01(hkey(rseed, ST_PICK, env, tg, (unsigned)lane)), navail, kk);
+        int cnt = 0;
+        for (int k = 0; k < A; ++k) {
+          if (av[k] == 0.f) continue;
+          if (cnt == kk) { arg = k; break; }
+          ++cnt;
+        }
+      }
+    }
+  }
+  battle_step_body(c, s, scale, t, arg, valid, live, e, w, lane, units, u, r, term, padded, length, won, nullptr, obs, state, SL,
+                   avail, T);
+}
+
 }  // namespace
 
 extern "C" int marl_battle_supported(int n_allies, int n_enemies, int A) { return bt_supported(n_allies, n_enemies, A) ? 1 : 0; }
@@ -159,4 +214,37 @@ extern "C" int marl_battle_step(unsigned types, int shield, int type_bits, float
                      t, act, units, u, r, term, padded, length, won, alive_next, obs, state, state_ld, avail, E, T);
   MARL_CHECK_LAUNCH();
   return 0;
+}
+
+template <bool SAMPLE>
+static int battle_fused_step(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0, int episode, int t,
+                             float eps, const float* q, int* units, int* u, float* r, float* term, float* padded, int* length,
+                             int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N, int M, int A,
+                             void* stream) {
+  BattleCfg cfg;
+  const int bad = battle_cfg(N, M, A, shield, type_bits, types, state_ld, T, cfg);
+  if (bad) return bad;
+  if (t < 0 || t >= T) return (int)hipErrorInvalidValue;
+  if (E <= 0) return 0;
+  hipLaunchKernelGGL(battle_fused_step_kernel<SAMPLE>, dim3((E + BT_WPB - 1) / BT_WPB), dim3(BT_WPB * MARL_WAVE), 0,
+                     (hipStream_t)stream, cfg, scale, rseed, env0, episode, t, eps, q, units, u, r, term, padded, length, won, obs,
+                     state, state_ld, avail, E, T);
+  MARL_CHECK_LAUNCH();
+  return 0;
+}
+
+extern "C" int marl_battle_fused_step(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0, int episode,
+                                      int t, float eps, const float* q, int* units, int* u, float* r, float* term, float* padded,
+                                      int* length, int* won, float* obs, float* state, long state_ld, float* avail, int E, int T,
+                                      int N, int M, int A, void* stream) {
+  return battle_fused_step<false>(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, u, r, term, padded, length,
+                                  won, obs, state, state_ld, avail, E, T, N, M, A, stream);
+}
+
+extern "C" int marl_battle_fused_step_sample(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0,
+                                             int episode, int t, float eps, const float* q, int* units, int* u, float* r, float* term,
+                                             float* padded, int* length, int* won, float* obs, float* state, long state_ld,
+                                             float* avail, int E, int T, int N, int M, int A, void* stream) {
+  return battle_fused_step<true>(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, u, r, term, padded, length,
+                                 won, obs, state, state_ld, avail, E, T, N, M, A, stream);
 }

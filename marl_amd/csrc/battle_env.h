@@ -1,5 +1,5 @@
 // The "battle" environment: a deterministic micro-combat simulator in SMAC's observation / state / action layout.
-// Its rules as __host__ __device__ functions, for battle.hip today and a fused-step or whole-rollout kernel later; numpy restatement:
+// Its rules as __host__ __device__ functions, for the per-step kernels (battle.hip) and the whole-rollout kernel (battle_rollout.hip); numpy restatement:
 // tests/battle_oracle.py - integer fields equal, float fields bit for bit (every feature is one correctly rounded fp32 operation on
 // integers: sqrtf of an integer, then one division).  The start positions are the only random part: hkey() draws on streams from 16 up.
 //
@@ -170,4 +170,17 @@ __host__ __device__ inline float bt_state(const BattleCfg& c, const int* un, con
   k -= na + ne;
   const int n = k / c.A;
   return act && act[n] == k - n * c.A ? 1.f : 0.f;
+}
+
+// ---- the host side of every launcher (battle.hip, battle_rollout.hip)
+// hipErrorInvalidValue unless the shape is one the kernels cover; cfg: the feature widths
+inline int battle_cfg(int N, int M, int A, int shield, int type_bits, unsigned types, long state_ld, int T, BattleCfg& cfg) {
+  if (!bt_supported(N, M, A) || (shield != 0 && shield != 1) || type_bits < 0 || type_bits > BT_TYPES - 1 || T < 1)
+    return (int)hipErrorInvalidValue;
+  cfg = bt_cfg(N, M, A, shield, type_bits, types);
+  for (int i = 0; i < N; ++i) {
+    const int type = bt_type(cfg, i);
+    if (type >= BT_TYPES || type > type_bits) return (int)hipErrorInvalidValue;     // a type the one-hot has no bit for
+  }
+  return state_ld < cfg.S ? (int)hipErrorInvalidValue : 0;
 }

@@ -7,6 +7,8 @@ feature is exact in fp32 - nothing here claims to be StarCraft.  Rules: csrc/bat
 
 The protocol is SyntheticSMACEnv's (RolloutWorker._generate_batched), without fused_step and whole_rollout: per lock-step the
 controller's launches, the action choice and ONE environment launch (``step`` writes slot t + 1, so ``observe`` launches nothing).
+``FusedBattleEnv`` (``--battle_fused``) adds the two: the choice inside the step's launch, and the whole rollout - reset, agent
+steps, choices and battle steps - in one persistent launch (csrc/battle_rollout.hip); the record is the same, bit for bit.
 """
 from __future__ import annotations
 
@@ -97,3 +99,43 @@ class BattleEnv:
 
     def save_replay(self):
         pass
+
+
+class FusedBattleEnv(BattleEnv):
+    """BattleEnv with the fused step and the whole-rollout kernel: RolloutWorker dispatches on the two attributes.
+    ``episode_limit``: a time limit below the map's (the kernels take T as a parameter)."""
+
+    def __init__(self, n_envs, map="3m", seed=1, env0=0, episode_limit=None):
+        super().__init__(n_envs, map, seed=seed, env0=env0)
+        if episode_limit is not None:
+            if not 1 <= int(episode_limit) <= self.episode_limit:
+                raise ValueError("battle: episode_limit %r is outside 1 .. %d of map %s" % (episode_limit, self.episode_limit, map))
+            self.episode_limit = int(episode_limit)
+
+    def fused_step(self, t, q, eps, rseed, rec, sample=False):
+        """the action choice + step in one launch (same record as select_actions / policy_sample, then step)"""
+        ops.battle_fused_step(self.type_mask, self.shield, self.type_bits, self.scale, rseed, self.env0, self.episode, t, eps, q,
+                              self.units, rec, self.n_envs, self.episode_limit, self.n_agents, self.n_enemies, self.n_actions,
+                              sample=sample)
+
+    def supports_whole_rollout(self):
+        return ops.battle_rollout_supported(self.n_agents, self.obs_shape, self.n_actions)
+
+    def whole_rollout(self, weights, eps_dev, rseed, rec, last_action, reuse_network, h_out=None, eps_sched=None, x6=False,
+                      sample=False):
+        """Reset and all episode_limit lock-steps in ONE persistent launch; same record and unit state as begin_episode and
+        fused_step called step by step.  The kernel evaluates the epsilon schedule itself (eps_sched; no device vector) and is the
+        fp32 one whatever x6 says.  sample: as fused_step(..., sample=True)."""
+        if eps_dev is not None or eps_sched is None:
+            raise ValueError("battle: the whole-rollout kernel takes the epsilon schedule (eps_sched), not a device vector")
+        self.episode += 1
+        # per-episode statistics written by the kernel, in a small rotation (SyntheticSMACEnv.whole_rollout)
+        ring = self.__dict__.setdefault("_stats_ring", [])
+        if len(ring) < 4:
+            ring.append(torch.empty(3, self.n_envs, dtype=torch.float32, device=rec.r.device))
+        self._stats_i = (getattr(self, "_stats_i", -1) + 1) % 4
+        stats = ring[min(self._stats_i, len(ring) - 1)]
+        ops.battle_rollout(weights, self.seed, rseed, self.env0, self.episode, self.type_mask, self.shield, self.type_bits,
+                           self.scale, self.units, rec, h_out, self.n_envs, self.episode_limit, self.n_agents, self.n_enemies,
+                           self.n_actions, last_action, reuse_network, stats, eps_sched, sample=sample)
+        rec.kernel_stats = stats

@@ -31,7 +31,7 @@ from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get
     get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args, get_lica_args
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
-from .env.battle import BattleEnv, battle_shapes
+from .env.battle import BattleEnv, FusedBattleEnv, battle_shapes
 from .runner import Runner
 from .utils.logging import Logger
 
@@ -156,7 +156,7 @@ def build(argv=None):
         n, o, s, a, t = MAPS[args.map]
         env = SyntheticSMACEnv(args.n_envs, n, o, s, a, t, seed=args.seed)
     elif args.env == 'battle':
-        env = BattleEnv(args.n_envs, args.map, seed=args.seed)
+        env = (FusedBattleEnv if args.battle_fused else BattleEnv)(args.n_envs, args.map, seed=args.seed)
     elif args.env == 'matrix':
         env = BatchedMatrixGame([[8, -12, -12], [-12, 0, 0], [-12, 0, 0]], args.n_envs, seed=args.seed)
         args.map = 'MatrixGame'

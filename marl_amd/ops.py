@@ -917,6 +917,45 @@ def battle_step(types, shield, type_bits, scale, t, act, units, rec, alive_next,
           "marl_battle_step")
 
 
+def battle_fused_step(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, rec, E, T, N, M, A, sample=False):
+    """the action choice (select_actions' rule and draws; sample: policy_sample's) and battle_step in one launch"""
+    lib = _lib.load()
+    fn, name = (lib.marl_battle_fused_step_sample, "marl_battle_fused_step_sample") if sample else \
+        (lib.marl_battle_fused_step, "marl_battle_fused_step")
+    check(fn(types, int(shield), type_bits, float(scale), int(rseed) & 0xFFFFFFFF, env0, episode, t, float(eps), _p(_f32(q)),
+             _p(_i32(units)), _p(_i32(rec.u)), _p(_f32(rec.r)), _p(_f32(rec.term)), _p(_f32(rec.padded)), _p(_i32(rec.length)),
+             _p(_i32(rec.won)), _p(_f32(rec.obs)), _p(_f32(rec.state)), rec.state.stride(-2), _p(_f32(rec.avail)), E, T, N, M, A,
+             _stream()), name)
+
+
+def battle_rollout_supported(N, O, A):
+    return bool(_lib.load().marl_battle_rollout_supported(int(N), int(O), int(A)))
+
+
+def battle_rollout_plan(E, N, O, A, last_action=True, reuse_network=True):
+    """(workgroups, environments per workgroup, row tiles per workgroup, dynamic LDS bytes) of a whole battle rollout"""
+    plan = (C.c_int * 4)()
+    check(_lib.load().marl_battle_rollout_plan(int(E), int(N), int(O), int(A), 1 if last_action else 0, 1 if reuse_network else 0,
+                                               plan), "marl_battle_rollout_plan")
+    return tuple(plan)
+
+
+def battle_rollout(w, seed, rseed, env0, episode, types, shield, type_bits, scale, units, rec, h_out, E, T, N, M, A, last_action,
+                   reuse_network, stats, eps_sched, sample=False):
+    """reset and all T lock-steps of the battle environment in ONE persistent launch (csrc/battle_rollout.hip): every field of rec,
+    the final unit state, stats (3, E) = reward sum | won | length (or None) and h_out (or None).  eps_sched = (eps0, anneal,
+    eps_min), evaluated inside the kernel in fp64; sample: the actions are drawn from the stochastic policy of the step's logits"""
+    e0, ea, em = eps_sched
+    lib = _lib.load()
+    fn, name = (lib.marl_battle_rollout_sample, "marl_battle_rollout_sample") if sample else \
+        (lib.marl_battle_rollout, "marl_battle_rollout")
+    check(fn(C.byref(w), int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, types, int(shield), type_bits, float(scale),
+             _p(_i32(units)), _p(_f32(rec.obs)), _p(_f32(rec.state)), rec.state.stride(-2), _p(_f32(rec.avail)), _p(_i32(rec.u)),
+             _p(_f32(rec.r)), _p(_f32(rec.term)), _p(_f32(rec.padded)), _p(_i32(rec.length)), _p(_i32(rec.won)), _p(h_out),
+             _p(_f32(stats)) if stats is not None else None, float(e0), float(ea), float(em), E, T, N, M, A,
+             1 if last_action else 0, 1 if reuse_network else 0, _stream()), name)
+
+
 def synth_rollout_supported(N, O, A):
     return bool(_lib.load().marl_synth_rollout_supported(N, O, A))
 

@@ -17,6 +17,7 @@ SEGS = {
     "wgrad": ["barrier", "work"],
     "bwd_pipe": ["product", "gates/dxp", "accum", "barrier"],
     "bwd": ["phaseB", "bar1", "phaseC", "dqwrite", "bar2"],
+    "battle": ["fc1", "bar1", "gru", "bar2", "fc2", "bar3", "choice", "bar4", "decide", "bar5", "apply", "bar6", "end+slot", "bar7"],
     "mlp3": ["xfin+stx", "fwd1", "fwd2", "dh2", "dh1+st", "bar1", "B1:dW1", "bar2", "stash2", "bar3", "B2:dW2,3", "bar4"],
 }
 
@@ -30,6 +31,8 @@ def main():
     fn = getattr(lib, "marl_debug_stamps_" + which.replace("_pipe", ""))
     fn.argtypes, fn.restype = [ctypes.c_void_p], ctypes.c_int
     assert fn(buf.data_ptr()) == 0
+    if which == "battle":          # python tools/stamps.py battle [envs] [map]: the battle whole-rollout kernel (csrc/battle_rollout.hip)
+        return battle(buf, E, sys.argv[3] if len(sys.argv) > 3 else "3s5z")
     from marl_amd.controller.share_params import SharedMAC
     from marl_amd.algorithm.q_learner import QLearner
     from marl_amd.rollout import RolloutWorker
@@ -51,6 +54,19 @@ def main():
         show(v[:, :8], names, "qmix forward", E, args.episode_limit)
         v = v[:, 8:]
     show(v, names, which, E, args.episode_limit)
+
+
+def battle(buf, E, name):
+    import tempfile
+    from marl_amd.controller.share_params import SharedMAC
+    from marl_amd.main import build
+    from marl_amd.rollout import RolloutWorker
+    tmp = os.path.join(tempfile.gettempdir(), "marl_battle_tool")      # build() only names the directories
+    args, env = build(["--env", "battle", "--map", name, "--alg", "qmix", "--n_envs", str(E), "--battle_fused", "True",
+                       "--result_dir", tmp + "/result", "--model_dir", tmp + "/model"])
+    RolloutWorker(env, SharedMAC(args), args).generate_episodes(E)
+    torch.cuda.synchronize()
+    show(buf.cpu().view(16, 16).numpy(), SEGS["battle"], "battle " + name, E, args.episode_limit)
 
 
 def show(v, names, which, E, T):

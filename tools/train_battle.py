@@ -6,14 +6,17 @@ greedy evaluation win rate every so many updates, beside two fixed policies play
     attack  attack the lowest-index attackable enemy, else move east (stop at the edge)
 
     python tools/train_battle.py [--algs qmix iql] [--updates 400] [--every 50] [--n_envs 64] [--anneal_steps 6000] [--seed 123]
+                                  [--battle_fused]
 
 One update = one lock-step rollout of n_envs episodes into the replay ring + one learner update on a sampled batch (the launcher's
-loop, marl_amd/runner.py).  One JSON line per evaluation."""
+loop, marl_amd/runner.py).  --battle_fused: the rollouts take the whole-rollout kernel, one launch each, straight into the replay
+ring.  One JSON line per evaluation; the last line of an algorithm carries the wall time per update."""
 import argparse
 import json
 import os
 import sys
 import tempfile
+import time
 
 import torch
 
@@ -57,6 +60,7 @@ def main():
     p.add_argument("--n_envs", type=int, default=64)
     p.add_argument("--anneal_steps", type=int, default=6000, help="lock-steps over which epsilon falls from 1 to 0.05")
     p.add_argument("--seed", type=int, default=123)
+    p.add_argument("--battle_fused", action="store_true", help="FusedBattleEnv: one launch per rollout")
     a = p.parse_args()
     for label, policy in (("stop", stop_policy), ("attack", attack_policy)):
         win, reward = play_fixed(policy, a.map, a.n_envs, a.seed)
@@ -64,12 +68,14 @@ def main():
     for alg in a.algs:
         with tempfile.TemporaryDirectory() as tmp:
             args, env = build(["--env", "battle", "--map", a.map, "--alg", alg, "--n_envs", str(a.n_envs), "--seed", str(a.seed),
-                               "--evaluate_epoch", "1", "--result_dir", tmp + "/result", "--model_dir", tmp + "/model"])
+                               "--evaluate_epoch", "1", "--result_dir", tmp + "/result", "--model_dir", tmp + "/model",
+                               "--battle_fused", str(a.battle_fused)])
             args.save_cycle = 10 ** 9
             args.anneal_epsilon = (args.epsilon - args.min_epsilon) / a.anneal_steps
             torch.manual_seed(a.seed)
             r = make_runner(args, env, Logger())
             w, wins, loss = r.rolloutWorker, [], float("nan")
+            spent = 0.0
             for k in range(a.updates + 1):
                 if k % a.every == 0:
                     win, reward = r.evaluate()
@@ -80,12 +86,18 @@ def main():
                     wins = []
                 if k == a.updates:
                     break
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
                 episodes, _, tags, steps = w.generate_episodes(a.n_envs)
                 wins += tags
                 r.time_steps += steps
                 r.buffer.store_episode(episodes)
                 loss = float(r.learner.train(r.buffer.sample(min(r.buffer.current_size, args.batch_size)), r.train_steps))
                 r.train_steps += 1
+                torch.cuda.synchronize()
+                spent += time.perf_counter() - t0
+            print(json.dumps({"alg": alg, "map": a.map, "battle_fused": a.battle_fused, "updates": a.updates,
+                              "ms_per_update": round(1e3 * spent / max(a.updates, 1), 3)}), flush=True)
 
 
 if __name__ == "__main__":
