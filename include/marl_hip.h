@@ -819,31 +819,42 @@ int marl_adam_step(float* p, const float* g, float* m, float* v, long n, float l
 int marl_select_actions(const float* q, const float* avail, long avail_es, const int* alive, float eps,
                         unsigned rseed, int env0, const int* tg, int tg0, int* act_out, long act_es,
                         int E, int N, int A, void* stream);
-/* Synthetic SMAC-shaped environment (stands in for StarCraft II, main.py:16-20).
- * Episode storage is (T+1)-slot: obs (E,T+1,N,O), state (E,T+1,state_ld >= S), avail (E,T+1,N,A).  state_ld is the
- * row stride of the state storage in floats: a multiple of 4 keeps every state row 16-byte aligned for any S (MMM2:
- * S = 322 -> 324), which the GEMM kernels downstream need for their vector loads; pad columns are written as zeros
- * or left untouched (allocate them zeroed). */
+/* The episode record every environment and rollout entry below takes: (T+1)-slot storage for what is observed, T slots for what a
+ * step produces.  state_ld is the row stride of the state storage in floats: a multiple of 4 keeps every state row 16-byte aligned
+ * for any S (MMM2: S = 322 -> 324), which the GEMM kernels downstream need for their vector loads; pad columns are written as zeros
+ * or left untouched (allocate them zeroed).  The rules every entry that takes one holds to:
+ *   - an entry reads only the fields its comment names (and the sizes); the others may be NULL;
+ *   - rec == NULL is hipErrorInvalidValue; otherwise E <= 0 (for the whole rollouts also T <= 0) returns 0 and launches nothing,
+ *     whatever the pointers are (the battle entries refuse a shape that is not the map's first);
+ *   - every other refusal is hipErrorInvalidValue, made before anything is dereferenced or written (the shape checks before w). */
+typedef struct {
+  float *obs, *state, *avail;   /* (E,T+1,N,O)  (E,T+1,state_ld >= S)  (E,T+1,N,A) */
+  long state_ld;
+  int* u;                       /* (E,T,N) */
+  float *r, *term, *padded;     /* (E,T) */
+  int *length, *won;            /* (E) */
+  int E, T, N, O, S, A;
+} marl_record_t;
+
+/* Synthetic SMAC-shaped environment (stands in for StarCraft II, main.py:16-20).  lengths: len / won (E) of the
+ * episode.  observe: reads length, writes slot t of obs / state / avail. */
 int marl_synth_lengths(unsigned seed, int env0, int episode, int* len, int* won, int E, int T, void* stream);
-int marl_synth_observe(unsigned seed, int env0, int episode, int t, const int* len, float* obs,
-                       float* state, long state_ld, float* avail, int E, int T, int N, int O, int S, int A, void* stream);
-/* reward / terminated / padded for step t given act (E,N) (rollout.py:86-96,122-133 for padding);
- * u (E,T,N) int32 gets the action or -1 on padding. alive_out[e] = (t+1 < len[e]) */
-int marl_synth_step(unsigned seed, int env0, int episode, int t, const int* len, const int* act,
-                    int* u, float* r, float* term, float* padded, int* alive_next, int E, int T, int N, int A,
+int marl_synth_observe(unsigned seed, int env0, int episode, int t, const marl_record_t* rec, void* stream);
+/* reward / terminated / padded for step t given act (E,N) (rollout.py:86-96,122-133 for padding): reads length, writes r / term /
+ * padded and u (the action, or -1 on padding) of step t; never touches obs / state / avail.  alive_next[e] = (t+1 < length[e]) */
+int marl_synth_step(unsigned seed, int env0, int episode, int t, const int* act, const marl_record_t* rec, int* alive_next,
                     void* stream);
 
 /* select + step + observe(t+1) of the synthetic env in ONE launch per lock-step (same arithmetic as the
- * three calls above; q is the (E,N,A) output of the T=1 agent unroll). */
-int marl_synth_fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const int* len,
-                          const float* q, float* obs, float* state, long state_ld, float* avail, int* u, float* r,
-                          float* term, float* padded, int E, int T, int N, int O, int S, int A, void* stream);
+ * three calls above; q is the (E,N,A) output of the T=1 agent unroll).  Reads length and slot t of avail; writes u / r / term /
+ * padded of step t and slot t + 1 of obs / state / avail; never touches won. */
+int marl_synth_fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const float* q,
+                          const marl_record_t* rec, void* stream);
 /* marl_synth_fused_step with the choice drawn from the stochastic policy of the agent's row of q (logits) and its availability at
  * slot t: marl_policy_sample's definition with eps as the mixing epsilon and x = u01(hash(rseed, SAMPLE, env0 + e, tg, n)).  Same
  * arguments; everything after the choice is marl_synth_fused_step's. */
-int marl_synth_fused_step_sample(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const int* len,
-                                 const float* q, float* obs, float* state, long state_ld, float* avail, int* u, float* r,
-                                 float* term, float* padded, int E, int T, int N, int O, int S, int A, void* stream);
+int marl_synth_fused_step_sample(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const float* q,
+                                 const marl_record_t* rec, void* stream);
 
 /* The WHOLE rollout of the synthetic env in one persistent launch (rollout_fused.hip): agent step,
  * epsilon-greedy choice, env step and next observation for all T lock-steps; weights and hidden state
@@ -852,22 +863,18 @@ int marl_synth_fused_step_sample(unsigned seed, unsigned rseed, int env0, int ep
  * launch-per-step path.  stats (optional, [3][E] floats): per episode  sum_t r | won | length - what
  * RolloutWorker.generate_episodes returns besides the batch (rollout.py:135-140), without extra launches.  Needs whole environments per workgroup: marl_synth_rollout_supported(). */
 int marl_synth_rollout_supported(int N, int O, int A);
-int marl_synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                       int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
-                       float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                       float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int O, int S,
-                       int A, int last_action, int reuse_network, void* stream);
+int marl_synth_rollout(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                       int episode, int fixed_len, const float* eps, float* h_out, float* stats, double eps0,
+                       double eps_anneal, double eps_min, int last_action, int reuse_network, void* stream);
 /* marl_synth_rollout with every action drawn from the stochastic policy of the step's logits instead of the epsilon-greedy choice:
  * marl_synth_rollout's argument list and meaning, the same marl_synth_rollout_supported() shapes and launch plan.  eps(t) - the
  * eps vector or the fp64 schedule - is the policy's mixing epsilon of lock-step t.  With x = u01(hash(rseed, SAMPLE, env, tg, n))
  * (one draw per environment, agent and global step tg) the action is marl_policy_sample's: with row_policy's scalars of the row, the
  * first k in index order with a_k = 1 whose running fp32 sum of (cw e_k + ew) / D over the available actions up to k exceeds x; the
  * last available action when rounding leaves none.  Rows past the episode's end get -1. */
-int marl_synth_rollout_sample(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                              int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
-                              float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                              float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int O, int S,
-                              int A, int last_action, int reuse_network, void* stream);
+int marl_synth_rollout_sample(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                              int episode, int fixed_len, const float* eps, float* h_out, float* stats, double eps0,
+                              double eps_anneal, double eps_min, int last_action, int reuse_network, void* stream);
 
 /* The same whole rollout with the agent step (network/q_network.py:16-21) as bf16x6 split products (rollout_x6.hip; args.gemm_mode =
  * "bf16x6"): same arguments, same environment, same epsilon-greedy choice, same record - the integer fields agree with
@@ -884,11 +891,9 @@ int marl_synth_rollout_x6_supported(int N, int O, int A);
  * plan[0] = decomposition (1 / 2), plan[1] = workgroups, plan[2] = row tiles per workgroup, plan[3] = environments per workgroup,
  * plan[4] = fc1 chunks of 32 input columns.  What bench.py's roofline model counts the executed products by. */
 int marl_synth_rollout_x6_plan(int E, int N, int O, int A, int last_action, int reuse_network, int* plan);
-int marl_synth_rollout_x6(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                          int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
-                          float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                          float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int O, int S,
-                          int A, int last_action, int reuse_network, void* stream);
+int marl_synth_rollout_x6(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                          int episode, int fixed_len, const float* eps, float* h_out, float* stats, double eps0,
+                          double eps_anneal, double eps_min, int last_action, int reuse_network, void* stream);
 
 /* ---- RTW reflection head (rtw_head.hip) -------------------------------------------------------
  * The parts of RTWAgent (network/RTW.py:16-57) beyond the RNNQNet agent, torch layouts, hidden_dim = attn_dim = 64:
@@ -1154,36 +1159,30 @@ int marl_g2anet_noise(unsigned seed, int env0, unsigned tg0, float* noise, int E
  * types: two bits per unit of a side, unit 0 lowest (0 marine, 1 stalker, 2 zealot); shield (0 / 1) and type_bits (0 .. 2) say
  * which feature columns the map has, A = 6 + M; observation width O = 4 + (M + N - 1)(5 + shield + type_bits) + 1 + shield +
  * type_bits, state width S = N (4 + shield + type_bits) + M (3 + shield + type_bits) + N A.  units (E, N + M, 5) int32: x, y, hp,
- * shield, cooldown, allies first.  The record is the synthetic environment's: obs (E,T+1,N,O), state (E,T+1,state_ld >= S), avail
- * (E,T+1,N,A), u (E,T,N), r / term / padded (E,T), length / won (E).  marl_battle_supported(): 1 <= n_allies = n_enemies <= 16
- * and A = 6 + n_enemies; the two entries return hipErrorInvalidValue for anything else (and for a type without a bit, state_ld
- * < S, t outside 0 .. T - 1) and launch nothing. */
+ * shield, cooldown, allies first.  The record is marl_record_t, with O and S the widths above: every entry returns
+ * hipErrorInvalidValue for any other O or S.  marl_battle_supported(): 1 <= n_allies = n_enemies <= 16 and A = 6 + n_enemies; the
+ * entries return hipErrorInvalidValue for anything else (and for a type without a bit, state_ld < S, t outside 0 .. T - 1) and
+ * launch nothing. */
 int marl_battle_supported(int n_allies, int n_enemies, int A);
 /* start of episode `episode`: unit state (positions from the counter hash of (seed, env0 + e, episode, unit), streams 16 .. 19),
- * length = T, won = 0, and slot 0 of obs / state / avail */
-int marl_battle_reset(unsigned seed, int env0, int episode, unsigned types, int shield, int type_bits, int* units, int* length,
-                      int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N, int M, int A,
-                      void* stream);
+ * length = T, won = 0, and slot 0 of obs / state / avail; never touches u / r / term / padded */
+int marl_battle_reset(unsigned seed, int env0, int episode, unsigned types, int shield, int type_bits, int* units,
+                      const marl_record_t* rec, int M, void* stream);
 /* lock-step t in one launch: reads act (E,N); writes u / r / term / padded of step t, length = t + 1 and won where the episode
  * ends here, alive_next (E; may be NULL) = 0 from the terminating step on, the new unit state and slot t + 1 of obs / state /
  * avail (the final observation at the terminating step).  Environments whose episode is over (t >= length) get u = -1, r = 0,
  * term = 1, padded = 1 and a zero slot.  r = (float)points * scale with points = hp + shield removed from enemies + 10 per kill +
  * 200 for the win; scale = 20 / (sum of enemy hp + shield + 10 M + 200) in fp32, from the caller. */
-int marl_battle_step(unsigned types, int shield, int type_bits, float scale, int t, const int* act, int* units, int* u, float* r,
-                     float* term, float* padded, int* length, int* won, int* alive_next, float* obs, float* state, long state_ld,
-                     float* avail, int E, int T, int N, int M, int A, void* stream);
+int marl_battle_step(unsigned types, int shield, int type_bits, float scale, int t, const int* act, int* units,
+                     const marl_record_t* rec, int* alive_next, int M, void* stream);
 /* The action choice and marl_battle_step in one launch.  q (E,1,N,A): ally n of a live environment chooses from its row and slot t's
  * availability in the record with marl_select_actions' epsilon-greedy rule and draws, keyed by (rseed, env0 + e, tg = episode (T + 1)
  * + t, n); -1 wherever t >= length[e].  Then the step, as marl_battle_step does it (no alive_next).  _sample: the choice is
  * marl_policy_sample's draw from the stochastic policy of the row instead, eps its mixing epsilon. */
 int marl_battle_fused_step(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0, int episode, int t,
-                           float eps, const float* q, int* units, int* u, float* r, float* term, float* padded, int* length,
-                           int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N, int M, int A,
-                           void* stream);
+                           float eps, const float* q, int* units, const marl_record_t* rec, int M, void* stream);
 int marl_battle_fused_step_sample(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0, int episode,
-                                  int t, float eps, const float* q, int* units, int* u, float* r, float* term, float* padded,
-                                  int* length, int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N,
-                                  int M, int A, void* stream);
+                                  int t, float eps, const float* q, int* units, const marl_record_t* rec, int M, void* stream);
 /* Whole battle rollout, ONE persistent launch (csrc/battle_rollout.hip): marl_battle_reset and, for t = 0 .. T - 1, the agent step
  * (fp32 MFMA, marl_synth_rollout's sequences: q bit for bit the T = 1 unroll's), the choice and marl_battle_step, with the unit state
  * and the hidden state in LDS.  Writes every element of obs / state (S columns of a row) / avail / u / r / term / padded / length /
@@ -1196,16 +1195,14 @@ int marl_battle_fused_step_sample(unsigned types, int shield, int type_bits, flo
  * workgroup (ceil(E / 256) until the row tiles are full), plan[2] = row tiles, plan[3] = dynamic LDS bytes. */
 int marl_battle_rollout_supported(int N, int O, int A);
 int marl_battle_rollout_plan(int E, int N, int O, int A, int last_action, int reuse_network, int* plan);
-int marl_battle_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, unsigned types,
-                        int shield, int type_bits, float scale, int* units, float* obs, float* state, long state_ld, float* avail,
-                        int* u, float* r, float* term, float* padded, int* length, int* won, float* h_out, float* stats,
-                        double eps0, double eps_anneal, double eps_min, int E, int T, int N, int M, int A, int last_action,
-                        int reuse_network, void* stream);
-int marl_battle_rollout_sample(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, unsigned types,
-                               int shield, int type_bits, float scale, int* units, float* obs, float* state, long state_ld,
-                               float* avail, int* u, float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                               float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int M, int A,
-                               int last_action, int reuse_network, void* stream);
+int marl_battle_rollout(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                        int episode, unsigned types, int shield, int type_bits, float scale, int* units, float* h_out,
+                        float* stats, double eps0, double eps_anneal, double eps_min, int M, int last_action, int reuse_network,
+                        void* stream);
+int marl_battle_rollout_sample(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                               int episode, unsigned types, int shield, int type_bits, float scale, int* units, float* h_out,
+                               float* stats, double eps0, double eps_anneal, double eps_min, int M, int last_action,
+                               int reuse_network, void* stream);
 
 const char* marl_hip_version(void);
 

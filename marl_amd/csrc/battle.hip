@@ -189,62 +189,61 @@ __global__ __launch_bounds__(BT_WPB * MARL_WAVE) void battle_fused_step_kernel(B
 
 extern "C" int marl_battle_supported(int n_allies, int n_enemies, int A) { return bt_supported(n_allies, n_enemies, A) ? 1 : 0; }
 
-extern "C" int marl_battle_reset(unsigned seed, int env0, int episode, unsigned types, int shield, int type_bits, int* units,
-                                 int* length, int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N,
-                                 int M, int A, void* stream) {
-  BattleCfg cfg;
-  const int bad = battle_cfg(N, M, A, shield, type_bits, types, state_ld, T, cfg);
+// every launcher's checks, in this order: a record, battle_cfg's refusals, the widths the record states against the ones the map
+// derives, lock-step t (reset: 0) inside the episode
+static int battle_record_cfg(const marl_record_t* rec, int M, unsigned types, int shield, int type_bits, int t, BattleCfg& cfg) {
+  if (!rec) return (int)hipErrorInvalidValue;
+  const int bad = battle_cfg(rec->N, M, rec->A, shield, type_bits, types, rec->state_ld, rec->T, cfg);
   if (bad) return bad;
-  if (E <= 0) return 0;
-  hipLaunchKernelGGL(battle_reset_kernel, dim3((E + BT_WPB - 1) / BT_WPB), dim3(BT_WPB * MARL_WAVE), 0, (hipStream_t)stream, cfg, seed,
-                     env0, episode, units, length, won, obs, state, state_ld, avail, E, T);
+  return rec->O != cfg.O || rec->S != cfg.S || t < 0 || t >= rec->T ? (int)hipErrorInvalidValue : 0;
+}
+
+extern "C" int marl_battle_reset(unsigned seed, int env0, int episode, unsigned types, int shield, int type_bits, int* units,
+                                 const marl_record_t* rec, int M, void* stream) {
+  BattleCfg cfg;
+  const int bad = battle_record_cfg(rec, M, types, shield, type_bits, 0, cfg);
+  if (bad) return bad;
+  if (rec->E <= 0) return 0;
+  hipLaunchKernelGGL(battle_reset_kernel, dim3((rec->E + BT_WPB - 1) / BT_WPB), dim3(BT_WPB * MARL_WAVE), 0, (hipStream_t)stream, cfg, seed,
+                     env0, episode, units, rec->length, rec->won, rec->obs, rec->state, rec->state_ld, rec->avail, rec->E, rec->T);
   MARL_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int marl_battle_step(unsigned types, int shield, int type_bits, float scale, int t, const int* act, int* units, int* u,
-                                float* r, float* term, float* padded, int* length, int* won, int* alive_next, float* obs,
-                                float* state, long state_ld, float* avail, int E, int T, int N, int M, int A, void* stream) {
+extern "C" int marl_battle_step(unsigned types, int shield, int type_bits, float scale, int t, const int* act, int* units,
+                                const marl_record_t* rec, int* alive_next, int M, void* stream) {
   BattleCfg cfg;
-  const int bad = battle_cfg(N, M, A, shield, type_bits, types, state_ld, T, cfg);
+  const int bad = battle_record_cfg(rec, M, types, shield, type_bits, t, cfg);
   if (bad) return bad;
-  if (t < 0 || t >= T) return (int)hipErrorInvalidValue;
-  if (E <= 0) return 0;
-  hipLaunchKernelGGL(battle_step_kernel, dim3((E + BT_WPB - 1) / BT_WPB), dim3(BT_WPB * MARL_WAVE), 0, (hipStream_t)stream, cfg, scale,
-                     t, act, units, u, r, term, padded, length, won, alive_next, obs, state, state_ld, avail, E, T);
+  if (rec->E <= 0) return 0;
+  hipLaunchKernelGGL(battle_step_kernel, dim3((rec->E + BT_WPB - 1) / BT_WPB), dim3(BT_WPB * MARL_WAVE), 0, (hipStream_t)stream, cfg, scale,
+                     t, act, units, rec->u, rec->r, rec->term, rec->padded, rec->length, rec->won, alive_next, rec->obs, rec->state,
+                     rec->state_ld, rec->avail, rec->E, rec->T);
   MARL_CHECK_LAUNCH();
   return 0;
 }
 
 template <bool SAMPLE>
 static int battle_fused_step(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0, int episode, int t,
-                             float eps, const float* q, int* units, int* u, float* r, float* term, float* padded, int* length,
-                             int* won, float* obs, float* state, long state_ld, float* avail, int E, int T, int N, int M, int A,
-                             void* stream) {
+                             float eps, const float* q, int* units, const marl_record_t* rec, int M, void* stream) {
   BattleCfg cfg;
-  const int bad = battle_cfg(N, M, A, shield, type_bits, types, state_ld, T, cfg);
+  const int bad = battle_record_cfg(rec, M, types, shield, type_bits, t, cfg);
   if (bad) return bad;
-  if (t < 0 || t >= T) return (int)hipErrorInvalidValue;
-  if (E <= 0) return 0;
-  hipLaunchKernelGGL(battle_fused_step_kernel<SAMPLE>, dim3((E + BT_WPB - 1) / BT_WPB), dim3(BT_WPB * MARL_WAVE), 0,
-                     (hipStream_t)stream, cfg, scale, rseed, env0, episode, t, eps, q, units, u, r, term, padded, length, won, obs,
-                     state, state_ld, avail, E, T);
+  if (rec->E <= 0) return 0;
+  hipLaunchKernelGGL(battle_fused_step_kernel<SAMPLE>, dim3((rec->E + BT_WPB - 1) / BT_WPB), dim3(BT_WPB * MARL_WAVE), 0,
+                     (hipStream_t)stream, cfg, scale, rseed, env0, episode, t, eps, q, units, rec->u, rec->r, rec->term, rec->padded,
+                     rec->length, rec->won, rec->obs, rec->state, rec->state_ld, rec->avail, rec->E, rec->T);
   MARL_CHECK_LAUNCH();
   return 0;
 }
 
 extern "C" int marl_battle_fused_step(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0, int episode,
-                                      int t, float eps, const float* q, int* units, int* u, float* r, float* term, float* padded,
-                                      int* length, int* won, float* obs, float* state, long state_ld, float* avail, int E, int T,
-                                      int N, int M, int A, void* stream) {
-  return battle_fused_step<false>(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, u, r, term, padded, length,
-                                  won, obs, state, state_ld, avail, E, T, N, M, A, stream);
+                                      int t, float eps, const float* q, int* units, const marl_record_t* rec, int M, void* stream) {
+  return battle_fused_step<false>(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, rec, M, stream);
 }
 
 extern "C" int marl_battle_fused_step_sample(unsigned types, int shield, int type_bits, float scale, unsigned rseed, int env0,
-                                             int episode, int t, float eps, const float* q, int* units, int* u, float* r, float* term,
-                                             float* padded, int* length, int* won, float* obs, float* state, long state_ld,
-                                             float* avail, int E, int T, int N, int M, int A, void* stream) {
-  return battle_fused_step<true>(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, u, r, term, padded, length,
-                                 won, obs, state, state_ld, avail, E, T, N, M, A, stream);
+                                             int episode, int t, float eps, const float* q, int* units, const marl_record_t* rec,
+                                             int M, void* stream) {
+  return battle_fused_step<true>(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, rec, M, stream);
 }

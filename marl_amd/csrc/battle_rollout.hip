@@ -511,46 +511,41 @@ extern "C" int marl_battle_rollout_plan(int E, int N, int O, int A, int last_act
 }
 
 template <bool SAMPLE>
-static int battle_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, unsigned types,
-                          int shield, int type_bits, float scale, int* units, float* obs, float* state, long state_ld, float* avail,
-                          int* u, float* r, float* term, float* padded, int* length, int* won, float* h_out, float* stats,
-                          double eps0, double eps_anneal, double eps_min, int E, int T, int N, int M, int A, int last_action,
-                          int reuse_network, void* stream) {
+static int battle_rollout(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0, int episode,
+                          unsigned types, int shield, int type_bits, float scale, int* units, float* h_out, float* stats,
+                          double eps0, double eps_anneal, double eps_min, int M, int last_action, int reuse_network, void* stream) {
+  if (!rec) return (int)hipErrorInvalidValue;
   BattleRollArgs a;
-  const int bad = battle_cfg(N, M, A, shield, type_bits, types, state_ld, T, a.c);
+  const int bad = battle_cfg(rec->N, M, rec->A, shield, type_bits, types, rec->state_ld, rec->T, a.c);
   if (bad) return bad;
-  if (E <= 0) return 0;
+  if (rec->O != a.c.O || rec->S != a.c.S) return (int)hipErrorInvalidValue;      // the widths the map derives
+  if (rec->E <= 0) return 0;
   int plan[4];
-  if (!battle_plan(E, N, a.c.O, A, last_action, reuse_network, plan)) return (int)hipErrorInvalidValue;
-  if (const int e = rollout_args(a, w, seed, rseed, env0, episode, 0, nullptr, obs, state, state_ld, avail, u, r, term, padded, length,
-                                 won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, a.c.O, a.c.S, A, last_action, reuse_network))
+  if (!battle_plan(rec->E, rec->N, rec->O, rec->A, last_action, reuse_network, plan)) return (int)hipErrorInvalidValue;
+  if (const int e = rollout_args(a, w, rec, seed, rseed, env0, episode, 0, nullptr, h_out, stats, eps0, eps_anneal, eps_min, last_action,
+                                 reuse_network))
     return e;
   a.KC = (a.I + 15) / 16;
   a.EPW = plan[1];
   a.RT = plan[2];
   a.scale = scale;
   a.units = units;
-  return launch_rollout(A <= 16 ? (const void*)battle_rollout_kernel<1, SAMPLE> : (const void*)battle_rollout_kernel<2, SAMPLE>,
+  return launch_rollout(rec->A <= 16 ? (const void*)battle_rollout_kernel<1, SAMPLE> : (const void*)battle_rollout_kernel<2, SAMPLE>,
                         plan[0], (size_t)plan[3], a, stream);
 }
 
-extern "C" int marl_battle_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                                   unsigned types, int shield, int type_bits, float scale, int* units, float* obs, float* state,
-                                   long state_ld, float* avail, int* u, float* r, float* term, float* padded, int* length, int* won,
-                                   float* h_out, float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
-                                   int M, int A, int last_action, int reuse_network, void* stream) {
-  return battle_rollout<false>(w, seed, rseed, env0, episode, types, shield, type_bits, scale, units, obs, state, state_ld, avail, u,
-                               r, term, padded, length, won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, M, A, last_action,
-                               reuse_network, stream);
+extern "C" int marl_battle_rollout(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                                   int episode, unsigned types, int shield, int type_bits, float scale, int* units, float* h_out,
+                                   float* stats, double eps0, double eps_anneal, double eps_min, int M, int last_action,
+                                   int reuse_network, void* stream) {
+  return battle_rollout<false>(w, rec, seed, rseed, env0, episode, types, shield, type_bits, scale, units, h_out, stats, eps0,
+                               eps_anneal, eps_min, M, last_action, reuse_network, stream);
 }
 
-extern "C" int marl_battle_rollout_sample(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                                          unsigned types, int shield, int type_bits, float scale, int* units, float* obs,
-                                          float* state, long state_ld, float* avail, int* u, float* r, float* term, float* padded,
-                                          int* length, int* won, float* h_out, float* stats, double eps0, double eps_anneal,
-                                          double eps_min, int E, int T, int N, int M, int A, int last_action, int reuse_network,
-                                          void* stream) {
-  return battle_rollout<true>(w, seed, rseed, env0, episode, types, shield, type_bits, scale, units, obs, state, state_ld, avail, u,
-                              r, term, padded, length, won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, M, A, last_action,
-                              reuse_network, stream);
+extern "C" int marl_battle_rollout_sample(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed,
+                                          int env0, int episode, unsigned types, int shield, int type_bits, float scale, int* units,
+                                          float* h_out, float* stats, double eps0, double eps_anneal, double eps_min, int M,
+                                          int last_action, int reuse_network, void* stream) {
+  return battle_rollout<true>(w, rec, seed, rseed, env0, episode, types, shield, type_bits, scale, units, h_out, stats, eps0,
+                              eps_anneal, eps_min, M, last_action, reuse_network, stream);
 }

@@ -162,31 +162,26 @@ __global__ void synth_fused_step_kernel(unsigned seed, unsigned rseed, int env0,
 }  // namespace
 
 template <bool SAMPLE>
-static int fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const int* len, const float* q,
-                      float* obs, float* state, long state_ld, float* avail, int* u, float* r, float* term, float* padded, int E,
-                      int T, int N, int O, int S, int A, void* stream) {
-  if (E <= 0) return 0;
-  if (N > 64 || state_ld < S) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(synth_fused_step_kernel<SAMPLE>, dim3(E), dim3(TPB), 0, (hipStream_t)stream, seed, rseed, env0, episode,
-                     t, eps, len, q, obs, state, state_ld, avail, u, r, term, padded, E, T, N, O, S, A);
+static int fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const float* q,
+                      const marl_record_t* rec, void* stream) {
+  if (!rec) return (int)hipErrorInvalidValue;
+  if (rec->E <= 0) return 0;
+  if (rec->N > 64 || rec->state_ld < rec->S) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(synth_fused_step_kernel<SAMPLE>, dim3(rec->E), dim3(TPB), 0, (hipStream_t)stream, seed, rseed, env0, episode,
+                     t, eps, rec->length, q, rec->obs, rec->state, rec->state_ld, rec->avail, rec->u, rec->r, rec->term, rec->padded,
+                     rec->E, rec->T, rec->N, rec->O, rec->S, rec->A);
   MARL_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int marl_synth_fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps,
-                                     const int* len, const float* q, float* obs, float* state, long state_ld,
-                                     float* avail, int* u, float* r, float* term, float* padded, int E, int T, int N,
-                                     int O, int S, int A, void* stream) {
-  return fused_step<false>(seed, rseed, env0, episode, t, eps, len, q, obs, state, state_ld, avail, u, r, term, padded, E, T, N, O,
-                           S, A, stream);
+extern "C" int marl_synth_fused_step(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps, const float* q,
+                                     const marl_record_t* rec, void* stream) {
+  return fused_step<false>(seed, rseed, env0, episode, t, eps, q, rec, stream);
 }
 
 extern "C" int marl_synth_fused_step_sample(unsigned seed, unsigned rseed, int env0, int episode, int t, float eps,
-                                            const int* len, const float* q, float* obs, float* state, long state_ld,
-                                            float* avail, int* u, float* r, float* term, float* padded, int E, int T, int N,
-                                            int O, int S, int A, void* stream) {
-  return fused_step<true>(seed, rseed, env0, episode, t, eps, len, q, obs, state, state_ld, avail, u, r, term, padded, E, T, N, O,
-                          S, A, stream);
+                                            const float* q, const marl_record_t* rec, void* stream) {
+  return fused_step<true>(seed, rseed, env0, episode, t, eps, q, rec, stream);
 }
 
 extern "C" int marl_select_actions(const float* q, const float* avail, long avail_es, const int* alive, float eps,
@@ -209,23 +204,23 @@ extern "C" int marl_synth_lengths(unsigned seed, int env0, int episode, int* len
   return 0;
 }
 
-extern "C" int marl_synth_observe(unsigned seed, int env0, int episode, int t, const int* len, float* obs,
-                                  float* state, long state_ld, float* avail, int E, int T, int N, int O, int S, int A,
-                                  void* stream) {
-  if (E <= 0) return 0;
-  if (state_ld < S) return (int)hipErrorInvalidValue;
-  hipLaunchKernelGGL(synth_observe_kernel, dim3(E), dim3(TPB), 0, (hipStream_t)stream, seed, env0, episode, t, len,
-                     obs, state, state_ld, avail, E, T, N, O, S, A);
+extern "C" int marl_synth_observe(unsigned seed, int env0, int episode, int t, const marl_record_t* rec, void* stream) {
+  if (!rec) return (int)hipErrorInvalidValue;
+  if (rec->E <= 0) return 0;
+  if (rec->state_ld < rec->S) return (int)hipErrorInvalidValue;
+  hipLaunchKernelGGL(synth_observe_kernel, dim3(rec->E), dim3(TPB), 0, (hipStream_t)stream, seed, env0, episode, t, rec->length,
+                     rec->obs, rec->state, rec->state_ld, rec->avail, rec->E, rec->T, rec->N, rec->O, rec->S, rec->A);
   MARL_CHECK_LAUNCH();
   return 0;
 }
 
-extern "C" int marl_synth_step(unsigned seed, int env0, int episode, int t, const int* len, const int* act, int* u,
-                               float* r, float* term, float* padded, int* alive_next, int E, int T, int N, int A,
-                               void* stream) {
-  if (E <= 0) return 0;
-  hipLaunchKernelGGL(synth_step_kernel, dim3((E + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream, seed, env0,
-                     episode, t, len, act, u, r, term, padded, alive_next, E, T, N, A);
+extern "C" int marl_synth_step(unsigned seed, int env0, int episode, int t, const int* act, const marl_record_t* rec,
+                               int* alive_next, void* stream) {
+  if (!rec) return (int)hipErrorInvalidValue;
+  if (rec->E <= 0) return 0;
+  hipLaunchKernelGGL(synth_step_kernel, dim3((rec->E + TPB - 1) / TPB), dim3(TPB), 0, (hipStream_t)stream, seed, env0,
+                     episode, t, rec->length, act, rec->u, rec->r, rec->term, rec->padded, alive_next, rec->E, rec->T, rec->N,
+                     rec->A);
   MARL_CHECK_LAUNCH();
   return 0;
 }

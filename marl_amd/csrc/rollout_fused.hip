@@ -556,15 +556,16 @@ extern "C" int marl_synth_rollout_supported(int N, int O, int A) {
 }
 
 template <bool SAMPLE>
-static int synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, int fixed_len,
-                         const float* eps, float* obs, float* state, long state_ld, float* avail, int* u, float* r, float* term,
-                         float* padded, int* length, int* won, float* h_out, float* stats, double eps0, double eps_anneal,
-                         double eps_min, int E, int T, int N, int O, int S, int A, int last_action, int reuse_network, void* stream) {
-  if (E <= 0 || T <= 0) return 0;
+static int synth_rollout(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                         int episode, int fixed_len, const float* eps, float* h_out, float* stats, double eps0, double eps_anneal,
+                         double eps_min, int last_action, int reuse_network, void* stream) {
+  if (!rec) return (int)hipErrorInvalidValue;
+  const int E = rec->E, N = rec->N, A = rec->A;
+  if (E <= 0 || rec->T <= 0) return 0;
   if (A > 32 || A < 1 || N < 1 || N > 64) return (int)hipErrorInvalidValue;
   RollArgs a;
-  if (const int e = rollout_args(a, w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded,
-                                 length, won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network))
+  if (const int e = rollout_args(a, w, rec, seed, rseed, env0, episode, fixed_len, eps, h_out, stats, eps0, eps_anneal, eps_min,
+                                 last_action, reuse_network))
     return e;
   a.KC = (a.I + 15) / 16;
   const int rt_max = max_rt(a.I, A);
@@ -579,20 +580,17 @@ static int synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned 
                         (E + epw - 1) / epw, roll_lds(a.I, A, a.RT), a, stream);
 }
 
-extern "C" int marl_synth_rollout(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                                  int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
-                                  float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                                  float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
-                                  int O, int S, int A, int last_action, int reuse_network, void* stream) {
-  return synth_rollout<false>(w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded, length,
-                              won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network, stream);
+extern "C" int marl_synth_rollout(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                                  int episode, int fixed_len, const float* eps, float* h_out, float* stats, double eps0,
+                                  double eps_anneal, double eps_min, int last_action, int reuse_network, void* stream) {
+  return synth_rollout<false>(w, rec, seed, rseed, env0, episode, fixed_len, eps, h_out, stats, eps0, eps_anneal, eps_min, last_action,
+                              reuse_network, stream);
 }
 
-extern "C" int marl_synth_rollout_sample(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                                         int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail,
-                                         int* u, float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                                         float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
-                                         int O, int S, int A, int last_action, int reuse_network, void* stream) {
-  return synth_rollout<true>(w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded, length,
-                             won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network, stream);
+extern "C" int marl_synth_rollout_sample(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed,
+                                         int env0, int episode, int fixed_len, const float* eps, float* h_out, float* stats,
+                                         double eps0, double eps_anneal, double eps_min, int last_action, int reuse_network,
+                                         void* stream) {
+  return synth_rollout<true>(w, rec, seed, rseed, env0, episode, fixed_len, eps, h_out, stats, eps0, eps_anneal, eps_min, last_action,
+                             reuse_network, stream);
 }

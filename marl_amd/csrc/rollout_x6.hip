@@ -604,21 +604,20 @@ extern "C" int marl_synth_rollout_x6_plan(int E, int N, int O, int A, int last_a
   return 0;
 }
 
-extern "C" int marl_synth_rollout_x6(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                                     int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
-                                     float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                                     float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
-                                     int O, int S, int A, int last_action, int reuse_network, void* stream) {
-  const bool use_v1 = rx6_use_v1(E, N, O, A, last_action, reuse_network);
-  if (use_v1)
-    return marl_rollout_x6_v1(w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded, length, won,
-                              h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network, stream);
-  if (E <= 0 || T <= 0) return 0;
-  if (!marl_synth_rollout_x6_supported_flags(N, O, A, last_action, reuse_network) || (reinterpret_cast<uintptr_t>(obs) & 15))
+extern "C" int marl_synth_rollout_x6(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0,
+                                     int episode, int fixed_len, const float* eps, float* h_out, float* stats, double eps0,
+                                     double eps_anneal, double eps_min, int last_action, int reuse_network, void* stream) {
+  if (!rec) return (int)hipErrorInvalidValue;
+  const int E = rec->E, N = rec->N, O = rec->O, A = rec->A;
+  if (rx6_use_v1(E, N, O, A, last_action, reuse_network))
+    return marl_rollout_x6_v1(w, rec, seed, rseed, env0, episode, fixed_len, eps, h_out, stats, eps0, eps_anneal, eps_min, last_action,
+                              reuse_network, stream);
+  if (E <= 0 || rec->T <= 0) return 0;
+  if (!marl_synth_rollout_x6_supported_flags(N, O, A, last_action, reuse_network) || (reinterpret_cast<uintptr_t>(rec->obs) & 15))
     return (int)hipErrorInvalidValue;
   RX6Args a;
-  if (const int e = rollout_args(a, w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded,
-                                 length, won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network))
+  if (const int e = rollout_args(a, w, rec, seed, rseed, env0, episode, fixed_len, eps, h_out, stats, eps0, eps_anneal, eps_min,
+                                 last_action, reuse_network))
     return e;
   a.KI = (a.I + 31) / 32 * 32;
   const int nk1 = a.KI > 160 ? 7 : a.KI > 96 ? 5 : 3;

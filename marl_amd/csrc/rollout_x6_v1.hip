@@ -534,16 +534,17 @@ __attribute__((visibility("hidden"))) int marl_rollout_x6_v1_epw(int E, int N, i
   return epw_max < 1 ? 0 : even_rounds_epw(E, epw_max);
 }
 
-__attribute__((visibility("hidden"))) int marl_rollout_x6_v1(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode,
-                                     int fixed_len, const float* eps, float* obs, float* state, long state_ld, float* avail, int* u,
-                                     float* r, float* term, float* padded, int* length, int* won, float* h_out,
-                                     float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N,
-                                     int O, int S, int A, int last_action, int reuse_network, void* stream) {
-  if (E <= 0 || T <= 0) return 0;
-  if (!marl_rollout_x6_v1_supported(N, O, A) || (reinterpret_cast<uintptr_t>(obs) & 15)) return (int)hipErrorInvalidValue;
+__attribute__((visibility("hidden"))) int marl_rollout_x6_v1(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed,
+                                     unsigned rseed, int env0, int episode, int fixed_len, const float* eps, float* h_out,
+                                     float* stats, double eps0, double eps_anneal, double eps_min, int last_action,
+                                     int reuse_network, void* stream) {
+  if (!rec) return (int)hipErrorInvalidValue;
+  const int E = rec->E, N = rec->N, A = rec->A;
+  if (E <= 0 || rec->T <= 0) return 0;
+  if (!marl_rollout_x6_v1_supported(N, rec->O, A) || (reinterpret_cast<uintptr_t>(rec->obs) & 15)) return (int)hipErrorInvalidValue;
   RX6Args a;
-  if (const int e = rollout_args(a, w, seed, rseed, env0, episode, fixed_len, eps, obs, state, state_ld, avail, u, r, term, padded,
-                                 length, won, h_out, stats, eps0, eps_anneal, eps_min, E, T, N, O, S, A, last_action, reuse_network))
+  if (const int e = rollout_args(a, w, rec, seed, rseed, env0, episode, fixed_len, eps, h_out, stats, eps0, eps_anneal, eps_min,
+                                 last_action, reuse_network))
     return e;
   a.KI = (a.I + 31) / 32 * 32;
   const int nk1 = a.KI > 96 ? 5 : 3;

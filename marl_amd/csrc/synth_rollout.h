@@ -34,26 +34,26 @@ struct RX6Args {
 
 }  // namespace
 
-// The fields RollArgs and RX6Args share, and the checks every whole-rollout launcher makes (a batch with E or T <= 0 launches
-// nothing: the launchers return before).  0, or hipErrorInvalidValue
+// The fields RollArgs and RX6Args share, and the checks every whole-rollout launcher makes (a null record is refused and a batch
+// with E or T <= 0 launches nothing: the launchers return before).  0, or hipErrorInvalidValue
 template <class Args>
-int rollout_args(Args& a, const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, int fixed_len,
-                 const float* eps, float* obs, float* state, long state_ld, float* avail, int* u, float* r, float* term,
-                 float* padded, int* length, int* won, float* h_out, float* stats, double eps0, double eps_anneal, double eps_min,
-                 int E, int T, int N, int O, int S, int A, int last_action, int reuse_network) {
-  if (w->H != H || state_ld < S) return (int)hipErrorInvalidValue;
+int rollout_args(Args& a, const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0, int episode,
+                 int fixed_len, const float* eps, float* h_out, float* stats, double eps0, double eps_anneal, double eps_min,
+                 int last_action, int reuse_network) {
+  a.E = rec->E; a.T = rec->T; a.N = rec->N; a.O = rec->O; a.S = rec->S; a.A = rec->A; a.SL = rec->state_ld;
+  if (w->H != H || a.SL < a.S) return (int)hipErrorInvalidValue;
   // record offsets are 32-bit element offsets inside the kernels
-  if ((double)E * (T + 1) * N * (O > A ? O : A) >= 2147483648.0 || (double)E * (T + 1) * state_ld >= 2147483648.0)
+  if ((double)a.E * (a.T + 1) * a.N * (a.O > a.A ? a.O : a.A) >= 2147483648.0 || (double)a.E * (a.T + 1) * a.SL >= 2147483648.0)
     return (int)hipErrorInvalidValue;
   a.W1 = w->fc1_w; a.b1 = w->fc1_b; a.Wih = w->w_ih; a.Whh = w->w_hh; a.bih = w->b_ih; a.bhh = w->b_hh;
   a.W2 = w->fc2_w; a.b2 = w->fc2_b;
-  a.eps = eps; a.eps0 = eps0; a.eps_anneal = eps_anneal; a.eps_min = eps_min; a.obs = obs; a.state = state; a.SL = state_ld; a.avail = avail;
-  a.u = u; a.r = r; a.term = term; a.padded = padded; a.length = length; a.won = won; a.h_out = h_out; a.stats = stats;
+  a.eps = eps; a.eps0 = eps0; a.eps_anneal = eps_anneal; a.eps_min = eps_min; a.h_out = h_out; a.stats = stats;
+  a.obs = rec->obs; a.state = rec->state; a.avail = rec->avail; a.u = rec->u; a.r = rec->r; a.term = rec->term; a.padded = rec->padded;
+  a.length = rec->length; a.won = rec->won;
   a.seed = seed; a.rseed = rseed; a.env0 = env0; a.episode = episode; a.fixed_len = fixed_len;
-  a.E = E; a.T = T; a.N = N; a.O = O; a.S = S; a.A = A;
   a.has_act = last_action ? 1 : 0; a.has_id = reuse_network ? 1 : 0;
-  a.I = O + (last_action ? A : 0) + (reuse_network ? N : 0);
-  a.R = (long)E * N;
+  a.I = a.O + (last_action ? a.A : 0) + (reuse_network ? a.N : 0);
+  a.R = (long)a.E * a.N;
   return 0;
 }
 
@@ -86,7 +86,6 @@ inline int even_rounds_epw(int E, int epw_max) {
 // width rounded up to 32; 0: none fits), the launch
 int marl_rollout_x6_v1_supported(int N, int O, int A);
 int marl_rollout_x6_v1_epw(int E, int N, int KI);
-int marl_rollout_x6_v1(const marl_agent_weights_t* w, unsigned seed, unsigned rseed, int env0, int episode, int fixed_len, const float* eps,
-                       float* obs, float* state, long state_ld, float* avail, int* u, float* r, float* term, float* padded, int* length,
-                       int* won, float* h_out, float* stats, double eps0, double eps_anneal, double eps_min, int E, int T, int N, int O,
-                       int S, int A, int last_action, int reuse_network, void* stream);
+int marl_rollout_x6_v1(const marl_agent_weights_t* w, const marl_record_t* rec, unsigned seed, unsigned rseed, int env0, int episode,
+                       int fixed_len, const float* eps, float* h_out, float* stats, double eps0, double eps_anneal, double eps_min,
+                       int last_action, int reuse_network, void* stream);

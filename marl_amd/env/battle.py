@@ -17,7 +17,7 @@ import torch
 
 from .. import ops
 from ..hostutil import require_cuda
-from .synthetic_smac import EpisodeRecord
+from .synthetic_smac import EpisodeRecord, next_kernel_stats
 
 MARINE, STALKER, ZEALOT = 0, 1, 2
 # (hp, shield, damage, cooldown) by type
@@ -82,14 +82,14 @@ class BattleEnv:
     def begin_episode(self, rec):
         self.episode += 1
         ops.battle_reset(self.seed, self.env0, self.episode, self.type_mask, self.shield, self.type_bits, self.units, rec,
-                         self.n_envs, self.episode_limit, self.n_agents, self.n_enemies, self.n_actions)
+                         self.n_enemies)
 
     def observe(self, t, rec):
         pass        # slot 0 came from begin_episode, slot t + 1 from step
 
     def step(self, t, act, rec, alive_next):
         ops.battle_step(self.type_mask, self.shield, self.type_bits, self.scale, t, act, self.units, rec, alive_next,
-                        self.n_envs, self.episode_limit, self.n_agents, self.n_enemies, self.n_actions)
+                        self.n_enemies)
 
     def global_step(self, t):
         return self.episode * (self.episode_limit + 1) + t
@@ -115,8 +115,7 @@ class FusedBattleEnv(BattleEnv):
     def fused_step(self, t, q, eps, rseed, rec, sample=False):
         """the action choice + step in one launch (same record as select_actions / policy_sample, then step)"""
         ops.battle_fused_step(self.type_mask, self.shield, self.type_bits, self.scale, rseed, self.env0, self.episode, t, eps, q,
-                              self.units, rec, self.n_envs, self.episode_limit, self.n_agents, self.n_enemies, self.n_actions,
-                              sample=sample)
+                              self.units, rec, self.n_enemies, sample=sample)
 
     def supports_whole_rollout(self):
         return ops.battle_rollout_supported(self.n_agents, self.obs_shape, self.n_actions)
@@ -129,13 +128,6 @@ class FusedBattleEnv(BattleEnv):
         if eps_dev is not None or eps_sched is None:
             raise ValueError("battle: the whole-rollout kernel takes the epsilon schedule (eps_sched), not a device vector")
         self.episode += 1
-        # per-episode statistics written by the kernel, in a small rotation (SyntheticSMACEnv.whole_rollout)
-        ring = self.__dict__.setdefault("_stats_ring", [])
-        if len(ring) < 4:
-            ring.append(torch.empty(3, self.n_envs, dtype=torch.float32, device=rec.r.device))
-        self._stats_i = (getattr(self, "_stats_i", -1) + 1) % 4
-        stats = ring[min(self._stats_i, len(ring) - 1)]
         ops.battle_rollout(weights, self.seed, rseed, self.env0, self.episode, self.type_mask, self.shield, self.type_bits,
-                           self.scale, self.units, rec, h_out, self.n_envs, self.episode_limit, self.n_agents, self.n_enemies,
-                           self.n_actions, last_action, reuse_network, stats, eps_sched, sample=sample)
-        rec.kernel_stats = stats
+                           self.scale, self.units, rec, h_out, self.n_enemies, last_action, reuse_network,
+                           next_kernel_stats(self, rec), eps_sched, sample=sample)

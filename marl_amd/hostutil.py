@@ -96,16 +96,14 @@ _STRUCTS = weakref.WeakKeyDictionary()
 def _struct_hit(owner, name, tensors=None):
     """the cached struct while every one of `tensors` (None: the tensors it was stored with) sits where it sat then, else None"""
     c = _STRUCTS.get(owner, {}).get(name)
-    if c is not None:
-        tlist, ptrs, w = c
-        tensors = tlist if tensors is None else tensors
-        if len(tensors) == len(ptrs) and all(q.data_ptr() == o and q.is_cuda for q, o in zip(tensors, ptrs)):
-            return w
+    if c is not None and [q.data_ptr() for q in (c[0] if tensors is None else tensors)] == c[1]:      # (the check every launch pays)
+        return c[2]
     return None
 
 
 def _struct_store(owner, name, tensors, w):
-    _STRUCTS.setdefault(owner, {})[name] = (tensors, [q.data_ptr() for q in tensors], w)
+    # device pointers only: a struct stored over a host tensor (None here) never hits
+    _STRUCTS.setdefault(owner, {})[name] = (tensors, [q.data_ptr() if q.is_cuda else None for q in tensors], w)
     return w
 
 

@@ -13,7 +13,7 @@ import torch
 from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
                    MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, MarlMaicGrads, MarlMaicInfer,
-                   MarlMaicInferGrads, MarlCommnetWeights, MarlCommnetGrads, MarlG2anetWeights, MarlG2anetGrads,
+                   MarlMaicInferGrads, MarlCommnetWeights, MarlCommnetGrads, MarlG2anetWeights, MarlG2anetGrads, MarlRecord,
                    check)
 
 
@@ -872,60 +872,69 @@ def synth_lengths(seed, env0, episode, length, won, E, T):
                                          _stream()), "marl_synth_lengths")
 
 
-def synth_observe(seed, env0, episode, t, length, obs, state, avail, E, T, N, O, S, A):
-    check(_lib.load().marl_synth_observe(int(seed) & 0xFFFFFFFF, env0, episode, t, _p(_i32(length)), _p(_f32(obs)),
-                                         _p(_f32(state)), state.stride(-2), _p(_f32(avail)), E, T, N, O, S, A, _stream()),
-          "marl_synth_observe")
+_RECORD_FIELDS = (("obs", _f32), ("state", _f32), ("avail", _f32), ("u", _i32), ("r", _f32), ("term", _f32), ("padded", _f32),
+                  ("length", _i32), ("won", _i32))
+# where the fields are looked up: EpisodeRecord's `state` is a fresh view of state_store at every read (same pointer and row stride)
+_RECORD_ATTRS = tuple("state_store" if f == "state" else f for f, _ in _RECORD_FIELDS)
+_cached_struct = None       # hostutil.cached_struct, bound at the first use: hostutil imports this module
 
 
-def synth_step(seed, env0, episode, t, length, act, u, r, term, padded, alive_next, E, T, N, A):
-    check(_lib.load().marl_synth_step(int(seed) & 0xFFFFFFFF, env0, episode, t, _p(_i32(length)), _p(_i32(act)),
-                                      _p(_i32(u)), _p(_f32(r)), _p(_f32(term)), _p(_f32(padded)), _p(alive_next),
-                                      E, T, N, A, _stream()), "marl_synth_step")
+def record(rec, cache=True):
+    """the MarlRecord of an object with EpisodeRecord's attributes (a field an entry does not read: None), by reference.  Kept on `rec`
+    and rebuilt only when a field's storage moved: a launch-per-step rollout builds it once.  cache = False: built for this call alone
+    (a whole rollout is ONE launch per record, usually a fresh view of the replay ring)"""
+    global _cached_struct
+    if _cached_struct is None:
+        from .hostutil import cached_struct as _cached_struct
+    ts = [getattr(rec, a, None) for a in _RECORD_ATTRS]
+    st = ts[1] = ts[1] if ts[1] is not None else getattr(rec, "state", None)
+    build = lambda: MarlRecord(state_ld=0 if st is None else st.stride(-2), E=rec.E, T=rec.T, N=rec.N, O=rec.O, S=rec.S, A=rec.A,
+                               **{f: kind(t).data_ptr() for (f, kind), t in zip(_RECORD_FIELDS, ts) if t is not None})
+    return C.byref(_cached_struct(rec, "record", [t for t in ts if t is not None], build) if cache else build())
 
 
-def synth_fused_step(seed, rseed, env0, episode, t, eps, length, q, obs, state, avail, u, r, term, padded, E, T, N, O, S, A,
-                     sample=False):
+def _entry(name, sample=False, x6=False):
+    """(function, its exact name for check) of an entry point and its _sample / _x6 variants"""
+    name += "_sample" if sample else "_x6" if x6 else ""
+    return getattr(_lib.load(), name), name
+
+
+def synth_observe(seed, env0, episode, t, rec):
+    check(_lib.load().marl_synth_observe(int(seed) & 0xFFFFFFFF, env0, episode, t, record(rec), _stream()), "marl_synth_observe")
+
+
+def synth_step(seed, env0, episode, t, act, rec, alive_next):
+    check(_lib.load().marl_synth_step(int(seed) & 0xFFFFFFFF, env0, episode, t, _p(_i32(act)), record(rec), _p(alive_next),
+                                      _stream()), "marl_synth_step")
+
+
+def synth_fused_step(seed, rseed, env0, episode, t, eps, q, rec, sample=False):
     """sample: the actions are drawn from the stochastic policy of q (logits) with eps as its mixing epsilon (policy_sample's rule)"""
-    lib = _lib.load()
-    fn, name = (lib.marl_synth_fused_step_sample, "marl_synth_fused_step_sample") if sample else \
-        (lib.marl_synth_fused_step, "marl_synth_fused_step")
-    check(fn(int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, t, float(eps),
-             _p(_i32(length)), _p(_f32(q)), _p(_f32(obs)), _p(_f32(state)), state.stride(-2),
-             _p(_f32(avail)),
-             _p(_i32(u)), _p(_f32(r)), _p(_f32(term)), _p(_f32(padded)), E, T, N, O, S, A,
-             _stream()), name)
+    fn, name = _entry("marl_synth_fused_step", sample)
+    check(fn(int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, t, float(eps), _p(_f32(q)), record(rec), _stream()), name)
 
 
 def battle_supported(n_allies, n_enemies, A):
     return bool(_lib.load().marl_battle_supported(n_allies, n_enemies, A))
 
 
-def battle_reset(seed, env0, episode, types, shield, type_bits, units, rec, E, T, N, M, A):
+def battle_reset(seed, env0, episode, types, shield, type_bits, units, rec, M):
     """start of an episode of the battle environment (csrc/battle.hip): unit state, length, won and slot 0 of the record"""
     check(_lib.load().marl_battle_reset(int(seed) & 0xFFFFFFFF, env0, episode, types, int(shield), type_bits, _p(_i32(units)),
-                                        _p(_i32(rec.length)), _p(_i32(rec.won)), _p(_f32(rec.obs)), _p(_f32(rec.state)),
-                                        rec.state.stride(-2), _p(_f32(rec.avail)), E, T, N, M, A, _stream()), "marl_battle_reset")
+                                        record(rec), M, _stream()), "marl_battle_reset")
 
 
-def battle_step(types, shield, type_bits, scale, t, act, units, rec, alive_next, E, T, N, M, A):
+def battle_step(types, shield, type_bits, scale, t, act, units, rec, alive_next, M):
     """lock-step t of the battle environment in one launch: step t of the record, the unit state and slot t + 1"""
-    check(_lib.load().marl_battle_step(types, int(shield), type_bits, float(scale), t, _p(_i32(act)), _p(_i32(units)),
-                                       _p(_i32(rec.u)), _p(_f32(rec.r)), _p(_f32(rec.term)), _p(_f32(rec.padded)),
-                                       _p(_i32(rec.length)), _p(_i32(rec.won)), _p(alive_next), _p(_f32(rec.obs)),
-                                       _p(_f32(rec.state)), rec.state.stride(-2), _p(_f32(rec.avail)), E, T, N, M, A, _stream()),
-          "marl_battle_step")
+    check(_lib.load().marl_battle_step(types, int(shield), type_bits, float(scale), t, _p(_i32(act)), _p(_i32(units)), record(rec),
+                                       _p(alive_next), M, _stream()), "marl_battle_step")
 
 
-def battle_fused_step(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, rec, E, T, N, M, A, sample=False):
+def battle_fused_step(types, shield, type_bits, scale, rseed, env0, episode, t, eps, q, units, rec, M, sample=False):
     """the action choice (select_actions' rule and draws; sample: policy_sample's) and battle_step in one launch"""
-    lib = _lib.load()
-    fn, name = (lib.marl_battle_fused_step_sample, "marl_battle_fused_step_sample") if sample else \
-        (lib.marl_battle_fused_step, "marl_battle_fused_step")
+    fn, name = _entry("marl_battle_fused_step", sample)
     check(fn(types, int(shield), type_bits, float(scale), int(rseed) & 0xFFFFFFFF, env0, episode, t, float(eps), _p(_f32(q)),
-             _p(_i32(units)), _p(_i32(rec.u)), _p(_f32(rec.r)), _p(_f32(rec.term)), _p(_f32(rec.padded)), _p(_i32(rec.length)),
-             _p(_i32(rec.won)), _p(_f32(rec.obs)), _p(_f32(rec.state)), rec.state.stride(-2), _p(_f32(rec.avail)), E, T, N, M, A,
-             _stream()), name)
+             _p(_i32(units)), record(rec), M, _stream()), name)
 
 
 def battle_rollout_supported(N, O, A):
@@ -940,20 +949,15 @@ def battle_rollout_plan(E, N, O, A, last_action=True, reuse_network=True):
     return tuple(plan)
 
 
-def battle_rollout(w, seed, rseed, env0, episode, types, shield, type_bits, scale, units, rec, h_out, E, T, N, M, A, last_action,
+def battle_rollout(w, seed, rseed, env0, episode, types, shield, type_bits, scale, units, rec, h_out, M, last_action,
                    reuse_network, stats, eps_sched, sample=False):
     """reset and all T lock-steps of the battle environment in ONE persistent launch (csrc/battle_rollout.hip): every field of rec,
     the final unit state, stats (3, E) = reward sum | won | length (or None) and h_out (or None).  eps_sched = (eps0, anneal,
     eps_min), evaluated inside the kernel in fp64; sample: the actions are drawn from the stochastic policy of the step's logits"""
-    e0, ea, em = eps_sched
-    lib = _lib.load()
-    fn, name = (lib.marl_battle_rollout_sample, "marl_battle_rollout_sample") if sample else \
-        (lib.marl_battle_rollout, "marl_battle_rollout")
-    check(fn(C.byref(w), int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, types, int(shield), type_bits, float(scale),
-             _p(_i32(units)), _p(_f32(rec.obs)), _p(_f32(rec.state)), rec.state.stride(-2), _p(_f32(rec.avail)), _p(_i32(rec.u)),
-             _p(_f32(rec.r)), _p(_f32(rec.term)), _p(_f32(rec.padded)), _p(_i32(rec.length)), _p(_i32(rec.won)), _p(h_out),
-             _p(_f32(stats)) if stats is not None else None, float(e0), float(ea), float(em), E, T, N, M, A,
-             1 if last_action else 0, 1 if reuse_network else 0, _stream()), name)
+    fn, name = _entry("marl_battle_rollout", sample)
+    check(fn(C.byref(w), record(rec, cache=False), int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, types, int(shield),
+             type_bits, float(scale), _p(_i32(units)), _p(h_out), _p(_f32(stats)) if stats is not None else None,
+             *map(float, eps_sched), M, 1 if last_action else 0, 1 if reuse_network else 0, _stream()), name)
 
 
 def synth_rollout_supported(N, O, A):
@@ -973,20 +977,15 @@ def synth_rollout_x6_plan(E, N, O, A, last_action=True, reuse_network=True):
 
 def synth_rollout(w, seed, rseed, env0, episode, fixed_len, eps, rec, h_out, E, T, N, O, S, A, last_action, reuse_network,
                   stats=None, eps_sched=None, x6=False, sample=False):
-    """eps: device (T,) epsilon per lock-step, or None with eps_sched = (eps0, anneal, eps_min): the per-step anneal of
-    rollout.py:100-101 is then evaluated inside the kernel (fp64, like the host loop) and no schedule crosses PCIe.
-    sample: the actions are drawn from the stochastic policy of the step's logits, eps(t) its mixing epsilon; always the fp32
-    kernel (x6 is ignored)."""
-    e0, ea, em = (0.0, 0.0, 0.0) if eps_sched is None else eps_sched
-    assert (eps is None) != (eps_sched is None)
-    lib = _lib.load()
-    fn = lib.marl_synth_rollout_sample if sample else lib.marl_synth_rollout_x6 if x6 else lib.marl_synth_rollout   # x6: the agent step as bf16x6 split products
-    check(fn(C.byref(w), int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode,
-                                         1 if fixed_len else 0, _p(_f32(eps)) if eps is not None else None, _p(_f32(rec.obs)), _p(_f32(rec.state)),
-                                         rec.state.stride(-2), _p(_f32(rec.avail)), _p(_i32(rec.u)), _p(_f32(rec.r)), _p(_f32(rec.term)),
-                                         _p(_f32(rec.padded)), _p(_i32(rec.length)), _p(_i32(rec.won)), _p(h_out),
-                                         _p(_f32(stats)) if stats is not None else None, float(e0), float(ea), float(em), E, T, N, O, S, A, 1 if last_action else 0, 1 if reuse_network else 0, _stream()),
-          "marl_synth_rollout_sample" if sample else "marl_synth_rollout")
+    """E .. A: the record's sizes once more, by position - bench.py's roofline model reads them off this call.  eps: device (T,) epsilon
+    per lock-step, or None with eps_sched = (eps0, anneal, eps_min): the per-step anneal of rollout.py:100-101 is then evaluated inside
+    the kernel (fp64, like the host loop) and no schedule crosses PCIe.  x6: the agent step as bf16x6 split products.  sample: the
+    actions are drawn from the stochastic policy of the step's logits, eps(t) its mixing epsilon; always the fp32 kernel (x6 is ignored)."""
+    assert (eps is None) != (eps_sched is None) and (E, T, N, O, S, A) == (rec.E, rec.T, rec.N, rec.O, rec.S, rec.A)
+    fn, name = _entry("marl_synth_rollout", sample, x6)
+    check(fn(C.byref(w), record(rec, cache=False), int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, 1 if fixed_len else 0,
+             _p(_f32(eps)) if eps is not None else None, _p(h_out), _p(_f32(stats)) if stats is not None else None,
+             *map(float, eps_sched or (0.0, 0.0, 0.0)), 1 if last_action else 0, 1 if reuse_network else 0, _stream()), name)
 
 
 def qmix_fused_supported(N, S, E):

@@ -99,6 +99,34 @@ def test_struct_layouts_match_the_host_c_compiler(tmp_path):
     assert got["marl_src_t"] == 144 and got["marl_src_t.emap0"] == 136          # (a 64-bit host: what the library is built for)
 
 
+# the entries that take the episode record, and the loose device arrays each keeps beside it (stream not counted)
+RECORD_ENTRIES = {"marl_synth_observe": (), "marl_synth_step": ("act", "alive_next"),
+                  "marl_synth_fused_step": ("q",), "marl_synth_fused_step_sample": ("q",),
+                  "marl_synth_rollout": ("eps", "h_out", "stats"), "marl_synth_rollout_sample": ("eps", "h_out", "stats"),
+                  "marl_synth_rollout_x6": ("eps", "h_out", "stats"),
+                  "marl_battle_reset": ("units",), "marl_battle_step": ("act", "units", "alive_next"),
+                  "marl_battle_fused_step": ("q", "units"), "marl_battle_fused_step_sample": ("q", "units"),
+                  "marl_battle_rollout": ("units", "h_out", "stats"), "marl_battle_rollout_sample": ("units", "h_out", "stats")}
+
+
+def test_the_episode_record_travels_as_one_struct():
+    from marl_amd import _lib
+    P, I, L, F, U = _lib.P, _lib.I, _lib.L, _lib.F, _lib.U
+    rec = _lib.STRUCTS["marl_record_t"]
+    assert rec is _lib.MarlRecord
+    assert rec._fields_ == [("obs", P), ("state", P), ("avail", P), ("state_ld", L), ("u", P), ("r", P), ("term", P), ("padded", P),
+                            ("length", P), ("won", P), ("E", I), ("T", I), ("N", I), ("O", I), ("S", I), ("A", I)]
+    assert len(RECORD_ENTRIES) == 13
+    for name, loose in RECORD_ENTRIES.items():
+        res, args = _lib.SIGNATURES[name]
+        assert res is I and args.count(ctypes.POINTER(rec)) == 1, name
+        assert args[-1] is P and args[:-1].count(P) <= len(loose), (name, "loose pointers beside the record (and the stream)")
+    # the three neighbours that keep their loose lists
+    assert _lib.SIGNATURES["marl_synth_lengths"] == (I, [U, I, I, P, P, I, I, P])
+    assert _lib.SIGNATURES["marl_select_actions"] == (I, [P, P, L, P, F, U, I, P, I, P, L, I, I, I, P])
+    assert _lib.SIGNATURES["marl_replay_gather"] == (I, [P, I, I, I, I] + [P] * 18)
+
+
 DEMO_HEADER = """/* a comment
  * over two lines */
 #ifndef DEMO_H

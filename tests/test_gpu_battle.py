@@ -119,18 +119,18 @@ def test_mmm2_sized_unit_counts_are_refused_without_writing():
     obs, state, avail, units, u = f(E, T + 1, N, O), f(E, T + 1, 324), f(E, T + 1, N, A), i(E, N + M, 5), i(E, T, N)
     r, term, padded, length, won, alive, act = f(E, T), f(E, T), f(E, T), i(E), i(E), i(E), i(E, N)
     p = lambda t: C.c_void_p(t.data_ptr())
+
+    def record(state_ld, N, O, S, A):
+        """the MarlRecord of the tensors above with these sizes, by reference"""
+        return C.byref(_lib.MarlRecord(state_ld=state_ld, E=E, T=T, N=N, O=O, S=S, A=A, **{k: t.data_ptr() for k, t in dict(
+            obs=obs, state=state, avail=avail, u=u, r=r, term=term, padded=padded, length=length, won=won).items()}))
     INVALID = 1                                                                            # hipErrorInvalidValue
-    assert lib.marl_battle_reset(1, 0, 0, 0, 1, 2, p(units), p(length), p(won), p(obs), p(state), 324, p(avail), E, T, N, M, A,
-                                 None) == INVALID
-    assert lib.marl_battle_step(0, 1, 2, 0.1, 0, p(act), p(units), p(u), p(r), p(term), p(padded), p(length), p(won), p(alive),
-                                p(obs), p(state), 324, p(avail), E, T, N, M, A, None) == INVALID
-    # a supported shape with a state row stride below S, a step outside the episode, a type without a type bit
-    assert lib.marl_battle_step(0, 0, 0, 0.1, 0, p(act), p(units), p(u), p(r), p(term), p(padded), p(length), p(won), p(alive),
-                                p(obs), p(state), 47, p(avail), E, T, 3, 3, 9, None) == INVALID
-    assert lib.marl_battle_step(0, 0, 0, 0.1, T, p(act), p(units), p(u), p(r), p(term), p(padded), p(length), p(won), p(alive),
-                                p(obs), p(state), 48, p(avail), E, T, 3, 3, 9, None) == INVALID
-    assert lib.marl_battle_reset(1, 0, 0, 0b100101, 0, 0, p(units), p(length), p(won), p(obs), p(state), 48, p(avail), E, T, 3, 3, 9,
-                                 None) == INVALID
+    assert lib.marl_battle_reset(1, 0, 0, 0, 1, 2, p(units), record(324, N, O, S, A), M, None) == INVALID
+    assert lib.marl_battle_step(0, 1, 2, 0.1, 0, p(act), p(units), record(324, N, O, S, A), p(alive), M, None) == INVALID
+    # a supported shape (3m: O = 30, S = 48) with a state row stride below S, a step outside the episode, a type without a type bit
+    assert lib.marl_battle_step(0, 0, 0, 0.1, 0, p(act), p(units), record(47, 3, 30, 48, 9), p(alive), 3, None) == INVALID
+    assert lib.marl_battle_step(0, 0, 0, 0.1, T, p(act), p(units), record(48, 3, 30, 48, 9), p(alive), 3, None) == INVALID
+    assert lib.marl_battle_reset(1, 0, 0, 0b100101, 0, 0, p(units), record(48, 3, 30, 48, 9), 3, None) == INVALID
     torch.cuda.synchronize()
     for t in (obs, state, avail, units, u, r, term, padded, length, won, alive, act):
         assert (t == 5).all().item()

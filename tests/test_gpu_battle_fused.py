@@ -310,13 +310,18 @@ def test_refusals_write_nothing():
     p = lambda t: C.c_void_p(t.data_ptr())
     INVALID = 1
 
+    fields = dict(obs=obs, state=state, avail=avail, u=u, r=r, term=term, padded=padded, length=length, won=won)
+
+    def record(sl, n, a):
+        """the MarlRecord of the tensors above with these sizes, by reference"""
+        return C.byref(_lib.MarlRecord(state_ld=sl, E=E, T=T, N=n, O=O, S=S, A=a, **{k: t.data_ptr() for k, t in fields.items()}))
+
     def whole(fn, types_=0, sl=S, n=N, m=M, a=A, tb=0):
-        return fn(C.byref(wts), 1, 2, 0, 0, types_, 0, tb, 0.1, p(units), p(obs), p(state), sl, p(avail), p(u), p(r), p(term),
-                  p(padded), p(length), p(won), p(h), p(stats), 0.5, 0.0, 0.05, E, T, n, m, a, 1, 1, None)
+        return fn(C.byref(wts), record(sl, n, a), 1, 2, 0, 0, types_, 0, tb, 0.1, p(units), p(h), p(stats), 0.5, 0.0, 0.05, m, 1, 1,
+                  None)
 
     def step(fn, t=0, sl=S, n=N, m=M, a=A):
-        return fn(0, 0, 0, 0.1, 2, 0, 0, t, 0.5, p(q), p(units), p(u), p(r), p(term), p(padded), p(length), p(won), p(obs), p(state),
-                  sl, p(avail), E, T, n, m, a, None)
+        return fn(0, 0, 0, 0.1, 2, 0, 0, t, 0.5, p(q), p(units), record(sl, n, a), m, None)
     for fn in (lib.marl_battle_rollout, lib.marl_battle_rollout_sample):
         assert whole(fn, sl=S - 1) == INVALID                   # battle_cfg's checks: the state's row stride,
         assert whole(fn, n=10, m=12, a=18) == INVALID           # MMM2's unit counts,
@@ -328,6 +333,61 @@ def test_refusals_write_nothing():
     torch.cuda.synchronize()
     for t in (obs, state, avail, units, u, r, term, padded, length, won, h, stats):
         assert (t == 5).all().item()
+
+
+def test_record_struct_null_wrong_widths_and_absent_fields():
+    """what only the record struct can express, on 3m with E = 3, T = 4: rec = NULL, and a record whose O or S is not the map's, are
+    refused by all six battle entries and nothing is written; marl_battle_reset runs with u / r / term / padded absent, to the same
+    bits"""
+    import ctypes as C
+    from marl_amd import _lib, ops
+    from marl_amd.env.battle import battle_shapes
+    from marl_amd.env.synthetic_smac import EpisodeRecord
+    lib = _lib.load()
+    E, T, M = 3, 4, 3
+    N, O, S, A, _ = battle_shapes("3m")
+    mac = _mac(_args("3m"))                            # (held: the struct points into its tensors)
+    wts = mac.agent.weights()
+    f = lambda *s: torch.full(s, 5.0, device=DEV)
+    i = lambda *s: torch.full(s, 5, dtype=torch.int32, device=DEV)
+    SL = S + 4                                         # a row stride that also holds S + 1 columns: only the width check can refuse
+    fields = dict(obs=f(E, T + 1, N, O + 1), state=f(E, T + 1, SL), avail=f(E, T + 1, N, A), u=i(E, T, N), r=f(E, T), term=f(E, T),
+                  padded=f(E, T), length=i(E), won=i(E))
+    units, h, stats, q, act, alive = i(E, N + M, 5), f(E * N, 64), f(3, E), f(E, 1, N, A), i(E, N), i(E)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    INVALID = 1
+
+    def calls(rec):
+        """the return codes of the six entries on `rec` (by reference, or None)"""
+        return [lib.marl_battle_reset(1, 0, 0, 0, 0, 0, p(units), rec, M, None),
+                lib.marl_battle_step(0, 0, 0, 0.1, 0, p(act), p(units), rec, p(alive), M, None)] + \
+               [fn(0, 0, 0, 0.1, 2, 0, 0, 0, 0.5, p(q), p(units), rec, M, None)
+                for fn in (lib.marl_battle_fused_step, lib.marl_battle_fused_step_sample)] + \
+               [fn(C.byref(wts), rec, 1, 2, 0, 0, 0, 0, 0, 0.1, p(units), p(h), p(stats), 0.5, 0.0, 0.05, M, 1, 1, None)
+                for fn in (lib.marl_battle_rollout, lib.marl_battle_rollout_sample)]
+    record = lambda o, s_: C.byref(_lib.MarlRecord(state_ld=SL, E=E, T=T, N=N, O=o, S=s_, A=A,
+                                                   **{k: t.data_ptr() for k, t in fields.items()}))
+    assert calls(None) == [INVALID] * 6
+    assert calls(record(O + 1, S)) == [INVALID] * 6 and calls(record(O, S + 1)) == [INVALID] * 6
+    torch.cuda.synchronize()
+    for t in list(fields.values()) + [units, h, stats, alive]:
+        assert (t.cpu() == 5).all().item()
+    # reset reads length / won / obs / state / avail only
+    full, bare = EpisodeRecord(E, T, N, O, S, A, DEV), EpisodeRecord(E, T, N, O, S, A, DEV)
+    bare.u = bare.r = bare.term = bare.padded = None
+    un = {}
+    for rec in (full, bare):
+        for k in ("obs", "state", "avail"):             # (a sentinel that compares equal to itself: slots 1 .. T keep it)
+            getattr(rec, k).fill_(-3.0)
+        rec.length.fill_(-7)
+        rec.won.fill_(-7)
+        un[rec] = torch.full((E, N + M, 5), -7, dtype=torch.int32, device=DEV)
+        ops.battle_reset(5, 0, 0, 0, False, 0, un[rec], rec, M)
+    torch.cuda.synchronize()
+    assert (full.length == T).all().item() and (full.won == 0).all().item() and not (full.obs[:, 0] == -3).all().item()
+    for k in ("obs", "state_store", "avail", "length", "won"):
+        assert torch.equal(getattr(full, k), getattr(bare, k)), k
+    assert torch.equal(un[full], un[bare]) and (full.u == -1).all().item()      # (u: as allocated)
 
 
 def _build(tmp_path, *more):

@@ -1577,9 +1577,11 @@ def test_rollout_kernels_match_numpy_env(dev):
     r, term, pad = (torch.empty(E, T, device=dev) for _ in range(3))
     alive = torch.ones(E, dtype=torch.int32, device=dev)
     act = torch.empty(E, N, dtype=torch.int32, device=dev)
+    rec = type("Record", (), dict(obs=obs, state=st, avail=av, u=u, r=r, term=term, padded=pad, length=length, won=won,
+                                  E=E, T=T, N=N, O=O, S=S, A=A))()
     rng = np.random.default_rng(0)
     for t in range(T + 1):
-        ops.synth_observe(5, 3, 2, t, length, obs, st, av, E, T, N, O, S, A)
+        ops.synth_observe(5, 3, 2, t, rec)
         live = (t <= L)
         ro = sy.obs(env, np.full(E, 2), t) * live[:, None, None]
         np.testing.assert_array_equal(obs[:, t].cpu().numpy(), ro.astype(np.float32))
@@ -1604,7 +1606,7 @@ def test_rollout_kernels_match_numpy_env(dev):
         al = alive.cpu().numpy().astype(bool)
         assert (got[al] == ref_act[al]).all()
         assert (got[~al] == -1).all()
-        ops.synth_step(5, 3, 2, t, length, act, u, r, term, pad, alive, E, T, N, A)
+        ops.synth_step(5, 3, 2, t, act, rec, alive)
         rr = sy.reward(env, np.full(E, 2), t, np.where(got < 0, 0, got))
         livet = t < L
         np.testing.assert_array_equal(r[:, t].cpu().numpy(), np.where(livet, rr, 0).astype(np.float32))

@@ -114,14 +114,20 @@ def test_three_paths_one_record(c):
     assert left_out < 0.05 * n_live
 
 
+def _record(E, T, N, O, S, A, state_ld=0, **tensors):
+    """a MarlRecord by reference: the sizes, and the data pointers of `tensors` (the other fields NULL)"""
+    import ctypes
+    from marl_amd import _lib
+    return ctypes.byref(_lib.MarlRecord(state_ld=state_ld, E=E, T=T, N=N, O=O, S=S, A=A, **{k: t.data_ptr() for k, t in tensors.items()}))
+
+
 def test_entry_points_zero_sizes_and_invalid_shapes():
     from marl_amd import _lib
     lib = _lib.load()
     s = torch.cuda.current_stream().cuda_stream
-    roll = lambda E, T, N, A: lib.marl_synth_rollout_sample(None, 1, 2, 0, 0, 0, None, None, None, 0, None, None, None, None, None,
-                                                            None, None, None, None, 0.3, 0.0, 0.0, E, T, N, 80, 120, A, 1, 1, s)
-    step = lambda E, N, A: lib.marl_synth_fused_step_sample(1, 2, 0, 0, 0, 0.3, None, None, None, None, 120, None, None, None, None,
-                                                            None, E, 8, N, 80, 120, A, s)
+    roll = lambda E, T, N, A: lib.marl_synth_rollout_sample(None, _record(E, T, N, 80, 120, A), 1, 2, 0, 0, 0, None, None, None,
+                                                            0.3, 0.0, 0.0, 1, 1, s)
+    step = lambda E, N, A: lib.marl_synth_fused_step_sample(1, 2, 0, 0, 0, 0.3, None, _record(E, 8, N, 80, 120, A, state_ld=120), s)
     assert roll(0, 8, 5, 11) == 0 and roll(4, 0, 5, 11) == 0 and step(0, 5, 11) == 0        # nothing to do: nothing launched
     assert roll(4, 8, 5, 33) == INVALID and roll(4, 8, 65, 11) == INVALID and roll(4, 8, 0, 11) == INVALID
     assert step(4, 65, 11) == INVALID          # (the fused step has no bound on A: marl_synth_fused_step's checks)
@@ -233,3 +239,33 @@ def test_runner_trains_on_whole_sampled_rollouts(alg, tmp_path):
     assert r.train_steps == 1 and np.isfinite(float(loss)) and not torch.equal(p0, r.learner._flat.flat)
     assert seen.count(True) == 1 and len(seen) >= 2               # the training rollout sampled in the kernel; evaluation is greedy
     assert getattr(env, "_stats_ring", None)
+
+
+def test_null_record_is_refused_and_unread_fields_may_be_absent():
+    """the record struct's two rules at the smallest shape that reaches them: every synthetic entry refuses rec = NULL before it looks
+    at anything else (the weights are NULL too), and marl_synth_step runs with obs / state / avail absent, to the same bits"""
+    from marl_amd import _lib, ops
+    from marl_amd.env.synthetic_smac import EpisodeRecord
+    lib = _lib.load()
+    s = torch.cuda.current_stream().cuda_stream
+    for fn in (lib.marl_synth_rollout, lib.marl_synth_rollout_sample, lib.marl_synth_rollout_x6):
+        assert fn(None, None, 1, 2, 0, 0, 0, None, None, None, 0.3, 0.0, 0.0, 1, 1, s) == INVALID
+    for fn in (lib.marl_synth_fused_step, lib.marl_synth_fused_step_sample):
+        assert fn(1, 2, 0, 0, 0, 0.3, None, None, s) == INVALID
+    assert lib.marl_synth_observe(1, 0, 0, 0, None, s) == INVALID and lib.marl_synth_step(1, 0, 0, 0, None, None, None, s) == INVALID
+    E, T, N, O, S, A = 3, 4, 2, 4, 5, 3
+    full, bare = EpisodeRecord(E, T, N, O, S, A, DEV), EpisodeRecord(E, T, N, O, S, A, DEV)
+    assert full.state.stride(-2) == 8
+    bare.obs = bare.state_store = bare.avail = None
+    act = torch.tensor([[0, 2], [1, 1], [2, 0]], dtype=torch.int32, device=DEV)
+    alive = {}
+    for rec in (full, bare):
+        ops.synth_lengths(src.ENV_SEED, 0, 0, rec.length, rec.won, E, T)
+        alive[rec] = torch.full((T, E), -9, dtype=torch.int32, device=DEV)
+        for t in range(T):
+            ops.synth_step(src.ENV_SEED, 0, 0, t, act, rec, alive[rec][t])
+    torch.cuda.synchronize()
+    assert (full.u >= 0).any().item()                    # (the steps ran: u starts at -1)
+    for f in ("u", "r", "term", "padded", "length", "won"):
+        assert torch.equal(getattr(full, f), getattr(bare, f)), f
+    assert torch.equal(alive[full], alive[bare])
