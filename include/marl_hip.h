@@ -655,6 +655,44 @@ int marl_iql_select(const float* q, const int* u, const float* q_sel, const floa
                     const float* padded, float mask_val, float* q_taken, float* q_next_bnt, int B, int T, int N, int A,
                     void* stream);
 
+/* ---- Weighted QMIX (wqmix.hip; Rashid et al., NeurIPS 2020 - the reference ships no WQMIX: the definition is this project's own) --
+ * Beside QMIX's eval agent and monotonic mixer (q, the continuation q_en, Q_tot) there are a central agent (qc; its target copy on
+ * the next inputs: qc_tgt) and an unconstrained central mixer Qc.  m = 1 - padded[b, t].
+ *
+ * marl_wqmix_select, one pass over the agent rows r = (b T + t) N + i, R = B T N.  q, qc, avail, q_en, qc_tgt, avail_next: (R, A);
+ * u (R) int32; padded (B T).  Per live row (m != 0):
+ *   q_taken[r] = q[r, u[r]],   qc_taken[r] = qc[r, u[r]]                       (a u outside [0, A): 0 for both)
+ *   u_next[r]  = first-index argmax of q_en[r, :] masked with avail_next (mask_val where it is 0),
+ *   qc_next[r] = qc_tgt[r, u_next[r]] masked the same way - marl_q_double_select's comparisons and value;
+ *   u_greedy[r] = first-index argmax of q[r, :] masked with avail - marl_q_masked_max's argmax -,  qc_greedy[r] = qc[r, u_greedy[r]]
+ *                 (not masked).  u_greedy and qc_greedy are optional (CW's); with both NULL q, qc and avail are read at u alone.
+ * avail / avail_next NULL: everything is available.  A live row with nothing available: index 0, qc_next = mask_val.
+ * A row with m = 0 gets exact zeros in the four values and -1 in the two indices; its row operands and its u enter no computation:
+ * they may hold NaN or any integer.  Up to A = 21 (31 without any availability) a wave stages 64 rows of each operand through LDS,
+ * beyond that a lane scans its row in global memory: same comparisons, same bits.
+ * Supported: 1 <= N <= 16, 1 <= A <= 32 (marl_wqmix_supported).  An unsupported shape, a NULL required pointer, B T N >= 2^31 or an
+ * output overlapping an input or another output: hipErrorInvalidValue, nothing launched.  B <= 0 or T <= 0: returns 0, no launch.
+ *
+ * marl_wqmix_loss, one pass over the rows (b, t), rows = B T.  q_tot, qc = Qc(qc_taken, s), qc_g = Qc(qc_greedy, s) (NULL: the OW
+ * weighting), qc_next_tot = Qc_target(qc_next, s'), r, term, padded: (rows); u, u_greedy: (rows, N) int32, read only with qc_g.
+ *   y = r + gamma qc_next_tot (1 - term)  (marl_td_loss's expression),   td = y - q_tot,   tdc = y - qc,
+ *   OW: w = 1 if td > 0, else alpha;     CW: w = 1 if y > qc_g or u[., i] == u_greedy[., i] for every agent i, else alpha,
+ *   dq_tot = - 2 w m (m td),   dqc = - 2 m (m tdc)   (un-normalised, as marl_td_loss's),   w (rows, optional),
+ *   out4 = { sum w (m td)^2,  sum m,  sum (m tdc)^2,  sum m [w == 1] }.
+ * The sums go through the fixed-order finish on ws = marl_loss_workspace() bytes over marl_td_loss's partition of the rows: with
+ * alpha = 1, dq_tot, out4[0], out4[1] equal marl_td_loss(q_tot, qc_next_tot, ..) and dqc, out4[2] equal marl_td_loss(qc,
+ * qc_next_tot, ..) bit for bit.  A row with m = 0 gets exact zeros in dq_tot, dqc and w and adds nothing to any sum, whatever its
+ * inputs hold (NaN included).  fp32, no float atomics: two calls give the same bits.  N outside 1..16, alpha outside [0, 1], a NULL
+ * required pointer (u / u_greedy with qc_g), rows >= 2^31 or an output overlapping an input or another output:
+ * hipErrorInvalidValue, nothing launched.  rows <= 0: returns 0, no launch. */
+int marl_wqmix_supported(int N, int A);
+int marl_wqmix_select(const float* q, const float* qc, const int* u, const float* avail, const float* q_en, const float* qc_tgt,
+                      const float* avail_next, const float* padded, float mask_val, float* q_taken, float* qc_taken,
+                      int* u_greedy, float* qc_greedy, int* u_next, float* qc_next, int B, int T, int N, int A, void* stream);
+int marl_wqmix_loss(const float* q_tot, const float* qc, const float* qc_g, const float* qc_next_tot, const float* r,
+                    const float* term, const float* padded, float gamma, const int* u, const int* u_greedy, float alpha,
+                    float* dq_tot, float* dqc, float* w, float* out4, float* ws, long rows, int N, void* stream);
+
 /* ---- stochastic policy of the policy-gradient learners (policy.hip; central-V, REINFORCE) --------
  * A row is one agent at one step: logits z (A floats, the agent's fc2 output), availability a in {0,1}^A, exploration rate eps:
  *   p = softmax(z) over all A actions,  n = sum_k a_k,  pt_k = a_k ((1 - eps) p_k + eps / n),  pi_k = pt_k / sum_j pt_j.

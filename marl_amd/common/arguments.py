@@ -44,6 +44,8 @@ def get_common_args(argv=None):
     p.add_argument('--qatten_heads', type=int, default=None)
     p.add_argument('--qatten_embed_dim', type=int, default=None)
     p.add_argument('--qatten_unit_dim', type=int, default=None)
+    # --alg ow_qmix / cw_qmix: the weight alpha in [0, 1] of the steps the weighting holds back; absent = get_wqmix_args' 0.5 / 0.75
+    p.add_argument('--wqmix_alpha', type=float, default=None)
     p.add_argument('--env', type=str, default='smac')
     # --env battle: the environment with the fused step and the whole-rollout kernel (env/battle.py: FusedBattleEnv)
     p.add_argument('--battle_fused', type=_bool, default=False)
@@ -175,6 +177,21 @@ def get_commnet_args(args):
 def get_g2anet_args(args):
     """reference :212-215"""
     return _assign(args, dict(attention_dim=32, hard=True))
+
+
+WQMIX_ALGS = ('ow_qmix', 'cw_qmix')
+
+
+def get_wqmix_args(args):
+    """This project's own table for Weighted QMIX (the reference ships none): wqmix_alpha = 0.5 for ow_qmix and 0.75 for cw_qmix
+    (the paper's SMAC values) and central_mixing_embed_dim = 256.  Values the caller set (not None) are kept; an alpha outside
+    [0, 1] is a ValueError."""
+    for k, v in dict(wqmix_alpha=0.5 if args.alg == 'ow_qmix' else 0.75, central_mixing_embed_dim=256).items():
+        if getattr(args, k, None) is None:
+            setattr(args, k, v)
+    if isinstance(args.wqmix_alpha, bool) or not 0.0 <= args.wqmix_alpha <= 1.0:
+        raise ValueError("wqmix_alpha must be a number in [0, 1], got %r" % (args.wqmix_alpha,))
+    return args
 
 
 def get_qatten_args(args):

@@ -4,6 +4,8 @@
     python -m marl_amd.main --env matrix --alg qplex --n_envs 32 --n_steps 20000
     python -m marl_amd.main --map 2s3z --alg iql --n_envs 1024 --n_steps 500000
     python -m marl_amd.main --map 2s3z --alg qatten --qatten_heads 4 --n_envs 1024 --n_steps 500000
+    python -m marl_amd.main --env matrix --alg ow_qmix --n_envs 32 --n_steps 20000
+    python -m marl_amd.main --env battle --map 3m --alg cw_qmix --wqmix_alpha 0.75 --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg central_v --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg coma --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --alg reinforce --policy_entropy_coef 0.01 --n_envs 64 --n_steps 200000
@@ -28,7 +30,7 @@ import sys
 from collections import namedtuple
 
 from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
-    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args, get_lica_args
+    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args, get_lica_args, get_wqmix_args, WQMIX_ALGS
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .env.battle import BattleEnv, FusedBattleEnv, battle_shapes
@@ -142,6 +144,8 @@ def build(argv=None):
         _share(actor.check)(args, n_agents=n, n_actions=a)      # refused before the environment is made
     get_RTW_args(args)
     get_maic_args(args)
+    if args.alg in WQMIX_ALGS:          # Weighted QMIX (WQMIXLearner): the table's alpha and central width; a --wqmix_alpha outside
+        get_wqmix_args(args)            # [0, 1] is refused before the environment is made
     if args.alg == 'qatten':            # the sizes the environment will report are the map's (the matrix game: 2 agents, state width 1):
         shapes = _map_shapes(args)
         args.n_agents, args.state_shape = (shapes[0], shapes[2]) if shapes is not None else (2, 1)

@@ -723,6 +723,75 @@ class QattenMixer(_Precision, nn.Module):
 
 
 # =====================================================================================
+class CentralFFMixer(_Precision, nn.Module):
+    """Weighted QMIX's central mixer (Rashid et al. 2020; the reference ships none), unconstrained - no abs(), no monotonicity:
+        Qc(q, s) = net([s | q]) + v(s),   net = Linear(S + N, E), ReLU, Linear(E, E), ReLU, Linear(E, E), ReLU, Linear(E, 1),
+                                          v   = Linear(S, E), ReLU, Linear(E, 1),       E = args.central_mixing_embed_dim (256)
+    The state columns come first in net's input row, and the row is never built: the first layer reads the two-segment source
+    (x0 = s, x1 = q) of marl_linear / marl_linear_wgrad.  Only the N agent columns of the first layer's input gradient are needed;
+    the weight view net.0.weight[:, S:] yields them.  Every layer goes through ``self._lin``, so args.mixer_dtype = "bf16" reaches
+    them; args.gemm_mode = "bf16x6" leaves the products on fp32 (no split kernel exists for these layers, as for Qatten's)."""
+
+    def __init__(self, args):
+        super().__init__()
+        self.args = args
+        S, N = int(np.prod(args.state_shape)), args.n_agents
+        E = getattr(args, "central_mixing_embed_dim", None) or 256
+        self.state_dim, self.embed_dim = S, E
+        self.net = _mlp(None, [S + N, E, E, E, 1])
+        self.v = _mlp(None, [S, E, 1])
+        self._s = Scratch()
+
+    def hip_forward(self, q, s, rows, ctx=None, tag="e"):
+        """q (rows, N), s (rows, S) or ops.Rows -> Qc (rows); with ctx the activations hip_backward needs are kept in it"""
+        E, dev, g = self.embed_dim, q.device, self._s.get
+        n0, n2, n4, n6 = _linears(self.net)
+        v0, v2 = _linears(self.v)
+        h1, h2, h3, hv = (g(k + tag, (rows, E), dev) for k in ("h1", "h2", "h3", "hv"))
+        out, vout = g("qc" + tag, (rows,), dev), g("v" + tag, (rows,), dev)
+        self._lin(n0).fwd(ops.src(x0=s, x1=q), h1, rows, act=1)
+        self._lin(n2).fwd(ops.src(h1), h2, rows, act=1)
+        self._lin(n4).fwd(ops.src(h2), h3, rows, act=1)
+        self._lin(n6).fwd(ops.src(h3), out.view(rows, 1), rows)
+        self._lin(v0).fwd(ops.src(s), hv, rows, act=1)
+        self._lin(v2).fwd(ops.src(hv), vout.view(rows, 1), rows)
+        ops.vec_add(out, vout, out, rows)
+        if ctx is not None:
+            ctx.update(s=s, q=q, h1=h1, h2=h2, h3=h3, hv=hv)
+        return out
+
+    def hip_backward(self, ctx, dqc, rows):
+        """dqc (rows) = dL/dQc -> dL/dq (rows, N); the parameter gradients are accumulated into .grad"""
+        E, S, N, dev, g = self.embed_dim, self.state_dim, self.args.n_agents, dqc.device, self._s.get
+        n0, n2, n4, n6 = _linears(self.net)
+        v0, v2 = _linears(self.v)
+        s, q, h1, h2, h3, hv = (ctx[k] for k in ("s", "q", "h1", "h2", "h3", "hv"))
+        dout = dqc.view(rows, 1)
+        da, db = g("da", (rows, E), dev), g("db", (rows, E), dev)
+        self._lin(v2).wgrad(dout, ops.src(hv), rows)
+        self._lin(v2).bwd_x(dout, da, rows)
+        self._lin(v0).wgrad(da, ops.src(s), rows, Yact=hv)
+        self._lin(n6).wgrad(dout, ops.src(h3), rows)
+        self._lin(n6).bwd_x(dout, da, rows)                                           # dh3 (before its ReLU)
+        self._lin(n4).wgrad(da, ops.src(h2), rows, Yact=h3)
+        self._lin(n4).bwd_x(da, db, rows, Yact=h3)                                    # dh2
+        self._lin(n2).wgrad(db, ops.src(h1), rows, Yact=h2)
+        self._lin(n2).bwd_x(db, da, rows, Yact=h2)                                    # dh1
+        self._lin(n0).wgrad(da, ops.src(x0=s, x1=q), rows, Yact=h1)
+        dq = g("dq", (rows, N), dev)
+        ops.linear(ops.src(da, gate=h1), n0.weight.data[:, S:], None, dq, rows, N, E, w_kmajor=True, bf16=self._bf16())
+        return dq
+
+    def forward(self, q_values, states):
+        dev = require_cuda("CentralFFMixer")
+        self.to(dev)
+        B = q_values.shape[0]
+        q = to_dev(q_values, dev).reshape(-1, self.args.n_agents)
+        s = to_dev(states, dev).reshape(-1, self.state_dim)
+        return self.hip_forward(q, s, q.shape[0]).clone().view(B, -1, 1)
+
+
+# =====================================================================================
 class _QtranFusedHead:
     """Fused path shared by QtranQBase (one-hot actions, A = n_actions) and QtranV (A = 0): csrc/qtran_fused.hip.
     The subclass provides ``_qt_layers()`` -> (enc.0, enc.2, head.0, head.2, head.4) and ``_qt_actions()``."""

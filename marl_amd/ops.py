@@ -595,6 +595,36 @@ def iql_select(q, u, q_sel, q_tgt, avail_next, padded, mask_val, q_taken, q_next
     return q_next_bnt
 
 
+def wqmix_supported(N, A):
+    return bool(_lib.load().marl_wqmix_supported(int(N), int(A)))
+
+
+def wqmix_select(q, qc, u, avail, q_en, qc_tgt, avail_next, padded, mask_val, q_taken, qc_taken, u_next, qc_next, B, T, N, A,
+                 u_greedy=None, qc_greedy=None):
+    """Weighted QMIX's selections in one pass over the R = B T N agent rows (csrc/wqmix.hip): the taken action's Q of the eval and
+    of the central agent, the double-Q greedy next action by q_en with the target central agent's masked Q there and - for CW, when
+    u_greedy / qc_greedy are given - the current greedy action by q with the central agent's Q there."""
+    _iql_rows(B, T, N, A, (q, qc, avail, q_en, qc_tgt, avail_next), (u, q_taken, qc_taken, u_next, qc_next, u_greedy, qc_greedy),
+              (padded,))
+    check(_lib.load().marl_wqmix_select(_p(_f32(q)), _p(_f32(qc)), _p(_i32(u)), _p(avail), _p(_f32(q_en)), _p(_f32(qc_tgt)),
+                                        _p(avail_next), _p(_f32(padded)), float(mask_val), _p(_f32(q_taken)), _p(_f32(qc_taken)),
+                                        _p(u_greedy), _p(qc_greedy), _p(_i32(u_next)), _p(_f32(qc_next)), int(B), int(T), int(N),
+                                        int(A), _stream()), "marl_wqmix_select")
+
+
+def wqmix_loss(q_tot, qc, qc_g, qc_next_tot, r, term, padded, gamma, u, u_greedy, alpha, dq_tot, dqc, out4, rows, N, w=None):
+    """Weighted QMIX's loss over the B T rows (csrc/wqmix.hip): the target of the target central mixer's value, the OW (qc_g None)
+    or CW weight, dq_tot = -2 w m (m td), dqc = -2 m (m tdc) and out4 = {sum w (m td)^2, sum m, sum (m tdc)^2, sum m [w == 1]}."""
+    lib = _lib.load()
+    for t, n in [(x, rows) for x in (q_tot, qc, qc_g, qc_next_tot, r, term, padded, dq_tot, dqc, w)] + \
+                [(x, rows * N) for x in (u, u_greedy)]:
+        assert t is None or (t.is_cuda and t.is_contiguous() and t.numel() >= n), "wqmix_loss: contiguous device arrays of the rows' sizes"
+    ws = WS.get("loss", lib.marl_loss_workspace(rows), q_tot.device)
+    check(lib.marl_wqmix_loss(_p(_f32(q_tot)), _p(_f32(qc)), _p(qc_g), _p(_f32(qc_next_tot)), _p(_f32(r)), _p(_f32(term)),
+                              _p(_f32(padded)), float(gamma), _p(u), _p(u_greedy), float(alpha), _p(_f32(dq_tot)), _p(_f32(dqc)),
+                              _p(w), _p(_f32(out4)), _p(ws), int(rows), int(N), _stream()), "marl_wqmix_loss")
+
+
 def policy_probs(logits, avail, eps, pi, rows, A):
     """pi (rows, A) of the stochastic policy (csrc/policy.hip): softmax of the logits, mixed with eps of the uniform policy over the
     available actions, renormalised over them; a row without an available action is all zeros"""

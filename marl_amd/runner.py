@@ -50,6 +50,10 @@ end in 'learner iql cannot find!'.
 ``args.alg == 'qatten'`` (no agent switch on): SharedMAC, the replay buffer and QLearner with QattenMixer (network/mixer.py).  With
 RTW, world_model or MAIC it raises ValueError before anything is built: their learners keep their own three-mixer tables.
 
+``args.alg == 'ow_qmix'`` / ``'cw_qmix'`` (no agent switch on): SharedMAC, the replay buffer and WQMIXLearner (algorithm/wqmix.py),
+Weighted QMIX.  The names are decided before the value-mixer branch, whose substring match would take them for qmix.  With RTW,
+world_model or MAIC it raises ValueError before anything is built.  Rollouts act through the eval agent alone.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -73,6 +77,7 @@ from .algorithm.maic_td_learner import MAICTDLearner
 from .algorithm.central_v import CentralVLearner
 from .algorithm.reinforce import ReinforceLearner
 from .algorithm.iql import IQLLearner
+from .algorithm.wqmix import WQMIXLearner, WQMIX_ALGS
 from .utils.logging import Logger
 
 
@@ -124,6 +129,10 @@ class Runner:
         on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
         if args.alg == 'qatten' and on:      # their learners keep their own three-mixer tables
             raise ValueError("qatten mixes the plain shared agent's values in QLearner: not with %s" % on[0].name)
+        wqmix = args.alg in WQMIX_ALGS       # decided before _value_mixer, whose substring match would take the names for qmix
+        if wqmix and on:
+            raise ValueError("%s trains the plain shared agent beside a central one in WQMIXLearner: not with %s"
+                             % (args.alg, on[0].name))
         self.on_policy = learner_cls is not None or args.alg in _ON_POLICY
         if self.on_policy:
             if on:
@@ -156,6 +165,8 @@ class Runner:
         self.logger = logger
         if self.on_policy:
             self.learner = (learner_cls or _ON_POLICY[args.alg])(self.mac, args)
+        elif wqmix:
+            self.learner = WQMIXLearner(self.mac, args)
         elif _value_mixer(args):
             self.learner = make_learner(self.mac, logger, args)
         elif _qtran(args):
