@@ -1242,6 +1242,61 @@ int marl_battle_rollout_sample(const marl_agent_weights_t* w, const marl_record_
                                float* stats, double eps0, double eps_anneal, double eps_min, int M, int last_action,
                                int reuse_network, void* stream);
 
+/* ---- MAVEN (maven.hip; Mahajan et al., NeurIPS 2019 - the reference ships no MAVEN: the definition is this project's own) ---------
+ * Sizes: K = noise_dim (1..32), H = 64, N agents (1..16), A actions (1..32), state width S, discriminator width D = 64.
+ * Noise: every episode carries one index k in [0, K): marl_maven_noise writes noise[e] = hkey(rseed, stream 24, env0 + e, tg0, 0) % K
+ *   for e < E (the counter hash of synth_env.h; stream 24 is declared in maven.hip), exploring or evaluating.
+ * Agent: the plain shared agent plus the tables noise_w (K, A, H), id_w (N, A, H), noise_b (K, A), id_b (N, A); for episode b with
+ *   noise k_b, agent n, hidden state h:   q'(b, t, n, :) = fc2(h) + (noise_w[k_b] + id_w[n]) h + noise_b[k_b] + id_b[n]
+ *   - a hyper-layer Linear(K + N -> A H) applied to [one-hot(k) | one-hot(n)], whose bias matrix is fc2.
+ * marl_maven_head_fwd: q (B, T, N, A) += the term, from hs (B, T, N, 64) and noise (B); an episode with k < 0 or k >= K is skipped:
+ *   its q rows are not touched and its hs rows are not read.  A rollout step is B = E, T = 1.  fp32 in either gemm_mode.
+ * marl_maven_head_bwd: g = scatter of the sparse pairs (dq_idx, dq_val) (both NULL: none) + dq_dense (NULL: 0), all over (B, T, N);
+ *   writes dq_out (B, T, N, A) = g and dhs (B, T, N, 64) = g (noise_w[k_b] + id_w[n]) (zeros for a skipped episode), and ADDS
+ *   d noise_w[k] += sum over the rows with k_b = k of g h^T, d id_w[n] += sum over the rows of agent n, d noise_b / d id_b likewise
+ *   (a skipped episode adds nothing).  Partials: one slab of ws per workgroup, episodes in order, slabs added in slab order.
+ * Discriminator, for a step (b, t) with m = 1 - padded:  p_n = softmax over the available actions of q'(b, t, n, :) (unavailable: 0),
+ *   x = [p_0 | .. | p_{N-1} | s_{b,t}],  logits = W2 relu(W1 x + b1) + b2  (W1 (D, N A + S), W2 (K, D)),  ce = logsumexp(logits) - logits[k_b].
+ * marl_maven_mi, one row launch over the rows = B T steps, forward and backward:  stats2[0] += sum m ce,  stats2[1] += sum m [argmax
+ *   logits == k_b] (first index);  the gradients of lambda_mi sum m ce are ADDED into g (W1, b1, W2, b2) and written to dq_dense
+ *   (B, T, N, A) through the softmax - exact zeros at padded steps and unavailable actions; no den factor (the optimizer divides).
+ *   ce (rows) receives the per-step ce (0 where padded).  avail of (b, t, n) is read at avail + e avail_bs + (t N + n) A and
+ *   the state row at state + (e state_bs + t) state_ld, with e = ep_map ? ep_map[b] : b (a replay sample reads the ring in place);
+ *   x exists in LDS only.  A padded step, and a step of an episode with k_b outside [0, K), reads neither q, avail nor state.
+ * Two calls on the same input give the same bits (no float atomics).  Supported (marl_maven_supported): the ranges above, D = 64 and
+ *   N A + S small enough for a 16-step tile of x in LDS (96 KB with the kernel's other tiles; N A + S <= 832 always fits).  An unsupported shape,
+ *   a NULL required pointer, a misaligned base (hs, noise_w, id_w in both head entries and W2: 16 bytes; every other base: 4 bytes), a short workspace, B T N >= 2^31 (the MI pass: B T > 2^31 - 2^20) or lambda_mi < 0 is
+ *   hipErrorInvalidValue before anything is read or written; B T = 0 launches nothing.
+ * marl_maven_plan (host only), plan[8]: [0] 16-step tiles per (episode, agent) of the head  [1] head forward workgroups  [2] slabs
+ *   (= workgroups) of the head backward  [3] 16-step tiles of the MI pass  [4] its workgroups = slabs  [5] its dynamic LDS bytes
+ *   [6] tiles the busiest MI workgroup walks  [7] LDS pitch of x in floats. */
+typedef struct {
+  const float *noise_w, *id_w, *noise_b, *id_b;
+} marl_maven_weights_t;
+typedef struct {
+  float *noise_w, *id_w, *noise_b, *id_b;
+} marl_maven_grads_t;
+typedef struct {
+  const float *w1, *b1, *w2, *b2;
+} marl_maven_disc_t;
+typedef struct {
+  float *w1, *b1, *w2, *b2;
+} marl_maven_disc_grads_t;
+int marl_maven_supported(int N, int A, int K, int S, int D);
+int marl_maven_plan(int B, int T, int N, int A, int K, int S, int* plan);
+size_t marl_maven_bwd_workspace(int B, int N, int A, int K);
+size_t marl_maven_mi_workspace(long rows, int N, int A, int K, int S);
+int marl_maven_noise(unsigned rseed, int env0, unsigned tg0, int K, int* noise, int E, void* stream);
+int marl_maven_head_fwd(const marl_maven_weights_t* w, const float* hs, const int* noise, float* q, int B, int T, int N, int A,
+                        int K, void* stream);
+int marl_maven_head_bwd(const marl_maven_weights_t* w, const marl_maven_grads_t* g, const float* hs, const int* noise,
+                        const int* dq_idx, const float* dq_val, const float* dq_dense, float* dq_out, float* dhs, float* ws,
+                        size_t ws_bytes, int B, int T, int N, int A, int K, void* stream);
+int marl_maven_mi(const marl_maven_disc_t* d, const marl_maven_disc_grads_t* g, const float* q, const float* avail,
+                  long avail_bs, const float* state, long state_ld, long state_bs, const int* ep_map, const int* noise,
+                  const float* padded, float lambda_mi, float* dq_dense, float* ce, float* stats2, float* ws, size_t ws_bytes,
+                  int B, int T, int N, int A, int S, int K, void* stream);
+
 const char* marl_hip_version(void);
 
 /* Experiment switches (A/B measurements, variant tests): one table per process; NO entry point reads the environment.

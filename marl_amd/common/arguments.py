@@ -46,6 +46,10 @@ def get_common_args(argv=None):
     p.add_argument('--qatten_unit_dim', type=int, default=None)
     # --alg ow_qmix / cw_qmix: the weight alpha in [0, 1] of the steps the weighting holds back; absent = get_wqmix_args' 0.5 / 0.75
     p.add_argument('--wqmix_alpha', type=float, default=None)
+    # --alg maven: the number of noise values K in [1, 32] and the weight of the mutual-information term (>= 0); absent = the table's
+    # noise_dim = 16 and lambda_mi = 0.001 (get_mixer_args / get_maven_args)
+    p.add_argument('--noise_dim', type=int, default=None)
+    p.add_argument('--lambda_mi', type=float, default=None)
     p.add_argument('--env', type=str, default='smac')
     # --env battle: the environment with the fused step and the whole-rollout kernel (env/battle.py: FusedBattleEnv)
     p.add_argument('--battle_fused', type=_bool, default=False)
@@ -95,7 +99,7 @@ def get_mixer_args(args):
     args.lambda_opt = 1
     args.lambda_nopt = 1
     args.grad_norm_clip = 10
-    args.noise_dim, args.lambda_mi, args.lambda_ql, args.entropy_coefficient = 16, 0.001, 1, 0.001   # MAVEN (unused here)
+    args.noise_dim, args.lambda_mi, args.lambda_ql, args.entropy_coefficient = 16, 0.001, 1, 0.001   # MAVEN (--alg maven reads the first two: get_maven_args)
     args.adv_hypernet_embed = 64
     args.num_kernel = 10
     args.adv_hypernet_layers = 3
@@ -191,6 +195,21 @@ def get_wqmix_args(args):
             setattr(args, k, v)
     if isinstance(args.wqmix_alpha, bool) or not 0.0 <= args.wqmix_alpha <= 1.0:
         raise ValueError("wqmix_alpha must be a number in [0, 1], got %r" % (args.wqmix_alpha,))
+    return args
+
+
+def get_maven_args(args):
+    """This project's own table for MAVEN (the reference's tables carry noise_dim = 16 and lambda_mi = 0.001 and ship no MAVEN to
+    read them): those two and the discriminator's width maven_discrim_dim = 64.  Values the caller set (not None) are kept; a
+    noise_dim outside [1, 32] or a negative lambda_mi is a ValueError."""
+    for k, v in dict(noise_dim=16, lambda_mi=0.001, maven_discrim_dim=64).items():
+        if getattr(args, k, None) is None:
+            setattr(args, k, v)
+    K, lam = args.noise_dim, args.lambda_mi
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 32:
+        raise ValueError("noise_dim must be an integer in [1, 32], got %r" % (K,))
+    if isinstance(lam, bool) or not lam >= 0.0:
+        raise ValueError("lambda_mi must be a number >= 0, got %r" % (lam,))
     return args
 
 

@@ -19,6 +19,7 @@ from ..network.world_model import Agent as WorldAgent
 from ..network.maic import MAICAgent
 from ..network.commnet import CommNetAgent, FRONT_A
 from ..network.g2anet import G2ANetAgent, tau_of
+from ..network.maven import MavenAgent, maven_shape_of
 
 
 class SharedMAC:
@@ -562,6 +563,62 @@ class G2ANetMAC(GroupHeadMAC):
         ag = self.agent
         ops.g2anet_head_bwd(ag.head_weights(), ag.head_grads(), hs, noise if self.hard else None, dlogits, dhs, G, self.n_agents,
                             self.n_actions, self.hard, self.tau)
+
+
+class MAVENMAC(SharedMAC):
+    """SharedMAC over a MavenAgent (network/maven.py; the project's own definition - DESIGN section 9).  Every pass is the agent unroll
+    followed by the noise-conditioned head (csrc/maven.hip), which adds (noise_w[k_b] + id_w[n]) h + noise_b[k_b] + id_b[n] to q.
+    Every episode carries one noise index k_b in [0, noise_dim): a batched rollout draws it at its first lock-step from the counter hash
+    keyed by (seed, environment, the rollout's first global step) - exploring or evaluating - keeps it in ``self.noise`` and leaves it
+    on the record (``rec.noise``), from where the replay ring and the learner's batch carry it.  The serial ``choose_action`` path has no
+    episode to hang the draw on and is not provided."""
+
+    head_name = "MAVEN"
+
+    def __init__(self, args):
+        self.noise_dim, _ = maven_shape_of(args)       # raises before anything is built
+        SharedMAC.__init__(self, args)
+        self.noise = None             # (E,) int32: the noise indices of the rollout in progress
+
+    def _build_agents(self, input_shape):
+        self.agent = MavenAgent(input_shape, self.args)
+
+    def choose_action(self, obs, last_action, agent_num, avail_actions, epsilon, evaluate=False):
+        raise NotImplementedError("MAVENMAC.choose_action: the noise index is drawn once per episode of a batched rollout - use a "
+                                  "batched rollout")
+
+    def _step_head(self, h_out, q, obs_full, avail, evaluate):
+        raise NotImplementedError("MAVENMAC has no serial step: the noise index is drawn once per episode of a batched rollout")
+
+    def rollout_head(self, h, q, rec, t, E, evaluate, rseed, env):
+        """at t = 0 the episodes' noise is drawn and left on the record; at every step q (E,1,N,A) += the head's term on h"""
+        if E == 0:
+            return
+        if t == 0:
+            self.noise = torch.empty(E, dtype=torch.int32, device=h.device)      # a fresh array: the last record keeps its own
+            ops.maven_noise(rseed, env.env0, env.global_step(0), self.noise_dim, self.noise, E)
+            rec.noise = self.noise
+        ops.maven_head_fwd(self.agent.maven_weights(), h, self.noise, q, E, 1, self.n_agents, self.n_actions, self.noise_dim)
+
+    def head(self, hs, noise, q, B, T):
+        """q (B,T,N,A) += the head's term from hs (B,T,N,64) and the episodes' noise (B,) int32"""
+        ops.maven_head_fwd(self.agent.maven_weights(), hs, noise, q, B, T, self.n_agents, self.n_actions, self.noise_dim)
+
+    def _maven_q_values(self, batch, T, which):
+        if not dict.__contains__(batch, "noise"):
+            raise ValueError("MAVENMAC needs the batch's noise indices (batch['noise'], one per episode)")
+        q, hs = self._batch_unroll(batch, T, which)
+        noise = to_dev(batch["noise"], q.device, torch.int32).view(q.shape[0])
+        self.head(hs, noise, q, q.shape[0], T)
+        return q, hs
+
+    def get_current_q_values(self, batch, max_episode_len):
+        """q (B,T,N,A) with the head's term for batch['noise'], and hs (B,T,N,H)"""
+        return self._maven_q_values(batch, max_episode_len, "cur")
+
+    def get_next_q_values(self, batch, max_episode_len):
+        """as get_current_q_values on (o_next, u_onehot[t])"""
+        return self._maven_q_values(batch, max_episode_len, "next")
 
 
 class RTWMAC(SharedMAC):

@@ -258,6 +258,8 @@ class DeviceBatch:
     def __init__(self):
         self.extra = {}
         self.ep_len = None      # per-episode lengths when obs is (T+1)-slot storage
+        self.noise = None       # (B,) int32: the episodes' MAVEN noise index, where the batch carries one
+        self.avail_store = None  # (tensor, floats per episode): where the current-step availability lies in place (from_record)
 
     @staticmethod
     def first_terminated_len(term, episode_limit, reducer=None):
@@ -318,6 +320,8 @@ class DeviceBatch:
         self.padded = cut("padded").view(B * T)
         self.avail = cut("avail_u").view(B * T * N, A)
         self.avail_next = cut("avail_u_next").view(B * T * N, A)
+        if dict.__contains__(batch, "noise"):
+            self.noise = to_dev(batch["noise"], device, torch.int32).view(B)
         return self
 
     @classmethod
@@ -397,6 +401,8 @@ class DeviceBatch:
             self._avail = rec.avail_cur[:, :T].reshape(E * T * N, A)
         self._avail_src = (rec, T) if rec.avail is not None else (big, T, idx, rec.length)
         self.avail_next = (rec.avail_next[:, :T] if fused else rec.avail[:, 1:T + 1]).reshape(E * T * N, A)
+        self.avail_store = (big.avail, (Ta + 1) * N * A)        # slot t of episode o_map[b] (no map: b), not masked past the episode's end
+        self.noise = getattr(rec, "noise", None)
         return self
 
     @property

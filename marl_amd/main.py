@@ -19,6 +19,7 @@
     python -m marl_amd.main --map 2s3z --alg coma+g2anet --n_envs 64 --n_steps 200000
     python -m marl_amd.main --map 2s3z --MAIC True --load_model True --evaluate True --evaluate_epoch 1 --n_envs 64
     python -m marl_amd.main --env battle --map 3m --alg qmix --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --env battle --map 3m --alg maven --noise_dim 16 --lambda_mi 0.001 --n_envs 64 --n_steps 200000
 
 ``--env synthetic`` (default) uses the synthetic SMAC-shaped device env with the dims of ``--map``;
 ``--env matrix`` the batched two-agent matrix game; ``--env battle`` the micro-combat simulator in SMAC's layout (env/battle.py:
@@ -30,7 +31,7 @@ import sys
 from collections import namedtuple
 
 from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get_maic_args, get_centralv_args, \
-    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args, get_lica_args, get_wqmix_args, WQMIX_ALGS
+    get_reinforce_args, get_coma_args, get_commnet_args, get_g2anet_args, get_mappo_args, get_qatten_args, get_lica_args, get_wqmix_args, get_maven_args, WQMIX_ALGS
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .env.battle import BattleEnv, FusedBattleEnv, battle_shapes
@@ -111,9 +112,30 @@ def _lica(args):
     lica_shape_of(args)
 
 
+def _maven(args, early=False):
+    """the MAVEN kernels' shape check (network/maven.py: maven_shape_of): a noise_dim, a lambda_mi or sizes outside their range are
+    a ValueError here.  ``early``: with the map's sizes, before the environment is made (the matrix game: 2 agents, 3 actions, width 1)"""
+    from .network.maven import maven_shape_of
+    if early:
+        shapes = _map_shapes(args)
+        n, s, a = (shapes[0], shapes[2], shapes[3]) if shapes is not None else (2, 1, 3)
+        maven_shape_of(args, n_agents=n, n_actions=a, state_shape=s)
+    else:
+        maven_shape_of(args)
+
+
 def build(argv=None):
     args = get_common_args(argv)
+    given_maven = (args.noise_dim, args.lambda_mi)      # get_mixer_args assigns the table's values over them
     get_mixer_args(args)
+    if args.alg == 'maven':
+        on = [sw for sw in ('RTW', 'world_model', 'MAIC') if getattr(args, sw, False)]
+        if on:
+            raise ValueError("maven trains the noise-conditioned shared agent in MAVENLearner: not with %s" % on[0])
+        for k, v in zip(('noise_dim', 'lambda_mi'), given_maven):
+            if v is not None:           # the table's values are defaults, not overrides of the switches
+                setattr(args, k, v)
+        get_maven_args(args)            # a bad --noise_dim / --lambda_mi is refused before anything is built
     if args.env == 'battle':
         battle_shapes(args.map)         # a map the battle environment does not have is refused before anything is built
     base, actor = actor_base(args.alg, entry=True)           # raises on a Q-learning algorithm with an actor suffix
@@ -154,6 +176,8 @@ def build(argv=None):
         shapes = _map_shapes(args)
         args.n_agents, args.n_actions, args.state_shape = (shapes[0], shapes[3], shapes[2]) if shapes is not None else (2, 3, 1)
         _lica(args)                     # refused before the environment is made
+    if args.alg == 'maven':
+        _maven(args, early=True)        # refused before the environment is made
     if args.env == 'smac':
         args.env = 'synthetic'
     if args.env == 'synthetic':
@@ -175,6 +199,8 @@ def build(argv=None):
         _qatten(args)                   # ... and with the environment's own sizes
     if args.alg == 'lica':
         _lica(args)
+    if args.alg == 'maven':
+        _maven(args)
     if actor is not None:
         _share(actor.check)(args)       # ... and the environment's agent and action counts with it, before a controller is built
     return args, env

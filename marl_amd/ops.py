@@ -14,7 +14,7 @@ from . import _lib
 from ._lib import (MarlSrc, MarlGroup, MarlAgentWeights, MarlAgentGrads, MarlQmixWeights, MarlMlp3Weights,
                    MarlQtranWeights, MarlRtwWeights, MarlWorldWeights, MarlWorldGrads, MarlMaicWeights, MarlMaicGrads, MarlMaicInfer,
                    MarlMaicInferGrads, MarlCommnetWeights, MarlCommnetGrads, MarlG2anetWeights, MarlG2anetGrads, MarlRecord,
-                   check)
+                   MarlMavenWeights, MarlMavenGrads, MarlMavenDisc, MarlMavenDiscGrads, check)
 
 
 def _p(t):
@@ -501,6 +501,94 @@ def lica_loss_bwd(hy, u, q_tgt, r, term, padded, gamma, q, dhy, dq_tot, out2, ro
     check(lib.marl_lica_loss_bwd(_p(_f32(hy)), hy.stride(0), _p(_i32(u)), _p(_f32(q_tgt)), _p(_f32(r)), _p(_f32(term)),
                                  _p(_f32(padded)), float(gamma), _p(_f32(q)), _p(_f32(dhy)), dhy.stride(0), _p(_f32(dq_tot)),
                                  _p(_f32(out2)), _p(ws), rows, N, A, E, _stream()), "marl_lica_loss_bwd")
+
+
+# ---- MAVEN (csrc/maven.hip): the episode noise, the noise-conditioned agent head, the MI pass
+MAVEN_TABLES = ("noise_w", "id_w", "noise_b", "id_b")
+MAVEN_DISC = (("w1", "l1.weight"), ("b1", "l1.bias"), ("w2", "l2.weight"), ("b2", "l2.bias"))
+
+
+def maven_supported(N, A, K, S, D=64):
+    """csrc/maven.hip covers the shape: N <= 16, A <= 32, K <= 32, D = 64 and N A + S within a 16-step tile of x in LDS"""
+    return bool(_lib.load().marl_maven_supported(int(N), int(A), int(K), int(S), int(D)))
+
+
+def maven_plan(B, T, N, A, K, S):
+    """(head tiles per (episode, agent), head forward workgroups, head backward slabs, MI tiles, MI workgroups = slabs, MI LDS bytes,
+    tiles the busiest MI workgroup walks, LDS pitch of x) - include/marl_hip.h: marl_maven_plan"""
+    plan = (C.c_int * 8)()
+    check(_lib.load().marl_maven_plan(int(B), int(T), int(N), int(A), int(K), int(S), plan), "marl_maven_plan")
+    return tuple(plan)
+
+
+def maven_weights(tensors, prefix="maven."):
+    """tensors: dict name -> tensor holding <prefix>noise_w (K,A,64), id_w (N,A,64), noise_b (K,A), id_b (N,A) -> marl_maven_weights_t"""
+    return _fill_struct(MarlMavenWeights, tensors, [(f, prefix + f, torch.float32) for f in MAVEN_TABLES])
+
+
+def maven_grads(grads, prefix="maven."):
+    """the gradient destinations of the same four tables -> marl_maven_grads_t"""
+    return _fill_struct(MarlMavenGrads, grads, [(f, prefix + f, torch.float32) for f in MAVEN_TABLES])
+
+
+def maven_disc(tensors):
+    """tensors: dict with l1.weight (64, N A + S), l1.bias, l2.weight (K, 64), l2.bias -> marl_maven_disc_t"""
+    return _fill_struct(MarlMavenDisc, tensors, [(f, name, torch.float32) for f, name in MAVEN_DISC])
+
+
+def maven_disc_grads(grads):
+    return _fill_struct(MarlMavenDiscGrads, grads, [(f, name, torch.float32) for f, name in MAVEN_DISC])
+
+
+def maven_noise(rseed, env0, tg0, K, noise, E):
+    """noise (E,) int32 <- hkey(rseed, stream 24, env0 + e, tg0, 0) % K"""
+    assert _i32(noise).is_contiguous() and noise.numel() >= E
+    check(_lib.load().marl_maven_noise(int(rseed) & 0xFFFFFFFF, int(env0), int(tg0) & 0xFFFFFFFF, int(K), _p(noise), int(E), _stream()),
+          "marl_maven_noise")
+
+
+def maven_head_fwd(w, hs, noise, q, B, T, N, A, K):
+    """q (B,T,N,A) += (noise_w[k_b] + id_w[n]) h + noise_b[k_b] + id_b[n] from hs (B,T,N,64) and noise (B,) int32; an episode whose
+    index is outside [0, K) is left alone"""
+    assert hs.is_contiguous() and q.is_contiguous() and hs.numel() >= B * T * N * 64 and q.numel() >= B * T * N * A
+    assert _i32(noise).is_contiguous() and noise.numel() >= B
+    check(_lib.load().marl_maven_head_fwd(C.byref(w), _p(_f32(hs)), _p(noise), _p(_f32(q)), int(B), int(T), int(N), int(A), int(K),
+                                          _stream()), "marl_maven_head_fwd")
+
+
+def maven_head_bwd(w, g, hs, noise, dq_idx, dq_val, dq_dense, dq_out, dhs, B, T, N, A, K):
+    """dq_out (B,T,N,A) = scatter(dq_idx, dq_val) + dq_dense (either may be None) and dhs (B,T,N,64) written; the four table
+    gradients added into g (slabs of episodes, summed in slab order)"""
+    lib = _lib.load()
+    R = B * T * N
+    assert hs.is_contiguous() and dq_out.is_contiguous() and dhs.is_contiguous() and dq_out.numel() >= R * A and dhs.numel() >= R * 64
+    assert _i32(noise).is_contiguous() and noise.numel() >= B
+    assert (dq_idx is None) == (dq_val is None)
+    if dq_idx is not None:
+        assert _i32(dq_idx).is_contiguous() and _f32(dq_val).is_contiguous() and dq_idx.numel() >= R and dq_val.numel() >= R
+    if dq_dense is not None:
+        assert _f32(dq_dense).is_contiguous() and dq_dense.numel() >= R * A
+    ws = WS.get("maven_bwd", lib.marl_maven_bwd_workspace(int(B), int(N), int(A), int(K)), hs.device)
+    check(lib.marl_maven_head_bwd(C.byref(w), C.byref(g), _p(_f32(hs)), _p(noise), _p(dq_idx), _p(dq_val), _p(dq_dense),
+                                  _p(_f32(dq_out)), _p(_f32(dhs)), _p(ws), ws.numel() * 4, int(B), int(T), int(N), int(A), int(K),
+                                  _stream()), "marl_maven_head_bwd")
+
+
+def maven_mi(d, g, q, avail, avail_bs, state, state_ld, state_bs, ep_map, noise, padded, lambda_mi, dq_dense, ce, stats2,
+             B, T, N, A, S, K):
+    """The MI pass over the B T steps (include/marl_hip.h: marl_maven_mi): stats2 += {sum m ce, sum m hit}, the discriminator's
+    gradients added into g, dq_dense (B,T,N,A) and ce (B T) written.  avail / state are read in place: episode b lies at
+    ep_map[b] (None: b) with strides avail_bs (floats per episode) and state_bs (rows per episode) x state_ld (floats per row)"""
+    lib = _lib.load()
+    assert q.is_contiguous() and dq_dense.is_contiguous() and dq_dense.numel() >= B * T * N * A and ce.numel() >= B * T
+    assert _i32(noise).is_contiguous() and noise.numel() >= B and _f32(padded).is_contiguous() and padded.numel() >= B * T
+    assert ep_map is None or (_i32(ep_map).is_contiguous() and ep_map.numel() >= B)
+    assert stats2.numel() == 2 and stats2.is_contiguous()
+    ws = WS.get("maven_mi", lib.marl_maven_mi_workspace(int(B) * int(T), int(N), int(A), int(K), int(S)), q.device)
+    check(lib.marl_maven_mi(C.byref(d), C.byref(g), _p(_f32(q)), _p(_f32(avail)), int(avail_bs), _p(_f32(state)), int(state_ld),
+                            int(state_bs), _p(ep_map), _p(noise), _p(padded), float(lambda_mi), _p(_f32(dq_dense)), _p(_f32(ce)),
+                            _p(_f32(stats2)), _p(ws), ws.numel() * 4, int(B), int(T), int(N), int(A), int(S), int(K), _stream()),
+          "marl_maven_mi")
 
 
 _FT_OUT = {}

@@ -54,6 +54,10 @@ RTW, world_model or MAIC it raises ValueError before anything is built: their le
 Weighted QMIX.  The names are decided before the value-mixer branch, whose substring match would take them for qmix.  With RTW,
 world_model or MAIC it raises ValueError before anything is built.  Rollouts act through the eval agent alone.
 
+``args.alg == 'maven'`` (no agent switch on): MAVENMAC, the replay buffer and MAVENLearner (algorithm/maven.py).  Rollouts take the
+per-step path (the whole-rollout kernels have no MAVEN head) and draw one noise index per episode, which the records and the replay ring
+carry.  With RTW, world_model or MAIC it raises ValueError, with overlapped rollouts NotImplementedError - before anything is built.
+
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
 from __future__ import annotations
@@ -66,7 +70,7 @@ import numpy as np
 import torch
 
 from .rollout import RolloutWorker
-from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC, MAICMAC, PolicyMAC
+from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC, MAICMAC, PolicyMAC, MAVENMAC
 from .common.replaybuffer import ReplayBuffer
 from .algorithm.q_learner import QLearner
 from .algorithm.qtran_learner import QTRANLearner
@@ -78,6 +82,7 @@ from .algorithm.central_v import CentralVLearner
 from .algorithm.reinforce import ReinforceLearner
 from .algorithm.iql import IQLLearner
 from .algorithm.wqmix import WQMIXLearner, WQMIX_ALGS
+from .algorithm.maven import MAVENLearner
 from .utils.logging import Logger
 
 
@@ -133,6 +138,13 @@ class Runner:
         if wqmix and on:
             raise ValueError("%s trains the plain shared agent beside a central one in WQMIXLearner: not with %s"
                              % (args.alg, on[0].name))
+        maven = args.alg == 'maven'
+        if maven and on:
+            raise ValueError("maven trains the noise-conditioned shared agent in MAVENLearner: not with %s" % on[0].name)
+        if maven and getattr(args, "overlap_rollout", False):
+            raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no MAVEN head")
+        if maven:
+            mac_cls = MAVENMAC
         self.on_policy = learner_cls is not None or args.alg in _ON_POLICY
         if self.on_policy:
             if on:
@@ -167,6 +179,8 @@ class Runner:
             self.learner = (learner_cls or _ON_POLICY[args.alg])(self.mac, args)
         elif wqmix:
             self.learner = WQMIXLearner(self.mac, args)
+        elif maven:
+            self.learner = MAVENLearner(self.mac, args)
         elif _value_mixer(args):
             self.learner = make_learner(self.mac, logger, args)
         elif _qtran(args):
@@ -272,7 +286,13 @@ class Runner:
         torch.save({"learner": self.learner.resume_state(), "epsilon": self.rolloutWorker.epsilon,
                     "time_steps": self.time_steps, "train_steps": self.train_steps, "evaluate_steps": self.evaluate_steps,
                     "eval_win_rates": list(self.eval_win_rates), "eval_episode_rewards": list(self.eval_episode_rewards),
-                    "env_episode": getattr(self.env, "episode", None), "np_random": np.random.get_state()}, path)
+                    "env_episode": getattr(self.env, "episode", None), "np_random": np.random.get_state(),
+                    "ring_noise": self._ring_noise()}, path)
+
+    def _ring_noise(self):
+        """the replay ring's per-episode noise (MAVEN) as a host tensor, or None where the ring holds none"""
+        rec = getattr(self.buffer, "record", None)
+        return None if rec is None or rec.noise is None else rec.noise.detach().cpu().clone()
 
     def load_resume(self, path):
         sd = torch.load(path, map_location="cpu", weights_only=False)
@@ -283,6 +303,11 @@ class Runner:
         if sd.get("env_episode") is not None and hasattr(self.env, "episode"):
             self.env.episode = sd["env_episode"]
         np.random.set_state(sd["np_random"])
+        noise, rec = sd.get("ring_noise"), getattr(self.buffer, "record", None)
+        if noise is not None and rec is not None and rec.E == noise.numel():      # (a ring not allocated yet refills with its own)
+            if rec.noise is None:
+                rec.noise = torch.zeros(rec.E, dtype=torch.int32, device=rec.obs.device)
+            rec.noise.copy_(noise)
 
     def evaluate(self):
         """reference runner.py:115-121."""

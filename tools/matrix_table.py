@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Trains --alg {qmix, ow_qmix, cw_qmix} on the launcher's matrix game ([[8, -12, -12], [-12, 0, 0], [-12, 0, 0]], the payoff of the
+"""Trains --alg {qmix, ow_qmix, cw_qmix, maven (the table of noise index 0)} on the launcher's matrix game ([[8, -12, -12], [-12, 0, 0], [-12, 0, 0]], the payoff of the
 Weighted QMIX paper) for --steps environment steps and prints ``get_q_and_q_tot_table()``: the 3 x 3 q_tot table and the two agents'
 Q rows, with the argmax of the table.  The paper's outcome is the weighted variants' argmax at (0, 0) where QMIX's is not; what
 happens here is recorded in DESIGN section 10, it is not a pass criterion.
@@ -18,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--alg", default="ow_qmix", choices=["qmix", "ow_qmix", "cw_qmix"])
+    ap.add_argument("--alg", default="ow_qmix", choices=["qmix", "ow_qmix", "cw_qmix", "maven"])
     ap.add_argument("--steps", type=int, default=20000)
     ap.add_argument("--n_envs", type=int, default=32)
     ap.add_argument("--seed", type=int, default=123)
