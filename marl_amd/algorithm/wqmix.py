@@ -23,22 +23,12 @@ import copy
 import torch
 
 from .. import ops
-from ..common.arguments import WQMIX_ALGS
+from ..common.arguments import WQMIX_ALGS, wqmix_alpha_of      # (the validator lives beside get_wqmix_args)
 from ..controller.share_params import SharedMAC
 from ..hostutil import flatten_module
 from ..network.mixer import QMixMixer, CentralFFMixer
 from .common import MASK_BIG, LearnerParams, FlatView, GradReducer, agent_backward
 from .q_learner import QLearner
-
-
-def wqmix_alpha_of(args):
-    """args.wqmix_alpha, a number in [0, 1] (unset: get_wqmix_args' 0.5 for ow_qmix, 0.75 for cw_qmix); anything else is an error"""
-    alpha = getattr(args, "wqmix_alpha", None)
-    if alpha is None:
-        alpha = 0.5 if args.alg == 'ow_qmix' else 0.75
-    if isinstance(alpha, bool) or not 0.0 <= alpha <= 1.0:
-        raise ValueError("wqmix_alpha must be a number in [0, 1], got %r" % (alpha,))
-    return float(alpha)
 
 
 class _Dbg(dict):

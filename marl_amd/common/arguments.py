@@ -3,6 +3,7 @@ import (matrix_game_test.py:9, main.py:3) exists with the same name and effect. 
 reference's ``type=bool`` treats any non-empty string as True), and ``--RTW`` / ``--load_model``
 default to False: the RTW research variant is outside the hot path and no checkpoint ships with this build."""
 import argparse
+import numbers
 
 
 def _bool(v):
@@ -186,16 +187,40 @@ def get_g2anet_args(args):
 WQMIX_ALGS = ('ow_qmix', 'cw_qmix')
 
 
+def wqmix_alpha_of(args):
+    """args.wqmix_alpha, a number in [0, 1] (unset: get_wqmix_args' 0.5 for ow_qmix, 0.75 for cw_qmix); anything else is an error"""
+    alpha = getattr(args, "wqmix_alpha", None)
+    if alpha is None:
+        alpha = 0.5 if args.alg == 'ow_qmix' else 0.75
+    if isinstance(alpha, bool) or not 0.0 <= alpha <= 1.0:
+        raise ValueError("wqmix_alpha must be a number in [0, 1], got %r" % (alpha,))
+    return float(alpha)
+
+
 def get_wqmix_args(args):
     """This project's own table for Weighted QMIX (the reference ships none): wqmix_alpha = 0.5 for ow_qmix and 0.75 for cw_qmix
     (the paper's SMAC values) and central_mixing_embed_dim = 256.  Values the caller set (not None) are kept; an alpha outside
     [0, 1] is a ValueError."""
-    for k, v in dict(wqmix_alpha=0.5 if args.alg == 'ow_qmix' else 0.75, central_mixing_embed_dim=256).items():
+    for k, v in dict(wqmix_alpha=wqmix_alpha_of(args), central_mixing_embed_dim=256).items():
         if getattr(args, k, None) is None:
             setattr(args, k, v)
-    if isinstance(args.wqmix_alpha, bool) or not 0.0 <= args.wqmix_alpha <= 1.0:
-        raise ValueError("wqmix_alpha must be a number in [0, 1], got %r" % (args.wqmix_alpha,))
     return args
+
+
+def noise_dim_of(args):
+    """args.noise_dim as the kernels take it: an int in [1, 32]; anything else is an error"""
+    K = getattr(args, "noise_dim", None)
+    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 32:
+        raise ValueError("noise_dim must be an integer in [1, 32], got %r" % (K,))
+    return K
+
+
+def lambda_mi_of(args):
+    """args.lambda_mi: a number >= 0; anything else is an error"""
+    lam = getattr(args, "lambda_mi", None)
+    if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not lam >= 0.0:
+        raise ValueError("lambda_mi must be a number >= 0, got %r" % (lam,))
+    return float(lam)
 
 
 def get_maven_args(args):
@@ -205,11 +230,8 @@ def get_maven_args(args):
     for k, v in dict(noise_dim=16, lambda_mi=0.001, maven_discrim_dim=64).items():
         if getattr(args, k, None) is None:
             setattr(args, k, v)
-    K, lam = args.noise_dim, args.lambda_mi
-    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 32:
-        raise ValueError("noise_dim must be an integer in [1, 32], got %r" % (K,))
-    if isinstance(lam, bool) or not lam >= 0.0:
-        raise ValueError("lambda_mi must be a number >= 0, got %r" % (lam,))
+    noise_dim_of(args)
+    lambda_mi_of(args)
     return args
 
 

@@ -12,30 +12,13 @@ state dict is RNNQNet's.  The arithmetic is csrc/maven.hip (the head kernel afte
 
 ``MavenDiscriminator`` is the parameter container of the MI pass: logits = l2(relu(l1([p_0 | .. | p_{N-1} | s]))), l1 (N A + S -> D),
 l2 (D -> K); its parameters sit in the learner's flat buffer and it has no target copy."""
-import numbers
-
 import torch
 import torch.nn as nn
 
 from .. import ops
+from ..common.arguments import noise_dim_of, lambda_mi_of      # (the validators live beside get_maven_args)
 from ..hostutil import cached_module_struct, cached_struct
 from .q_network import RNNQNet
-
-
-def noise_dim_of(args):
-    """args.noise_dim as the kernels take it: an int in [1, 32]; anything else is an error"""
-    K = getattr(args, "noise_dim", None)
-    if isinstance(K, bool) or not isinstance(K, int) or not 1 <= K <= 32:
-        raise ValueError("noise_dim must be an integer in [1, 32], got %r" % (K,))
-    return K
-
-
-def lambda_mi_of(args):
-    """args.lambda_mi: a number >= 0; anything else is an error"""
-    lam = getattr(args, "lambda_mi", None)
-    if isinstance(lam, bool) or not isinstance(lam, numbers.Real) or not lam >= 0.0:
-        raise ValueError("lambda_mi must be a number >= 0, got %r" % (lam,))
-    return float(lam)
 
 
 def maven_shape_of(args, n_agents=None, n_actions=None, state_shape=None):

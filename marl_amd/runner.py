@@ -9,54 +9,17 @@ of one update - the reference has lag 0, which is why this is off by default), w
 excludes, and the cadence of runner.py:85-98 (store -> train_steps updates -> log -> save) is unchanged.
 ``"lag1_serial"`` runs the same schedule on one stream (the parity check of the overlapped mode: identical losses).
 
-``args.RTW`` (with reuse_network, reference runner.py:20-23,46-49): RTWMAC and RTWQLearner.  Evaluation and rollouts run
-(the per-step path; no overlapped rollouts); training raises the reference's TypeError.  Divergence: the reference pairs
-RTWMAC with the plain QTRANLearner for qtran_base / qtran_alt, which cannot run on an RTW controller; here that
-combination raises NotImplementedError.
+The controller, the learner and the refusals of ``args.alg`` are its row's in algorithms.py (``lookup``); ``args.RTW`` /
+``args.world_model`` / ``args.MAIC`` put the controller and learner of their row of ``_AGENT_SWITCHES`` in their place, for vdn / qmix /
+qplex (rollouts then take the per-step path).  ``args.MAIC_train`` (with MAIC): MAICTDLearner, which trains the MAIC agent on the TD
+loss and, with ``args.mi_loss_weight`` / ``args.entropy_loss_weight`` positive, on its MI and attention-entropy losses.  Every refusal
+comes before anything is built; a name without a learner ends in 'learner <name> cannot find!' after the controller, the worker
+and the buffer exist.
 
-``args.world_model`` (a switch of this project; the reference runner never builds the pair): SharedMACWithState and
-QLearnerWithState (reference controller/share_params.py:185-387, algorithm/q_learner_state.py) for vdn / qmix / qplex.
-Rollouts take the per-step path.  With RTW it raises ValueError, with qtran_* the reference's ValueError, with overlapped
-rollouts NotImplementedError.
-
-``args.MAIC`` (a switch of this project; the reference ships network/MAIC.py without a controller or a learner): MAICMAC and
-MAICQLearner for vdn / qmix / qplex.  Evaluation and rollouts run (the per-step path); ``learner.train`` raises
-NotImplementedError and touches nothing.  With RTW or world_model it raises ValueError, with qtran_* or overlapped rollouts
-NotImplementedError - all before anything is built.
-
-``args.MAIC_train`` (with MAIC): the learner is MAICTDLearner, which trains the agent on the TD loss through the message
-head's backward pass and, with ``args.mi_loss_weight`` / ``args.entropy_loss_weight`` positive, on the agent's MI and
-attention-entropy losses (csrc/maic_aux.hip); the refusals above hold for it too.  Without MAIC it raises ValueError before
-anything is built, and so does a positive loss weight without MAIC_train.
-
-``args.alg == 'central_v'`` / ``'reinforce'``: PolicyMAC and CentralVLearner (algorithm/central_v.py) or ReinforceLearner
-(algorithm/reinforce.py), trained ON-POLICY: the episodes a rollout just
-generated are the batch of the one update that follows it - nothing goes through the replay buffer - and the learner is told the
-exploration rate they were drawn at.  With RTW / world_model / MAIC it raises ValueError, with overlapped rollouts
-NotImplementedError (an on-policy update needs the weights the last one wrote) - before anything is built.
-``learner_cls`` (a constructor argument): a further on-policy learner over PolicyMAC, named by the caller instead of by the runner's
-own table; everything above holds for it.  The launcher passes COMALearner (algorithm/coma.py) for ``--alg coma``
-(``main.make_runner``); a Runner built without it keeps answering 'learner coma cannot find!', as it always has.  ``--alg lica``
-gets LICALearner (algorithm/lica.py) the same way: PolicyMAC, on-policy batches, and a Runner on the bare name answers
-'learner lica cannot find!'.
-``mac_cls`` (a constructor argument, with ``learner_cls``): the stochastic controller that learner trains in the place of PolicyMAC - the
-launcher passes the GroupHeadMAC subclass of its actor table (CommNetMAC for the three ``+commnet`` algorithms, G2ANetMAC for the three
-``+g2anet`` ones); a Runner built on a bare ``+commnet`` / ``+g2anet`` name answers 'cannot find!' too.
-
-``args.alg == 'iql'`` (no agent switch on): SharedMAC, the replay buffer and IQLLearner (algorithm/iql.py), independent Q-learning
-without a mixer.  With an agent switch the name is answered as before: world_model refuses it as an unknown mixer, RTW and MAIC
-end in 'learner iql cannot find!'.
-
-``args.alg == 'qatten'`` (no agent switch on): SharedMAC, the replay buffer and QLearner with QattenMixer (network/mixer.py).  With
-RTW, world_model or MAIC it raises ValueError before anything is built: their learners keep their own three-mixer tables.
-
-``args.alg == 'ow_qmix'`` / ``'cw_qmix'`` (no agent switch on): SharedMAC, the replay buffer and WQMIXLearner (algorithm/wqmix.py),
-Weighted QMIX.  The names are decided before the value-mixer branch, whose substring match would take them for qmix.  With RTW,
-world_model or MAIC it raises ValueError before anything is built.  Rollouts act through the eval agent alone.
-
-``args.alg == 'maven'`` (no agent switch on): MAVENMAC, the replay buffer and MAVENLearner (algorithm/maven.py).  Rollouts take the
-per-step path (the whole-rollout kernels have no MAVEN head) and draw one noise index per episode, which the records and the replay ring
-carry.  With RTW, world_model or MAIC it raises ValueError, with overlapped rollouts NotImplementedError - before anything is built.
+``learner_cls`` (a constructor argument): an on-policy learner over PolicyMAC, named by the caller instead of by the row - what the
+rows say of ``on_policy`` holds for it.  ``main.make_runner`` passes the learner of the ``launcher_only`` rows so; a Runner built
+on such a bare name answers 'cannot find!'.  ``mac_cls`` (with ``learner_cls``): the stochastic controller that learner trains in
+the place of PolicyMAC.
 
 Full resume: ``save_resume`` / ``load_resume`` carry what the reference's checkpoints lack - optimizer
 state, target networks, epsilon, the loop counters, the numpy RNG state (the replay ring refills)."""
@@ -70,7 +33,8 @@ import numpy as np
 import torch
 
 from .rollout import RolloutWorker
-from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC, MAICMAC, PolicyMAC, MAVENMAC
+from .algorithms import UNKNOWN, lookup, qtran, value_mixer
+from .controller.share_params import SharedMAC, SharedMACWithState, RTWMAC, MAICMAC, PolicyMAC, MAVENMAC, CommNetMAC, G2ANetMAC  # noqa: F401
 from .common.replaybuffer import ReplayBuffer
 from .algorithm.q_learner import QLearner
 from .algorithm.qtran_learner import QTRANLearner
@@ -78,51 +42,50 @@ from .algorithm.rtw_q_learner import RTWQLearner
 from .algorithm.q_learner_state import QLearnerWithState
 from .algorithm.maic_q_learner import MAICQLearner
 from .algorithm.maic_td_learner import MAICTDLearner
-from .algorithm.central_v import CentralVLearner
-from .algorithm.reinforce import ReinforceLearner
-from .algorithm.iql import IQLLearner
-from .algorithm.wqmix import WQMIXLearner, WQMIX_ALGS
-from .algorithm.maven import MAVENLearner
+from .algorithm.central_v import CentralVLearner  # noqa: F401  (the rows' classes: algorithms.py names them, __init__ finds them here)
+from .algorithm.reinforce import ReinforceLearner  # noqa: F401
+from .algorithm.coma import COMALearner  # noqa: F401
+from .algorithm.ppo import PPOLearner  # noqa: F401
+from .algorithm.lica import LICALearner  # noqa: F401
+from .algorithm.iql import IQLLearner  # noqa: F401
+from .algorithm.wqmix import WQMIXLearner  # noqa: F401
+from .algorithm.maven import MAVENLearner  # noqa: F401
 from .utils.logging import Logger
-
-
-def _qtran(args):
-    return args.alg.find('qtran_base') > -1 or args.alg.find('qtran_alt') > -1
-
-
-def _value_mixer(args):
-    return any(args.alg.find(a) > -1 for a in ('vdn', 'qmix', 'qplex'))
 
 
 # One row per agent switch: the controller, the learner, and its refusals as (exception type, text) - combined with a
 # switch of an earlier row, with a learner it cannot drive, with overlapped rollouts.  The rows and a row's checks run in
-# this order, before anything is built; the types differ per row on purpose (module docstring).
+# this order, before anything is built.  The types differ per row on purpose: the reference pairs RTWMAC with the plain
+# QTRANLearner, which cannot run (NotImplementedError here); world_model with qtran_* gives the reference's own ValueError
+# (q_learner_state.py:32); the reference never builds the world-model or the MAIC pair, whose other refusals are this project's.
 _Switch = collections.namedtuple("_Switch", "name mac learner combined alg_refused alg overlap")
 _AGENT_SWITCHES = (
     _Switch("RTW", RTWMAC, lambda mac, logger, args: RTWQLearner(mac, logger, args),
             None,
-            _qtran, (NotImplementedError, "RTW with a QTRAN learner is not supported (the reference's QTRANLearner cannot "
-                                          "drive an RTW controller)"),
+            lambda args: qtran(args.alg), (NotImplementedError, "RTW with a QTRAN learner is not supported (the reference's "
+                                                                "QTRANLearner cannot drive an RTW controller)"),
             (NotImplementedError, "overlapped rollouts use the whole-rollout kernel, which has no RTW head")),
     _Switch("world_model", SharedMACWithState, lambda mac, logger, args: QLearnerWithState(mac, args),
             (ValueError, "world_model and RTW are two different agents: choose one"),
-            lambda args: not _value_mixer(args), (ValueError, "Mixer {} not recognised."),     # q_learner_state.py:32
+            lambda args: not value_mixer(args.alg), (ValueError, "Mixer {} not recognised."),     # q_learner_state.py:32
             (NotImplementedError, "overlapped rollouts use the whole-rollout kernel, which has no world-model head")),
     _Switch("MAIC", MAICMAC,
             lambda mac, logger, args: (MAICTDLearner if getattr(args, "MAIC_train", False) else MAICQLearner)(mac, args),
             (ValueError, "MAIC, RTW and world_model are three different agents: choose one"),
-            _qtran, (NotImplementedError, "MAIC with a QTRAN learner is not supported"),
+            lambda args: qtran(args.alg), (NotImplementedError, "MAIC with a QTRAN learner is not supported"),
             (NotImplementedError, "overlapped rollouts use the whole-rollout kernel, which has no MAIC head")),
 )
 
 
-_ON_POLICY = {'central_v': CentralVLearner, 'reinforce': ReinforceLearner}      # policy-gradient learners over PolicyMAC
+def switches_on(args):
+    """the rows of _AGENT_SWITCHES whose switch is on, in table order"""
+    return [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
 
 
 class Runner:
     def __init__(self, env, logger, args, learner_cls=None, mac_cls=None):
         self.env = env
-        policy_mac_cls = mac_cls if mac_cls is not None else PolicyMAC
+        # ---- the checks that hold for every algorithm
         if not args.reuse_network:
             raise NotImplementedError("only the shared-parameter controller (reuse_network) is on the hot path")
         if getattr(args, "MAIC_train", False) and not getattr(args, "MAIC", False):
@@ -130,34 +93,32 @@ class Runner:
         if (getattr(args, "mi_loss_weight", 0) > 0 or getattr(args, "entropy_loss_weight", 0) > 0) \
                 and not getattr(args, "MAIC_train", False):
             raise ValueError("mi_loss_weight / entropy_loss_weight are terms of MAICTDLearner's loss: they need MAIC_train")
-        mac_cls, make_learner = SharedMAC, lambda mac, logger, args: QLearner(mac, args)
-        on = [sw for sw in _AGENT_SWITCHES if getattr(args, sw.name, False)]
-        if args.alg == 'qatten' and on:      # their learners keep their own three-mixer tables
-            raise ValueError("qatten mixes the plain shared agent's values in QLearner: not with %s" % on[0].name)
-        wqmix = args.alg in WQMIX_ALGS       # decided before _value_mixer, whose substring match would take the names for qmix
-        if wqmix and on:
-            raise ValueError("%s trains the plain shared agent beside a central one in WQMIXLearner: not with %s"
-                             % (args.alg, on[0].name))
-        maven = args.alg == 'maven'
-        if maven and on:
-            raise ValueError("maven trains the noise-conditioned shared agent in MAVENLearner: not with %s" % on[0].name)
-        if maven and getattr(args, "overlap_rollout", False):
-            raise NotImplementedError("overlapped rollouts use the whole-rollout kernel, which has no MAVEN head")
-        if maven:
-            mac_cls = MAVENMAC
-        self.on_policy = learner_cls is not None or args.alg in _ON_POLICY
+        # ---- the row's refusals, then the switch rows'
+        row = lookup(args.alg)
+        if row.launcher_only and learner_cls is None:
+            row = UNKNOWN
+        on, overlap = switches_on(args), getattr(args, "overlap_rollout", False)
+        if on and row.no_switch:
+            raise ValueError(row.no_switch % (args.alg, on[0].name))
+        if overlap and row.no_overlap:
+            raise NotImplementedError(row.no_overlap)
+        self.on_policy = learner_cls is not None or row.on_policy
         if self.on_policy:
             if on:
                 raise ValueError("%s trains the plain shared agent as a policy: not with %s" % (args.alg, on[0].name))
-            if getattr(args, "overlap_rollout", False):
+            if overlap:
                 raise NotImplementedError("%s is on-policy: a rollout needs the weights the last update wrote" % args.alg)
-            mac_cls = policy_mac_cls
         for sw in on:
-            for hit, refusal in ((sw is not on[0], sw.combined), (sw.alg_refused(args), sw.alg),
-                                 (getattr(args, "overlap_rollout", False), sw.overlap)):
+            for hit, refusal in ((sw is not on[0], sw.combined), (sw.alg_refused(args), sw.alg), (overlap, sw.overlap)):
                 if hit:
                     raise refusal[0](refusal[1].format(args.alg))
-            mac_cls, make_learner = sw.mac, sw.learner
+        # ---- building: the classes are this module's attributes of the row's names, looked up now
+        if on:                          # a switch's learner stands in for QLearner; it drives no other row's
+            mac_cls, make_learner = on[0].mac, on[0].learner if row.learner == 'QLearner' else None
+        else:                           # (mac_cls stands in for an on-policy learner's PolicyMAC alone)
+            mac_cls = self.on_policy and mac_cls or globals()['PolicyMAC' if learner_cls else row.mac]
+            learner_cls = learner_cls or row.learner and globals()[row.learner]
+            make_learner = learner_cls and (lambda mac, logger, args: learner_cls(mac, args))
         if mac_cls is MAICMAC:
             from .common.arguments import get_maic_args
             get_maic_args(args)
@@ -175,27 +136,14 @@ class Runner:
         os.makedirs(self.save_path, exist_ok=True)
         logger.setup_tb(self.save_path + '/tb/other')
         self.logger = logger
-        if self.on_policy:
-            self.learner = (learner_cls or _ON_POLICY[args.alg])(self.mac, args)
-        elif wqmix:
-            self.learner = WQMIXLearner(self.mac, args)
-        elif maven:
-            self.learner = MAVENLearner(self.mac, args)
-        elif _value_mixer(args):
-            self.learner = make_learner(self.mac, logger, args)
-        elif _qtran(args):
-            self.learner = QTRANLearner(self.mac, args)
-        elif args.alg == 'qatten':
-            self.learner = QLearner(self.mac, args)
-        elif args.alg == 'iql' and not on:
-            self.learner = IQLLearner(self.mac, args)
-        else:
+        if make_learner is None:
             raise ValueError('learner {} cannot find!'.format(args.alg))
+        self.learner = make_learner(self.mac, logger, args)
         if args.load_model:
             self.learner.load_models()
         self.time_steps, self.train_steps, self.evaluate_steps = 0, 0, -1     # loop counters (restored by load_resume)
         self.losses = []
-        self.overlap = getattr(args, "overlap_rollout", False)
+        self.overlap = overlap
         self._side = None
         self._mac_roll = None
         if getattr(args, "resume", ""):
