@@ -1242,6 +1242,34 @@ int marl_battle_rollout_sample(const marl_agent_weights_t* w, const marl_record_
                                float* stats, double eps0, double eps_anneal, double eps_min, int M, int last_action,
                                int reuse_network, void* stream);
 
+/* ---- hunt environment (hunt.hip; rules: csrc/hunt_env.h) ------------------------------------------------------
+ * Predator-prey with a lone-catch penalty: N predators (the agents) and M prey on a G x G grid, A = 6 (stay, four moves, catch).  A
+ * prey is captured when two or more predators next to it catch in the same step (10 points); a prey with exactly one catcher costs
+ * the team the penalty, which travels as the integer pen4 = 4 x penalty (0 .. 64).  Observation width O = 77 (a 5 x 5 window of
+ * [another predator, a live prey, off the grid], then the own x and y ratios), state width S = 2 N + 3 M.  units (E, N + M, 3) int32:
+ * x, y, live, predators first.  The record is marl_record_t, with O and S the widths above: every entry returns hipErrorInvalidValue
+ * for any other O or S.  marl_hunt_supported(): 2 <= N <= 16, 1 <= M <= 16, 3 <= G <= 32 and A = 6; the entries return
+ * hipErrorInvalidValue for anything else (and for pen4 outside 0 .. 64, state_ld < S, t outside 0 .. T - 1) and launch nothing. */
+int marl_hunt_supported(int N, int M, int G, int A);
+/* start of episode `episode`: unit state (positions from the counter hash of (seed, env0 + e, episode, unit), streams 32 .. 35, every
+ * unit live), length = T, won = 0, and slot 0 of obs / state / avail; never touches u / r / term / padded */
+int marl_hunt_reset(unsigned seed, int env0, int episode, int G, int M, int* units, const marl_record_t* rec, void* stream);
+/* lock-step t in one launch: reads act (E,N); writes u / r / term / padded of step t, length = t + 1 and won where the episode
+ * ends here (no prey left: won = 1; or t + 1 = T), alive_next (E; may be NULL) = 0 from the terminating step on, the new unit state
+ * and slot t + 1 of obs / state / avail (the final observation at the terminating step).  Environments whose episode is over
+ * (t >= length) get u = -1, r = 0, term = 1, padded = 1 and a zero slot.  r = (float)(40 captures - pen4 lone attempts) * 0.25f;
+ * the prey that stay walk by the counter hash of (seed, env0 + e, tg = episode (T + 1) + t, prey), stream 36. */
+int marl_hunt_step(unsigned seed, int env0, int episode, int G, int pen4, int t, const int* act, int* units,
+                   const marl_record_t* rec, int* alive_next, int M, void* stream);
+/* The action choice and marl_hunt_step in one launch.  q (E,1,N,A): predator n of a live environment chooses from its row and slot
+ * t's availability in the record with marl_select_actions' epsilon-greedy rule and draws, keyed by (rseed, env0 + e, tg, n); -1
+ * wherever t >= length[e].  Then the step, as marl_hunt_step does it (no alive_next).  _sample: the choice is marl_policy_sample's
+ * draw from the stochastic policy of the row instead, eps its mixing epsilon. */
+int marl_hunt_fused_step(unsigned seed, unsigned rseed, int env0, int episode, int G, int pen4, int t, float eps, const float* q,
+                         int* units, const marl_record_t* rec, int M, void* stream);
+int marl_hunt_fused_step_sample(unsigned seed, unsigned rseed, int env0, int episode, int G, int pen4, int t, float eps,
+                                const float* q, int* units, const marl_record_t* rec, int M, void* stream);
+
 /* ---- MAVEN (maven.hip; Mahajan et al., NeurIPS 2019 - the reference ships no MAVEN: the definition is this project's own) ---------
  * Sizes: K = noise_dim (1..32), H = 64, N agents (1..16), A actions (1..32), state width S, discriminator width D = 64.
  * Noise: every episode carries one index k in [0, K): marl_maven_noise writes noise[e] = hkey(rseed, stream 24, env0 + e, tg0, 0) % K

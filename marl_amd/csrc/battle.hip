@@ -4,29 +4,12 @@
 // the same sum), then all 64 lanes write the slot's N O + S + N A floats as three contiguous runs, 16 bytes a lane where a run's
 // address allows (a run starts on any 4-byte boundary: N O is 90 floats on 3m).
 #include "battle_env.h"
-#include "policy_rows.h"
+#include "env_slot.h"
 #include "../../include/marl_hip.h"
 
 namespace {
 constexpr int BT_WPB = 4;                       // environments (waves) per workgroup
 constexpr int BT_UNITS = 2 * BT_MAX_SIDE;
-
-// p[0 .. n) = f(0 .. n) by the 64 lanes of a wave: scalar stores up to the first 16-byte boundary and after the last, f32x4 between
-template <class F>
-__device__ __forceinline__ void write_run(float* p, int n, int lane, F f) {
-  int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2;
-  if (head > n) head = n;
-  const int body = (n - head) >> 2;
-  if (lane < head) p[lane] = f(lane);
-  for (int q = lane; q < body; q += MARL_WAVE) {
-    const int k = head + 4 * q;
-    f32x4 v;
-    v[0] = f(k); v[1] = f(k + 1); v[2] = f(k + 2); v[3] = f(k + 3);
-    *reinterpret_cast<f32x4*>(p + k) = v;
-  }
-  const int tail = head + 4 * body;
-  if (tail + lane < n) p[tail + lane] = f(tail + lane);
-}
 
 // slot `slot` of environment e from the unit state un (LDS); act: the step's recorded actions (LDS) or NULL; !live: zeros
 __device__ __forceinline__ void write_slot(const BattleCfg& c, const int* un, const int* act, bool live, float* obs, float* state,
@@ -153,34 +136,9 @@ __global__ __launch_bounds__(BT_WPB * MARL_WAVE) void battle_fused_step_kernel(B
   const bool live = valid && t < length[e];
   const int N = c.N, A = c.A;
   int arg = -1;
-  if (live && lane < N) {
-    const unsigned env = (unsigned)(env0 + (int)e), tg = env_tg(episode, T, t);
-    const float* qa = q + (e * N + lane) * A;
-    const float* av = avail + ((e * (T + 1) + t) * N + lane) * A;
-    if constexpr (SAMPLE) {
-      const RowPolicy p = row_policy(qa, av, A, eps);
-      arg = row_sample(p, qa, av, A, u01(hkey(rseed, ST_SAMPLE, env, tg, (unsigned)lane)));
-    } else {
-      float best = 0.f; int navail = 0;
-      for (int k = 0; k < A; ++k) {
-        if (av[k] == 0.f) continue;
-        ++navail;
-        if (arg < 0 || qa[k] > best) { best = qa[k]; arg = k; }
-      }
-      if (arg < 0) arg = 0;
-      const bool explore = u01(hkey(rseed, ST_EXPLORE, env, tg, (unsigned)lane)) < eps;
-      if (explore && navail > 0) {
-        int kk;
-        env_pick(u01(hkey(rseed, ST_PICK, env, tg, (unsigned)lane)), navail, kk);
-        int cnt = 0;
-        for (int k = 0; k < A; ++k) {
-          if (av[k] == 0.f) continue;
-          if (cnt == kk) { arg = k; break; }
-          ++cnt;
-        }
-      }
-    }
-  }
+  if (live && lane < N)
+    arg = env_choose<SAMPLE>(q + (e * N + lane) * A, avail + ((e * (T + 1) + t) * N + lane) * A, A, eps, rseed,
+                             (unsigned)(env0 + (int)e), env_tg(episode, T, t), lane);
   battle_step_body(c, s, scale, t, arg, valid, live, e, w, lane, units, u, r, term, padded, length, won, nullptr, obs, state, SL,
                    avail, T);
 }

@@ -8,7 +8,9 @@
 #include "common.h"
 
 // (ST_SAMPLE: the draws of the stochastic policy, policy.hip.  Its number is also the MAIC latent noise's, maic_head.hip: the two
-// never meet, a policy controller has no head.  ST_GUMBEL: the logistic noise of G2ANet's hard attention, g2anet.hip)
+// never meet, a policy controller has no head.  ST_GUMBEL: the logistic noise of G2ANet's hard attention, g2anet.hip.  Streams
+// other files declare: 16 .. 19 the battle starts, battle_env.h; 24 MAVEN's noise index, maven.hip; 32 .. 36 the hunt environment's
+// starts HT_PX, HT_PY, HT_QX, HT_QY and its prey walk HT_MOVE, hunt_env.h)
 enum { ST_OBS = 0, ST_STATE, ST_AVAIL, ST_REWARD, ST_LEN, ST_WON, ST_EXPLORE, ST_PICK, ST_SAMPLE, ST_GUMBEL };
 
 __host__ __device__ inline unsigned mix32(unsigned x) {

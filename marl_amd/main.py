@@ -20,11 +20,14 @@
     python -m marl_amd.main --map 2s3z --MAIC True --load_model True --evaluate True --evaluate_epoch 1 --n_envs 64
     python -m marl_amd.main --env battle --map 3m --alg qmix --n_envs 64 --n_steps 200000
     python -m marl_amd.main --env battle --map 3m --alg maven --noise_dim 16 --lambda_mi 0.001 --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --env hunt --map 4v2 --alg qmix --n_envs 64 --n_steps 200000
+    python -m marl_amd.main --env hunt --map 4v2_p2 --alg cw_qmix --n_envs 64 --n_steps 200000
 
 ``--env synthetic`` (default) uses the synthetic SMAC-shaped device env with the dims of ``--map``;
 ``--env matrix`` the batched two-agent matrix game; ``--env battle`` the micro-combat simulator in SMAC's layout (env/battle.py:
-maps 3m, 2s3z, 3s5z), the one environment here whose outcome depends on the actions.  StarCraft II itself is not vendored by the
-reference."""
+maps 3m, 2s3z, 3s5z), whose outcome depends on the actions; ``--env hunt`` predator-prey with a lone-catch penalty (env/hunt.py: maps
+2v1, 4v2, 8v8, each with an optional penalty suffix as in 4v2_p2 or 8v8_p1.5), the task monotonic mixing fails on.  StarCraft II
+itself is not vendored by the reference."""
 from __future__ import annotations
 
 import importlib
@@ -36,6 +39,7 @@ from .common.arguments import get_common_args, get_mixer_args, get_RTW_args, get
 from .env.synthetic_smac import SyntheticSMACEnv
 from .env.single_state_matrix_game import BatchedMatrixGame
 from .env.battle import BattleEnv, FusedBattleEnv, battle_shapes
+from .env.hunt import HuntEnv, hunt_shapes
 from .runner import Runner, switches_on
 from .utils.logging import Logger
 
@@ -46,10 +50,12 @@ _SIZE_AT = dict(n_agents=0, state_shape=2, n_actions=3)
 
 def _map_shapes(args):
     """(agents, observation, state, actions, episode limit) of --map, known before the environment is made: ``MAPS`` for the synthetic
-    environment, the battle environment's own table for ``--env battle`` (a map it does not have is a ValueError); where no map says
-    them, the matrix game's"""
+    environment, the battle and hunt environments' own tables for ``--env battle`` / ``--env hunt`` (a map they do not have is a
+    ValueError); where no map says them, the matrix game's"""
     if args.env == 'battle':
         return battle_shapes(args.map)
+    if args.env == 'hunt':
+        return hunt_shapes(args.map)
     return MAPS[args.map] if args.env in ('smac', 'synthetic') else _MATRIX_GAME
 
 
@@ -94,6 +100,8 @@ def build(argv=None):
     vars(args).update(kept)             # ... and so are a table's
     if args.env == 'battle':
         battle_shapes(args.map)         # a map the battle environment does not have is refused before anything is built
+    if args.env == 'hunt':
+        hunt_shapes(args.map)           # (and one the hunt environment does not have, penalty suffix included)
     _, actor = actor_base(args.alg, entry=True)              # raises on any other algorithm with an actor suffix
     if actor is not None and on:
         raise ValueError("%s trains the %s actor as a policy: not with %s" % (args.alg, actor.title, on[0]))
@@ -107,6 +115,8 @@ def build(argv=None):
         env = SyntheticSMACEnv(args.n_envs, n, o, s, a, t, seed=args.seed)
     elif args.env == 'battle':
         env = (FusedBattleEnv if args.battle_fused else BattleEnv)(args.n_envs, args.map, seed=args.seed)
+    elif args.env == 'hunt':
+        env = HuntEnv(args.n_envs, args.map, seed=args.seed)
     elif args.env == 'matrix':
         env = BatchedMatrixGame([[8, -12, -12], [-12, 0, 0], [-12, 0, 0]], args.n_envs, seed=args.seed)
         args.map = 'MatrixGame'

@@ -1078,6 +1078,29 @@ def battle_rollout(w, seed, rseed, env0, episode, types, shield, type_bits, scal
              *map(float, eps_sched), M, 1 if last_action else 0, 1 if reuse_network else 0, _stream()), name)
 
 
+def hunt_supported(N, M, G, A):
+    return bool(_lib.load().marl_hunt_supported(int(N), int(M), int(G), int(A)))
+
+
+def hunt_reset(seed, env0, episode, G, M, units, rec):
+    """start of an episode of the hunt environment (csrc/hunt.hip): unit state, length, won and slot 0 of the record"""
+    check(_lib.load().marl_hunt_reset(int(seed) & 0xFFFFFFFF, env0, episode, G, M, _p(_i32(units)), record(rec), _stream()),
+          "marl_hunt_reset")
+
+
+def hunt_step(seed, env0, episode, G, pen4, t, act, units, rec, alive_next, M):
+    """lock-step t of the hunt environment in one launch: step t of the record, the unit state and slot t + 1"""
+    check(_lib.load().marl_hunt_step(int(seed) & 0xFFFFFFFF, env0, episode, G, pen4, t, _p(_i32(act)), _p(_i32(units)), record(rec),
+                                     _p(alive_next), M, _stream()), "marl_hunt_step")
+
+
+def hunt_fused_step(seed, rseed, env0, episode, G, pen4, t, eps, q, units, rec, M, sample=False):
+    """the action choice (select_actions' rule and draws; sample: policy_sample's) and hunt_step in one launch"""
+    fn, name = _entry("marl_hunt_fused_step", sample)
+    check(fn(int(seed) & 0xFFFFFFFF, int(rseed) & 0xFFFFFFFF, env0, episode, G, pen4, t, float(eps), _p(_f32(q)), _p(_i32(units)),
+             record(rec), M, _stream()), name)
+
+
 def synth_rollout_supported(N, O, A):
     return bool(_lib.load().marl_synth_rollout_supported(N, O, A))
 

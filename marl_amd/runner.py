@@ -129,7 +129,7 @@ class Runner:
         self.args = args
         self.eval_win_rates = []
         self.eval_episode_rewards = []
-        if self.args.env in ('smac', 'synthetic', 'matrix', 'battle'):
+        if self.args.env in ('smac', 'synthetic', 'matrix', 'battle', 'hunt'):
             self.save_path = self.args.result_dir + '/' + args.alg + '/' + args.map
         else:
             raise ValueError("env {} dose not exist!".format(self.args.env))
